@@ -1,11 +1,25 @@
 """bench.py — benchmarks of the TOAD gated-attention MIL hot path on MI355X.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5                      # headline (the driver's run)
+    python bench.py --gpus 1 --steps 20 --warmup 5                      # headline (the driver's run): timed steps + the result line only
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full               # ... plus every other leg listed below
+    python bench.py ... --dump-outputs DIR                               # ... and what the last timed step computed, as DIR/<name>.npy
     python bench.py --gpus N --steps K --warmup W                        # N > 1 started plainly: re-executes itself under torch.distributed.run
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W           # (what the driver runs for N > 1; same thing)
     python bench.py --config 2 | 3 | 4 | 5 [--gpus N]                    # BASELINE.json configs 2-5 (5 = bench_extract.py)
     python bench.py --dropin [--patches N]                               # the reference's own call sequence, timed
+
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs if given and prints the JSON line: metric, value, unit,
+ms_per_step, higher_is_better, dtype, config, last_loss, and `roofline` (read from the HIP events inside the timed steps themselves).
+Everything that needs runs of its own - roofline_mfma, sustained, allreduce, the prepared / batched / ingest / per_slide / dropin legs and
+every cpu_baseline - is measured only with --full (each still switchable off by its own --no-* / --sustain-seconds option).
+
+--dump-outputs DIR  after the timed steps: what the last of them handed its caller, float32 .npy files (at most 64 MB in all; an array
+             beyond its share is replaced by a fixed, seeded sample of its elements). Step configurations: loss [slides of this rank, 3]
+             (the device loss vectors dp.step returns), params [P] (the flat parameter buffer after the optimiser step), grad [P] (the
+             flat gradient the step applied). --config 2: a_raw, m, stats of the last pool launch; --dropin: the result dict of the last
+             model(data, sex) and params; --config 5: bag (the extracted features) besides loss / params / grad. Inputs are seeded, so
+             two builds run with the same arguments can be compared output for output.
 
 Headline (no --config). A "step" = one optimiser step of slide-sharded data parallel training: every rank runs
 forward + weighted CE + backward over its own synthetic 100,000-patch x 1024-d bag - the RAW fp32 [N,1024] tensor, already
@@ -373,9 +387,10 @@ def time_ingest(dp, n: int, dev, slides_per_leg: int = 12):
     return out
 
 
-def time_dropin(n: int, steps: int, warmup: int, dev, host_reads: bool):
+def time_dropin(n: int, steps: int, warmup: int, dev, host_reads: bool, keep=None):
     """The reference's train_loop body (utils/core_utils_mtl_concat.py:201-234) on the drop-in module, resident bags.
-    host_reads adds what the reference's loop reads back per slide (two loss .item(), Y_hat / site_hat for the loggers)."""
+    host_reads adds what the reference's loop reads back per slide (two loss .item(), Y_hat / site_hat for the loggers).
+    `keep` (a dict) receives what the last timed step handed its caller: the model's result dict and the parameters after Adam."""
     from toad_amd import TOAD_fc_mtl_concat
     torch.manual_seed(1)
     model = TOAD_fc_mtl_concat(dropout=False, n_classes=C)
@@ -396,15 +411,20 @@ def time_dropin(n: int, steps: int, warmup: int, dev, host_reads: bool):
         loss.backward()
         opt.step()
         opt.zero_grad()
+        return res
 
     for i in range(warmup):
         one(i)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(steps):
-        one(i)
+        res = one(i)
     torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / steps * 1e3
+    ms = (time.perf_counter() - t0) / steps * 1e3
+    if keep is not None:
+        keep.update({k: v.detach() for k, v in res.items() if torch.is_tensor(v)})
+        keep["params"] = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+    return ms
 
 
 def time_allreduce(dp, dev, world: int, backend: str):
@@ -461,6 +481,25 @@ def emit(out: dict) -> None:
         os.write(_REAL_STDOUT, line)
 
 
+DUMP_BUDGET_BYTES = 64 << 20          # --dump-outputs: all files together
+
+
+def write_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: every array as out_dir/<name>.npy, float32 (float64 stays float64). An array larger than its even share of
+    DUMP_BUDGET_BYTES is replaced by a fixed sample of its flattened elements: the indices depend only on its size (seed 0), so two runs
+    with the same arguments sample the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_BUDGET_BYTES - 4096 * len(arrays)) // max(1, len(arrays))        # (4 KB per file for the .npy header)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def run_config2(args, dev):
     """Pool forward only, one resident 100k-patch bag (BASELINE config 2)."""
     from toad_amd import ops
@@ -474,11 +513,13 @@ def run_config2(args, dev):
     ops.enable_timing(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        ops.gated_pool_fwd(p, D, h, wc, bc)
+        res = ops.gated_pool_fwd(p, D, h, wc, bc)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     calls, tot_ms = ops.collect_timing()["pool_fwd"]
     ops.enable_timing(False)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, dict(zip(("a_raw", "m", "stats"), res)))
     t = tot_ms / calls * 1e-3
     bw = pool_fwd_bytes(n) / t
     out = {"metric": "fused gated-attention pool forward, algorithmic HBM GB/s (100k-patch x 1024-d bag)", "value": round(bw / 1e9, 1),
@@ -489,7 +530,7 @@ def run_config2(args, dev):
            "roofline": {"bound": "hbm", "kernel": "gated_pool_fwd_kernel<2,3,4,true> + gated_pool_combine_kernel", "achieved": round(bw / 1e9, 1),
                         "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": round(bw / HBM_PEAK, 4), "traffic": measured_pool_traffic(n),
                         "algorithmic_bytes": pool_fwd_bytes(n), "us_per_launch": round(t * 1e6, 2)}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_pool(n)
         out["speedup_vs_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
     emit(out)
@@ -520,6 +561,11 @@ def main():
     ap.add_argument("--no-ingest", action="store_true", help="headline run without the host-memory ingest legs (fp32 / fp16 bags over PCIe through BagPrefetcher)")
     ap.add_argument("--ingest-slides", type=int, default=12, help="slides per ingest leg")
     ap.add_argument("--no-per-slide", action="store_true", help="--config 3 without the per_slide leg (one optimiser step per 10k-patch slide: the reference's own semantics)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, every other measurement: roofline_mfma, sustained, allreduce, the prepared / batched / ingest / "
+                         "per_slide / dropin legs, cpu_baseline (each still switchable off by its own option); off: the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all; see the header)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for plumbing tests)")
     ap.add_argument("--ragged", action="store_true",
                     help="config 4 only: log-normal slide lengths (same 64 x 50k = 3.2 M patches in total, sigma 0.7, seeded) dealt with "
@@ -538,7 +584,8 @@ def main():
         sys.argv = [os.path.join(REPO, "bench_extract.py"), "--gpus", str(args.gpus)] + \
                    (["--steps", str(args.steps)] if "--steps" in sys.argv else []) + \
                    (["--warmup", str(args.warmup)] if "--warmup" in sys.argv else []) + \
-                   (["--no-cpu-baseline"] if args.no_cpu_baseline else [])
+                   (["--no-cpu-baseline"] if args.no_cpu_baseline or not args.full else []) + \
+                   (["--dump-outputs", args.dump_outputs] if args.dump_outputs else [])
         return bench_extract.main()
     # `python bench.py --gpus N` started plainly: spawn the N ranks (torch.distributed.run, 127.0.0.1) and exit with their code
     launch.maybe_self_launch(__file__, sys.argv[1:], args.gpus, single_device=args.single_device)
@@ -563,13 +610,18 @@ def main():
         return run_config2(args, dev)
     if args.dropin:
         n = args.patches or 100_000
-        ms = time_dropin(n, args.steps, args.warmup, dev, host_reads=False)
-        ms_h = time_dropin(n, args.steps, args.warmup, dev, host_reads=True)
-        emit({"metric": f"drop-in train_loop body, {n}-patch bags", "value": round(1e3 / ms, 2), "unit": "slides/s", "n_gpus": 1,
-                          "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4), "ms_per_step_with_host_reads": round(ms_h, 4),
-                          "higher_is_better": True, "dtype": "f32", "data": "synthetic",
-                          "config": {"workload": "model(data, sex) + nn.CrossEntropyLoss x2 + loss.backward() + torch.optim.Adam.step() + zero_grad() "
-                                                 "(utils/core_utils_mtl_concat.py:206-234) on toad_amd.TOAD_fc_mtl_concat, resident bags"}})
+        kept = {}
+        ms = time_dropin(n, args.steps, args.warmup, dev, host_reads=False, keep=kept)
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, kept)
+        out = {"metric": f"drop-in train_loop body, {n}-patch bags", "value": round(1e3 / ms, 2), "unit": "slides/s", "n_gpus": 1,
+               "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
+               "higher_is_better": True, "dtype": "f32", "data": "synthetic",
+               "config": {"workload": "model(data, sex) + nn.CrossEntropyLoss x2 + loss.backward() + torch.optim.Adam.step() + zero_grad() "
+                                      "(utils/core_utils_mtl_concat.py:206-234) on toad_amd.TOAD_fc_mtl_concat, resident bags"}}
+        if args.full:
+            out["ms_per_step_with_host_reads"] = round(time_dropin(n, args.steps, args.warmup, dev, host_reads=True), 4)
+        emit(out)
         return
 
     from toad_amd import TOAD_fc_mtl_concat, ops
@@ -661,19 +713,23 @@ def main():
     elapsed = time.perf_counter() - t0
     timing = ops.collect_timing()
     timed_calls = ops.timing_call_count()                  # library calls of the timed region (every ev_stride-th one carried events)
-    k_instr = min(args.steps, 10)
-    ops.enable_timing(True, level=2, prealloc=18 * k_instr * len(slides[0]))
-    for i in range(k_instr):
-        dp.step(slides[i % nbags], global_slides)
-    timing_gemm = ops.collect_timing()
     ops.enable_timing(False)
-    sync()
     last_loss = float(losses[-1][0].item()) * global_slides
+    if args.dump_outputs and rank == 0:                    # what the last timed step handed its caller, before any other leg steps on
+        write_outputs(args.dump_outputs, {"loss": torch.stack([lv.reshape(-1) for lv in losses]), "params": dp.flat, "grad": dp.flat_grad})
+    timing_gemm, k_instr = None, min(args.steps, 10)
+    if args.full:
+        ops.enable_timing(True, level=2, prealloc=18 * k_instr * len(slides[0]))
+        for i in range(k_instr):
+            dp.step(slides[i % nbags], global_slides)
+        timing_gemm = ops.collect_timing()
+        ops.enable_timing(False)
+    sync()
 
     # sustained rate: keep stepping for >= --sustain-seconds (same barrier + synchronize bracketing); long enough for the clock
     # governor to settle and for an external utilisation sampler (the driver's gpu_busy) to land inside it
     sus_steps, sus_t = 0, 0.0
-    if args.config in (0, 3) and args.sustain_seconds > 0:
+    if args.full and args.config in (0, 3) and args.sustain_seconds > 0:
         chunk = max(args.steps, 10)
         sync()
         t1 = time.perf_counter()
@@ -689,7 +745,7 @@ def main():
             if flag.item() > 0 or sus_steps >= 200000:
                 break
 
-    allreduce = time_allreduce(dp, dev, world, args.backend)
+    allreduce = time_allreduce(dp, dev, world, args.backend) if args.full else {}
     per_rank = None
     if world > 1:
         t = torch.tensor([elapsed, sus_t], device=dev, dtype=torch.float64)
@@ -705,9 +761,11 @@ def main():
         rows = [[float(v) for v in r.tolist()] for r in allr]
         per_rank = {"step_ms": [round(r[0], 4) for r in rows], "step_ms_min": round(min(r[0] for r in rows), 4),
                     "step_ms_max": round(max(r[0] for r in rows), 4), "pool_fwd_us": [round(r[1], 2) for r in rows],
-                    "allreduce_us": [round(r[2], 2) for r in rows], "patches_per_step": [int(r[3]) for r in rows],
+                    "patches_per_step": [int(r[3]) for r in rows],
                     "what": "step_ms = a rank's own wall time per step up to its local synchronize (before the closing barrier); ms_per_step of "
                             "the line is the max over ranks including the barrier"}
+        if allreduce:                                                   # (--full)
+            per_rank["allreduce_us"] = [round(r[2], 2) for r in rows]
         # what a first real multi-GPU run needs to attribute lost scaling without a re-run: the fastest rank's own step time over the job's
         # step time (max over ranks, closing barrier included). 1.0 = nobody waited; the gap is imbalance + collective + barrier skew.
         per_rank["scaling_efficiency_vs_per_rank_min"] = round(per_rank["step_ms_min"] / (elapsed / args.steps * 1e3), 4)
@@ -762,17 +820,19 @@ def main():
                                "achieved": round(pool_bw / 1e9, 1), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
                                "frac": round(pool_bw / HBM_PEAK, 4), "traffic": measured_pool_traffic(n) if slides_per_call == 1 else None,
                                "algorithmic_bytes": int(pool_bytes), "us_per_launch": round(pool_t * 1e6, 2)}
+        if timing_gemm:
             out["roofline_mfma"] = gemm_roofline(timing_gemm, k_instr * patches_per_rank_step)
             out["roofline_mfma"]["measured_in"] = f"{k_instr} instrumented steps right after the timed region (18 events per library call)"
             out["op_us_per_slide"] = {k: round(v[1] / (k_instr * len(slides[0])) * 1e3, 1) for k, v in timing_gemm.items()}
         if sus_steps:
             out["sustained"] = {"value": round(global_slides * sus_steps / sus_t, 3), "unit": "slides/s", "steps": sus_steps,
                                 "seconds": round(sus_t, 3), "ms_per_step": round(sus_t / sus_steps * 1e3, 3)}
-        out["allreduce"] = allreduce
+        if allreduce:
+            out["allreduce"] = allreduce
         if per_rank is not None:
             out["per_rank"] = per_rank
         out["last_loss"] = round(last_loss, 5)
-        if world == 1 and args.config == 0 and not prepared and args.bag_dtype == "fp32" and n >= 64 and ops.x16_ok(n) and not args.no_prepared_legs:
+        if world == 1 and args.config == 0 and not prepared and args.bag_dtype == "fp32" and n >= 64 and ops.x16_ok(n) and not args.no_prepared_legs and args.full:
             # (b) the ingest pipeline's loop: conversion of bag i+1 on a side stream while step i runs, everything inside the timed loop
             sec = time_prepared_pipelined(dp, slides, global_slides, args.steps, args.warmup, dev, sync)
             out["prepared_pipelined"] = {"value": round(global_slides / sec, 3), "unit": "slides/s", "ms_per_step": round(sec * 1e3, 3), "steps": args.steps,
@@ -790,7 +850,7 @@ def main():
             out["prepared_resident"] = {"value": round(global_slides * 1e3 / pre_ms, 3), "unit": "slides/s", "ms_per_step": round(pre_ms, 3), "steps": args.steps,
                                         "what": "the step alone on bags converted BEFORE the timed region (toad_mil_step_xp_f32); the conversion it leaves out costs",
                                         "prepare_us_per_bag": time_prepare(n, dev)}
-        if world == 1 and args.config == 0 and len(slides[0]) == 1 and not prepared and args.bag_dtype == "fp32" and not args.no_prepared_legs:
+        if world == 1 and args.config == 0 and len(slides[0]) == 1 and not prepared and args.bag_dtype == "fp32" and not args.no_prepared_legs and args.full:
             # (d) the data-parallel trainer's own mode on the same bags: FIVE slides per optimiser step, landed back to back, through ONE ragged multi-slide
             # call (toad_mil_multi_step_f32: 500k rows fill the 256 x 256 tile plan and the per-call helpers are paid once per five slides). `value` above
             # stays the reference's semantics - one optimiser step per slide (utils/core_utils_mtl_concat.py:200-234).
@@ -813,9 +873,9 @@ def main():
             out["batched"] = {"value": round(k5 * 1e3 / b_ms, 3), "unit": "slides/s", "slides_per_step": k5, "ms_per_step": round(b_ms, 3), "steps": k5_steps,
                               "what": "five 100k-patch slides per optimiser step through ONE ragged multi-slide call of 500k rows (SlideShardedDP's own batching; bags landed "
                                       "back to back as BagPrefetcher(arena_rows=...) lands them); not `value`, which keeps one optimiser step per slide"}
-        if world == 1 and args.config == 0 and len(slides[0]) == 1 and not prepared and args.bag_dtype == "fp32" and not args.no_ingest:
+        if world == 1 and args.config == 0 and len(slides[0]) == 1 and not prepared and args.bag_dtype == "fp32" and not args.no_ingest and args.full:
             out["ingest"] = time_ingest(dp, n, dev, args.ingest_slides)
-        if world == 1 and args.config == 3 and len(slides[0]) > 1 and not args.no_per_slide:
+        if world == 1 and args.config == 3 and len(slides[0]) > 1 and not args.no_per_slide and args.full:
             # the reference's own training semantics on this bag size: ONE optimiser step per slide (utils/core_utils_mtl_concat.py:200-234; its loaders
             # are batch_size = 1, utils/utils.py:51-55). `value` above is the data-parallel trainer's mode (a rank's slides share one ragged call).
             one = [[make_slide(300 + b, n, dev, prepared=False)] for b in range(2)]
@@ -837,7 +897,7 @@ def main():
                                 "op_us_per_slide": {k_: round(v[1] / 10 * 1e3, 1) for k_, v in tg.items()},
                                 "what": "one optimiser step per 10,000-patch slide (toad_mil_step_f32 + toad_adam_step_f32): the reference's train_loop "
                                         "semantics; no event packets inside the timed loop"}
-        if world == 1 and args.config in (0, 3) and not args.no_dropin:
+        if world == 1 and args.config in (0, 3) and not args.no_dropin and args.full:
             k = max(args.steps, 10)
             ms = time_dropin(n, k, 3, dev, host_reads=False)
             ms_h = time_dropin(n, k, 3, dev, host_reads=True)
@@ -845,7 +905,7 @@ def main():
                              "ms_per_step_with_host_reads": round(ms_h, 4), "vs_fused_step": round(ms / (ms_per_step / len(slides[0])), 3),
                              "what": "model(data, sex) + nn.CrossEntropyLoss x2 + loss.backward() + torch.optim.Adam(model.parameters()).step() + "
                                      "zero_grad() (utils/core_utils_mtl_concat.py:206-234); host reads = the loop's .item() / int() per slide"}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and not args.no_cpu_baseline and args.full:
             # the CPU port on ONE slide of this configuration's size (config 4: one 50,000-patch slide; the 64-slide step is 64 of them)
             out["cpu_baseline"] = cpu_baseline_step(n, budget_s=12.0 if n >= 50_000 else 15.0, min_reps=3 if n >= 50_000 else 10)      # ~10-15 s of host work: the lease is GPU time
             out["speedup_vs_cpu"] = round(value / out["cpu_baseline"]["value"], 1)

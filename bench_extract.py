@@ -30,7 +30,7 @@ if REPO not in sys.path:
 import torch
 import torch.distributed as dist
 
-from bench import C, MFMA_EQ_PEAK, SPLIT_TERMS, _physical_cores, claim_stdout, emit
+from bench import C, MFMA_EQ_PEAK, SPLIT_TERMS, _physical_cores, claim_stdout, emit, write_outputs
 
 FLOP_PER_TILE = 8_562_671_616          # sum of 2*M*K*N over the 43 convolutions at 256x256 (stem K = 147), SURVEY 8d config 5: 8.56 GFLOP
 
@@ -110,6 +110,8 @@ def main():
     ap.add_argument("--tiles", type=int, default=2048, help="tiles (= patches) per slide")
     ap.add_argument("--chunk", type=int, default=512, help="tiles per extractor call")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (bag, loss, params, grad) as DIR/<name>.npy (bench.py's header)")
     args = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0")); local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     from toad_amd import launch
@@ -163,6 +165,8 @@ def main():
         losses = step(True)
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, {"bag": bag, "loss": torch.stack([lv.reshape(-1) for lv in losses]), "params": dp.flat, "grad": dp.flat_grad})
     ext_ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)

@@ -19,7 +19,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_config4_through_the_torchrun_path_with_rccl(cuda):
     from toad_amd import launch
     cmd = launch.self_launch_cmd(os.path.join(REPO, "bench.py"), ["--config", "4", "--gpus", "1", "--steps", "2", "--warmup", "1",
-                                                                   "--no-cpu-baseline", "--backend", "nccl"], 1)
+                                                                   "--full", "--no-cpu-baseline", "--backend", "nccl"], 1)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=560)
@@ -47,7 +47,7 @@ def test_world_two_plumbing_on_one_gpu_over_gloo(cuda, extra, scaling, slides):
     JSON line from rank 0. RCCL refuses two ranks on one GPU, so the collective runs over gloo here (`--single-device --backend gloo`: a plumbing
     switch, never a measurement); the RCCL call itself is covered at world 1 above."""
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--single-device", "--backend", "gloo", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-dropin", "--sustain-seconds", "0"] + extra
+           "--full", "--no-cpu-baseline", "--no-dropin", "--sustain-seconds", "0"] + extra
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=560)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -74,7 +74,7 @@ def test_world_eight_plumbing_on_one_gpu_over_gloo(cuda, extra, scaling, slides)
     GPU), never a measurement: the value is asserted to be self-consistent, not fast. `--ragged` deals 64 slides of log-normal length with
     dp.shard_by_length: the patch counts per rank must balance to a few percent and cover all 3.2 M patches exactly once."""
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--single-device", "--backend", "gloo", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-dropin", "--sustain-seconds", "0"] + extra
+           "--full", "--no-cpu-baseline", "--no-dropin", "--sustain-seconds", "0"] + extra
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=860)
     assert r.returncode == 0, r.stderr[-3000:]

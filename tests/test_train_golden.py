@@ -59,7 +59,18 @@ def check_run(g, final, probs, site_probs, res, tol_p, tol_o):
         assert abs(res["cls_auc"] - sc[1]) <= 0.02 and abs(res["site_auc"] - sc[3]) <= 0.02   # rank statistics of 30 slides
 
 
-def test_oracle_replays_reference_training_run_cpu(tg):
+CAPTURE_THREADS = 16         # torch CPU threads of the captured run: fp32 GEMM sums split by thread count, so the replay uses the same count
+
+
+@pytest.fixture
+def capture_threads():
+    before = torch.get_num_threads()
+    torch.set_num_threads(CAPTURE_THREADS)
+    yield
+    torch.set_num_threads(before)
+
+
+def test_oracle_replays_reference_training_run_cpu(tg, capture_threads):
     g, c, slides, epochs, lr, reg, seed0 = tg
     plist = [torch.nn.Parameter(v.clone()) for v in (orc.closed_form_params(c)[k] for k in orc.PARAM_KEYS)]
     opt = torch.optim.SGD(plist, lr=lr, momentum=0.9, weight_decay=reg)                      # utils/utils.py:66-67

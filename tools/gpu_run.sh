@@ -25,7 +25,7 @@ for what in "$@"; do
       timeout ${arg:-1800} python -m pytest tests -q -m gpu > $OUT/pytest_all.log 2>&1
       echo "rc=$?" >> $OUT/pytest_all.log; grep -E "^(FAILED|ERROR)|passed|failed" $OUT/pytest_all.log | tail -30 ;;
     bench)
-      timeout 600 python bench.py ${arg:---steps 20 --warmup 5 --no-cpu-baseline --sustain-seconds 3} > $OUT/bench.json 2> $OUT/bench.err
+      timeout 600 python bench.py ${arg:---full --steps 20 --warmup 5 --no-cpu-baseline --sustain-seconds 3} > $OUT/bench.json 2> $OUT/bench.err
       tail -c 1500 $OUT/bench.json; tail -3 $OUT/bench.err ;;
     ab)
       for r in 1 2; do for b in prepared fp32; do TOAD_BAG=$b timeout 300 python tools/ab_step.py ${arg:-100000} 30; done; done 2>&1 | grep -v amdgpu.ids | tee $OUT/ab.txt ;;
@@ -34,8 +34,8 @@ for what in "$@"; do
       python tools/summarize_rocprof.py $(find $OUT/prof -name "*kernel_stats.csv" | head -1) "$TAG fused step N=${arg:-100000} (8 steps, raw fp32 bag)" > $OUT/kernel_stats.md 2>&1
       head -24 $OUT/kernel_stats.md ;;
     bstats)         # rocprofv3 --kernel-trace --stats of the bench command itself (the summary the bench line's kernel times are checked against)
-      (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bprof -o p -- python $ROOT/bench.py ${arg:---steps 20 --warmup 5 --no-cpu-baseline --sustain-seconds 0} > $OUT/bprof.json 2> $OUT/bprof.err)
-      python tools/summarize_rocprof.py $(find $OUT/bprof -name "*kernel_stats.csv" | head -1) "$TAG: rocprofv3 --kernel-trace --stats -- python bench.py ${arg:---steps 20 --warmup 5 --no-cpu-baseline --sustain-seconds 0}" > $OUT/bench_kernel_stats.md 2>&1
+      (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bprof -o p -- python $ROOT/bench.py ${arg:---full --steps 20 --warmup 5 --no-cpu-baseline --sustain-seconds 0} > $OUT/bprof.json 2> $OUT/bprof.err)
+      python tools/summarize_rocprof.py $(find $OUT/bprof -name "*kernel_stats.csv" | head -1) "$TAG: rocprofv3 --kernel-trace --stats -- python bench.py ${arg:---full --steps 20 --warmup 5 --no-cpu-baseline --sustain-seconds 0}" > $OUT/bench_kernel_stats.md 2>&1
       head -16 $OUT/bench_kernel_stats.md; tail -c 300 $OUT/bprof.json ;;
     pmc)
       (cd /tmp && timeout 400 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU GRBM_GUI_ACTIVE \
