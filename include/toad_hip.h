@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define TOAD_ABI_VERSION 13
+#define TOAD_ABI_VERSION 14
 
 enum { TOAD_OK = 0, TOAD_EINVAL = -1, TOAD_ESHAPE = -2, TOAD_EWORKSPACE = -3, TOAD_EALIGN = -4 };
 enum { TOAD_ACT_NONE = 0, TOAD_ACT_RELU = 1 };
@@ -418,6 +418,38 @@ int toad_mil_multi_step_f32(const float *const *params, float *const *grads, flo
                             float w_cls, float w_site, int C, int D, float drop_p, uint64_t seed,
                             float *loss_out, float *logits_out, float *site_logits_out, void *ws, size_t ws_bytes, void **events,
                             void *stream);
+
+/* ---- ragged multi-slide forward and backward as two calls (ABI 14) -------------------------------------------------------------
+ * toad_mil_multi_step_f32 with the loss taken by the caller, so that any loss of the batch's outputs trains through the same batched
+ * kernels: the pair is toad_mil_fwd_f32 / toad_mil_bwd_f32 for a batch of B slides concatenated in Xcat [sum N_b, 1024] (offsets, B, D,
+ * limits: as toad_mil_multi_step_f32; sum N_b < 2^20). Same kernels, operands and order as the fused step: for the same (drop_p, seed) the
+ * dropout masks and every activation are bitwise the fused step's (trunk masks hash the element index of the CONCATENATION; slide b's pooling
+ * masks use seeds + 2 b 0x9E3779B97F4A7C15), and the gradients differ from it only through the caller's dlogits / dsite. Agrees with B calls of
+ * toad_mil_fwd_f32 to fp32 round-off (operand scales are taken per 256-row block of the concatenation), not bitwise.
+ *
+ * Memory. `arena` (toad_mil_multi_arena_bytes) receives the saved activations, the per-slide pooling records, a device copy of the offsets and
+ * the DENSE per-slide outputs; toad_mil_multi_arena_layout() returns their byte offsets (relative to `arena` rounded up to
+ * toad_mil_buffer_align(sum N_b)), in this order (TOAD_MIL_MULTI_ARENA_SLOTS entries):
+ *   0 H1 [sum N_b,512]  1 H [sum N_b,512]  2 P [sum N_b,2D]  3 A_raw [sum N_b,2]  4 Mcat [B,2,513]
+ *   5 logits [B,C]  6 Y_prob [B,C]  7 Y_hat [B] (int64)  8 site_logits [B,2]  9 site_prob [B,2]  10 site_hat [B] (int64)
+ * The backward only reads the arena, so it may run more than once for one forward. `scratch` (toad_mil_multi_scratch_bytes) is temporary. */
+#define TOAD_MIL_MULTI_ARENA_SLOTS 11
+size_t toad_mil_multi_arena_bytes(int64_t Ntot, int B, int C, int D);
+int toad_mil_multi_arena_layout(int64_t Ntot, int B, int C, int D, int64_t *offsets /* [TOAD_MIL_MULTI_ARENA_SLOTS] */);
+size_t toad_mil_multi_scratch_bytes(int64_t Ntot, int B, int C, int D);
+
+/* Forward: models/model_toad.py:90-116 for every slide of the batch. offsets : HOST array [B+1]; sex : DEVICE array [B]. */
+int toad_mil_multi_fwd_f32(const float *const *params, const float *Xcat, const int64_t *offsets, int B, const float *sex, int C, int D,
+                           float drop_p, uint64_t seed, void *arena, size_t arena_bytes, void *scratch, size_t scratch_bytes, void *stream);
+
+/* Backward of toad_mil_multi_fwd_f32 for the same (params, Xcat, offsets, arena, drop_p, seed): the caller's loss and loss.backward()
+ * (utils/core_utils_mtl_concat.py:213-231) given dlogits [B,C] and dsite [B,2] (dense, d loss / d outputs) and optionally dA_ext [sum N_b,2]
+ * (gradient arriving through the raw scores, by row of the concatenation) and dMcat_ext [B,2,513] (through the features). grads = beta*grads +
+ * the gradient summed over the batch, the 12 slots of toad_mil_multi_step_f32. No dX, no dsex. */
+int toad_mil_multi_bwd_f32(const float *const *params, float *const *grads, float beta, const float *Xcat, const int64_t *offsets, int B,
+                           int C, int D, float drop_p, uint64_t seed, const void *arena, size_t arena_bytes,
+                           const float *dlogits, const float *dsite, const float *dA_ext, const float *dMcat_ext,
+                           void *scratch, size_t scratch_bytes, void *stream);
 
 #ifdef __cplusplus
 }

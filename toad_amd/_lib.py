@@ -11,7 +11,7 @@ from ctypes import c_char_p, c_float, c_int, c_int64, c_size_t, c_uint64, c_void
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtoad_hip.so")      # the one library the product loads (A/B builds: tools/ab/select_lib.py rebinds this in the TOOL's process)
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 P, I64, I, F, SZ, U64 = c_void_p, c_int64, c_int, c_float, c_size_t, c_uint64
 
@@ -73,6 +73,11 @@ SIGNATURES = {
     "toad_mil_multi_ws_bytes": (SZ, [I64, I, I, I]),
     "toad_mil_multi_step_f32": (I, [P, P, F, P, P, I, P, P, P, F, F, I, I, F, U64, P, P, P, P, SZ, P, P]),
     "toad_mil_step_xp_f32": (I, [P, P, F, P, P, P, P, P, F, F, I64, I, I, F, U64, P, P, P, P, SZ, P, P]),
+    "toad_mil_multi_arena_bytes": (SZ, [I64, I, I, I]),
+    "toad_mil_multi_arena_layout": (I, [I64, I, I, I, P]),
+    "toad_mil_multi_scratch_bytes": (SZ, [I64, I, I, I]),
+    "toad_mil_multi_fwd_f32": (I, [P, P, P, I, P, I, I, F, U64, P, SZ, P, SZ, P]),
+    "toad_mil_multi_bwd_f32": (I, [P, P, F, P, P, I, I, I, F, U64, P, SZ, P, P, P, P, P, SZ, P]),
 }
 
 _lib = None

@@ -144,7 +144,8 @@ int launch_pool_fwd_batch(const float *Pa, const float *Pb, int64_t ldp, const f
 int launch_pool_bwd_batch(const float *Pa, const float *Pb, int64_t ldp, const float *H, const float *Wc, const float *A_raw, const float *stats,
                           int s_stride, const float *M, const float *dM, int m_stride, float *dPa, float *dPb, int64_t ldd, float *dH, float *dWc,
                           float *dbc, float beta, void *ws, const int64_t *seg_dev, int B, int64_t max_n, int L, int D, int T, float drop_p,
-                          uint64_t seed_a, uint64_t seed_b, hipStream_t st, float *dp_amax = nullptr, float *row_bound = nullptr, int64_t n_rows = 0);
+                          uint64_t seed_a, uint64_t seed_b, hipStream_t st, float *dp_amax = nullptr, float *row_bound = nullptr, int64_t n_rows = 0,
+                          const float *dA_ext = nullptr);            // dA_ext: [sum N_b, T] gradient of the raw scores, by row of the concatenation
 // batched heads + weighted CE + heads backward of the ragged multi-slide step (heads.hip): one workgroup per slide, then the head-weight gradients
 struct HeadsBatch {          // per-slide records, all with the same byte stride `rec` (slide b of array p: (char *)p + b * rec)
     const float *M; float *Mcat, *logits, *yprob; int64_t *yhat; float *slog, *sprob; int64_t *shat; float *dM, *dl, *ds; size_t rec;
@@ -152,6 +153,15 @@ struct HeadsBatch {          // per-slide records, all with the same byte stride
 int launch_heads_batch(const HeadsBatch &hb, const float *sex, const float *Wcls, const float *bcls, const float *Wsite, const float *bsite,
                        const int64_t *label, const int64_t *site, float w_cls, float w_site, float *loss_out, float *dWcls, float *dbcls,
                        float *dWsite, float *dbsite, float beta, int B, int L, int C, hipStream_t st);
+// the same heads without the loss, for the split multi-slide forward / backward (heads.hip): per-slide M / dM records of stride m_stride floats,
+// dense outputs [B][2][L+1] Mcat, [B][C] logits / Y_prob, [B][2] site logits / probabilities, [B] hats; the backward takes dense dlogits [B][C],
+// dsite [B][2], dMcat_ext [B][2][L+1] (or NULL), writes dM and dl_rec / ds_rec (B records of 2 (L+1) floats) and sums the head-weight gradients
+int launch_heads_fwd_batch(const float *M, int m_stride, const float *sex, const float *Wcls, const float *bcls, const float *Wsite, const float *bsite,
+                           float *Mcat, float *logits, float *yprob, int64_t *yhat, float *slog, float *sprob, int64_t *shat, int B, int L, int C,
+                           hipStream_t st);
+int launch_heads_bwd_batch(const float *Mcat, const float *dlogits, const float *dsite, const float *dMcat_ext, const float *Wcls, const float *Wsite,
+                           float *dM, int m_stride, float *dl_rec, float *ds_rec, float *dWcls, float *dbcls, float *dWsite, float *dbsite, float beta,
+                           int B, int L, int C, hipStream_t st);
 struct WgradDeferred;
 int launch_wgrad(const float *dY, const float *dy_amax, const float *X, const float *x_amax, float *dW, float *db, int64_t M,
                  int64_t N, int64_t K, float beta, void *ws, hipStream_t st, const char *what, int x_mode = TOAD_X_F32,

@@ -758,13 +758,17 @@ int toad::launch_pool_fwd_batch(const float *Pa, const float *Pb, int64_t ldp, c
 int toad::launch_pool_bwd_batch(const float *Pa, const float *Pb, int64_t ldp, const float *H, const float *Wc, const float *A_raw, const float *stats,
                                 int s_stride, const float *M, const float *dM, int m_stride, float *dPa, float *dPb, int64_t ldd, float *dH, float *dWc,
                                 float *dbc, float beta, void *ws, const int64_t *seg_dev, int B, int64_t max_n, int L, int D, int T, float drop_p,
-                                uint64_t seed_a, uint64_t seed_b, hipStream_t st, float *dp_amax, float *row_bound, int64_t n_rows) {
+                                uint64_t seed_a, uint64_t seed_b, hipStream_t st, float *dp_amax, float *row_bound, int64_t n_rows,
+                                const float *dA_ext) {
     const char *what = "toad_gated_pool_bwd_f32 (batched)";
     if (!shape_ok(L, D, T) || B < 1 || B > 4096) { set_error("%s: unsupported shape", what); return TOAD_ESHAPE; }
     const DropArgs da = make_drop(drop_p, seed_a), db = make_drop(drop_p, seed_b);
     const int gx = batch_gx(max_n, B);
-    // dp_amax (optional) + row_bound (n_rows floats of scratch): the abs-max ARRAY of dP over the concatenation, from a per-row bound table
-    launch_bwd(L, D, T, gx, st, Pa, Pb, ldp, H, Wc, A_raw, stats, M, dM, nullptr, dPa, dPb, ldd, dH, (float *)ws, dp_amax ? row_bound : nullptr, 0, da, db, seg_dev, B,
+    // dp_amax (optional) + row_bound (n_rows floats of scratch): the abs-max ARRAY of dP over the concatenation, from a per-row bound table.
+    // dA_ext (optional, [n_rows, T]) is indexed by row of the CONCATENATION, like A_raw: the kernel moves both by the slide's first row seg[y]
+    // and reads row r of the slide at (seg[y] + r) * T + t. It enters dS (the scores' gradient), hence dP, dWc, dbc and the per-row |dP| bound;
+    // the pooled addend dH_pool of the attention dgrad (step.hip pool_rowrec_kernel records) is softmax(A) dM and depends on dM only.
+    launch_bwd(L, D, T, gx, st, Pa, Pb, ldp, H, Wc, A_raw, stats, M, dM, dA_ext, dPa, dPb, ldd, dH, (float *)ws, dp_amax ? row_bound : nullptr, 0, da, db, seg_dev, B,
                m_stride, s_stride);
     if (int rc = check_launch(what)) return rc;
     const int n = T * D + T, nred = (n + 3) / 4;

@@ -42,10 +42,17 @@ __global__ __launch_bounds__(1024) void heads_fwd_kernel(const float *__restrict
                                                          const float *__restrict__ Wsite, const float *__restrict__ bsite,
                                                          float *Mcat, float *logits, float *Y_prob, int64_t *Y_hat,
                                                          float *site_logits, float *site_prob, int64_t *site_hat, int L,
-                                                         int C) {
+                                                         int C, int m_stride) {
     extern __shared__ float s_m[];   // [2][L+1]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int LP = L + 1;
+    // m_stride != 0: batched launch (toad_mil_multi_fwd_f32): blockIdx.x = slide b, whose pooled features are the record M + b * m_stride
+    // floats; sex is read at [b] and every output is written DENSE at row b ([B][2][L+1], [B][C], [B][2], [B]). One slide: m_stride = 0.
+    if (m_stride) {
+        const int64_t b = blockIdx.x;
+        M += b * m_stride; sex += b;
+        Mcat += b * 2 * LP; logits += b * C; Y_prob += b * C; Y_hat += b; site_logits += 2 * b; site_prob += 2 * b; site_hat += b;
+    }
     const float sx = sex[0];
     for (int e = tid; e < 2 * LP; e += 1024) {
         const int t = e / LP, k = e % LP;
@@ -104,6 +111,29 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float *__restrict_
         if (dMcat_ext) d += dMcat_ext[L] + dMcat_ext[LP + L];
         dsex[0] = d;
     }
+}
+
+// Batched heads backward from the caller's gradients (toad_mil_multi_bwd_f32): grid.y = slide b, grid.x covers the L+1 columns. Per slide
+// dM[t, k] into the record dM + b * m_stride - the dM row of heads_bwd_kernel, same arithmetic and order - and dlogits_b / dsite_b copied into the
+// per-slide records (byte stride `rec`) that heads_wgrad_batch_kernel sums the head-weight gradients from. dlogits [B][C], dsite [B][2],
+// dMcat_ext [B][2][L+1] (or NULL) are dense.
+__global__ __launch_bounds__(256) void heads_bwd_batch_kernel(const float *__restrict__ dlogits, const float *__restrict__ dsite,
+                                                               const float *__restrict__ Wcls, const float *__restrict__ Wsite,
+                                                               const float *__restrict__ dMcat_ext, float *dM, int m_stride, float *dl_rec,
+                                                               float *ds_rec, int64_t rec, int L, int C) {
+    const int LP = L + 1;
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    const int64_t b = blockIdx.y;
+    dlogits += b * C; dsite += 2 * b; dM += b * m_stride;
+    if (dMcat_ext) dMcat_ext += b * 2 * LP;
+    if (k < C) reinterpret_cast<float *>(reinterpret_cast<char *>(dl_rec) + b * rec)[k] = dlogits[k];
+    if (k < 2) reinterpret_cast<float *>(reinterpret_cast<char *>(ds_rec) + b * rec)[k] = dsite[k];
+    if (k >= L) return;
+    float d0 = 0.f;
+    for (int c = 0; c < C; ++c) d0 = fmaf(dlogits[c], Wcls[(int64_t)c * LP + k], d0);
+    const float d1 = fmaf(dsite[1], Wsite[LP + k], dsite[0] * Wsite[k]);
+    dM[k] = d0 + (dMcat_ext ? dMcat_ext[k] : 0.f);
+    dM[L + k] = d1 + (dMcat_ext ? dMcat_ext[LP + k] : 0.f);
 }
 
 // one wave: loss and d loss / d logits for w_cls*CE(logits,label) + w_site*CE(site_logits,site)
@@ -355,7 +385,7 @@ extern "C" int toad_heads_fwd_f32(const float *M, const float *sex, const float 
     if (!M || !sex || !Wcls || !bcls || !Wsite || !bsite || !Mcat || !logits || !Y_prob || !Y_hat || !site_logits || !site_prob || !site_hat) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
     if (L <= 0 || L > 8192 || C <= 0 || C > 1024) { set_error("%s: unsupported L=%d C=%d", what, L, C); return TOAD_ESHAPE; }
     hipLaunchKernelGGL(heads_fwd_kernel, dim3(1), dim3(1024), 2 * (L + 1) * sizeof(float), (hipStream_t)stream, M, sex, Wcls,
-                       bcls, Wsite, bsite, Mcat, logits, Y_prob, Y_hat, site_logits, site_prob, site_hat, L, C);
+                       bcls, Wsite, bsite, Mcat, logits, Y_prob, Y_hat, site_logits, site_prob, site_hat, L, C, 0);
     return check_launch(what);
 }
 
@@ -417,6 +447,30 @@ int toad::launch_heads_batch(const HeadsBatch &hb, const float *sex, const float
     if (int rc = check_launch(what)) return rc;
     hipLaunchKernelGGL(heads_wgrad_batch_kernel, dim3(((C + 2) * (L + 1) + 255) / 256), dim3(256), 0, st, (const float *)hb.dl, (const float *)hb.ds,
                        (const float *)hb.Mcat, (int64_t)hb.rec, dWcls, dbcls, dWsite, dbsite, beta, B, L, C);
+    return check_launch(what);
+}
+
+// ---- batched heads without the loss (toad_mil_multi_fwd_f32 / toad_mil_multi_bwd_f32): one workgroup per slide ----
+int toad::launch_heads_fwd_batch(const float *M, int m_stride, const float *sex, const float *Wcls, const float *bcls, const float *Wsite,
+                                 const float *bsite, float *Mcat, float *logits, float *yprob, int64_t *yhat, float *slog, float *sprob,
+                                 int64_t *shat, int B, int L, int C, hipStream_t st) {
+    const char *what = "toad_heads_fwd_f32 (batched)";
+    if (L <= 0 || L > 8192 || C <= 0 || C > 1024 || B < 1 || m_stride < 2 * L) { set_error("%s: unsupported L=%d C=%d B=%d", what, L, C, B); return TOAD_ESHAPE; }
+    hipLaunchKernelGGL(heads_fwd_kernel, dim3(B), dim3(1024), 2 * (L + 1) * sizeof(float), st, M, sex, Wcls, bcls, Wsite, bsite, Mcat, logits, yprob,
+                       yhat, slog, sprob, shat, L, C, m_stride);
+    return check_launch(what);
+}
+int toad::launch_heads_bwd_batch(const float *Mcat, const float *dlogits, const float *dsite, const float *dMcat_ext, const float *Wcls,
+                                 const float *Wsite, float *dM, int m_stride, float *dl_rec, float *ds_rec, float *dWcls, float *dbcls,
+                                 float *dWsite, float *dbsite, float beta, int B, int L, int C, hipStream_t st) {
+    const char *what = "toad_heads_bwd_f32 (batched)";
+    if (L <= 0 || L > 8192 || C <= 0 || C > 1024 || C > L || B < 1 || m_stride < 2 * L) { set_error("%s: unsupported L=%d C=%d B=%d", what, L, C, B); return TOAD_ESHAPE; }
+    const int64_t rec = (int64_t)2 * (L + 1) * sizeof(float);           // the stride of the dense Mcat rows: dl / ds records share it
+    hipLaunchKernelGGL(heads_bwd_batch_kernel, dim3((L + 1 + 255) / 256, B), dim3(256), 0, st, dlogits, dsite, Wcls, Wsite, dMcat_ext, dM, m_stride,
+                       dl_rec, ds_rec, rec, L, C);
+    if (int rc = check_launch(what)) return rc;
+    hipLaunchKernelGGL(heads_wgrad_batch_kernel, dim3(((C + 2) * (L + 1) + 255) / 256), dim3(256), 0, st, (const float *)dl_rec, (const float *)ds_rec,
+                       Mcat, rec, dWcls, dbcls, dWsite, dbsite, beta, B, L, C);
     return check_launch(what);
 }
 

@@ -560,62 +560,42 @@ static MultiSmall multi_small_layout(int B, char *base) {
     m.total = up(c.off, 256);
     return m;
 }
-}  // namespace toad
 
-extern "C" size_t toad_mil_multi_ws_bytes(int64_t Ntot, int B, int C, int D) {
-    if (B <= 0 || B > 4096 || C > 512) return 0;
-    const size_t a = toad_mil_step_ws_bytes(Ntot, C, D);
-    return a ? a + multi_small_layout(B, nullptr).total + 4096 : 0;
-}
-
-extern "C" int toad_mil_multi_step_f32(const float *const *params, float *const *grads, float beta, const float *Xcat,
-                                        const int64_t *offsets, int B, const float *sex, const int64_t *label, const int64_t *site,
-                                        float w_cls, float w_site, int C, int D, float drop_p, uint64_t seed,
-                                        float *loss_out, float *logits_out, float *site_logits_out, void *ws, size_t ws_bytes, void **events,
-                                        void *stream) {
-    const char *what = "toad_mil_multi_step_f32";
-    if (!params || !grads || !Xcat || !offsets || !sex || !label || !site || !loss_out || !ws) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+// Argument checks shared by the three multi-slide entry points (the row offsets are a HOST array): B, offsets, shape, drop_p. -> N, longest slide.
+static int multi_batch_ok(const int64_t *offsets, int B, int C, int D, float drop_p, const char *what, int64_t &N, int64_t &max_n) {
     if (B <= 0 || B > 4096) { set_error("%s: B must be in [1, 4096]", what); return TOAD_EINVAL; }
     if (offsets[0] != 0) { set_error("%s: offsets[0] must be 0", what); return TOAD_EINVAL; }
     for (int b = 0; b < B; ++b) if (offsets[b + 1] <= offsets[b]) { set_error("%s: slide %d is empty or offsets decrease", what, b); return TOAD_EINVAL; }
-    const int64_t N = offsets[B];
+    N = offsets[B];
     const MilShape s{N, C, D};
     if (!shape_ok(s) || !h2_nt_ok(N, kL, kL0, kL0, kL)) { set_error("%s: unsupported shape sum N=%lld C=%d D=%d", what, (long long)N, C, D); return TOAD_ESHAPE; }
     if (!(drop_p >= 0.f && drop_p < 1.f)) { set_error("%s: drop_p must be in [0,1)", what); return TOAD_EINVAL; }
-    if (!aligned16(Xcat)) { set_error("%s: Xcat must be 16-byte aligned", what); return TOAD_EALIGN; }
-    if (ws_bytes < toad_mil_multi_ws_bytes(N, B, C, D)) { set_error("%s: workspace too small", what); return TOAD_EWORKSPACE; }
-    Params p;
-    if (!load_params(params, p, what)) return TOAD_EINVAL;
-    for (int i = 0; i < 12; ++i) if (!grads[i]) { set_error("%s: null gradient slot %d", what, i); return TOAD_EINVAL; }
-    char *ab = align_base(ws, N);
-    int64_t o[TOAD_MIL_ARENA_SLOTS];
-    char *sb = align_base(ab + arena_layout(s, o), N);
-    const Fwd f = arena_view(s, ab);
-    const Scratch w = scratch_layout(s, sb);
-    char *mb = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(sb + w.total) + 255) & ~(uintptr_t)255);
-    const MultiSmall ms = multi_small_layout(B, mb);
-    hipStream_t st = (hipStream_t)stream;
-    const StreamEvents ev{events, st};
-    const int D2 = 2 * D;
+    max_n = 0;
+    for (int b = 0; b < B; ++b) if (offsets[b + 1] - offsets[b] > max_n) max_n = offsets[b + 1] - offsets[b];
+    return TOAD_OK;
+}
+
+// ---- the forward and backward blocks of the multi-slide calls, shared by the fused step (toad_mil_multi_step_f32) and the split pair
+// (toad_mil_multi_fwd_f32 / toad_mil_multi_bwd_f32); `ms` supplies the per-slide records (stats, M, dM: kSlideRec bytes each), the device
+// copy of the offsets and the pooling partials.
+// Forward: one launch splits the weight operands (with the two dgrad operands and the backward's abs-max arrays when a backward follows
+// with the same weights inside the same call, as in forward_body), the three GEMMs over all rows, the batched pool forward + merge.
+template <typename Ev>
+static int multi_forward_body(const MilShape &s, const Params &p, const float *Xcat, const Fwd &f, const Scratch &w, const MultiSmall &ms, int B,
+                              int64_t max_n, float drop_p, uint64_t seed, bool with_backward_operands, hipStream_t st, Ev ev, const char *what) {
+    const int64_t N = s.N;
+    const int D = s.D, D2 = 2 * D;
     const DropSeeds ds = drop_seeds(drop_p, seed);
     const EpiScalars relu1{1, 1.f, make_drop(drop_p, ds.s1)}, relu2{1, 1.f, make_drop(drop_p, ds.s2)}, lin{0, 1.f, make_drop(0.f, 0)};
-    const EpiScalars msk{0, ds.mscale, make_drop(0.f, 0)};
     const H2Pool nopool{nullptr, nullptr, nullptr, 0};
-    // the slides' row offsets go to the device FIRST: the source is the caller's pageable array, so the runtime stages the copy before it
-    // returns and orders it behind whatever the stream already holds - in front of the GEMMs that wait is nothing, behind them it was the
-    // three forward GEMMs on every call (the host lost its launch run-ahead)
-    if (hipMemcpyAsync(ms.seg, offsets, (size_t)(B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st) != hipSuccess) {
-        set_error("%s: copying the slide offsets to the device failed: %s", what, hipGetErrorString(hipGetLastError()));
-        return TOAD_EINVAL;
-    }
-    // ---- forward: one launch splits the five weight operands and zeroes both groups of abs-max arrays; three GEMMs over all rows
     {
         const H2Operand ops5[5] = {{p.w1, kL0, 1, kL, kL0, w.planes[W_1], w.binv[W_1]}, {p.w2, kL, 1, kL, kL, w.planes[W_2], w.binv[W_2]},
                                    {p.wab, kL, 1, D2, kL, w.planes[W_AB], w.binv[W_AB]}, {p.wab, 1, kL, kL, D2, w.planes[W_ABT], w.binv[W_ABT]},
                                    {p.w2, 1, kL, kL, kL, w.planes[W_2T], w.binv[W_2T]}};
         const int nz = (int)(((char *)f.amax_h - (char *)f.amax_x) / sizeof(float) + toad_amax_floats(N));
         const int nzb = (int)(((char *)w.amax_dZ1 - (char *)w.amax_dP) / sizeof(float) + toad_amax_floats(N));
-        TOAD_TRY(launch_split_h2(ops5, 5, f.amax_x, nz, st, what, w.amax_dP, nzb));
+        if (with_backward_operands) TOAD_TRY(launch_split_h2(ops5, 5, f.amax_x, nz, st, what, w.amax_dP, nzb));
+        else TOAD_TRY(launch_split_h2(ops5, 3, f.amax_x, nz, st, what));
     }
     // the concatenated bags are measured inside the first GEMM (no abs-max pass of its own), which fills f.amax_x for the weight gradient below
     const bool self_measure = nt_run_ok(N, kL, kL0);
@@ -624,31 +604,33 @@ extern "C" int toad_mil_multi_step_f32(const float *const *params, float *const 
                                  w.slabs, f.amax_h1, f.bits_h1, st, what, TOAD_X_F32, 1, 1, self_measure ? f.amax_x : nullptr, self_measure ? w.slab_ke : nullptr)); ev(3);
     ev(4); TOAD_TRY(launch_nt_h2(f.H1, kL, f.amax_h1, w.planes[W_2], w.binv[W_2], f.H, kL, N, kL, kL, p.b2, relu2, nullptr, nullptr, nullptr, nopool, w.slabs, f.amax_h, f.bits_h, st, what)); ev(5);
     ev(6); TOAD_TRY(launch_nt_h2(f.H, kL, f.amax_h, w.planes[W_AB], w.binv[W_AB], f.P, D2, N, D2, kL, p.bab, lin, nullptr, nullptr, nullptr, nopool, w.slabs, nullptr, nullptr, st, what)); ev(7);
-    // ---- all slides at once (blockIdx.y = slide): fused pool forward on each row range + merge; heads + weighted CE + heads backward with
-    // one workgroup per slide, then the head-weight gradients summed over the batch; pooling backward (dP rows, the pooling gradient
-    // dH_pool rows into the dZ2 buffer, dWc / dbc summed over the batch). Five launches + two small copies, whatever B is - a 64-slide
-    // batch of 256-patch bags was 320 launches of mostly idle kernels when this ran slide by slide.
-    int64_t max_n = 0;
-    for (int b = 0; b < B; ++b) if (offsets[b + 1] - offsets[b] > max_n) max_n = offsets[b + 1] - offsets[b];
+    // ---- all slides at once (blockIdx.y = slide): fused pool forward on each row range + merge. Together with the heads and the pooling backward
+    // below, a fixed number of launches whatever B is - a 64-slide batch of 256-patch bags was 320 launches of mostly idle kernels when this ran
+    // slide by slide.
     const int rec_f = (int)(kSlideRec / sizeof(float));
     ev(0); TOAD_TRY(launch_pool_fwd_batch(f.P, f.P + D, D2, f.H, p.wc, p.bc, f.A_raw, ms.M, rec_f, ms.stats, rec_f, ms.pool_ws, ms.seg, B, max_n, kL, D, kT, drop_p,
                                    ds.sa, ds.sb, st)); ev(1);
-    const HeadsBatch hb{ms.M, ms.Mcat, ms.logits, ms.yprob, ms.yhat, ms.slog, ms.sprob, ms.shat, ms.dM, ms.dl, ms.dsv, kSlideRec};
-    TOAD_TRY(launch_heads_batch(hb, sex, p.wcls, p.bcls, p.wsite, p.bsite, label, site, w_cls, w_site, loss_out, grads[8], grads[9], grads[10], grads[11], beta,
-                                B, kL, C, st));
-    if (logits_out && hipMemcpy2DAsync(logits_out, (size_t)C * sizeof(float), ms.logits, kSlideRec, (size_t)C * sizeof(float), B, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        set_error("%s: copying the per-slide logits failed: %s", what, hipGetErrorString(hipGetLastError()));
-        return TOAD_EINVAL;
-    }
-    if (site_logits_out && hipMemcpy2DAsync(site_logits_out, 2 * sizeof(float), ms.slog, kSlideRec, 2 * sizeof(float), B, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        set_error("%s: copying the per-slide site logits failed: %s", what, hipGetErrorString(hipGetLastError()));
-        return TOAD_EINVAL;
-    }
+    return TOAD_OK;
+}
+
+// Backward from the slides' dM records (ms.dM) and, optionally, the gradient of the raw scores dA_ext [N, 2]: the batched pooling backward (dP rows,
+// dWc / dbc summed over the batch), then the three backward GEMMs and the three weight gradients over all rows. The two dgrad operands and the
+// backward's abs-max arrays must have been split / zeroed already (by multi_forward_body's launch in the fused step, by the split backward's own).
+template <typename Ev>
+static int multi_backward_body(const MilShape &s, const Params &p, float *const *grads, float beta, const float *Xcat, const Fwd &f, const Scratch &w,
+                               const MultiSmall &ms, int B, int64_t max_n, const float *dA_ext, float drop_p, uint64_t seed, hipStream_t st, Ev ev,
+                               const char *what) {
+    const int64_t N = s.N;
+    const int D = s.D, D2 = 2 * D;
+    const DropSeeds ds = drop_seeds(drop_p, seed);
+    const EpiScalars msk{0, ds.mscale, make_drop(0.f, 0)};
+    const H2Pool nopool{nullptr, nullptr, nullptr, 0};
+    const int rec_f = (int)(kSlideRec / sizeof(float));
     // (round 5: no dH_pool output any more - the attention dgrad below recomputes the pooling gradient per row from the records written here, like the
     // one-slide step does from A_raw and its statistics: 410 MB less HBM traffic per 100k rows. The records live in dZ1's buffer behind the row bounds.)
     float *rowrec = w.dZ1 + ((N + 3) & ~(int64_t)3);
     TOAD_TRY(launch_pool_bwd_batch(f.P, f.P + D, D2, f.H, p.wc, f.A_raw, ms.stats, rec_f, ms.M, ms.dM, rec_f, w.dP, w.dP + D, D2, nullptr, grads[6], grads[7], beta,
-                                   ms.pool_ws, ms.seg, B, max_n, kL, D, kT, drop_p, ds.sa, ds.sb, st, w.amax_dP, w.dZ1, N));
+                                   ms.pool_ws, ms.seg, B, max_n, kL, D, kT, drop_p, ds.sa, ds.sb, st, w.amax_dP, w.dZ1, N, dA_ext));
     {
         int64_t gx = (max_n + 255) / 256;
         if (gx > 64) gx = 64;
@@ -681,4 +663,190 @@ extern "C" int toad_mil_multi_step_f32(const float *const *params, float *const 
         TOAD_TRY(launch_wgrad_reduce(dw, 3, st, what)); ev(17);
     }
     return TOAD_OK;
+}
+}  // namespace toad
+
+extern "C" size_t toad_mil_multi_ws_bytes(int64_t Ntot, int B, int C, int D) {
+    if (B <= 0 || B > 4096 || C > 512) return 0;
+    const size_t a = toad_mil_step_ws_bytes(Ntot, C, D);
+    return a ? a + multi_small_layout(B, nullptr).total + 4096 : 0;
+}
+
+extern "C" int toad_mil_multi_step_f32(const float *const *params, float *const *grads, float beta, const float *Xcat,
+                                        const int64_t *offsets, int B, const float *sex, const int64_t *label, const int64_t *site,
+                                        float w_cls, float w_site, int C, int D, float drop_p, uint64_t seed,
+                                        float *loss_out, float *logits_out, float *site_logits_out, void *ws, size_t ws_bytes, void **events,
+                                        void *stream) {
+    const char *what = "toad_mil_multi_step_f32";
+    if (!params || !grads || !Xcat || !offsets || !sex || !label || !site || !loss_out || !ws) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    int64_t N = 0, max_n = 0;
+    TOAD_TRY(multi_batch_ok(offsets, B, C, D, drop_p, what, N, max_n));
+    const MilShape s{N, C, D};
+    if (!aligned16(Xcat)) { set_error("%s: Xcat must be 16-byte aligned", what); return TOAD_EALIGN; }
+    if (ws_bytes < toad_mil_multi_ws_bytes(N, B, C, D)) { set_error("%s: workspace too small", what); return TOAD_EWORKSPACE; }
+    Params p;
+    if (!load_params(params, p, what)) return TOAD_EINVAL;
+    for (int i = 0; i < 12; ++i) if (!grads[i]) { set_error("%s: null gradient slot %d", what, i); return TOAD_EINVAL; }
+    char *ab = align_base(ws, N);
+    int64_t o[TOAD_MIL_ARENA_SLOTS];
+    char *sb = align_base(ab + arena_layout(s, o), N);
+    const Fwd f = arena_view(s, ab);
+    const Scratch w = scratch_layout(s, sb);
+    char *mb = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(sb + w.total) + 255) & ~(uintptr_t)255);
+    const MultiSmall ms = multi_small_layout(B, mb);
+    hipStream_t st = (hipStream_t)stream;
+    const StreamEvents ev{events, st};
+    // the slides' row offsets go to the device FIRST: the source is the caller's pageable array, so the runtime stages the copy before it
+    // returns and orders it behind whatever the stream already holds - in front of the GEMMs that wait is nothing, behind them it was the
+    // three forward GEMMs on every call (the host lost its launch run-ahead)
+    if (hipMemcpyAsync(ms.seg, offsets, (size_t)(B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st) != hipSuccess) {
+        set_error("%s: copying the slide offsets to the device failed: %s", what, hipGetErrorString(hipGetLastError()));
+        return TOAD_EINVAL;
+    }
+    // ---- forward: one launch splits the five weight operands and zeroes both groups of abs-max arrays; three GEMMs over all rows; batched pool
+    TOAD_TRY(multi_forward_body(s, p, Xcat, f, w, ms, B, max_n, drop_p, seed, true, st, ev, what));
+    // heads + weighted CE + heads backward with one workgroup per slide, then the head-weight gradients summed over the batch
+    const HeadsBatch hb{ms.M, ms.Mcat, ms.logits, ms.yprob, ms.yhat, ms.slog, ms.sprob, ms.shat, ms.dM, ms.dl, ms.dsv, kSlideRec};
+    TOAD_TRY(launch_heads_batch(hb, sex, p.wcls, p.bcls, p.wsite, p.bsite, label, site, w_cls, w_site, loss_out, grads[8], grads[9], grads[10], grads[11], beta,
+                                B, kL, C, st));
+    if (logits_out && hipMemcpy2DAsync(logits_out, (size_t)C * sizeof(float), ms.logits, kSlideRec, (size_t)C * sizeof(float), B, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        set_error("%s: copying the per-slide logits failed: %s", what, hipGetErrorString(hipGetLastError()));
+        return TOAD_EINVAL;
+    }
+    if (site_logits_out && hipMemcpy2DAsync(site_logits_out, 2 * sizeof(float), ms.slog, kSlideRec, 2 * sizeof(float), B, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        set_error("%s: copying the per-slide site logits failed: %s", what, hipGetErrorString(hipGetLastError()));
+        return TOAD_EINVAL;
+    }
+    // ---- pooling backward, backward GEMMs and weight gradients over all rows (the dgrad operands were split by the forward's launch)
+    return multi_backward_body(s, p, grads, beta, Xcat, f, w, ms, B, max_n, nullptr, drop_p, seed, st, ev, what);
+}
+
+// ---- the ragged multi-slide forward and backward as two calls (ABI 14) -----------------------------------------------------------------------
+// toad_mil_multi_step_f32 with the loss left to the caller: toad_mil_multi_fwd_f32 runs its forward block (weight split, three GEMMs over all rows,
+// batched pool forward) and the heads of every slide, writing dense per-slide outputs into a caller-owned ARENA next to the activations the backward
+// reads; toad_mil_multi_bwd_f32 takes the caller's dlogits / dsite (and optionally dA, dMcat), runs the batched heads backward and then the fused
+// step's backward block. Same kernels, operands and order as the fused step, so for the same (drop_p, seed) the masks and every activation are
+// bitwise the fused step's; the gradients differ from it only through the caller's dlogits.
+namespace toad {
+enum { MA_H1 = 0, MA_H, MA_P, MA_ARAW, MA_MCAT, MA_LOGITS, MA_YPROB, MA_YHAT, MA_SLOG, MA_SPROB, MA_SHAT };
+struct MultiIO {
+    MultiSmall ms;                                   // stats / M / seg in the arena, dM / pool_ws in the scratch (the other records are not used)
+    float *Mcat, *logits, *yprob, *slog, *sprob; int64_t *yhat, *shat;
+    float *dl, *ds;                                  // dlogits / dsite records for heads_wgrad_batch_kernel (stride of a dense Mcat row)
+    size_t arena_total, scratch_total;
+};
+// Arena: the one-slide layout (H1, H, P, A_raw, abs-max arrays, ReLU images; its one-slide head slots stay unused), then the per-slide records
+// the backward reads, the device copy of the offsets and the dense outputs. Scratch: the one-slide scratch, then dM / dlogits / dsite records
+// and the pooling partials. Offsets are relative to the bases rounded up by align_base; `offsets` (optional) receives the MA_* slots.
+static MultiIO multi_io_layout(const MilShape &s, int B, char *ab, char *sb, int64_t *offsets = nullptr) {
+    MultiIO m{};
+    int64_t o[TOAD_MIL_ARENA_SLOTS];
+    Carver a;
+    a.off = arena_layout(s, o);
+    auto PA = [&](size_t off) { return ab ? ab + off : nullptr; };
+    const size_t n = (size_t)B * kSlideRec, rec = (size_t)2 * (kL + 1) * sizeof(float);
+    m.ms.stats = (float *)PA(a.take(n, 256)); m.ms.M = (float *)PA(a.take(n, 256));
+    m.ms.seg = (int64_t *)PA(a.take((size_t)(B + 1) * sizeof(int64_t), 256));
+    const size_t oMcat = a.take((size_t)B * rec, 256), oLog = a.take((size_t)B * s.C * 4, 256), oYp = a.take((size_t)B * s.C * 4, 256);
+    const size_t oYh = a.take((size_t)B * 8, 256), oSl = a.take((size_t)B * 8, 256), oSp = a.take((size_t)B * 8, 256), oSh = a.take((size_t)B * 8, 256);
+    m.Mcat = (float *)PA(oMcat); m.logits = (float *)PA(oLog); m.yprob = (float *)PA(oYp); m.yhat = (int64_t *)PA(oYh);
+    m.slog = (float *)PA(oSl); m.sprob = (float *)PA(oSp); m.shat = (int64_t *)PA(oSh);
+    m.arena_total = up(a.off, 256);
+    Carver c;
+    c.off = scratch_layout(s, nullptr).total;
+    auto PS = [&](size_t off) { return sb ? sb + off : nullptr; };
+    m.ms.dM = (float *)PS(c.take(n, 256));
+    m.dl = (float *)PS(c.take((size_t)B * rec, 256)); m.ds = (float *)PS(c.take((size_t)B * rec, 256));
+    m.ms.pool_ws = PS(c.take(pool_batch_ws_bytes(B, kL, 384, kT), 4096));
+    m.scratch_total = up(c.off, 256);
+    if (offsets) {
+        const int64_t v[TOAD_MIL_MULTI_ARENA_SLOTS] = {o[A_H1], o[A_H], o[A_P], o[A_ARAW], (int64_t)oMcat, (int64_t)oLog, (int64_t)oYp, (int64_t)oYh,
+                                                       (int64_t)oSl, (int64_t)oSp, (int64_t)oSh};
+        for (int i = 0; i < TOAD_MIL_MULTI_ARENA_SLOTS; ++i) offsets[i] = v[i];
+    }
+    return m;
+}
+static bool multi_sizes_ok(const MilShape &s, int B) { return B >= 1 && B <= 4096 && shape_ok(s); }
+}  // namespace toad
+
+extern "C" size_t toad_mil_multi_arena_bytes(int64_t Ntot, int B, int C, int D) {
+    const MilShape s{Ntot, C, D};
+    return multi_sizes_ok(s, B) ? multi_io_layout(s, B, nullptr, nullptr).arena_total + big_align(Ntot) : 0;
+}
+extern "C" size_t toad_mil_multi_scratch_bytes(int64_t Ntot, int B, int C, int D) {
+    const MilShape s{Ntot, C, D};
+    return multi_sizes_ok(s, B) ? multi_io_layout(s, B, nullptr, nullptr).scratch_total + big_align(Ntot) : 0;
+}
+extern "C" int toad_mil_multi_arena_layout(int64_t Ntot, int B, int C, int D, int64_t *offsets) {
+    const MilShape s{Ntot, C, D};
+    if (!multi_sizes_ok(s, B) || !offsets) { set_error("toad_mil_multi_arena_layout: bad shape"); return TOAD_ESHAPE; }
+    multi_io_layout(s, B, nullptr, nullptr, offsets);
+    return TOAD_OK;
+}
+
+// (the arena / scratch bases are rounded up to toad_mil_buffer_align(sum N_b) inside the allocations, as in toad_mil_fwd_f32)
+static int multi_buffers_ok(const MilShape &s, int B, const void *arena, size_t arena_bytes, void *scratch, size_t scratch_bytes, const char *what,
+                            char *&ab, char *&sb, MultiIO &io) {
+    ab = align_base(const_cast<void *>(arena), s.N);
+    sb = align_base(scratch, s.N);
+    io = multi_io_layout(s, B, ab, sb);
+    if ((size_t)(ab - (const char *)arena) + io.arena_total > arena_bytes) { set_error("%s: arena too small", what); return TOAD_EWORKSPACE; }
+    if ((size_t)(sb - (char *)scratch) + io.scratch_total > scratch_bytes) { set_error("%s: scratch too small", what); return TOAD_EWORKSPACE; }
+    return TOAD_OK;
+}
+
+extern "C" int toad_mil_multi_fwd_f32(const float *const *params, const float *Xcat, const int64_t *offsets, int B, const float *sex, int C, int D,
+                                       float drop_p, uint64_t seed, void *arena, size_t arena_bytes, void *scratch, size_t scratch_bytes,
+                                       void *stream) {
+    const char *what = "toad_mil_multi_fwd_f32";
+    if (!params || !Xcat || !offsets || !sex || !arena || !scratch) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    int64_t N = 0, max_n = 0;
+    TOAD_TRY(multi_batch_ok(offsets, B, C, D, drop_p, what, N, max_n));
+    const MilShape s{N, C, D};
+    if (!aligned16(Xcat)) { set_error("%s: Xcat must be 16-byte aligned", what); return TOAD_EALIGN; }
+    char *ab, *sb;
+    MultiIO io;
+    TOAD_TRY(multi_buffers_ok(s, B, arena, arena_bytes, scratch, scratch_bytes, what, ab, sb, io));
+    Params p;
+    if (!load_params(params, p, what)) return TOAD_EINVAL;
+    const Fwd f = arena_view(s, ab);
+    const Scratch w = scratch_layout(s, sb);
+    hipStream_t st = (hipStream_t)stream;
+    // (the offsets stay in the arena: the backward's pooling launches read them from there)
+    if (hipMemcpyAsync(io.ms.seg, offsets, (size_t)(B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st) != hipSuccess) {
+        set_error("%s: copying the slide offsets to the device failed: %s", what, hipGetErrorString(hipGetLastError()));
+        return TOAD_EINVAL;
+    }
+    TOAD_TRY(multi_forward_body(s, p, Xcat, f, w, io.ms, B, max_n, drop_p, seed, false, st, NoEvents{}, what));
+    return launch_heads_fwd_batch(io.ms.M, (int)(kSlideRec / sizeof(float)), sex, p.wcls, p.bcls, p.wsite, p.bsite, io.Mcat, io.logits, io.yprob, io.yhat,
+                                  io.slog, io.sprob, io.shat, B, kL, C, st);
+}
+
+extern "C" int toad_mil_multi_bwd_f32(const float *const *params, float *const *grads, float beta, const float *Xcat, const int64_t *offsets, int B,
+                                       int C, int D, float drop_p, uint64_t seed, const void *arena, size_t arena_bytes, const float *dlogits,
+                                       const float *dsite, const float *dA_ext, const float *dMcat_ext, void *scratch, size_t scratch_bytes,
+                                       void *stream) {
+    const char *what = "toad_mil_multi_bwd_f32";
+    if (!params || !grads || !Xcat || !offsets || !arena || !scratch || !dlogits || !dsite) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    int64_t N = 0, max_n = 0;
+    TOAD_TRY(multi_batch_ok(offsets, B, C, D, drop_p, what, N, max_n));
+    const MilShape s{N, C, D};
+    if (!aligned16(Xcat)) { set_error("%s: Xcat must be 16-byte aligned", what); return TOAD_EALIGN; }
+    char *ab, *sb;
+    MultiIO io;
+    TOAD_TRY(multi_buffers_ok(s, B, arena, arena_bytes, scratch, scratch_bytes, what, ab, sb, io));
+    Params p;
+    if (!load_params(params, p, what)) return TOAD_EINVAL;
+    for (int i = 0; i < 12; ++i) if (!grads[i]) { set_error("%s: null gradient slot %d", what, i); return TOAD_EINVAL; }
+    const Fwd f = arena_view(s, ab);
+    const Scratch w = scratch_layout(s, sb);
+    hipStream_t st = (hipStream_t)stream;
+    // the two dgrad operands (read transposed in place) and the three abs-max arrays of this pass (dP, dZ2, dZ1): one launch, as in backward_body
+    const H2Operand ops[2] = {{p.wab, 1, kL, kL, 2 * D, w.planes[W_ABT], w.binv[W_ABT]}, {p.w2, 1, kL, kL, kL, w.planes[W_2T], w.binv[W_2T]}};
+    const int nz = (int)(((char *)w.amax_dZ1 - (char *)w.amax_dP) / sizeof(float) + toad_amax_floats(N));
+    TOAD_TRY(launch_split_h2(ops, 2, w.amax_dP, nz, st, what));
+    // heads backward per slide (dM records + dlogits / dsite records), then the head-weight gradients summed over the batch
+    TOAD_TRY(launch_heads_bwd_batch(io.Mcat, dlogits, dsite, dMcat_ext, p.wcls, p.wsite, io.ms.dM, (int)(kSlideRec / sizeof(float)), io.dl, io.ds, grads[8],
+                                    grads[9], grads[10], grads[11], beta, B, kL, C, st));
+    return multi_backward_body(s, p, grads, beta, Xcat, f, w, io.ms, B, max_n, dA_ext, drop_p, seed, st, NoEvents{}, what);
 }

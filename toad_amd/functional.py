@@ -239,3 +239,40 @@ class ToadMIL(torch.autograd.Function):
         if not ctx.need_dsex:
             dsex = None
         return (dx, dsex) + tuple(g[k] for k in SLOTS) + (None, None, None, None)
+
+
+class ToadMILBatch(torch.autograd.Function):
+    """autograd bridge of a BATCH of slides: inputs (xcat [sum N_b, 1024], sex [B], offsets (B + 1 ints), 14 parameters in SLOTS order, wab,
+    bab, drop_p, seed); outputs (logits [B,C], site_logits [B,2], a_raw [sum N_b,2], features [B,2,513], and the non-differentiable Y_prob,
+    Y_hat [B,1], site_prob, site_hat [B,1]).
+
+    forward = toad_mil_multi_fwd_f32, backward = toad_mil_multi_bwd_f32: one C call each, whatever the loss. The arena (activations of the
+    concatenation) is owned by the autograd context, so backward(retain_graph=True) can be followed by another backward. Train-mode dropout
+    draws the masks of toad_mil_multi_step_f32 for the same (drop_p, seed): streams over the CONCATENATED rows, not the per-slide masks of
+    ToadMIL. No gradient reaches the bags or the sexes."""
+
+    @staticmethod
+    def forward(ctx, xcat, sex, offsets, *params):
+        w = dict(zip(SLOTS, params[:14]))
+        w["wab"], w["bab"] = params[14], params[15]
+        drop_p, seed = params[16], params[17]
+        arena, o = ops.mil_multi_fwd(w, xcat, sex, drop_p, seed, offsets=offsets)
+        ctx.w, ctx.arena, ctx.drop = w, arena, (drop_p, seed)
+        ret = (o["logits"], o["site_logits"], o["a_raw"], o["features"], o["y_prob"], o["y_hat"], o["site_prob"], o["site_hat"])
+        ctx.mark_non_differentiable(ret[4], ret[5], ret[6], ret[7])
+        return ret
+
+    @staticmethod
+    def backward(ctx, dlogits, dsite, da, dfeat, *unused):
+        w, arena = ctx.w, ctx.arena
+        dev = w["wcls"].device
+        dlogits = torch.zeros((arena.b, arena.c), device=dev) if dlogits is None else dlogits.contiguous()
+        dsite = torch.zeros((arena.b, 2), device=dev) if dsite is None else dsite.contiguous()
+        da = None if da is None else da.contiguous()
+        dfeat = None if dfeat is None else dfeat.contiguous()
+        g = {k: torch.empty_like(w[k]) for k in ops.STEP_SLOTS}
+        drop_p, seed = ctx.drop
+        ops.mil_multi_bwd(w, g, 0.0, None, None, arena, dlogits, dsite, da, dfeat, drop_p, seed)
+        d = w["wa"].shape[0]
+        g["wa"], g["wb"], g["ba"], g["bb"] = g["wab"][:d], g["wab"][d:], g["bab"][:d], g["bab"][d:]
+        return (None, None, None) + tuple(g[k] for k in SLOTS) + (None, None, None, None)

@@ -405,3 +405,77 @@ class TOAD_fc_mtl_concat(nn.Module):
             out.append(res)
             off += n
         return out
+
+    def forward_batch(self, bags, sexes, return_features=False):
+        """Forward over a BATCH of slides of different lengths WITH autograd (no reference counterpart: the reference steps slide by slide,
+        utils/core_utils_mtl_concat.py:200-234). ``bags``: a list of [N_b, 1024] device tensors (fp16 / bf16 / fp64 bags are up-cast to fp32);
+        ``sexes``: one entry per bag (a [B] device tensor, or a list of device tensors / numbers). Returns one result dict per slide with the
+        keys of ``forward`` (``features`` when asked); every tensor is a view into the batch's outputs, so a loss over any of them - e.g.
+        ``sum(f(out[b]) for b in range(B))`` - back-propagates through ONE library call (toad_mil_multi_bwd_f32), as ONE forward call
+        (toad_mil_multi_fwd_f32) produced them: the trunk / attention GEMMs run once over the concatenated bags, pooling and heads per slide.
+        Under ``torch.no_grad()`` (or with frozen parameters) it is a one-call multi-slide forward whose outputs are copies.
+
+        Differences from ``model(data, sex)`` slide by slide, all at fp32 round-off: the GEMM operand scales are taken per 256-row block of the
+        CONCATENATED bags (values agree to round-off, not bitwise), and train-mode dropout (``dropout=True``, ``model.train()``) draws ONE seed per
+        call (``_draw_dropout``) whose masks are those of ``ops.mil_multi_step`` / toad_mil_multi_step_f32 for the same (drop_p, seed) - streams
+        over the concatenated rows - not the per-slide masks. No gradient reaches the bags or the sexes (a bag or sex that requires grad is
+        refused), and PreparedBag inputs are not taken. Limits: at most 4,096 slides and 1,048,575 rows per call; split larger batches."""
+        if any(getattr(b, "is_prepared_bag", False) for b in bags):
+            raise TypeError("forward_batch concatenates fp32 bags; pass the tensors, not PreparedBag objects")
+        if len(bags) != len(sexes):
+            raise ValueError(f"forward_batch: one sex entry per bag (got {len(bags)} bags and {len(sexes)} sexes)")
+        if len(bags) == 0:
+            return []
+        for b in bags:
+            if not torch.is_tensor(b) or b.dim() != 2 or b.shape[1] != self.size_dict["big"][0]:
+                raise ValueError("forward_batch: every bag must be an [N, 1024] tensor")
+            if b.shape[0] == 0:
+                raise ValueError("forward_batch: empty bag (N = 0): the batched kernels need at least one patch per slide; forward it with model(data, sex)")
+        rows = sum(int(b.shape[0]) for b in bags)
+        if len(bags) > ops.MULTI_MAX_SLIDES:
+            raise ValueError(f"forward_batch: {len(bags)} slides exceed the limit of {ops.MULTI_MAX_SLIDES} slides per call; split the batch")
+        if rows > ops.MULTI_MAX_ROWS:
+            raise ValueError(f"forward_batch: {rows} concatenated rows exceed the limit of {ops.MULTI_MAX_ROWS} rows per call; split the batch")
+        if any(b.requires_grad for b in bags) or any(torch.is_tensor(s_) and s_.requires_grad for s_ in ([sexes] if torch.is_tensor(sexes) else sexes)):
+            raise ValueError("forward_batch: no gradient with respect to the bags or the sexes on this route; detach them or use model(data, sex)")
+        for b in bags:
+            _require_cuda(b, "bag")
+        if torch.is_tensor(sexes):
+            _require_cuda(sexes, "sexes")
+            sex = sexes.to(torch.float32).reshape(-1).contiguous()
+        else:
+            for s_ in sexes:
+                if torch.is_tensor(s_):
+                    _require_cuda(s_, "sex")
+            sex = torch.cat([torch.as_tensor(s_, dtype=torch.float32, device=bags[0].device).reshape(1) for s_ in sexes])
+        drop_p, seed = _draw_dropout(self._dropout and self.training)
+        w = self._weights()
+        _require_cuda(w["w1"], "model parameters")
+        xcat, offsets = ops._concat_bags([b if b.dtype == torch.float32 else b.float() for b in bags])
+        sp = [w[k] for k in F_.SLOTS]
+        if torch.is_grad_enabled() and any(p.requires_grad for p in sp):
+            logits, site_logits, a_raw, feats, y_prob, y_hat, site_prob, site_hat = F_.ToadMILBatch.apply(
+                xcat, sex, tuple(offsets), *sp, w["wab"], w["bab"], drop_p, seed)
+        else:
+            # no backward will follow: the activations go to the cached arena the next such forward reuses, and the outputs are COPIED out
+            # (views would keep ~7 KB per patch alive for as long as a caller holds one of them)
+            wd = {k: v.detach() for k, v in w.items()}
+            _, o = ops.mil_multi_fwd(wd, xcat, sex, drop_p, seed, offsets=offsets, cached_arena=True)
+            parts = (o["logits"], o["y_prob"], o["site_logits"], o["site_prob"], o["features"])
+            small = torch.cat([t.reshape(-1) for t in parts])                                   # one small copy
+            sizes = [t.numel() for t in parts]
+            logits, y_prob, site_logits, site_prob, feats = (v.view(t.shape) for v, t in zip(small.split(sizes), parts))
+            hats = torch.cat([o["y_hat"], o["site_hat"]], 1)
+            y_hat, site_hat = hats[:, 0:1], hats[:, 1:2]
+            a_raw = o["a_raw"].clone()
+        out = []
+        for b in range(len(bags)):
+            r0, r1 = offsets[b], offsets[b + 1]
+            res = {}
+            if return_features:
+                res["features"] = feats[b]                              # M after the sex concat, [2, L+1]
+            res.update({"logits": logits[b:b + 1], "Y_prob": y_prob[b:b + 1], "Y_hat": y_hat[b:b + 1],
+                        "site_logits": site_logits[b:b + 1], "site_prob": site_prob[b:b + 1], "site_hat": site_hat[b:b + 1],
+                        "A": a_raw[r0:r1].t()})                         # pre-softmax scores, [2, N_b]
+            out.append(res)
+        return out

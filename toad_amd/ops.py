@@ -879,6 +879,122 @@ def mil_bwd(w, grads, beta: float, bag, arena: MilArena, dlogits, dsite, da_ext=
     return dx, dsex
 
 
+# ---- a batch of slides: forward and backward as one C call each (toad_mil_multi_fwd_f32 / toad_mil_multi_bwd_f32, ABI 14) ------------------
+MULTI_ARENA_SLOTS = ("h1", "h", "p", "a_raw", "mcat", "logits", "y_prob", "y_hat", "site_logits", "site_prob", "site_hat")
+MULTI_MAX_SLIDES = 4096                    # csrc/step.hip multi_batch_ok
+MULTI_MAX_ROWS = (1 << 20) - 1             # sum N_b: the concatenation is ONE launch of the NT kernels (32-bit row offsets, h2_nt_ok)
+
+
+class MilMultiArena(MilArena):
+    """The forward arena of a batch of slides (toad_mil_multi_arena_layout): saved activations of the concatenation, per-slide pooling
+    records, the device copy of the offsets and the dense per-slide outputs, as typed views of ONE allocation. Keeps the concatenated bag
+    and the offsets the forward ran on (the backward needs both)."""
+
+    def __init__(self, xcat: torch.Tensor, offsets, c: int, d: int, cached: bool = False):
+        import ctypes
+        n, nb = int(xcat.shape[0]), len(offsets) - 1
+        self.n, self.c, self.d, self.b = n, c, d, nb
+        self.xcat, self.offsets = xcat, tuple(offsets)
+        lib = _lib.load()
+        nbytes = int(lib.toad_mil_multi_arena_bytes(n, nb, c, d))
+        if nbytes == 0:
+            raise ValueError(f"unsupported batch (rows {n}, slides {nb}, C={c}, D={d})")
+        offs = (ctypes.c_int64 * len(MULTI_ARENA_SLOTS))()
+        _lib.check(lib.toad_mil_multi_arena_layout(n, nb, c, d, offs), "toad_mil_multi_arena_layout")
+        self.buf = _ws(nbytes, xcat.device, "eval_arena")[:nbytes] if cached else torch.empty(nbytes, dtype=torch.uint8, device=xcat.device)
+        self.base = (-self.buf.data_ptr()) % int(lib.toad_mil_buffer_align(n))
+        self.off = {k: int(o) for k, o in zip(MULTI_ARENA_SLOTS, offs)}
+
+    def outputs(self):
+        """Dense per-slide outputs (views of the arena): logits [B,C], site_logits [B,2], a_raw [sum N_b,2], features [B,2,513],
+        y_prob [B,C], y_hat [B,1], site_prob [B,2], site_hat [B,1]."""
+        v, nb, c = self.view, self.b, self.c
+        return dict(logits=v("logits", (nb, c)), site_logits=v("site_logits", (nb, 2)), a_raw=v("a_raw", (self.n, 2)), features=v("mcat", (nb, 2, 513)),
+                    y_prob=v("y_prob", (nb, c)), y_hat=v("y_hat", (nb, 1), torch.int64), site_prob=v("site_prob", (nb, 2)),
+                    site_hat=v("site_hat", (nb, 1), torch.int64))
+
+
+def _concat_bags(bags, offsets=None):
+    """(xcat, offsets): a list of fp32 [N_b, 1024] bags concatenated once (bags already back to back in one allocation are taken as they are), or
+    an already concatenated tensor with its B + 1 row offsets."""
+    if offsets is None:
+        bags = [b.contiguous() for b in bags]
+        offsets = [0]
+        for b in bags:
+            offsets.append(offsets[-1] + int(b.shape[0]))
+        xcat = bags[0] if len(bags) == 1 else _adjacent_rows(bags)
+        return (torch.cat(bags, 0) if xcat is None else xcat), offsets
+    return bags, [int(o) for o in offsets]
+
+
+def _multi_scratch(n: int, nb: int, c: int, d: int, dev) -> torch.Tensor:
+    nbytes = int(_lib.load().toad_mil_multi_scratch_bytes(n, nb, c, d))
+    if nbytes == 0:
+        raise ValueError(f"unsupported batch (rows {n}, slides {nb}, C={c}, D={d})")
+    return _ws(nbytes, dev, "mil")
+
+
+def mil_multi_fwd(w, bags_or_xcat, sex, drop_p: float = 0.0, seed: int = 0, offsets=None, cached_arena: bool = False):
+    """models/model_toad.py:90-116 for a BATCH of slides in ONE library call (toad_mil_multi_fwd_f32): the trunk / attention GEMMs run once over
+    the concatenated bags, pooling and heads per slide. ``bags``: a list of fp32 [N_b, 1024] device tensors (concatenated here, once), or ONE
+    concatenated tensor with ``offsets`` (B + 1 row offsets); ``sex`` [B] float32 on the device. Returns (arena, outputs): the MilMultiArena the backward needs
+    and MilMultiArena.outputs(). Dropout masks are those of mil_multi_step for the same (drop_p, seed). ``cached_arena``: forward-only use (see
+    MilArena): clone what you keep."""
+    import ctypes
+    xcat, offsets = _concat_bags(bags_or_xcat, offsets)
+    nb = len(offsets) - 1
+    _chk(xcat, "bags"); _chk(sex, "sex")
+    if xcat.dim() != 2 or nb < 1 or xcat.shape[0] != offsets[-1] or sex.numel() != nb:
+        raise ValueError("mil_multi_fwd: one sex entry per slide and offsets[-1] == rows of the concatenation")
+    ws_t = [w[k] for k in STEP_SLOTS]
+    for k, t in zip(STEP_SLOTS, ws_t):
+        _chk(t, k)
+    n, c, d = _step_dims(w, xcat)
+    lib = _lib.load()
+    arena = MilMultiArena(xcat, offsets, c, d, cached=cached_arena)
+    scratch = _multi_scratch(n, nb, c, d, xcat.device)
+    offs = (ctypes.c_int64 * (nb + 1))(*offsets)
+    with _timed("mil_multi_fwd"):
+        _lib.check(lib.toad_mil_multi_fwd_f32(_ptr_array(ws_t), _p(xcat), offs, nb, _p(sex), c, d, float(drop_p), int(seed), _p(arena.buf), arena.buf.numel(),
+                                              _p(scratch), scratch.numel(), _stream()), "toad_mil_multi_fwd_f32")
+    return arena, arena.outputs()
+
+
+def mil_multi_bwd(w, grads, beta: float, xcat, offsets, arena: MilMultiArena, dlogits, dsite, da_ext=None, dmcat_ext=None, drop_p: float = 0.0,
+                  seed: int = 0):
+    """Backward of mil_multi_fwd in ONE library call (toad_mil_multi_bwd_f32): grads[slot] = beta*grads[slot] + the gradient summed over the batch,
+    from dlogits [B,C], dsite [B,2] and optionally da_ext [sum N_b,2] (through the raw scores) and dmcat_ext [B,2,513] (through the features).
+    ``xcat`` / ``offsets`` as for mil_multi_fwd (None: the ones the forward ran on, kept by the arena); the same (drop_p, seed) as the forward."""
+    import ctypes
+    if xcat is None:
+        xcat, offsets = arena.xcat, list(arena.offsets)
+    else:
+        xcat, offsets = _concat_bags(xcat, offsets)
+    nb = len(offsets) - 1
+    if tuple(offsets) != arena.offsets or xcat.shape[0] != arena.n:
+        raise ValueError("mil_multi_bwd: the offsets / bags must be those of the forward that filled the arena")
+    _chk(xcat, "bags"); _chk(dlogits, "dlogits"); _chk(dsite, "dsite")
+    _chk(da_ext, "da_ext", allow_none=True); _chk(dmcat_ext, "dmcat_ext", allow_none=True)
+    ws_t = [w[k] for k in STEP_SLOTS]
+    gs_t = [grads[k] for k in STEP_SLOTS]
+    for k, t in zip(STEP_SLOTS, gs_t):
+        _chk(t, "grad " + k)
+    n, c, d = arena.n, arena.c, arena.d
+    if tuple(dlogits.shape) != (nb, c) or tuple(dsite.shape) != (nb, 2):
+        raise ValueError(f"mil_multi_bwd: dlogits must be [{nb},{c}] and dsite [{nb},2]")
+    if da_ext is not None and tuple(da_ext.shape) != (n, 2):
+        raise ValueError(f"mil_multi_bwd: da_ext must be [{n},2]")
+    if dmcat_ext is not None and tuple(dmcat_ext.shape) != (nb, 2, 513):
+        raise ValueError(f"mil_multi_bwd: dmcat_ext must be [{nb},2,513]")
+    lib = _lib.load()
+    scratch = _multi_scratch(n, nb, c, d, xcat.device)
+    offs = (ctypes.c_int64 * (nb + 1))(*offsets)
+    with _timed("mil_multi_bwd"):
+        _lib.check(lib.toad_mil_multi_bwd_f32(_ptr_array(ws_t), _ptr_array(gs_t), float(beta), _p(xcat), offs, nb, c, d, float(drop_p), int(seed),
+                                              _p(arena.buf), arena.buf.numel(), _p(dlogits), _p(dsite), _p(da_ext), _p(dmcat_ext), _p(scratch),
+                                              scratch.numel(), _stream()), "toad_mil_multi_bwd_f32")
+
+
 # ---- feature-extractor pieces (conv.hip) --------------------------------------------------------------------------
 def linear_act_res_fwd(x, w, b, residual, act: int) -> torch.Tensor:
     """Y = act(X W^T + b + residual): a convolution-as-GEMM with folded BN, the bottleneck's skip add and ReLU."""
