@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define TOAD_ABI_VERSION 14
+#define TOAD_ABI_VERSION 15
 
 enum { TOAD_OK = 0, TOAD_EINVAL = -1, TOAD_ESHAPE = -2, TOAD_EWORKSPACE = -3, TOAD_EALIGN = -4 };
 enum { TOAD_ACT_NONE = 0, TOAD_ACT_RELU = 1 };
@@ -63,6 +63,26 @@ int toad_linear_h2_ok(int64_t M, int64_t N, int64_t K);
  * the dgrad epilogue reads 1/32 of the bytes an fp32 relu_src costs. Only whole tiles of the persistent kernel use it; the
  * caller still passes relu_src (remainder tiles, other kernels). Both calls must see the same M and the same N (= dgrad's K). */
 size_t toad_relu_bits_bytes(int64_t M, int64_t N);
+/* ABI 15 (host-side query, touches no device): which 256 x 256 output tiles of ONE NT launch [M,K] x [N,K]^T touch their words of the bit image.
+ * tile_map [ceil(M/256) * ceil(N/256)] bytes, row-major over (row tile, column tile): non-zero = the launch computes the tile whole and writes
+ * its bit words (a forward) or reads them (a dgrad, TOAD_BITS_READER; M, N = the shape of relu_src, K = the dgrad's reduction) - 1 on the
+ * 256 x 256 plan, 2 when the launch runs on half-height tiles, which are never split (then every entry is 2); 0 = the tile is cut
+ * into K-slices and finished by the fix-up kernel, which writes no bits and masks with the fp32 relu_src - or the launch does not use the
+ * image at all. The map comes from the code that decides the launch, so "every tile a dgrad reads was written by the forward of the layer",
+ *   reads(M, N, K_b, flags) <= writes(M, N, K_f, 0)   for every K_f, K_b and every flag combination accepted,
+ * can be checked without a GPU (tests/test_relu_bits_plan.py). flags: what changes the launch path -
+ *   TOAD_BITS_READER        the dgrad that reads the image (relu_src + relu_bits) instead of the forward that writes it
+ *   TOAD_BITS_ADDEND        an addend buffer;  TOAD_BITS_POOL  the recomputed pooling addend;  TOAD_BITS_POOL_BATCHED  its multi-slide form
+ *   TOAD_BITS_A16 / _APT    a forward whose A operand is an fp16 / a prepared (plane-tiled) bag
+ *   TOAD_BITS_SELF_MEASURE  a forward that measures its fp32 A operand itself (x_amax == NULL)
+ *   TOAD_BITS_ROWS          the launches the whole-slide calls make of the product: row chunks of 1,047,552 rows (M may exceed one launch)
+ *   TOAD_BITS_STEP_L1       the first trunk Linear of the whole-slide calls (N = 512, K = 1024; _A16 / _APT = the bag's format) or, with
+ *                           _READER, the dgrad that masks with its output (K = 512) - including the calls' choice to hand that dgrad the
+ *                           fp32 activations only when the bag was fp16 / prepared. Implies _ROWS.
+ * Returns TOAD_OK, TOAD_ESHAPE for a shape toad_linear_h2_ok refuses, TOAD_EINVAL for a combination the launcher refuses. */
+enum { TOAD_BITS_READER = 1, TOAD_BITS_ADDEND = 2, TOAD_BITS_POOL = 4, TOAD_BITS_POOL_BATCHED = 8, TOAD_BITS_A16 = 16, TOAD_BITS_APT = 32,
+       TOAD_BITS_SELF_MEASURE = 64, TOAD_BITS_ROWS = 128, TOAD_BITS_STEP_L1 = 256 };
+int toad_relu_bits_plan(int64_t M, int64_t N, int64_t K, int flags, uint8_t *tile_map);
 
 /* Y[M,N] = act(X[M,K] W[N,K]^T + bias[N]).   bias may be NULL.
  * Replaces nn.Linear(+nn.ReLU): models/model_toad.py:59 and :62 (trunk, act=RELU) and the

@@ -25,7 +25,9 @@ for i in range(cases):
     try:
         h2 = ops.h2_ok(m, n, k)
         if h2:
-            y, ya, bits = ops.linear_act_fwd(xd, wd, bd, 1, want_bits=True)
+            # the image lands in a buffer of known contents, 0x00 and 0xFF in turn: a tile the dgrad below reads and this forward did not write shows
+            poison = torch.full((ops.relu_bits_bytes(m, n),), 0xFF if i % 2 else 0x00, dtype=torch.uint8, device=dev)
+            y, ya, bits = ops.linear_act_fwd(xd, wd, bd, 1, bits_out=poison)
         else:
             y, bits, ya = ops.linear_act_fwd(xd, wd, bd, 1), None, None
         ref = (x.double() @ w.double().t() + b.double()).clamp_min(0)
@@ -49,12 +51,16 @@ for i in range(cases):
             dw2, _ = ops.linear_wgrad(dyd, bag)
             e = rel(dw2, dwr); msgs.append(f"wgrad(prepared) {e:.1e}"); ok = ok and e <= 2e-5
         # dgrad with this layer's ReLU mask as bits: mask rows of a [M,N] gradient need a weight with N as its OUTPUT dimension
-        if bits is not None and ops.h2_ok(m, n, n):
-            w2 = torch.randn(n, n, generator=g) / n ** 0.5
-            dz = torch.randn(m, n, generator=g)
+        # (reader reductions: the layer's own width when it is a whole number of 32-deep stages, and one drawn from the depths that matter -
+        #  32 is ONE stage, which cannot be K-split)
+        for kb in ([n] if ops.h2_ok(m, n, n) else []) + [rng.choice([32, 64, 512, 768])]:
+            if bits is None:
+                break
+            w2 = torch.randn(kb, n, generator=g) / kb ** 0.5
+            dz = torch.randn(m, kb, generator=g)
             dm = ops.linear_dgrad(dz.to(dev), ops.transpose(w2.to(dev)), relu_src=y, relu_bits=bits)
             dmr = (dz.double() @ w2.double()) * (y.cpu() > 0)
-            e = rel(dm, dmr); msgs.append(f"dgrad(bits) {e:.1e}"); ok = ok and e <= 2e-5
+            e = rel(dm, dmr); msgs.append(f"dgrad(bits, K{kb}) {e:.1e}"); ok = ok and e <= 2e-5
     except RuntimeError as ex:
         msgs.append("REFUSED " + str(ex)[:90]); ok = True
     if not ok:

@@ -14,7 +14,7 @@ def _lib():
 
 def test_multi_fwd_bwd_report_argument_errors_without_a_gpu():
     lib = _lib()
-    assert lib.toad_abi_version() == 14
+    assert lib.toad_abi_version() == 15
     err = lambda: lib.toad_last_error().decode()              # noqa: E731
     one = ctypes.c_void_p(1 << 21)                            # non-null, aligned fake pointers: every check below comes before a device access
     big = 1 << 40

@@ -11,7 +11,7 @@ from ctypes import c_char_p, c_float, c_int, c_int64, c_size_t, c_uint64, c_void
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtoad_hip.so")      # the one library the product loads (A/B builds: tools/ab/select_lib.py rebinds this in the TOOL's process)
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 P, I64, I, F, SZ, U64 = c_void_p, c_int64, c_int, c_float, c_size_t, c_uint64
 
@@ -25,6 +25,7 @@ SIGNATURES = {
     "toad_linear_h2_ok": (I, [I64, I64, I64]),
     "toad_linear_ws_bytes": (SZ, [I64, I64, I64]),
     "toad_relu_bits_bytes": (SZ, [I64, I64]),
+    "toad_relu_bits_plan": (I, [I64, I64, I64, I, P]),
     "toad_linear_act_fwd_f32": (I, [P, P, P, P, I64, I64, I64, I, F, U64, P, P, P, P, SZ, P]),
     "toad_linear_dgrad_f32": (I, [P, P, P, P, F, P, I64, I64, I64, P, P, P, I, P, P, P, P, SZ, P]),
     "toad_dropout_mask_f32": (I, [P, I64, F, U64, P]),

@@ -105,6 +105,12 @@ struct H2Pool { const float *a_raw, *stats, *dM; int T; };                      
 struct EpiScalars { int relu; float mask_scale; DropArgs drop; int stagger = 0; };                           // epilogue scalars of every NT kernel; stagger: gemm_h2.inc
 bool h2_nt_ok(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldc);
 bool nt_half_tiles(int64_t M, int64_t N);               // fp32-A products of this shape run on half-height tiles (no K-split: every tile writes / reads the ReLU bit image)
+// what ONE launch of launch_nt_h2 does about the one-bit ReLU image (gemm_f32.hip, "the one-bit ReLU image contract"): rc / why = the launcher's
+// refusal of the combination, half = half-height tiles (every tile whole), read_bits = a dgrad takes its whole tiles' mask from the image
+struct NtRoute { int rc; const char *why; bool half, read_bits; };
+NtRoute nt_route(int64_t M, int64_t N, int64_t K, int a_mode, bool run_mode, bool addend, int pool_T, bool mask_src, bool mask_bits, int a_stride,
+                 int y_stride);
+void nt_bits_tile_map(int64_t M, int64_t N, int64_t K, const NtRoute &r, unsigned char *tile_map);
 bool nt_run_ok(int64_t M, int64_t N, int64_t K);       // the first GEMM may measure its fp32 A operand itself (gemm_h2.inc AMODE 3)
 size_t h2_planes_bytes(int64_t N, int64_t K);
 size_t h2_binv_bytes(int64_t N);

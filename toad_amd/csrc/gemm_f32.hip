@@ -214,6 +214,54 @@ bool nt_half_tiles(int64_t M, int64_t N) {
     return g <= 2;
 }
 
+// ---- the one-bit ReLU image contract ---------------------------------------------------------------------------------------------------
+// A forward NT launch writes the bit words of its WHOLE tiles only, the dgrad launch of the same layer reads the bit words of ITS whole tiles
+// (K-split remainder tiles go through the fix-up kernel on both sides, which knows the fp32 activations only). So every tile a reader takes
+// from the image must be a tile the writer - a launch with the same M and N and another K - left there: reads(M, N, K_b) must be a subset of
+// writes(M, N, K_f). nt_route is the ONE place that decides what a launch of launch_nt_h2 does about it (which tile height, whether the image
+// is read at all); nt_bits_tile_map lists the tiles with the plan the kernel itself runs (nt_plan, nt_row_tile). toad_relu_bits_plan
+// (step.hip) exposes both to the host, and tests/test_relu_bits_plan.py holds the inclusion over every shape class without a GPU.
+NtRoute nt_route(int64_t M, int64_t N, int64_t K, int a_mode, bool run_mode, bool addend, int pool_T, bool mask_src, bool mask_bits,
+                 int a_stride, int y_stride) {
+    NtRoute r{TOAD_OK, nullptr, false, false};
+    auto refuse = [&](const char *why) { r.rc = TOAD_EINVAL; r.why = why; return r; };
+    if (run_mode && (addend || mask_src || mask_bits || pool_T > 0 || a_stride != 1))
+        return refuse("the self-measuring operand mode is a plain forward with per-block scales");
+    if (a_mode != TOAD_X_F32) {   // fp16 / plane-tiled A: 256-row tiles always, plain forward only
+        if (addend || mask_src || mask_bits || pool_T > 0) return refuse("the fp16 / plane-tiled operand kernels have no addend / mask / pooling epilogue");
+        return r;
+    }
+    if (pool_T > 0 && addend) return refuse("an addend buffer and the recomputed pooling addend are mutually exclusive");
+    if (mask_bits && !mask_src) return refuse("the one-bit ReLU image needs the fp32 relu_src as well (remainder tiles)");
+    // short operands: half-height tiles, whole K per workgroup, no fix-up launch (the epilogues the MIL step uses; per-block abs-max arrays)
+    r.half = !addend && (pool_T == 0 || mask_src) && a_stride == 1 && y_stride == 1 && nt_half_tiles(M, N);
+    // Whether nt_plan splits a remainder tile is a function of the tile counts for every reduction of at least TWO 32-deep stages. A one-stage
+    // reduction cannot be split, so its launch would take every remainder tile whole - and read bit words that the forward of the layer (a longer
+    // reduction, which split those tiles) never wrote. Such a reader masks with the fp32 activations instead: same tiles, same sums.
+    r.read_bits = mask_bits;
+    if (mask_bits && !r.half && K / BK < 2) {
+        const int tiles_m = (int)((M + PB - 1) / PB), tiles_n = (int)((N + PB - 1) / PB);
+        for (int x = 0; x < kNumXCD; ++x) if (nt_plan(x, tiles_m, tiles_n, 2).g > 1) r.read_bits = false;
+    }
+    if ((pool_T >> 8) && ((pool_T & 255) != 2 || !r.read_bits)) return refuse("the batched pooled addend is instantiated for 2 tasks on the one-bit ReLU image");
+    return r;
+}
+// tile_map[tm * tiles_n + tn] != 0 for every 256 x 256 output tile that a launch on route `r` computes whole, i.e. whose bit words it writes
+// (forward) or reads (dgrad with r.read_bits): 1 = a whole tile of the 256 x 256 plan, 2 = the launch runs on half-height tiles (all of them
+// whole). Tiles cut into K-slices stay 0. The caller zeroes the map.
+void nt_bits_tile_map(int64_t M, int64_t N, int64_t K, const NtRoute &r, unsigned char *tile_map) {
+    const int tiles_m = (int)((M + PB - 1) / PB), tiles_n = (int)((N + PB - 1) / PB);
+    if (r.half) {                                              // half-height tiles are never split: both halves of every 256-row block
+        for (int64_t i = 0; i < (int64_t)tiles_m * tiles_n; ++i) tile_map[i] = 2;
+        return;
+    }
+    for (int x = 0; x < kNumXCD; ++x) {
+        const NtPlan pl = nt_plan(x, tiles_m, tiles_n, (int)(K / BK));
+        const int whole = pl.rounds * PB_BLOCKS_PER_XCD + (pl.g == 1 ? pl.rem : 0);
+        for (int q = 0; q < whole; ++q) tile_map[(int64_t)nt_row_tile(q, tiles_n, x) * tiles_n + q % tiles_n] = 1;
+    }
+}
+
 // split up to 6 weight operands into planes + inverse row scales with ONE launch
 int launch_split_h2(const H2Operand *ops, int n, float *zero, int zero_n, hipStream_t st, const char *what, float *zero2, int zero2_n) {
     H2SplitBatch b;
@@ -265,9 +313,11 @@ int launch_nt_h2(const float *A, int64_t lda, const float *a_amax, const unsigne
     // a_amax == NULL with a_amax_out (fp32 A, plain forward): the kernel measures A itself, stage by stage (AMODE 3, gemm_h2.inc), fills
     // a_amax_out (zeroed by the caller) and slab_ke; the fix-up then reads the completed array
     const bool run_mode = a_mode == TOAD_X_F32 && !a_amax && a_amax_out;
+    const NtRoute rt = nt_route(M, N, K, a_mode, run_mode, addend != nullptr, pool.T, mask_src != nullptr, mask_bits != nullptr, a_stride, y_stride);
+    if (rt.rc) { set_error("%s: %s", what, rt.why); return rt.rc; }
     if (run_mode) {
-        if (addend || mask_src || mask_bits || pool.T > 0 || a_stride != 1 || !slab_ke) { set_error("%s: the self-measuring operand mode is a plain forward with per-block scales", what); return TOAD_EINVAL; }
-        if (nt_half_tiles(M, N)) {
+        if (!slab_ke) { set_error("%s: the self-measuring operand mode is a plain forward with per-block scales", what); return TOAD_EINVAL; }
+        if (rt.half) {
             hipLaunchKernelGGL((gemm_nt_h2_big_kernel<false, false, 0, 3, 128>), dim3(PB_GRID), dim3(512), H2_SMEM_HALF_RUN, st, A, lda, (const float *)nullptr, planes,
                                binv, C, ldc, (int)M, (int)N, (int)K, bias, es, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr,
                                (const float *)nullptr, (const float *)nullptr, 0, slabs, y_amax, bits_out, (int)((M + 127) / 128), tiles_n, a_stride, y_stride, a_amax_out, slab_ke);
@@ -292,8 +342,7 @@ int launch_nt_h2(const float *A, int64_t lda, const float *a_amax, const unsigne
         }
         return rcr;
     }
-    if (a_mode != TOAD_X_F32) {   // A is fp16 [M, lda halves] or plane-tiled: plain forward only (no addend / mask / pooling variants are instantiated)
-        if (addend || mask_src || mask_bits || pool.T > 0) { set_error("%s: the fp16 / plane-tiled operand kernels have no addend / mask / pooling epilogue", what); return TOAD_EINVAL; }
+    if (a_mode != TOAD_X_F32) {   // A is fp16 [M, lda halves] or plane-tiled: plain forward only (no addend / mask / pooling variants are instantiated; nt_route)
         if (a_mode == TOAD_X_PT)
             hipLaunchKernelGGL((gemm_nt_h2_big_kernel<false, false, 0, 2>), dim3(PB_GRID), dim3(512), H2_SMEM_PT, st, A, lda, a_amax, planes,
                                binv, C, ldc, (int)M, (int)N, (int)K, bias, es, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr,
@@ -319,25 +368,26 @@ int launch_nt_h2(const float *A, int64_t lda, const float *a_amax, const unsigne
         }
         return rc16;
     }
-    if (pool.T > 0 && addend) { set_error("%s: an addend buffer and the recomputed pooling addend are mutually exclusive", what); return TOAD_EINVAL; }
-    // whole tiles read the one-bit ReLU image when the caller has it (mask_bits), the fix-up kernel always reads the fp32 mask_src
+    // whole tiles read the one-bit ReLU image when the caller has it (mask_bits) and this launch's whole tiles are whole tiles of the forward
+    // that wrote it (nt_route), the fix-up kernel always reads the fp32 mask_src
+    if (!rt.read_bits) mask_bits = nullptr;
     const float *msrc = mask_bits ? reinterpret_cast<const float *>(mask_bits) : mask_src;
 #define TOAD_LAUNCH_H2(P, A_, M_)                                                                                                     \
     hipLaunchKernelGGL((gemm_nt_h2_big_kernel<P, A_, M_>), dim3(PB_GRID), dim3(512), H2_SMEM, st, A, lda, a_amax, planes, binv, C, ldc, (int)M, \
                        (int)N, (int)K, bias, es, addend, msrc, pool.a_raw, pool.stats, pool.dM, pool.T, slabs, y_amax, bits_out, tiles_m, tiles_n, a_stride, y_stride, (float *)nullptr, (int *)nullptr)
     const int msk = mask_bits ? 2 : (mask_src ? 1 : 0);
-    if (mask_bits && !mask_src) { set_error("%s: the one-bit ReLU image needs the fp32 relu_src as well (remainder tiles)", what); return TOAD_EINVAL; }
-    // short operands: half-height tiles, whole K per workgroup, no fix-up launch (the epilogues the MIL step uses; per-block abs-max arrays)
-    if (!addend && (pool.T == 0 || msk == 2) && a_stride == 1 && y_stride == 1 && nt_half_tiles(M, N)) {
+    if (rt.half) {               // short operands: half-height tiles, whole K per workgroup, no fix-up launch (nt_route)
         const int tm128 = (int)((M + 127) / 128);
 #define TOAD_LAUNCH_H2_HALF(P, M_, AM)                                                                                                   \
         hipLaunchKernelGGL((gemm_nt_h2_big_kernel<P, false, M_, AM, 128>), dim3(PB_GRID), dim3(512), H2_SMEM_HALF, st, A, lda, a_amax, planes, binv, C, ldc, \
                            (int)M, (int)N, (int)K, bias, es, (const float *)nullptr, msrc, pool.a_raw, pool.stats, pool.dM, pool.T, slabs, y_amax, bits_out,    \
                            tm128, tiles_n, a_stride, y_stride, (float *)nullptr, (int *)nullptr)
         if (pool.T >> 8) {
-            if ((pool.T & 255) != 2 || !aligned16(pool.a_raw)) { set_error("%s: the batched pooled addend is instantiated for 2 tasks on the one-bit ReLU image", what); return TOAD_EINVAL; }
+            if (!aligned16(pool.a_raw)) { set_error("%s: the batched pooled addend is instantiated for 2 tasks on the one-bit ReLU image", what); return TOAD_EINVAL; }
             TOAD_LAUNCH_H2_HALF(true, 2, 4);
-        } else if (pool.T > 0) TOAD_LAUNCH_H2_HALF(true, 2, 0);
+        } else if (pool.T > 0) {     // (fp32 mask: the per-op dgrad without a bit image - the same tiles and sums as with one, like the plain dgrad below)
+            if (msk == 2) TOAD_LAUNCH_H2_HALF(true, 2, 0); else TOAD_LAUNCH_H2_HALF(true, 1, 0);
+        }
         else if (msk == 2) TOAD_LAUNCH_H2_HALF(false, 2, 0);
         else if (msk == 1) TOAD_LAUNCH_H2_HALF(false, 1, 0);       // (fp32 mask: the per-op dgrad without a bit image; same tiles, same sums as with one)
         else TOAD_LAUNCH_H2_HALF(false, 0, 0);
@@ -345,7 +395,7 @@ int launch_nt_h2(const float *A, int64_t lda, const float *a_amax, const unsigne
         return check_launch(what);
     }
     if (pool.T >> 8) {       // batched pooled addend: per-row records + per-slide dM (the ragged multi-slide step; gemm_h2_epilogue.inc PBATCH)
-        if ((pool.T & 255) != 2 || msk != 2 || !aligned16(pool.a_raw)) { set_error("%s: the batched pooled addend is instantiated for 2 tasks on the one-bit ReLU image", what); return TOAD_EINVAL; }
+        if (!aligned16(pool.a_raw)) { set_error("%s: the batched pooled addend is instantiated for 2 tasks on the one-bit ReLU image", what); return TOAD_EINVAL; }
         hipLaunchKernelGGL((gemm_nt_h2_big_kernel<true, false, 2, 4>), dim3(PB_GRID), dim3(512), H2_SMEM, st, A, lda, a_amax, planes, binv, C, ldc, (int)M, (int)N, (int)K, bias,
                            es, (const float *)nullptr, msrc, pool.a_raw, pool.stats, pool.dM, pool.T, slabs, y_amax, bits_out, tiles_m, tiles_n, a_stride, y_stride,
                            (float *)nullptr, (int *)nullptr);

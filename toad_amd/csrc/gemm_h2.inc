@@ -421,7 +421,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_h2_big_kernel(
     // tile q of this XCD -> first row / column, column-tile index, exponent of the A scale of its 256-row block
     struct Tile { int m0, n0, tn, ke, tmi; };
     auto tile_of = [&](int q) {
-        const int tmt = (q / tiles_n) * kNumXCD + xcd;             // row tile (TM rows); tmi = the 256-row block its rows lie in (abs-max slot)
+        const int tmt = nt_row_tile(q, tiles_n, xcd);              // row tile (TM rows); tmi = the 256-row block its rows lie in (abs-max slot)
         const int tmi = TM == PB ? tmt : (tmt * TM) / PB;
         return Tile{tmt * TM, (q % tiles_n) * PB, q % tiles_n, (A16 || ARUN) ? 0 : h2_exp_from_amax(a_amax[tmi * a_stride]), tmi};
     };

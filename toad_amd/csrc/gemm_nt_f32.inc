@@ -220,7 +220,8 @@ __host__ __device__ inline NtPlan nt_plan(int xcd, int tiles_m, int tiles_n, int
     // XCD holds a few more tiles than the others (16,500 rows x 512 columns: XCD 0 has 18 tiles -> whole tiles, the other seven 16 -> two slices each)
     // the seven finish early and idle, and their slices still cost slabs and the fix-up LAUNCH: that shape ran 11 % slower than 20,000 rows
     // (profiles/r06q_size_sweep.txt). Each XCD takes the smallest g that still ends with the slowest one (exact integer arithmetic in units of
-    // 1 / lcm(1..16) tile times). Whether a remainder tile is split at all (g > 1) stays a function of the tile counts only, never of nk.
+    // 1 / lcm(1..16) tile times). Whether a remainder tile is split at all (g > 1) stays a function of the tile counts only for every nk >= 2 (a
+    // one-stage reduction, nk = 1, cannot be split: such a dgrad does not read the ReLU bit image - nt_route, gemm_f32.hip; tests/test_relu_bits_plan.py).
     if (g > 1) {
         constexpr int LCM = 720720;
         int t_max = 0;
@@ -237,6 +238,9 @@ __host__ __device__ inline NtPlan nt_plan(int xcd, int tiles_m, int tiles_n, int
     p.g = g;
     return p;
 }
+// item q of an XCD's work list (its tiles, row-major over the row tiles this XCD owns) -> the row tile it computes; the column tile is q % tiles_n.
+// Host and device: the persistent kernel places its tiles with it and the host-side bit-image query (nt_bits_tile_map, gemm_f32.hip) reports them.
+__host__ __device__ inline int nt_row_tile(int q, int tiles_n, int xcd) { return (q / tiles_n) * kNumXCD + xcd; }
 
 // shared by the GEMM (direct tiles) and the fix-up kernel (slab sums): v = one float4 of 4 consecutive columns.
 // NOTE: bias/addend/mask are passed to the kernels as DIRECT pointer arguments. Inside a by-value struct

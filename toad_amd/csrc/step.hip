@@ -9,6 +9,7 @@
 // dgrad epilogue recomputes it), and three dependent tail launches (heads + CE + heads backward are one single-workgroup kernel
 // in the fused step).
 #include "common.h"
+#include <string.h>
 
 namespace toad {
 
@@ -159,6 +160,10 @@ static DropSeeds drop_seeds(float drop_p, uint64_t seed) {          // must matc
 // TN kernels, which take any M.
 constexpr int64_t kChunkRows = 4092 * 256;                  // 1,047,552 rows: 4,290,772,992 bytes of a 1024-wide fp32 operand
 constexpr uint64_t kChunkSeedStep = 0xD1B54A32D192ED03ull;
+// the launches of nt_rows: chunk j covers rows [nt_row_chunk_first(j), + nt_row_chunk_rows(M, j)); also what toad_relu_bits_plan composes its map over
+static int nt_row_chunks(int64_t M) { return M <= kChunkRows ? 1 : (int)((M + kChunkRows - 1) / kChunkRows); }
+static int64_t nt_row_chunk_first(int j) { return (int64_t)j * kChunkRows; }
+static int64_t nt_row_chunk_rows(int64_t M, int j) { const int64_t left = M - nt_row_chunk_first(j); return left < kChunkRows ? left : kChunkRows; }
 static bool nt_rows_ok(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldc) {
     return h2_nt_ok(M < kChunkRows ? M : kChunkRows, N, K, lda, ldc);
 }
@@ -171,9 +176,8 @@ static int nt_rows(const float *A, int64_t lda, const float *a_amax, const unsig
                             a_mode, 1, 1, a_amax_out, slab_ke);
     if (a_mode != TOAD_X_F32) { set_error("%s: an fp16 / prepared bag is limited to the kernels' 32-bit row offsets", what); return TOAD_ESHAPE; }
     const int64_t bits_per_blk = (int64_t)((N + 255) / 256) * 8 * 2 * 64;          // 64-bit words of the ReLU image per 256-row block (toad_relu_bits_bytes)
-    int j = 0;
-    for (int64_t c0 = 0; c0 < M; c0 += kChunkRows, ++j) {
-        const int64_t m = M - c0 < kChunkRows ? M - c0 : kChunkRows, blk = c0 / H2_ROWBLK;
+    for (int j = 0; j < nt_row_chunks(M); ++j) {
+        const int64_t c0 = nt_row_chunk_first(j), m = nt_row_chunk_rows(M, j), blk = c0 / H2_ROWBLK;
         EpiScalars e = es;
         if (e.drop.thresh) e.drop.seed += (uint64_t)j * kChunkSeedStep;
         H2Pool pl = pool;
@@ -183,6 +187,13 @@ static int nt_rows(const float *A, int64_t lda, const float *a_amax, const unsig
                               bits_out ? bits_out + blk * bits_per_blk : nullptr, st, what, a_mode, 1, 1, a_amax_out ? a_amax_out + blk : nullptr, slab_ke));
     }
     return TOAD_OK;
+}
+
+// The dgrad of the second trunk Linear masks with H1, whose bit image the FIRST Linear wrote. An fp16 / prepared bag ran that Linear on 256-row
+// tiles, whose K-split remainder tiles leave no bits; where the dgrad - an fp32-A product - would run on half-height tiles, which read the bit
+// image for EVERY tile, it takes the fp32 activations instead (fp32 bags: both launches follow nt_half_tiles(N, 512) alike).
+static bool step_dgrad1_reads_bits(int x_mode, int64_t N) {
+    return x_mode == TOAD_X_F32 || !nt_half_tiles(N < kChunkRows ? N : kChunkRows, kL);
 }
 
 // forward up to the pooled features: trunk, stacked attention GEMM, fused gated pool. `ev` records bench events (or nothing).
@@ -276,7 +287,7 @@ static int backward_body(const MilShape &s, const Params &p, float *const *grads
         if (!wbatch) { ev(12); TOAD_TRY(launch_wgrad(w.dZ2, w.amax_dZ2, f.H1, f.amax_h1, grads[2], grads[3], N, kL, kL, beta, w.wgrad_ws2, st, what, TOAD_X_F32, &dw[1])); ev(13); }
         // (an fp16 / prepared bag ran its first Linear on 256-row tiles, whose K-split remainder tiles leave no bits; where this dgrad would run on
         //  half-height tiles - which read the bit image for EVERY tile - it takes the fp32 activations instead)
-        const unsigned long long *bits1 = (x_mode == TOAD_X_F32 || !nt_half_tiles(N < kChunkRows ? N : kChunkRows, kL)) ? f.bits_h1 : nullptr;
+        const unsigned long long *bits1 = step_dgrad1_reads_bits(x_mode, N) ? f.bits_h1 : nullptr;
         ev(14); TOAD_TRY(nt_rows(w.dZ2, kL, w.amax_dZ2, w.planes[W_2T], w.binv[W_2T], w.dZ1, kL, N, kL, kL, nullptr, msk, nullptr, f.H1, bits1, nopool,
                                  w.slabs, w.amax_dZ1, nullptr, st, what)); ev(15);
         if (wbatch) {         // (bench events: the one launch + the reduction are booked under the first weight gradient's pair, the other two pairs are empty)
@@ -318,6 +329,40 @@ struct StreamEvents {
 }  // namespace toad
 
 using namespace toad;
+
+// Host-side query of the one-bit ReLU image plan (include/toad_hip.h; no device needed): the tiles whose bit words ONE launch_nt_h2 launch - or,
+// with TOAD_BITS_ROWS, the launches nt_rows makes of it - writes (forward) or reads (dgrad), from the code that decides the launch (nt_route,
+// nt_bits_tile_map, nt_row_chunks, step_dgrad1_reads_bits).
+extern "C" int toad_relu_bits_plan(int64_t M, int64_t N, int64_t K, int flags, uint8_t *tile_map) {
+    const char *what = "toad_relu_bits_plan";
+    const int known = TOAD_BITS_READER | TOAD_BITS_ADDEND | TOAD_BITS_POOL | TOAD_BITS_POOL_BATCHED | TOAD_BITS_A16 | TOAD_BITS_APT |
+                      TOAD_BITS_SELF_MEASURE | TOAD_BITS_ROWS | TOAD_BITS_STEP_L1;
+    if (!tile_map || (flags & ~known) || ((flags & TOAD_BITS_A16) && (flags & TOAD_BITS_APT)) || ((flags & TOAD_BITS_POOL) && (flags & TOAD_BITS_POOL_BATCHED))) {
+        set_error("%s: bad argument", what); return TOAD_EINVAL;
+    }
+    const bool reader = flags & TOAD_BITS_READER, step_l1 = flags & TOAD_BITS_STEP_L1, rows = step_l1 || (flags & TOAD_BITS_ROWS);
+    const int x_mode = (flags & TOAD_BITS_A16) ? TOAD_X_F16 : (flags & TOAD_BITS_APT) ? TOAD_X_PT : TOAD_X_F32;
+    if (step_l1 && (N != kL || K != (reader ? kL : kL0))) { set_error("%s: TOAD_BITS_STEP_L1 is the 1024 -> 512 Linear and the 512-deep dgrad behind it", what); return TOAD_ESHAPE; }
+    // the A operand of the launch: the bag in its own format for the step's first Linear, else what the flags say; the dgrad of the step reads fp32 dZ2
+    const int a_mode = (step_l1 && reader) ? TOAD_X_F32 : x_mode;
+    if (M < 1 || N < 1 || K < 1 || M > INT32_MAX - H2_ROWBLK || N > INT32_MAX - H2_ROWBLK) { set_error("%s: bad shape", what); return TOAD_ESHAPE; }
+    const int64_t lda = K, ldc = N;
+    bool ok = (rows && a_mode == TOAD_X_F32) ? nt_rows_ok(M, N, K, lda, ldc) : h2_nt_ok(M, N, K, lda, ldc);
+    if (x_mode != TOAD_X_F32 && rows) ok = ok && M <= kChunkRows && h2_nt_ok(M, kL, kL0, kL0, kL);      // (an fp16 / prepared bag is ONE launch: nt_rows refuses to chunk it)
+    if (!ok) { set_error("%s: not a shape of the fp16 two-piece NT kernel (toad_linear_h2_ok)", what); return TOAD_ESHAPE; }
+    const int tiles_n = (int)((N + 255) / 256);
+    memset(tile_map, 0, (size_t)((M + 255) / 256) * tiles_n);
+    const bool bits = reader && (!step_l1 || step_dgrad1_reads_bits(x_mode, M));          // (the step hands the image to its dgrad or not)
+    const int pool_T = (flags & TOAD_BITS_POOL_BATCHED) ? (2 | (8 << 8)) : (flags & TOAD_BITS_POOL) ? 2 : 0;
+    const int n_chunks = rows ? nt_row_chunks(M) : 1;
+    for (int j = 0; j < n_chunks; ++j) {
+        const int64_t c0 = rows ? nt_row_chunk_first(j) : 0, m = rows ? nt_row_chunk_rows(M, j) : M;
+        const NtRoute r = nt_route(m, N, K, a_mode, (flags & TOAD_BITS_SELF_MEASURE) != 0, (flags & TOAD_BITS_ADDEND) != 0, pool_T, reader, bits, 1, 1);
+        if (r.rc) { set_error("%s: %s", what, r.why); return r.rc; }
+        if (!reader || r.read_bits) nt_bits_tile_map(m, N, K, r, tile_map + (c0 / H2_ROWBLK) * tiles_n);
+    }
+    return TOAD_OK;
+}
 
 extern "C" size_t toad_mil_arena_bytes(int64_t N, int C, int D) {
     const MilShape s{N, C, D};

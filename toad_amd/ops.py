@@ -181,21 +181,37 @@ def _up(v: int, q: int) -> int:
 
 
 def _row_chunks(m: int, row_bytes: int):
-    """Row ranges of one NT launch each: whole operand when its bytes fit 32-bit offsets, else multiples of 256 rows."""
-    if m * row_bytes < (1 << 32):
+    """Row ranges of one NT launch each. By ROWS, with the fixed step of the whole-slide calls (csrc/step.hip nt_rows: one launch up to
+    _CHUNK_ROWS rows, then chunks of _CHUNK_ROWS), whatever the operand's width up to 1024 floats: the forward of a layer and the dgrad that
+    reads its one-bit ReLU image have operands of different widths and must still cut the rows at the same places, since a launch reads the
+    image by ITS OWN tile plan (toad_relu_bits_plan). Only rows wider than 1024 floats take a smaller step (32-bit byte offsets)."""
+    step = _CHUNK_ROWS if _CHUNK_ROWS * row_bytes < (1 << 32) else max(256, ((1 << 32) - 1) // row_bytes // 256 * 256)
+    if m <= step:
         return [(0, m)]
-    step = max(256, min(_CHUNK_ROWS, ((1 << 32) - 1) // row_bytes // 256 * 256))
     return [(r0, min(m, r0 + step)) for r0 in range(0, m, step)]
 
 
+def _bits_chunks_ok(m: int, row_bytes: int) -> bool:
+    """True when an operand of this width is cut like every operand of at most 1024 floats per row - the only geometry in which a one-bit ReLU
+    image is produced (linear_act_fwd) or consumed (linear_dgrad); any other cut masks with the fp32 activations."""
+    return _row_chunks(m, row_bytes) == _row_chunks(m, 4)
+
+
 def linear_act_fwd(x, w, b, act: int, out: Optional[torch.Tensor] = None, drop_p: float = 0.0, drop_seed: int = 0,
-                   x_amax: Optional[torch.Tensor] = None, want_amax: bool = False, want_bits: bool = False):
+                   x_amax: Optional[torch.Tensor] = None, want_amax: bool = False, want_bits: bool = False,
+                   bits_out: Optional[torch.Tensor] = None):
     """Y = dropout_p(act(X W^T + b)); X [M,K], W [N,K], b [N] or None. drop_p = 0 disables dropout.
     x_amax: abs-max array of X (else measured inside). want_amax: also return the abs-max array of Y -> (Y, y_amax).
-    want_bits (act = RELU, h2_ok shapes): also return the one-bit image of Y for the dgrad of this layer -> (Y, y_amax, bits).
-    Shapes outside the two-piece kernels' envelope are zero-padded (K to a multiple of 32, N to a multiple of 4) and operands of >= 2^32 bytes
-    run as row chunks (train-mode dropout then draws chunk j's masks from drop_seed + j * kChunkSeedStep, like the whole-slide calls)."""
+    want_bits (act = RELU, h2_ok shapes): also return the one-bit image of Y for the dgrad of this layer -> (Y, y_amax, bits); bits is None
+    where no image is produced (an output width that is not a multiple of 4, rows wider than 1024 floats cut into chunks).
+    bits_out (implies want_bits): uint8 destination of the image, at least relu_bits_bytes(M, N) bytes; row chunks write their slices of it.
+    Shapes outside the two-piece kernels' envelope are zero-padded (K to a multiple of 32, N to a multiple of 4) and operands of more than
+    _CHUNK_ROWS rows run as row chunks (_row_chunks). Train-mode dropout then draws chunk j's masks from drop_seed + j * kChunkSeedStep at the
+    chunk-local element index: for operands of at most 1024 floats per row these are the chunks, and therefore the masks, of the whole-slide
+    calls (csrc/step.hip nt_rows); wider rows are cut into shorter chunks and draw other masks."""
     _chk(x, "x"); _chk(w, "w"); _chk(b, "b", allow_none=True); _chk(x_amax, "x_amax", allow_none=True)
+    _chk(bits_out, "bits_out", dtype=torch.uint8, allow_none=True)
+    want_bits = want_bits or bits_out is not None
     m, k = x.shape
     n, k2 = w.shape
     if k != k2 or (b is not None and b.numel() != n):
@@ -212,26 +228,39 @@ def linear_act_fwd(x, w, b, act: int, out: Optional[torch.Tensor] = None, drop_p
         else:
             bp = b
         yp = out if (out is not None and np_ == n) else torch.empty((m, np_), dtype=torch.float32, device=x.device)
-        amaxs, bitss = [], []
+        # the image: one buffer, every chunk writes the blocks of its rows (chunks start at multiples of 256 rows). Only in the chunk geometry
+        # the dgrad of the layer will use as well (_bits_chunks_ok), and only where the kernel that writes it runs
+        bits = None
+        if want_bits and np_ == n and _bits_chunks_ok(m, kp * 4) and all(h2_ok(r1 - r0, n, kp) for r0, r1 in chunks):
+            nbits = relu_bits_bytes(m, n)
+            if bits_out is not None and bits_out.numel() < nbits:
+                raise ValueError(f"linear_act_fwd: bits_out needs {nbits} bytes")
+            bits = bits_out[:nbits] if bits_out is not None else torch.empty((nbits,), dtype=torch.uint8, device=x.device)
+        per_blk = relu_bits_bytes(256, n)
+        amaxs = []
         for j, (r0, r1) in enumerate(chunks):
-            xa = None if x_amax is None else x_amax[r0 // 256:(r1 + 255) // 256].contiguous()
+            b0, b1 = r0 // 256, (r1 + 255) // 256
+            xa = None if x_amax is None else x_amax[b0:b1].contiguous()
             res = linear_act_fwd(xp[r0:r1], wp, bp, act, out=yp[r0:r1], drop_p=drop_p, drop_seed=(drop_seed + j * _CHUNK_SEED_STEP) & _M64,
-                                 x_amax=xa, want_amax=want_amax or want_bits, want_bits=want_bits and np_ == n)
+                                 x_amax=xa, want_amax=want_amax or want_bits, bits_out=None if bits is None else bits[b0 * per_blk:b1 * per_blk])
             if want_amax or want_bits:
                 amaxs.append(res[1])
-                if want_bits:
-                    bitss.append(res[2] if np_ == n else None)
         y = yp if np_ == n else yp[:, :n].contiguous()
         if out is not None and y is not out:
             out.copy_(y); y = out
         if want_bits:
-            return y, torch.cat(amaxs), (torch.cat(bitss) if all(t is not None for t in bitss) else None)
+            return y, torch.cat(amaxs), bits
         return (y, torch.cat(amaxs)) if want_amax else y
     y = out if out is not None else torch.empty((m, n), dtype=torch.float32, device=x.device)
     _chk(y, "out")
     lib = _lib.load()
     y_amax = torch.empty((amax_floats(m),), dtype=torch.float32, device=x.device) if (want_amax or want_bits) else None
-    bits = torch.empty((relu_bits_bytes(m, n),), dtype=torch.uint8, device=x.device) if (want_bits and h2_ok(m, n, k)) else None
+    bits = None
+    if want_bits and h2_ok(m, n, k):
+        nbits = relu_bits_bytes(m, n)
+        if bits_out is not None and bits_out.numel() < nbits:
+            raise ValueError(f"linear_act_fwd: bits_out needs {nbits} bytes")
+        bits = bits_out[:nbits] if bits_out is not None else torch.empty((nbits,), dtype=torch.uint8, device=x.device)
     ws = _ws(lib.toad_linear_ws_bytes(m, n, k), x.device)
     with _timed("gemm_fwd"):
         _lib.check(lib.toad_linear_act_fwd_f32(_p(x), _p(w), _p(b), _p(y), m, k, n, act, float(drop_p), int(drop_seed),
@@ -273,6 +302,8 @@ def linear_dgrad(dy, wt, addend=None, relu_src=None, out: Optional[torch.Tensor]
         addp, srcp = _pad_cols(addend, kp), _pad_cols(relu_src, kp)
         poolp = None if pool is None else (pool[0], pool[1], _pad_cols(pool[2], kp))
         dxp = out if (out is not None and kp == k) else torch.empty((m, kp), dtype=torch.float32, device=dy.device)
+        if not _bits_chunks_ok(m, np_ * 4):                # not the chunks the forward of the layer wrote its image in: mask with relu_src alone
+            relu_bits = None
         amaxs = []
         for (r0, r1) in chunks:
             b0, b1 = r0 // 256, (r1 + 255) // 256
