@@ -79,9 +79,13 @@ size_t toad_relu_bits_bytes(int64_t M, int64_t N);
  *   TOAD_BITS_STEP_L1       the first trunk Linear of the whole-slide calls (N = 512, K = 1024; _A16 / _APT = the bag's format) or, with
  *                           _READER, the dgrad that masks with its output (K = 512) - including the calls' choice to hand that dgrad the
  *                           fp32 activations only when the bag was fp16 / prepared. Implies _ROWS.
+ *   TOAD_BITS_MULTI         with _STEP_L1: the same pair as the ragged multi-slide calls launch it - ONE launch each (no row chunks), and an fp16
+ *                           concatenation (_A16) runs its first Linear on half-height tiles wherever an fp32 one does, so the dgrad is ALWAYS
+ *                           handed the image (the one-slide x16 calls keep 256-row tiles and the rule above). No _APT, no _ROWS; with _A16 the
+ *                           totals toad_mil_multi_x16_ok refuses are TOAD_ESHAPE.
  * Returns TOAD_OK, TOAD_ESHAPE for a shape toad_linear_h2_ok refuses, TOAD_EINVAL for a combination the launcher refuses. */
 enum { TOAD_BITS_READER = 1, TOAD_BITS_ADDEND = 2, TOAD_BITS_POOL = 4, TOAD_BITS_POOL_BATCHED = 8, TOAD_BITS_A16 = 16, TOAD_BITS_APT = 32,
-       TOAD_BITS_SELF_MEASURE = 64, TOAD_BITS_ROWS = 128, TOAD_BITS_STEP_L1 = 256 };
+       TOAD_BITS_SELF_MEASURE = 64, TOAD_BITS_ROWS = 128, TOAD_BITS_STEP_L1 = 256, TOAD_BITS_MULTI = 512 };
 int toad_relu_bits_plan(int64_t M, int64_t N, int64_t K, int flags, uint8_t *tile_map);
 
 /* Y[M,N] = act(X[M,K] W[N,K]^T + bias[N]).   bias may be NULL.
@@ -470,6 +474,34 @@ int toad_mil_multi_bwd_f32(const float *const *params, float *const *grads, floa
                            int C, int D, float drop_p, uint64_t seed, const void *arena, size_t arena_bytes,
                            const float *dlogits, const float *dsite, const float *dA_ext, const float *dMcat_ext,
                            void *scratch, size_t scratch_bytes, void *stream);
+
+/* ---- fp16 feature bags on the ragged multi-slide route (an ADDITIVE extension of ABI 15: TOAD_ABI_VERSION stays 15, nothing above changes;
+ * a library built before these symbols existed reports the same version, so loaders must name a missing symbol - toad_amd/_lib.py does) ----
+ * toad_mil_multi_{step,fwd,bwd}_f32 for bags stored as fp16: Xcat16 [sum N_b, 1024] halves, 16-byte aligned, as they lie in a feature store
+ * or an fp16 landing buffer (the reference up-casts whatever the .pt file holds on its way to nn.Linear, datasets/dataset_mtl_concat.py:358-373
+ * -> models/model_toad.py:91; its loop steps one such slide per iteration, utils/core_utils_mtl_concat.py:200-234). No up-cast pass and no
+ * fp32 copy: the first Linear reads the halves as first pieces with scale 1 (two MFMA terms, no abs-max array, half the bytes), and so does its
+ * weight gradient - for calls of at most 262,144 rows inside the ONE launch that computes all three trunk weight gradients. Everything behind
+ * the first Linear is the fp32 route's. Results are those of the *_f32 call on the up-cast bags: the same products with power-of-two scales,
+ * summed in the same order - the first Linear takes half-height tiles exactly where the fp32 call does, and the one-launch weight gradient
+ * keeps the fp32 call's row splits - so the two agree within 1e-6 of each tensor's scale (tests/test_gpu_multi_x16.py). One-bit ReLU image:
+ * both Linears write the tiles the dgrads read, as on the fp32 route (toad_relu_bits_plan, TOAD_BITS_STEP_L1 | TOAD_BITS_MULTI | TOAD_BITS_A16).
+ * Argument order, workspace / arena / scratch sizes and layouts (the queries above serve both), `events`, slide limit and validation: those of
+ * the *_f32 calls. Rows: toad_mil_multi_x16_ok(sum N_b) - the one-slide rule of toad_mil_x16_ok (64 <= N, N * 4096 < 2^32) applied to the
+ * concatenation and cut at the rows ONE launch of the whole-slide calls covers: 64 <= sum N_b <= 1,047,552 (4,092 blocks of 256 rows; the fp32
+ * calls take 1,023 rows more). TOAD_ESHAPE otherwise (callers up-cast such batches). No dX, no dsex. */
+int toad_mil_multi_x16_ok(int64_t Ntot);
+int toad_mil_multi_step_x16_f32(const float *const *params, float *const *grads, float beta, const void *Xcat16,
+                                const int64_t *offsets, int B, const float *sex, const int64_t *label, const int64_t *site,
+                                float w_cls, float w_site, int C, int D, float drop_p, uint64_t seed,
+                                float *loss_out, float *logits_out, float *site_logits_out, void *ws, size_t ws_bytes, void **events,
+                                void *stream);
+int toad_mil_multi_fwd_x16_f32(const float *const *params, const void *Xcat16, const int64_t *offsets, int B, const float *sex, int C, int D,
+                               float drop_p, uint64_t seed, void *arena, size_t arena_bytes, void *scratch, size_t scratch_bytes, void *stream);
+int toad_mil_multi_bwd_x16_f32(const float *const *params, float *const *grads, float beta, const void *Xcat16, const int64_t *offsets, int B,
+                               int C, int D, float drop_p, uint64_t seed, const void *arena, size_t arena_bytes,
+                               const float *dlogits, const float *dsite, const float *dA_ext, const float *dMcat_ext,
+                               void *scratch, size_t scratch_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -79,6 +79,11 @@ SIGNATURES = {
     "toad_mil_multi_scratch_bytes": (SZ, [I64, I, I, I]),
     "toad_mil_multi_fwd_f32": (I, [P, P, P, I, P, I, I, F, U64, P, SZ, P, SZ, P]),
     "toad_mil_multi_bwd_f32": (I, [P, P, F, P, P, I, I, I, F, U64, P, SZ, P, P, P, P, P, SZ, P]),
+    # fp16 bags on the ragged multi-slide route: an additive extension of ABI 15 (the version number does not change)
+    "toad_mil_multi_x16_ok": (I, [I64]),
+    "toad_mil_multi_step_x16_f32": (I, [P, P, F, P, P, I, P, P, P, F, F, I, I, F, U64, P, P, P, P, SZ, P, P]),
+    "toad_mil_multi_fwd_x16_f32": (I, [P, P, P, I, P, I, I, F, U64, P, SZ, P, SZ, P]),
+    "toad_mil_multi_bwd_x16_f32": (I, [P, P, F, P, P, I, I, I, F, U64, P, SZ, P, P, P, P, P, SZ, P]),
 }
 
 _lib = None
@@ -95,7 +100,12 @@ def load() -> ctypes.CDLL:
             "toad_amd has no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError if the symbol is not exported
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            # (additions inside one ABI version - the x16 multi-slide calls of ABI 15 - cannot be told apart by toad_abi_version)
+            raise RuntimeError(f"{LIB_PATH} does not export {name}: it was built from older sources; rebuild "
+                               "(python -m toad_amd.build --force)") from None
         fn.restype = res
         fn.argtypes = args
     got = lib.toad_abi_version()

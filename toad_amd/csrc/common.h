@@ -109,7 +109,7 @@ bool nt_half_tiles(int64_t M, int64_t N);               // fp32-A products of th
 // refusal of the combination, half = half-height tiles (every tile whole), read_bits = a dgrad takes its whole tiles' mask from the image
 struct NtRoute { int rc; const char *why; bool half, read_bits; };
 NtRoute nt_route(int64_t M, int64_t N, int64_t K, int a_mode, bool run_mode, bool addend, int pool_T, bool mask_src, bool mask_bits, int a_stride,
-                 int y_stride);
+                 int y_stride, bool a16_half = false);      // a16_half: an fp16 A operand follows nt_half_tiles too (the multi-slide calls; launch_nt_h2)
 void nt_bits_tile_map(int64_t M, int64_t N, int64_t K, const NtRoute &r, unsigned char *tile_map);
 bool nt_run_ok(int64_t M, int64_t N, int64_t K);       // the first GEMM may measure its fp32 A operand itself (gemm_h2.inc AMODE 3)
 size_t h2_planes_bytes(int64_t N, int64_t K);
@@ -122,7 +122,8 @@ int launch_nt_h2(const float *A, int64_t lda, const float *a_amax, const unsigne
                  int64_t ldc, int64_t M, int64_t N, int64_t K, const float *bias, EpiScalars es, const float *addend,
                  const float *mask_src, const unsigned long long *mask_bits, H2Pool pool, float *slabs, float *y_amax,
                  unsigned long long *bits_out, hipStream_t st, const char *what, int a_mode = TOAD_X_F32, int a_stride = 1, int y_stride = 1,
-                 float *a_amax_out = nullptr, int *slab_ke = nullptr);   // a_amax == NULL + a_amax_out (zeroed) + slab_ke [256]: A is measured inside the GEMM
+                 float *a_amax_out = nullptr, int *slab_ke = nullptr,    // a_amax == NULL + a_amax_out (zeroed) + slab_ke [256]: A is measured inside the GEMM
+                 bool a16_half = false);                                 // fp16 A on half-height tiles where fp32 A would run on them (nt_half_tiles)
 size_t pt_bytes_host(int64_t rows, int64_t cols);                                                          // bytes of a plane-tiled tensor
 int launch_pt_split(const float *X, int64_t ld, int64_t M, int64_t K, const float *amax, unsigned short *pt, hipStream_t st, const char *what);
 int launch_pool_bwd(const float *Pa, const float *Pb, int64_t ldp, const float *H, const float *Wc, const float *A_raw, const float *stats,
@@ -176,9 +177,10 @@ int launch_wgrad(const float *dY, const float *dy_amax, const float *X, const fl
 struct WgradDeferred { const float *slab; float *out; int64_t n; const float *slab2; float *out2; int64_t n2; int nsplit; float beta; const float *scales; };
 int launch_wgrad_reduce(const WgradDeferred *d, int count, hipStream_t st, const char *what);
 // two or three weight gradients over the SAME M rows in one launch (gemm_tn_h2_batch_kernel): fp32 operands with their abs-max arrays, one slab
-// area (toad_linear_wgrad_ws_bytes) each; always deferred - the caller reduces them with launch_wgrad_reduce
+// area (toad_linear_wgrad_ws_bytes) each; always deferred - the caller reduces them with launch_wgrad_reduce. x_mode: how the job's X lies in
+// memory; the LAST of three jobs may be TOAD_X_F16 (the feature bag of the first Linear stored as halves [M][K]: no abs-max array, scale 1).
 constexpr int64_t kTnBatchMaxRows = 262144;
-struct WgradJob { const float *dY, *dy_amax, *X, *x_amax; float *dW, *db; int64_t N, K; void *ws; };
+struct WgradJob { const float *dY, *dy_amax, *X, *x_amax; float *dW, *db; int64_t N, K; void *ws; int x_mode = TOAD_X_F32; };
 bool wgrad_batch_ok(int64_t M, const WgradJob *jobs, int n, size_t ws_bytes_each);
 int launch_wgrad_batch(const WgradJob *jobs, int n, int64_t M, float beta, hipStream_t st, const char *what, WgradDeferred *defer);
 

@@ -87,9 +87,11 @@ static void cfg() {
         TOAD_ATTR((gemm_nt_h2_big_kernel<true, false, 2, 0, 128>), H2_SMEM_HALF);
         TOAD_ATTR((gemm_nt_h2_big_kernel<true, false, 2, 4, 128>), H2_SMEM_HALF);
         TOAD_ATTR((gemm_nt_h2_big_kernel<false, false, 0, 3, 128>), H2_SMEM_HALF_RUN);
+        TOAD_ATTR((gemm_nt_h2_big_kernel<false, false, 0, 1, 128>), H2_SMEM_HALF);       // fp16 bags of the multi-slide calls
         TOAD_ATTR(gemm_tn_h2_big_kernel<false>, TN2_SMEM);
         TOAD_ATTR(gemm_tn_h2_big_kernel<true>, TN2_SMEM);
-        TOAD_ATTR(gemm_tn_h2_batch_kernel, TN2_SMEM);
+        TOAD_ATTR(gemm_tn_h2_batch_kernel<false>, TN2_SMEM);
+        TOAD_ATTR(gemm_tn_h2_batch_kernel<true>, TN2_SMEM);          // third product on the fp16 bag
         TOAD_ATTR(gemm_tn_pt_kernel, TP_SMEM);
         TOAD_ATTR(gemm_nt_f32_kernel, NT_SMEM);
         TOAD_ATTR(gemm_tn_f32_kernel, TN_SMEM);
@@ -222,13 +224,15 @@ bool nt_half_tiles(int64_t M, int64_t N) {
 // is read at all); nt_bits_tile_map lists the tiles with the plan the kernel itself runs (nt_plan, nt_row_tile). toad_relu_bits_plan
 // (step.hip) exposes both to the host, and tests/test_relu_bits_plan.py holds the inclusion over every shape class without a GPU.
 NtRoute nt_route(int64_t M, int64_t N, int64_t K, int a_mode, bool run_mode, bool addend, int pool_T, bool mask_src, bool mask_bits,
-                 int a_stride, int y_stride) {
+                 int a_stride, int y_stride, bool a16_half) {
     NtRoute r{TOAD_OK, nullptr, false, false};
     auto refuse = [&](const char *why) { r.rc = TOAD_EINVAL; r.why = why; return r; };
     if (run_mode && (addend || mask_src || mask_bits || pool_T > 0 || a_stride != 1))
         return refuse("the self-measuring operand mode is a plain forward with per-block scales");
-    if (a_mode != TOAD_X_F32) {   // fp16 / plane-tiled A: 256-row tiles always, plain forward only
+    if (a_mode != TOAD_X_F32) {   // fp16 / plane-tiled A: plain forward only, on 256-row tiles - except the fp16 bags of the multi-slide calls (a16_half),
+                                  // which take half-height tiles exactly where an fp32 A would (the same plan as the fp32 call on the up-cast bags)
         if (addend || mask_src || mask_bits || pool_T > 0) return refuse("the fp16 / plane-tiled operand kernels have no addend / mask / pooling epilogue");
+        r.half = a16_half && a_mode == TOAD_X_F16 && a_stride == 1 && y_stride == 1 && nt_half_tiles(M, N);
         return r;
     }
     if (pool_T > 0 && addend) return refuse("an addend buffer and the recomputed pooling addend are mutually exclusive");
@@ -302,7 +306,7 @@ int launch_nt_h2(const float *A, int64_t lda, const float *a_amax, const unsigne
                         int64_t ldc, int64_t M, int64_t N, int64_t K, const float *bias, EpiScalars es, const float *addend,
                         const float *mask_src, const unsigned long long *mask_bits, H2Pool pool, float *slabs, float *y_amax,
                         unsigned long long *bits_out, hipStream_t st, const char *what, int a_mode, int a_stride, int y_stride, float *a_amax_out,
-                        int *slab_ke) {
+                        int *slab_ke, bool a16_half) {
     const int tiles_m = (int)((M + PB - 1) / PB), tiles_n = (int)((N + PB - 1) / PB);
     (void)cfg();
     // Staggered workgroup starts (gemm_h2.inc) for launches of at least two tiles per workgroup: the 32 workgroups of an XCD start spread over
@@ -313,7 +317,7 @@ int launch_nt_h2(const float *A, int64_t lda, const float *a_amax, const unsigne
     // a_amax == NULL with a_amax_out (fp32 A, plain forward): the kernel measures A itself, stage by stage (AMODE 3, gemm_h2.inc), fills
     // a_amax_out (zeroed by the caller) and slab_ke; the fix-up then reads the completed array
     const bool run_mode = a_mode == TOAD_X_F32 && !a_amax && a_amax_out;
-    const NtRoute rt = nt_route(M, N, K, a_mode, run_mode, addend != nullptr, pool.T, mask_src != nullptr, mask_bits != nullptr, a_stride, y_stride);
+    const NtRoute rt = nt_route(M, N, K, a_mode, run_mode, addend != nullptr, pool.T, mask_src != nullptr, mask_bits != nullptr, a_stride, y_stride, a16_half);
     if (rt.rc) { set_error("%s: %s", what, rt.why); return rt.rc; }
     if (run_mode) {
         if (!slab_ke) { set_error("%s: the self-measuring operand mode is a plain forward with per-block scales", what); return TOAD_EINVAL; }
@@ -343,6 +347,13 @@ int launch_nt_h2(const float *A, int64_t lda, const float *a_amax, const unsigne
         return rcr;
     }
     if (a_mode != TOAD_X_F32) {   // A is fp16 [M, lda halves] or plane-tiled: plain forward only (no addend / mask / pooling variants are instantiated; nt_route)
+        if (rt.half) {            // fp16 A, short operand: half-height tiles, whole K per workgroup, no fix-up launch
+            hipLaunchKernelGGL((gemm_nt_h2_big_kernel<false, false, 0, 1, 128>), dim3(PB_GRID), dim3(512), H2_SMEM_HALF, st, A, lda, (const float *)nullptr, planes,
+                               binv, C, ldc, (int)M, (int)N, (int)K, bias, es, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr,
+                               (const float *)nullptr, (const float *)nullptr, 0, slabs, y_amax, bits_out, (int)((M + 127) / 128), tiles_n, a_stride, y_stride,
+                               (float *)nullptr, (int *)nullptr);
+            return check_launch(what);
+        }
         if (a_mode == TOAD_X_PT)
             hipLaunchKernelGGL((gemm_nt_h2_big_kernel<false, false, 0, 2>), dim3(PB_GRID), dim3(512), H2_SMEM_PT, st, A, lda, a_amax, planes,
                                binv, C, ldc, (int)M, (int)N, (int)K, bias, es, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr,
@@ -814,7 +825,9 @@ int toad::launch_wgrad(const float *dY, const float *dy_amax, const float *X, co
 
 // ---- up to three weight gradients of one backward pass in ONE launch (gemm_tn_h2_batch_kernel, gemm_h2.inc) ----------------------------------
 // Plan: as many row splits as keep every item on its own workgroup (PB_GRID / tiles of all products), each at least four 32-row stages deep for
-// bags that have the rows (one stage for tiny ones), all of the same depth.
+// bags that have the rows (one stage for tiny ones), all of the same depth - also when the last job's X is the fp16 bag (x_mode TOAD_X_F16),
+// whose items issue two MFMA terms per product instead of three: the same splits as the fp32 route keep every sum in the fp32 route's order
+// (gemm_h2.inc, gemm_tn_h2_batch_kernel: a plan with deeper fp16-operand items was measured and missed the routes' 1e-6 agreement).
 struct TnBatchPlan { int nsplit, rows_per_split, tiles_all; };
 static TnBatchPlan tn_batch_plan(int64_t M, const WgradJob *jobs, int n) {
     TnBatchPlan p{0, 0, 0};
@@ -835,7 +848,11 @@ bool toad::wgrad_batch_ok(int64_t M, const WgradJob *jobs, int n, size_t ws_byte
     const TnBatchPlan p = tn_batch_plan(M, jobs, n);
     if (p.nsplit < 1) return false;
     for (int i = 0; i < n; ++i) {
-        if (!jobs[i].dY || !jobs[i].X || !jobs[i].dy_amax || !jobs[i].x_amax || !jobs[i].dW || !jobs[i].ws || !tn_big_ok(M, jobs[i].N, jobs[i].K)) return false;
+        // fp32 operands with their abs-max arrays; the last of three may be the fp16 bag (no abs-max array; 16-byte loads of 8 halves per row)
+        const bool x16 = jobs[i].x_mode == TOAD_X_F16;
+        if (jobs[i].x_mode != TOAD_X_F32 && !(x16 && i == 2)) return false;
+        if (!jobs[i].dY || !jobs[i].X || !jobs[i].dy_amax || (!x16 && !jobs[i].x_amax) || !jobs[i].dW || !jobs[i].ws || !tn_big_ok(M, jobs[i].N, jobs[i].K)) return false;
+        if (x16 && (jobs[i].K % 8 != 0 || !aligned16(jobs[i].X))) return false;
         const size_t need = (size_t)p.nsplit * (size_t)(jobs[i].N * jobs[i].K + jobs[i].N) * sizeof(float) + (size_t)(2 * h2_nblk(M) + 64) * sizeof(float);
         if (need > ws_bytes_each) return false;
     }
@@ -844,18 +861,22 @@ bool toad::wgrad_batch_ok(int64_t M, const WgradJob *jobs, int n, size_t ws_byte
 int toad::launch_wgrad_batch(const WgradJob *jobs, int n, int64_t M, float beta, hipStream_t st, const char *what, WgradDeferred *defer) {
     const TnBatchPlan p = tn_batch_plan(M, jobs, n);
     (void)cfg();
+    const bool x16 = n == 3 && jobs[2].x_mode == TOAD_X_F16;         // (wgrad_batch_ok: only the last of three)
     const float *A[3], *aam[3], *B[3], *bam[3]; float *slab[3], *cs[3], *sc[3]; int I[3], J[3];
     for (int i = 0; i < 3; ++i) {
         const WgradJob &j = jobs[i < n ? i : 0];
-        A[i] = j.dY; aam[i] = j.dy_amax; B[i] = j.X; bam[i] = j.x_amax; I[i] = (int)j.N; J[i] = (int)j.K;
+        A[i] = j.dY; aam[i] = j.dy_amax; B[i] = j.X; bam[i] = j.x_mode == TOAD_X_F16 ? nullptr : j.x_amax; I[i] = (int)j.N; J[i] = (int)j.K;
         slab[i] = reinterpret_cast<float *>(j.ws);
         cs[i] = j.db ? slab[i] + (size_t)p.nsplit * j.N * j.K : nullptr;
         sc[i] = slab[i] + (size_t)p.nsplit * (size_t)(j.N * j.K + j.N);
         if (i < n) defer[i] = WgradDeferred{slab[i], j.dW, j.N * j.K, cs[i], j.db, j.db ? j.N : 0, p.nsplit, beta, sc[i]};
     }
-    hipLaunchKernelGGL(gemm_tn_h2_batch_kernel, dim3(PB_GRID), dim3(512), TN2_SMEM, st, A[0], aam[0], B[0], bam[0], slab[0], cs[0], sc[0], I[0], J[0],
-                       A[1], aam[1], B[1], bam[1], slab[1], cs[1], sc[1], I[1], J[1], A[2], aam[2], B[2], bam[2], slab[2], cs[2], sc[2], I[2], J[2], n, (int)M,
-                       p.rows_per_split, p.nsplit);
+#define TOAD_LAUNCH_TN_BATCH(X16_)                                                                                                                       \
+    hipLaunchKernelGGL(gemm_tn_h2_batch_kernel<X16_>, dim3(PB_GRID), dim3(512), TN2_SMEM, st, A[0], aam[0], B[0], bam[0], slab[0], cs[0], sc[0], I[0], J[0], \
+                       A[1], aam[1], B[1], bam[1], slab[1], cs[1], sc[1], I[1], J[1], A[2], aam[2], B[2], bam[2], slab[2], cs[2], sc[2], I[2], J[2], n, (int)M, \
+                       p.rows_per_split, p.nsplit)
+    if (x16) TOAD_LAUNCH_TN_BATCH(true); else TOAD_LAUNCH_TN_BATCH(false);
+#undef TOAD_LAUNCH_TN_BATCH
     return check_launch(what);
 }
 

@@ -351,7 +351,9 @@ __device__ __forceinline__ float h2_fast_exp(float x) { return __builtin_amdgcn_
 // one per workgroup: no slabs, no fix-up. Same 8 waves (4 x 2), each now 32 x 128 (acc[1][4]: 12 MFMAs per k16 step against 10 ds_read_b128), one
 // staged octet per thread and stage instead of two; the plane image keeps its 256-row geometry (the upper half stays unused). A tile's operand
 // scale still comes from its 256-row block of the abs-max array (two tiles share a slot), the ReLU bit image keeps its per-256-row-block layout
-// (gemm_h2_epilogue.inc: epi_vwave / epi_a0). Instantiated for the MIL step's epilogues only (no residual addend, no fp16 / plane-tiled A).
+// (gemm_h2_epilogue.inc: epi_vwave / epi_a0). Instantiated for the MIL step's epilogues only (no residual addend, no plane-tiled A), and for the
+// fp16 bags of the ragged multi-slide calls (AMODE 1: the plain forward; one 16-byte load per staged octet): the concatenation's first Linear then
+// runs on the tile plan of the fp32 call on the up-cast bags - the same sums in the same order - and loses its K-split fix-up launch like it.
 constexpr int RUN_MARGIN = 3;
 template <bool POOL, bool ADD, int MASK, int AMODE = 0, int TM = PB>
 __global__ __launch_bounds__(512, 2) void gemm_nt_h2_big_kernel(
@@ -366,7 +368,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_h2_big_kernel(
     constexpr bool A16 = AMODE == 1, APT = AMODE == 2, ARUN = AMODE == 3;
     constexpr int NA = TM / 128;                                 // 32-row sub-tiles per wave = octets a thread stages per stage (2, or 1 for half-height tiles)
     constexpr int WROWS = TM / 4;                                // rows per wave row group (64 / 32)
-    static_assert(TM == PB || (TM == 128 && !ADD && !A16 && !APT), "half-height tiles: fp32 A, no addend buffer");
+    static_assert(TM == PB || (TM == 128 && !ADD && !APT), "half-height tiles: fp32 or fp16 A, no addend buffer");
+    constexpr int A_LD = A16 ? 1 : 2;                            // 16-byte loads per staged octet (8 halves / 8 floats)
     constexpr int A_SLOTS = APT ? 3 : 2;
     // LDS geometry of the A plane image: [plane][k-group 0..3][row ^ (k-group << 2)] 16-byte entries, TM rows per k-group
     constexpr int A_KG_BYTES = TM * 16, A_PLANE_BYTES = 4 * A_KG_BYTES, A_SLOT_BYTES = 2 * A_PLANE_BYTES;      // 256 rows: 4,096 / 16,384 / 32,768
@@ -657,9 +660,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_h2_big_kernel(
         }
         if (NB == 3 && total > 1) dma_b(1, c1.kt, t1.tn);  // three B slots: stage 1's planes are requested here, every later stage two steps ahead
         load_a1(0, c1.kt); if (E1) load_a1(1, c1.kt);      // (a repeat of stage 0 when there is only one stage)
-        if (NB == 3) {                                     // B(0) has landed; B(1) (4 requests per wave, when there is a stage 1) and the stage-1 loads (2) stay in flight
-            if (total > 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        if (NB == 3) {                                     // B(0) has landed; B(1) (4 requests per wave, when there is a stage 1) and the stage-1 loads (2; 1 for fp16 A) stay in flight
+            if (total > 1) { if (A_LD == 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); }
+            else if (A_LD == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
         } else if (A16 || !E1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");   // B(0) has landed; the stage-1 loads (4; 2 for fp16 A or one octet) stay in flight
         else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     }
@@ -745,9 +749,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_h2_big_kernel(
                 if (t2.m0 != aoff_m0[1]) { set_aoff1(1, t2.m0); aoff_m0[1] = t2.m0; }
                 load_a1(1, c2.kt);
             }
-            if (NB == 3) {          // B(step+1) (requested a step ago) done; this step's B(step+2) requests (4 per wave, if any) and A loads (2) stay in flight
-                if (more2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            if (NB == 3) {          // B(step+1) (requested a step ago) done; this step's B(step+2) requests (4 per wave, if any) and A loads (2; 1 for fp16 A) stay in flight
+                if (more2) { if (A_LD == 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); }
+                else if (A_LD == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
             } else if (A16 || !E1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");   // B(step+1) (and older stores) done; the A loads (4 / 2) stay in flight
             else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         }
@@ -1234,6 +1239,14 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_h2_big_kernel(
 // Item k = split * tiles_all + tile (split-major: the items of one split share their operand rows in one XCD's L2); workgroup b runs item
 // (b % 8) * 32 + b / 8, i.e. XCD x holds the contiguous items [32 x, 32 x + 32). Values are exactly those of gemm_tn_h2_big_kernel with the same
 // rows_per_split (same stage order inside an item, same fixed-order slab sum).
+// X16: product 2's B operand is the fp16 feature bag (gemm_tn_h2_body's B16: two MFMA terms per product, scale 1, no abs-max array), products
+// 0 and 1 stay fp32; a workgroup picks its body by product (workgroup-uniform, both bodies share the LDS image and the register budget). The
+// plan is the SAME as for three fp32 products, so products 0 and 1 are bitwise those of the fp32 launch and product 2 sums the same non-zero
+// terms in the same order as the fp32 launch on the up-cast bag. (Its items finish after two thirds of the MFMA work of the others. A plan that
+// gave them their own, 3/2 deeper row splits and the fp32 products the workgroups that frees was measured on the 10k ... 100k-row batches:
+// every sum then runs in another order than on the fp32 route and dWab / dbab / dW1 moved by up to 1.6e-6 of their magnitude, beyond the
+// 1e-6 the fp16 route promises against the fp32 one - tests/test_gpu_multi_x16.py - so the launch keeps one depth for all items.)
+template <bool X16 = false>
 __global__ __launch_bounds__(512, 2) void gemm_tn_h2_batch_kernel(
     const float *__restrict__ A0, const float *__restrict__ aam0, const float *__restrict__ B0, const float *__restrict__ bam0, float *__restrict__ slab0,
     float *__restrict__ cs0, float *__restrict__ sc0, int I0, int J0,
@@ -1250,6 +1263,11 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_h2_batch_kernel(
     const int split = k / tiles_all, tt = k - split * tiles_all;
     const int g = tt < t0 ? 0 : (tt < t0 + t1 ? 1 : 2);                      // workgroup-uniform
     const int tile = tt - (g == 0 ? 0 : (g == 1 ? t0 : t0 + t1));
+    if (X16 && g == 2) {                                                     // the product on the fp16 bag (ldb in halves)
+        gemm_tn_h2_body<true, true>(A2, I2, aam2, B2, J2, nullptr, slab2, cs2, sc2, Mred, I2, J2, rows_per_split, ti2, tj2, nsplit, split, tile,
+                                    split == 0 && tile == 0);
+        return;
+    }
     const float *A = g == 0 ? A0 : (g == 1 ? A1 : A2), *aam = g == 0 ? aam0 : (g == 1 ? aam1 : aam2);
     const float *B = g == 0 ? B0 : (g == 1 ? B1 : B2), *bam = g == 0 ? bam0 : (g == 1 ? bam1 : bam2);
     float *slab = g == 0 ? slab0 : (g == 1 ? slab1 : slab2), *cs = g == 0 ? cs0 : (g == 1 ? cs1 : cs2), *sc = g == 0 ? sc0 : (g == 1 ? sc1 : sc2);

@@ -272,14 +272,15 @@ static int backward_body(const MilShape &s, const Params &p, float *const *grads
         TOAD_TRY(launch_pool_bwd(f.P, f.P + s.D, D2, f.H, p.wc, f.A_raw, f.stats, f.M, dM, dA_ext, w.dP, w.dP + s.D, D2, nullptr,
                                  grads[6], grads[7], beta, w.amax_dP, false, w.poolb_ws, w.poolb_ws_bytes, N, kL, s.D, kT, drop_p, ds.sa, ds.sb, st));
         WgradDeferred dw[3];
-        // Bags of at most kTnBatchMaxRows rows (raw fp32): the three weight gradients wait for the end of the pass and run as ONE launch
+        // Bags of at most kTnBatchMaxRows rows (raw fp32, or fp16 as stored: the launch's third product then runs the B16 body): the three weight
+        // gradients wait for the end of the pass and run as ONE launch
         // (launch_wgrad_batch: dP / dZ2 / dZ1 and the saved activations all still exist then) - a third of the slab traffic and two launches less
         // than three launches of the per-XCD plan: 10k patches 142 -> 86 us, 100k patches 724 -> 661 us of the step's weight-gradient time
         // (profiles/r06*); at 500k concatenated rows the two orders measure the same, and longer calls keep the interleaved one.
         const WgradJob wj[3] = {{w.dP, w.amax_dP, f.H, f.amax_h, grads[4], grads[5], D2, kL, w.wgrad_ws},
                                 {w.dZ2, w.amax_dZ2, f.H1, f.amax_h1, grads[2], grads[3], kL, kL, w.wgrad_ws2},
-                                {w.dZ1, w.amax_dZ1, X, f.amax_x, grads[0], grads[1], kL, kL0, w.wgrad_ws3}};
-        const bool wbatch = x_mode == TOAD_X_F32 && wgrad_batch_ok(N, wj, 3, w.wgrad_ws_bytes);
+                                {w.dZ1, w.amax_dZ1, X, x_mode == TOAD_X_F32 ? f.amax_x : nullptr, grads[0], grads[1], kL, kL0, w.wgrad_ws3, x_mode}};
+        const bool wbatch = wgrad_batch_ok(N, wj, 3, w.wgrad_ws_bytes);          // (refuses a prepared bag: its third product has a kernel of its own)
         if (!wbatch) { ev(8); TOAD_TRY(launch_wgrad(w.dP, w.amax_dP, f.H, f.amax_h, grads[4], grads[5], N, D2, kL, beta, w.wgrad_ws, st, what, TOAD_X_F32, &dw[0])); ev(9); }
         // dZ2 = (dP Wab + dH_pool) * (H > 0): the pooling gradient dH_pool is recomputed in the epilogue from A_raw, stats, dM
         ev(10); TOAD_TRY(nt_rows(w.dP, D2, w.amax_dP, w.planes[W_ABT], w.binv[W_ABT], w.dZ2, kL, N, kL, D2, nullptr, msk, nullptr, f.H, f.bits_h,
@@ -336,11 +337,17 @@ using namespace toad;
 extern "C" int toad_relu_bits_plan(int64_t M, int64_t N, int64_t K, int flags, uint8_t *tile_map) {
     const char *what = "toad_relu_bits_plan";
     const int known = TOAD_BITS_READER | TOAD_BITS_ADDEND | TOAD_BITS_POOL | TOAD_BITS_POOL_BATCHED | TOAD_BITS_A16 | TOAD_BITS_APT |
-                      TOAD_BITS_SELF_MEASURE | TOAD_BITS_ROWS | TOAD_BITS_STEP_L1;
+                      TOAD_BITS_SELF_MEASURE | TOAD_BITS_ROWS | TOAD_BITS_STEP_L1 | TOAD_BITS_MULTI;
     if (!tile_map || (flags & ~known) || ((flags & TOAD_BITS_A16) && (flags & TOAD_BITS_APT)) || ((flags & TOAD_BITS_POOL) && (flags & TOAD_BITS_POOL_BATCHED))) {
         set_error("%s: bad argument", what); return TOAD_EINVAL;
     }
-    const bool reader = flags & TOAD_BITS_READER, step_l1 = flags & TOAD_BITS_STEP_L1, rows = step_l1 || (flags & TOAD_BITS_ROWS);
+    // TOAD_BITS_MULTI: the pair as the ragged multi-slide calls launch it (multi_forward_body / multi_backward_body): ONE launch each, no row chunks,
+    // an fp16 concatenation on half-height tiles where an fp32 one is, and the dgrad always handed the image; no prepared bags on that route
+    const bool multi = flags & TOAD_BITS_MULTI;
+    if (multi && (!(flags & TOAD_BITS_STEP_L1) || (flags & (TOAD_BITS_APT | TOAD_BITS_ROWS)))) {
+        set_error("%s: TOAD_BITS_MULTI goes with TOAD_BITS_STEP_L1, an fp32 or fp16 bag and no row chunks", what); return TOAD_EINVAL;
+    }
+    const bool reader = flags & TOAD_BITS_READER, step_l1 = flags & TOAD_BITS_STEP_L1, rows = (step_l1 && !multi) || (flags & TOAD_BITS_ROWS);
     const int x_mode = (flags & TOAD_BITS_A16) ? TOAD_X_F16 : (flags & TOAD_BITS_APT) ? TOAD_X_PT : TOAD_X_F32;
     if (step_l1 && (N != kL || K != (reader ? kL : kL0))) { set_error("%s: TOAD_BITS_STEP_L1 is the 1024 -> 512 Linear and the 512-deep dgrad behind it", what); return TOAD_ESHAPE; }
     // the A operand of the launch: the bag in its own format for the step's first Linear, else what the flags say; the dgrad of the step reads fp32 dZ2
@@ -349,15 +356,16 @@ extern "C" int toad_relu_bits_plan(int64_t M, int64_t N, int64_t K, int flags, u
     const int64_t lda = K, ldc = N;
     bool ok = (rows && a_mode == TOAD_X_F32) ? nt_rows_ok(M, N, K, lda, ldc) : h2_nt_ok(M, N, K, lda, ldc);
     if (x_mode != TOAD_X_F32 && rows) ok = ok && M <= kChunkRows && h2_nt_ok(M, kL, kL0, kL0, kL);      // (an fp16 / prepared bag is ONE launch: nt_rows refuses to chunk it)
+    if (multi && x_mode == TOAD_X_F16) ok = ok && toad_mil_multi_x16_ok(M);                              // (the totals the fp16 multi-slide calls take)
     if (!ok) { set_error("%s: not a shape of the fp16 two-piece NT kernel (toad_linear_h2_ok)", what); return TOAD_ESHAPE; }
     const int tiles_n = (int)((N + 255) / 256);
     memset(tile_map, 0, (size_t)((M + 255) / 256) * tiles_n);
-    const bool bits = reader && (!step_l1 || step_dgrad1_reads_bits(x_mode, M));          // (the step hands the image to its dgrad or not)
+    const bool bits = reader && (!step_l1 || multi || step_dgrad1_reads_bits(x_mode, M));          // (the step hands the image to its dgrad or not)
     const int pool_T = (flags & TOAD_BITS_POOL_BATCHED) ? (2 | (8 << 8)) : (flags & TOAD_BITS_POOL) ? 2 : 0;
     const int n_chunks = rows ? nt_row_chunks(M) : 1;
     for (int j = 0; j < n_chunks; ++j) {
         const int64_t c0 = rows ? nt_row_chunk_first(j) : 0, m = rows ? nt_row_chunk_rows(M, j) : M;
-        const NtRoute r = nt_route(m, N, K, a_mode, (flags & TOAD_BITS_SELF_MEASURE) != 0, (flags & TOAD_BITS_ADDEND) != 0, pool_T, reader, bits, 1, 1);
+        const NtRoute r = nt_route(m, N, K, a_mode, (flags & TOAD_BITS_SELF_MEASURE) != 0, (flags & TOAD_BITS_ADDEND) != 0, pool_T, reader, bits, 1, 1, multi);
         if (r.rc) { set_error("%s: %s", what, r.why); return r.rc; }
         if (!reader || r.read_bits) nt_bits_tile_map(m, N, K, r, tile_map + (c0 / H2_ROWBLK) * tiles_n);
     }
@@ -627,7 +635,8 @@ static int multi_batch_ok(const int64_t *offsets, int B, int C, int D, float dro
 // with the same weights inside the same call, as in forward_body), the three GEMMs over all rows, the batched pool forward + merge.
 template <typename Ev>
 static int multi_forward_body(const MilShape &s, const Params &p, const float *Xcat, const Fwd &f, const Scratch &w, const MultiSmall &ms, int B,
-                              int64_t max_n, float drop_p, uint64_t seed, bool with_backward_operands, hipStream_t st, Ev ev, const char *what) {
+                              int64_t max_n, float drop_p, uint64_t seed, bool with_backward_operands, hipStream_t st, Ev ev, const char *what,
+                              int x_mode) {
     const int64_t N = s.N;
     const int D = s.D, D2 = 2 * D;
     const DropSeeds ds = drop_seeds(drop_p, seed);
@@ -642,11 +651,15 @@ static int multi_forward_body(const MilShape &s, const Params &p, const float *X
         if (with_backward_operands) TOAD_TRY(launch_split_h2(ops5, 5, f.amax_x, nz, st, what, w.amax_dP, nzb));
         else TOAD_TRY(launch_split_h2(ops5, 3, f.amax_x, nz, st, what));
     }
-    // the concatenated bags are measured inside the first GEMM (no abs-max pass of its own), which fills f.amax_x for the weight gradient below
-    const bool self_measure = nt_run_ok(N, kL, kL0);
-    if (!self_measure) TOAD_TRY(launch_absmax(Xcat, kL0, N, kL0, f.amax_x, false, st, what));
-    ev(2); TOAD_TRY(launch_nt_h2(Xcat, kL0, self_measure ? nullptr : f.amax_x, w.planes[W_1], w.binv[W_1], f.H1, kL, N, kL, kL0, p.b1, relu1, nullptr, nullptr, nullptr, nopool,
-                                 w.slabs, f.amax_h1, f.bits_h1, st, what, TOAD_X_F32, 1, 1, self_measure ? f.amax_x : nullptr, self_measure ? w.slab_ke : nullptr)); ev(3);
+    // the concatenated fp32 bags are measured inside the first GEMM (no abs-max pass of its own), which fills f.amax_x for the weight gradient below;
+    // fp16 bags (TOAD_X_F16: Xcat points to halves) are first pieces with scale 1 - the A16 kernel, no abs-max array, nothing to measure. The launch
+    // takes half-height tiles where the fp32 one does (a16_half): both routes then sum the same products in the same order, and both write the
+    // ReLU image of H1 for every tile the dgrad below reads (toad_relu_bits_plan, TOAD_BITS_MULTI)
+    const bool x16 = x_mode == TOAD_X_F16;
+    const bool self_measure = !x16 && nt_run_ok(N, kL, kL0);
+    if (!x16 && !self_measure) TOAD_TRY(launch_absmax(Xcat, kL0, N, kL0, f.amax_x, false, st, what));
+    ev(2); TOAD_TRY(launch_nt_h2(Xcat, kL0, (x16 || self_measure) ? nullptr : f.amax_x, w.planes[W_1], w.binv[W_1], f.H1, kL, N, kL, kL0, p.b1, relu1, nullptr, nullptr, nullptr, nopool,
+                                 w.slabs, f.amax_h1, f.bits_h1, st, what, x_mode, 1, 1, self_measure ? f.amax_x : nullptr, self_measure ? w.slab_ke : nullptr, x16)); ev(3);
     ev(4); TOAD_TRY(launch_nt_h2(f.H1, kL, f.amax_h1, w.planes[W_2], w.binv[W_2], f.H, kL, N, kL, kL, p.b2, relu2, nullptr, nullptr, nullptr, nopool, w.slabs, f.amax_h, f.bits_h, st, what)); ev(5);
     ev(6); TOAD_TRY(launch_nt_h2(f.H, kL, f.amax_h, w.planes[W_AB], w.binv[W_AB], f.P, D2, N, D2, kL, p.bab, lin, nullptr, nullptr, nullptr, nopool, w.slabs, nullptr, nullptr, st, what)); ev(7);
     // ---- all slides at once (blockIdx.y = slide): fused pool forward on each row range + merge. Together with the heads and the pooling backward
@@ -664,7 +677,7 @@ static int multi_forward_body(const MilShape &s, const Params &p, const float *X
 template <typename Ev>
 static int multi_backward_body(const MilShape &s, const Params &p, float *const *grads, float beta, const float *Xcat, const Fwd &f, const Scratch &w,
                                const MultiSmall &ms, int B, int64_t max_n, const float *dA_ext, float drop_p, uint64_t seed, hipStream_t st, Ev ev,
-                               const char *what) {
+                               const char *what, int x_mode) {
     const int64_t N = s.N;
     const int D = s.D, D2 = 2 * D;
     const DropSeeds ds = drop_seeds(drop_p, seed);
@@ -690,13 +703,15 @@ static int multi_backward_body(const MilShape &s, const Params &p, float *const 
     WgradDeferred dw[3];
     const WgradJob wj[3] = {{w.dP, w.amax_dP, f.H, f.amax_h, grads[4], grads[5], D2, kL, w.wgrad_ws},
                             {w.dZ2, w.amax_dZ2, f.H1, f.amax_h1, grads[2], grads[3], kL, kL, w.wgrad_ws2},
-                            {w.dZ1, w.amax_dZ1, Xcat, f.amax_x, grads[0], grads[1], kL, kL0, w.wgrad_ws3}};
+                            {w.dZ1, w.amax_dZ1, Xcat, x_mode == TOAD_X_F32 ? f.amax_x : nullptr, grads[0], grads[1], kL, kL0, w.wgrad_ws3, x_mode}};
     const bool wbatch = wgrad_batch_ok(N, wj, 3, w.wgrad_ws_bytes);          // a short batch: the three weight gradients as one launch at the end (backward_body)
     if (!wbatch) { ev(8); TOAD_TRY(launch_wgrad(w.dP, w.amax_dP, f.H, f.amax_h, grads[4], grads[5], N, D2, kL, beta, w.wgrad_ws, st, what, TOAD_X_F32, &dw[0])); ev(9); }
     // dZ2 = (dP Wab + dH_pool) * (H > 0): dH_pool[row] = sum_t w_t(row) dM_t[slide(row)] recomputed in the epilogue (batched pooled addend)
     ev(10); TOAD_TRY(launch_nt_h2(w.dP, D2, w.amax_dP, w.planes[W_ABT], w.binv[W_ABT], w.dZ2, kL, N, kL, D2, nullptr, msk, nullptr, f.H, f.bits_h,
                                   H2Pool{rowrec, nullptr, ms.dM, kT | (rec_f << 8)}, w.slabs, w.amax_dZ2, nullptr, st, what)); ev(11);
     if (!wbatch) { ev(12); TOAD_TRY(launch_wgrad(w.dZ2, w.amax_dZ2, f.H1, f.amax_h1, grads[2], grads[3], N, kL, kL, beta, w.wgrad_ws2, st, what, TOAD_X_F32, &dw[1])); ev(13); }
+    // (the image of H1 is safe to read for an fp16 bag as well: its first Linear ran on half-height tiles wherever this dgrad does - multi_forward_body's
+    //  a16_half - unlike the one-slide x16 calls, whose A16 forward keeps 256-row tiles and which therefore go by step_dgrad1_reads_bits)
     ev(14); TOAD_TRY(launch_nt_h2(w.dZ2, kL, w.amax_dZ2, w.planes[W_2T], w.binv[W_2T], w.dZ1, kL, N, kL, kL, nullptr, msk, nullptr, f.H1, f.bits_h1, nopool, w.slabs,
                                   w.amax_dZ1, nullptr, st, what)); ev(15);
     if (wbatch) {
@@ -704,7 +719,7 @@ static int multi_backward_body(const MilShape &s, const Params &p, float *const 
         TOAD_TRY(launch_wgrad_reduce(dw, 3, st, what)); ev(9);
         ev(12); ev(13); ev(16); ev(17);
     } else {
-        ev(16); TOAD_TRY(launch_wgrad(w.dZ1, w.amax_dZ1, Xcat, f.amax_x, grads[0], grads[1], N, kL, kL0, beta, w.wgrad_ws3, st, what, TOAD_X_F32, &dw[2]));
+        ev(16); TOAD_TRY(launch_wgrad(w.dZ1, w.amax_dZ1, Xcat, f.amax_x, grads[0], grads[1], N, kL, kL0, beta, w.wgrad_ws3, st, what, x_mode, &dw[2]));
         TOAD_TRY(launch_wgrad_reduce(dw, 3, st, what)); ev(17);
     }
     return TOAD_OK;
@@ -717,16 +732,28 @@ extern "C" size_t toad_mil_multi_ws_bytes(int64_t Ntot, int B, int C, int D) {
     return a ? a + multi_small_layout(B, nullptr).total + 4096 : 0;
 }
 
-extern "C" int toad_mil_multi_step_f32(const float *const *params, float *const *grads, float beta, const float *Xcat,
-                                        const int64_t *offsets, int B, const float *sex, const int64_t *label, const int64_t *site,
-                                        float w_cls, float w_site, int C, int D, float drop_p, uint64_t seed,
-                                        float *loss_out, float *logits_out, float *site_logits_out, void *ws, size_t ws_bytes, void **events,
-                                        void *stream) {
-    const char *what = "toad_mil_multi_step_f32";
+// fp16 bags on the multi-slide route: the total the A16 first Linear and the B16 weight gradient take as ONE launch each - the one-slide rule
+// (toad_mil_x16_ok) applied to the concatenation, up to the rows one launch of the whole-slide calls covers (kChunkRows: what nt_rows hands the
+// A16 kernel for one slide)
+extern "C" int toad_mil_multi_x16_ok(int64_t Ntot) { return (Ntot <= kChunkRows && toad_mil_x16_ok(Ntot)) ? 1 : 0; }
+static int multi_x16_check(int x_mode, int64_t N, const char *what) {
+    if (x_mode == TOAD_X_F16 && !toad_mil_multi_x16_ok(N)) {
+        set_error("%s: fp16 bags need 64 <= sum N_b <= 1047552 (toad_mil_multi_x16_ok), got %lld", what, (long long)N);
+        return TOAD_ESHAPE;
+    }
+    return TOAD_OK;
+}
+
+static int mil_multi_step_impl(const float *const *params, float *const *grads, float beta, const float *Xcat,
+                               const int64_t *offsets, int B, const float *sex, const int64_t *label, const int64_t *site,
+                               float w_cls, float w_site, int C, int D, float drop_p, uint64_t seed,
+                               float *loss_out, float *logits_out, float *site_logits_out, void *ws, size_t ws_bytes, void **events,
+                               void *stream, int x_mode, const char *what) {
     if (!params || !grads || !Xcat || !offsets || !sex || !label || !site || !loss_out || !ws) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
     int64_t N = 0, max_n = 0;
     TOAD_TRY(multi_batch_ok(offsets, B, C, D, drop_p, what, N, max_n));
     const MilShape s{N, C, D};
+    TOAD_TRY(multi_x16_check(x_mode, N, what));
     if (!aligned16(Xcat)) { set_error("%s: Xcat must be 16-byte aligned", what); return TOAD_EALIGN; }
     if (ws_bytes < toad_mil_multi_ws_bytes(N, B, C, D)) { set_error("%s: workspace too small", what); return TOAD_EWORKSPACE; }
     Params p;
@@ -749,7 +776,7 @@ extern "C" int toad_mil_multi_step_f32(const float *const *params, float *const 
         return TOAD_EINVAL;
     }
     // ---- forward: one launch splits the five weight operands and zeroes both groups of abs-max arrays; three GEMMs over all rows; batched pool
-    TOAD_TRY(multi_forward_body(s, p, Xcat, f, w, ms, B, max_n, drop_p, seed, true, st, ev, what));
+    TOAD_TRY(multi_forward_body(s, p, Xcat, f, w, ms, B, max_n, drop_p, seed, true, st, ev, what, x_mode));
     // heads + weighted CE + heads backward with one workgroup per slide, then the head-weight gradients summed over the batch
     const HeadsBatch hb{ms.M, ms.Mcat, ms.logits, ms.yprob, ms.yhat, ms.slog, ms.sprob, ms.shat, ms.dM, ms.dl, ms.dsv, kSlideRec};
     TOAD_TRY(launch_heads_batch(hb, sex, p.wcls, p.bcls, p.wsite, p.bsite, label, site, w_cls, w_site, loss_out, grads[8], grads[9], grads[10], grads[11], beta,
@@ -763,7 +790,25 @@ extern "C" int toad_mil_multi_step_f32(const float *const *params, float *const 
         return TOAD_EINVAL;
     }
     // ---- pooling backward, backward GEMMs and weight gradients over all rows (the dgrad operands were split by the forward's launch)
-    return multi_backward_body(s, p, grads, beta, Xcat, f, w, ms, B, max_n, nullptr, drop_p, seed, st, ev, what);
+    return multi_backward_body(s, p, grads, beta, Xcat, f, w, ms, B, max_n, nullptr, drop_p, seed, st, ev, what, x_mode);
+}
+extern "C" int toad_mil_multi_step_f32(const float *const *params, float *const *grads, float beta, const float *Xcat,
+                                        const int64_t *offsets, int B, const float *sex, const int64_t *label, const int64_t *site,
+                                        float w_cls, float w_site, int C, int D, float drop_p, uint64_t seed,
+                                        float *loss_out, float *logits_out, float *site_logits_out, void *ws, size_t ws_bytes, void **events,
+                                        void *stream) {
+    return mil_multi_step_impl(params, grads, beta, Xcat, offsets, B, sex, label, site, w_cls, w_site, C, D, drop_p, seed, loss_out, logits_out,
+                               site_logits_out, ws, ws_bytes, events, stream, TOAD_X_F32, "toad_mil_multi_step_f32");
+}
+// the same step for bags stored as fp16 (utils/core_utils_mtl_concat.py:200-234 over a batch; the reference up-casts whatever the .pt file holds,
+// datasets/dataset_mtl_concat.py:358-373): Xcat16 [sum N_b, 1024] halves as they lie in the feature store, no fp32 copy
+extern "C" int toad_mil_multi_step_x16_f32(const float *const *params, float *const *grads, float beta, const void *Xcat16,
+                                            const int64_t *offsets, int B, const float *sex, const int64_t *label, const int64_t *site,
+                                            float w_cls, float w_site, int C, int D, float drop_p, uint64_t seed,
+                                            float *loss_out, float *logits_out, float *site_logits_out, void *ws, size_t ws_bytes, void **events,
+                                            void *stream) {
+    return mil_multi_step_impl(params, grads, beta, reinterpret_cast<const float *>(Xcat16), offsets, B, sex, label, site, w_cls, w_site, C, D, drop_p,
+                               seed, loss_out, logits_out, site_logits_out, ws, ws_bytes, events, stream, TOAD_X_F16, "toad_mil_multi_step_x16_f32");
 }
 
 // ---- the ragged multi-slide forward and backward as two calls (ABI 14) -----------------------------------------------------------------------
@@ -840,14 +885,14 @@ static int multi_buffers_ok(const MilShape &s, int B, const void *arena, size_t 
     return TOAD_OK;
 }
 
-extern "C" int toad_mil_multi_fwd_f32(const float *const *params, const float *Xcat, const int64_t *offsets, int B, const float *sex, int C, int D,
-                                       float drop_p, uint64_t seed, void *arena, size_t arena_bytes, void *scratch, size_t scratch_bytes,
-                                       void *stream) {
-    const char *what = "toad_mil_multi_fwd_f32";
+static int mil_multi_fwd_impl(const float *const *params, const float *Xcat, const int64_t *offsets, int B, const float *sex, int C, int D,
+                              float drop_p, uint64_t seed, void *arena, size_t arena_bytes, void *scratch, size_t scratch_bytes,
+                              void *stream, int x_mode, const char *what) {
     if (!params || !Xcat || !offsets || !sex || !arena || !scratch) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
     int64_t N = 0, max_n = 0;
     TOAD_TRY(multi_batch_ok(offsets, B, C, D, drop_p, what, N, max_n));
     const MilShape s{N, C, D};
+    TOAD_TRY(multi_x16_check(x_mode, N, what));
     if (!aligned16(Xcat)) { set_error("%s: Xcat must be 16-byte aligned", what); return TOAD_EALIGN; }
     char *ab, *sb;
     MultiIO io;
@@ -862,20 +907,33 @@ extern "C" int toad_mil_multi_fwd_f32(const float *const *params, const float *X
         set_error("%s: copying the slide offsets to the device failed: %s", what, hipGetErrorString(hipGetLastError()));
         return TOAD_EINVAL;
     }
-    TOAD_TRY(multi_forward_body(s, p, Xcat, f, w, io.ms, B, max_n, drop_p, seed, false, st, NoEvents{}, what));
+    TOAD_TRY(multi_forward_body(s, p, Xcat, f, w, io.ms, B, max_n, drop_p, seed, false, st, NoEvents{}, what, x_mode));
     return launch_heads_fwd_batch(io.ms.M, (int)(kSlideRec / sizeof(float)), sex, p.wcls, p.bcls, p.wsite, p.bsite, io.Mcat, io.logits, io.yprob, io.yhat,
                                   io.slog, io.sprob, io.shat, B, kL, C, st);
 }
-
-extern "C" int toad_mil_multi_bwd_f32(const float *const *params, float *const *grads, float beta, const float *Xcat, const int64_t *offsets, int B,
-                                       int C, int D, float drop_p, uint64_t seed, const void *arena, size_t arena_bytes, const float *dlogits,
-                                       const float *dsite, const float *dA_ext, const float *dMcat_ext, void *scratch, size_t scratch_bytes,
+extern "C" int toad_mil_multi_fwd_f32(const float *const *params, const float *Xcat, const int64_t *offsets, int B, const float *sex, int C, int D,
+                                       float drop_p, uint64_t seed, void *arena, size_t arena_bytes, void *scratch, size_t scratch_bytes,
                                        void *stream) {
-    const char *what = "toad_mil_multi_bwd_f32";
+    return mil_multi_fwd_impl(params, Xcat, offsets, B, sex, C, D, drop_p, seed, arena, arena_bytes, scratch, scratch_bytes, stream, TOAD_X_F32,
+                              "toad_mil_multi_fwd_f32");
+}
+// models/model_toad.py:90-116 for every slide of a batch whose bags are stored as fp16 (Xcat16 [sum N_b, 1024] halves)
+extern "C" int toad_mil_multi_fwd_x16_f32(const float *const *params, const void *Xcat16, const int64_t *offsets, int B, const float *sex, int C, int D,
+                                           float drop_p, uint64_t seed, void *arena, size_t arena_bytes, void *scratch, size_t scratch_bytes,
+                                           void *stream) {
+    return mil_multi_fwd_impl(params, reinterpret_cast<const float *>(Xcat16), offsets, B, sex, C, D, drop_p, seed, arena, arena_bytes, scratch,
+                              scratch_bytes, stream, TOAD_X_F16, "toad_mil_multi_fwd_x16_f32");
+}
+
+static int mil_multi_bwd_impl(const float *const *params, float *const *grads, float beta, const float *Xcat, const int64_t *offsets, int B,
+                              int C, int D, float drop_p, uint64_t seed, const void *arena, size_t arena_bytes, const float *dlogits,
+                              const float *dsite, const float *dA_ext, const float *dMcat_ext, void *scratch, size_t scratch_bytes,
+                              void *stream, int x_mode, const char *what) {
     if (!params || !grads || !Xcat || !offsets || !arena || !scratch || !dlogits || !dsite) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
     int64_t N = 0, max_n = 0;
     TOAD_TRY(multi_batch_ok(offsets, B, C, D, drop_p, what, N, max_n));
     const MilShape s{N, C, D};
+    TOAD_TRY(multi_x16_check(x_mode, N, what));
     if (!aligned16(Xcat)) { set_error("%s: Xcat must be 16-byte aligned", what); return TOAD_EALIGN; }
     char *ab, *sb;
     MultiIO io;
@@ -893,5 +951,20 @@ extern "C" int toad_mil_multi_bwd_f32(const float *const *params, float *const *
     // heads backward per slide (dM records + dlogits / dsite records), then the head-weight gradients summed over the batch
     TOAD_TRY(launch_heads_bwd_batch(io.Mcat, dlogits, dsite, dMcat_ext, p.wcls, p.wsite, io.ms.dM, (int)(kSlideRec / sizeof(float)), io.dl, io.ds, grads[8],
                                     grads[9], grads[10], grads[11], beta, B, kL, C, st));
-    return multi_backward_body(s, p, grads, beta, Xcat, f, w, io.ms, B, max_n, dA_ext, drop_p, seed, st, NoEvents{}, what);
+    return multi_backward_body(s, p, grads, beta, Xcat, f, w, io.ms, B, max_n, dA_ext, drop_p, seed, st, NoEvents{}, what, x_mode);
+}
+extern "C" int toad_mil_multi_bwd_f32(const float *const *params, float *const *grads, float beta, const float *Xcat, const int64_t *offsets, int B,
+                                       int C, int D, float drop_p, uint64_t seed, const void *arena, size_t arena_bytes, const float *dlogits,
+                                       const float *dsite, const float *dA_ext, const float *dMcat_ext, void *scratch, size_t scratch_bytes,
+                                       void *stream) {
+    return mil_multi_bwd_impl(params, grads, beta, Xcat, offsets, B, C, D, drop_p, seed, arena, arena_bytes, dlogits, dsite, dA_ext, dMcat_ext, scratch,
+                              scratch_bytes, stream, TOAD_X_F32, "toad_mil_multi_bwd_f32");
+}
+// loss.backward() (utils/core_utils_mtl_concat.py:213-231) of toad_mil_multi_fwd_x16_f32 for the same fp16 bags
+extern "C" int toad_mil_multi_bwd_x16_f32(const float *const *params, float *const *grads, float beta, const void *Xcat16, const int64_t *offsets, int B,
+                                           int C, int D, float drop_p, uint64_t seed, const void *arena, size_t arena_bytes, const float *dlogits,
+                                           const float *dsite, const float *dA_ext, const float *dMcat_ext, void *scratch, size_t scratch_bytes,
+                                           void *stream) {
+    return mil_multi_bwd_impl(params, grads, beta, reinterpret_cast<const float *>(Xcat16), offsets, B, C, D, drop_p, seed, arena, arena_bytes, dlogits,
+                              dsite, dA_ext, dMcat_ext, scratch, scratch_bytes, stream, TOAD_X_F16, "toad_mil_multi_bwd_x16_f32");
 }

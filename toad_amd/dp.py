@@ -71,6 +71,8 @@ def hip_batch_grad(model, grads: Dict[str, torch.Tensor], slides: Sequence[Slide
     """One library call for a whole shard of (small) slides: the trunk / attention GEMMs of forward and backward run once over the
     concatenated bags, pooling / heads / loss per slide (toad_mil_multi_step_f32). grads = beta*grads + scale * sum_b d loss_b.
     ``xcat`` / ``offsets``: the bags already concatenated on the device (an ingest buffer); else they are concatenated here.
+    A shard whose bags are all fp16 runs as stored (toad_mil_multi_step_x16_f32: no up-cast, and no copy when the bags lie back to back in
+    an fp16 landing buffer); any other mix of dtypes is up-cast to fp32 (``SlideShardedDP.accumulate`` cuts its runs where the dtype changes).
     Returns the per-slide loss vectors [B, 3]."""
     from . import ops
     from .model_toad import _draw_dropout
@@ -80,8 +82,7 @@ def hip_batch_grad(model, grads: Dict[str, torch.Tensor], slides: Sequence[Slide
     label = torch.cat([s[2].reshape(1) for s in slides])
     site = torch.cat([s[3].reshape(1) for s in slides])
     if xcat is None:
-        bags = [s[0].float() if s[0].dtype != torch.float32 else s[0] for s in slides]
-        loss, _, _ = ops.mil_multi_step(w, grads, beta, bags, sex, label, site, w_cls * scale, w_site * scale, drop_p, seed)
+        loss, _, _ = ops.mil_multi_step(w, grads, beta, [s[0] for s in slides], sex, label, site, w_cls * scale, w_site * scale, drop_p, seed)
     else:
         loss, _, _ = ops.mil_multi_step(w, grads, beta, xcat, sex, label, site, w_cls * scale, w_site * scale, drop_p, seed, offsets=offsets)
     return loss
@@ -176,9 +177,10 @@ class SlideShardedDP:
     def accumulate(self, slides: Sequence[Slide], global_slides: int, overwrite: bool = True, batched: Optional[bool] = None):
         """grads (+)= sum over ``slides`` of d(loss)/d(params) / global_slides. With ``overwrite`` the
         first slide is written with beta = 0, which replaces a zeroing pass over the bucket.
-        ``batched`` (default: when this rank holds several fp32 bags of at most BATCH_MAX_PATCHES patches and the default slide
+        ``batched`` (default: when this rank holds several bags of at most BATCH_MAX_PATCHES patches and the default slide
         function is in use): consecutive small slides go through ONE ragged multi-slide call per <= BATCH_ROWS rows
-        (hip_batch_grad): same gradient to fp32 round-off, a fraction of the launches."""
+        (hip_batch_grad): same gradient to fp32 round-off, a fraction of the launches. A run is also cut where the dtype of the bags
+        changes, so fp16 bags go to the x16 multi-slide call as stored and a mixed shard becomes several calls, not an up-cast."""
         self._check_flat()
         if not slides:
             if overwrite:
@@ -192,7 +194,8 @@ class SlideShardedDP:
             losses, first, i = [], True, 0
             while i < len(slides):
                 j, rows = i, 0
-                while j < len(slides) and small(slides[j]) and rows + slides[j][0].shape[0] <= self.batch_rows:
+                while j < len(slides) and small(slides[j]) and rows + slides[j][0].shape[0] <= self.batch_rows \
+                        and slides[j][0].dtype == slides[i][0].dtype:
                     rows += slides[j][0].shape[0]; j += 1
                 beta = 0.0 if (overwrite and first) else 1.0
                 if j - i >= 2:

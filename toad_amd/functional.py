@@ -246,7 +246,8 @@ class ToadMILBatch(torch.autograd.Function):
     bab, drop_p, seed); outputs (logits [B,C], site_logits [B,2], a_raw [sum N_b,2], features [B,2,513], and the non-differentiable Y_prob,
     Y_hat [B,1], site_prob, site_hat [B,1]).
 
-    forward = toad_mil_multi_fwd_f32, backward = toad_mil_multi_bwd_f32: one C call each, whatever the loss. The arena (activations of the
+    forward = toad_mil_multi_fwd_f32, backward = toad_mil_multi_bwd_f32 (their *_x16_f32 forms for an fp16 xcat, which the arena then keeps
+    as stored: half the bytes of the bag held between forward and backward): one C call each, whatever the loss. The arena (activations of the
     concatenation) is owned by the autograd context, so backward(retain_graph=True) can be followed by another backward. Train-mode dropout
     draws the masks of toad_mil_multi_step_f32 for the same (drop_p, seed): streams over the CONCATENATED rows, not the per-slide masks of
     ToadMIL. No gradient reaches the bags or the sexes."""

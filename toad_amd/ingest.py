@@ -38,13 +38,19 @@ class BagPrefetcher:
     """Iterate ``(bag, label, site, sex)`` device tensors in record order with ``depth`` bags in flight."""
 
     def __init__(self, records: Sequence[Record], device: Union[str, torch.device], depth: int = 2, workers: int = 2,
-                 dtype: Optional[torch.dtype] = torch.float32, prepare: bool = False, arena_rows: int = 0):
+                 dtype: Optional[torch.dtype] = torch.float32, prepare: bool = False, arena_rows: int = 0,
+                 arena_dtype: torch.dtype = torch.float32):
         """``arena_rows`` > 0: consecutive fp32 bags are landed BACK TO BACK in device buffers of that many rows (a new buffer when the next bag
         does not fit; a bag longer than the buffer gets an allocation of its own) and handed out as views. Bags that share a buffer are their own
         concatenation, so ``SlideShardedDP`` / ``ops.mil_multi_step`` batch them into one ragged multi-slide call without copying a row
         (``ops._adjacent_rows``); set it to the DP wrapper's ``batch_rows``. A buffer is released when the last view of it dies - so ONE retained
         bag keeps its whole landing buffer alive (``arena_rows`` x features x 4 bytes: 2 GB at 524,288 rows of 1,024 features); hold copies, not
         views, of bags that must outlive their step. One buffer serves one feature width: a bag of another width starts a fresh buffer.
+        ``arena_dtype``: the element type of the landing buffers. ``torch.float32`` (default): fp16 / bf16 files are up-cast while they land.
+        ``torch.float16`` (together with ``dtype=torch.float16``): fp16 files land AS THEY ARE - half the link bytes and half the buffer (1 GB at
+        524,288 rows) - and are handed out as fp16 views, which ``ops._adjacent_rows`` joins like fp32 ones, so the batched trainer reads them
+        through the x16 multi-slide calls (toad_mil_multi_step_x16_f32) with no up-cast and no copy. A file that is NOT fp16 is down-cast on
+        landing: that loses bits (11-bit significands, |x| <= 65504), and it is the caller's choice - it asked for fp16.
         ``prepare``: hand the consumer ``ops.PreparedBag`` objects instead of fp32 tensors (toad_bag_prepare_f32, ABI 9): right behind
         its host-to-device copy, on the COPY stream, every bag is brought into the plane-tiled two-piece form the first Linear and its
         weight gradient take by LDS-DMA, and the fp32 copy is released. The training stream then never measures or splits the bag
@@ -65,21 +71,25 @@ class BagPrefetcher:
             raise ValueError("BagPrefetcher(prepare=True) needs a HIP device (toad_amd has no CPU path)")
         self.copy_stream = torch.cuda.Stream(device=self.device) if self.on_gpu else None
         self.arena_rows = max(0, int(arena_rows))
-        if self.arena_rows and (self.prepare or dtype is not torch.float32):
-            raise ValueError("BagPrefetcher(arena_rows=...) lands fp32 bags: leave dtype at torch.float32 and prepare off")
+        if arena_dtype not in (torch.float32, torch.float16):
+            raise ValueError("BagPrefetcher(arena_dtype=...) must be torch.float32 or torch.float16")
+        self.arena_dtype = arena_dtype
+        if self.arena_rows and (self.prepare or dtype is not arena_dtype):
+            raise ValueError("BagPrefetcher(arena_rows=...) lands fp32 bags: leave dtype at torch.float32 and prepare off "
+                             "(fp16 landing buffers: dtype=torch.float16 together with arena_dtype=torch.float16)")
         self._arena: Optional[torch.Tensor] = None              # current landing buffer [arena_rows, features] and the rows already taken
         self._arena_used = 0
 
     def _land(self, t: torch.Tensor) -> torch.Tensor:
-        """Device fp32 copy of host bag ``t`` inside the current landing buffer (called on the copy stream, in record order)."""
+        """Device copy (in ``arena_dtype``) of host bag ``t`` inside the current landing buffer (called on the copy stream, in record order)."""
         n, k = t.shape
         if n > self.arena_rows or n == 0:
-            return t.to(self.device, non_blocking=True).to(torch.float32)
+            return t.to(self.device, non_blocking=True).to(self.arena_dtype)
         if self._arena is None or self._arena.shape[1] != k or self._arena_used + n > self.arena_rows:
-            self._arena = torch.empty((self.arena_rows, k), dtype=torch.float32, device=self.device)
+            self._arena = torch.empty((self.arena_rows, k), dtype=self.arena_dtype, device=self.device)
             self._arena_used = 0
         view = self._arena[self._arena_used:self._arena_used + n]
-        view.copy_(t, non_blocking=True)                        # H2D (+ up-cast of fp16 / bf16 files) straight into place
+        view.copy_(t, non_blocking=True)                        # H2D (+ the cast of a file of another dtype) straight into place
         self._arena_used += n
         return view
 

@@ -408,7 +408,9 @@ class TOAD_fc_mtl_concat(nn.Module):
 
     def forward_batch(self, bags, sexes, return_features=False):
         """Forward over a BATCH of slides of different lengths WITH autograd (no reference counterpart: the reference steps slide by slide,
-        utils/core_utils_mtl_concat.py:200-234). ``bags``: a list of [N_b, 1024] device tensors (fp16 / bf16 / fp64 bags are up-cast to fp32);
+        utils/core_utils_mtl_concat.py:200-234). ``bags``: a list of [N_b, 1024] device tensors. fp16 bags stay fp16 when ALL bags of the call are
+        fp16 (toad_mil_multi_{fwd,bwd}_x16_f32: no up-cast, no copy when they lie back to back in one buffer, and the fp16 concatenation is what
+        the autograd context holds for the backward; batches below 64 rows in total are up-cast); bf16 / fp64 bags and mixed lists are up-cast to fp32;
         ``sexes``: one entry per bag (a [B] device tensor, or a list of device tensors / numbers). Returns one result dict per slide with the
         keys of ``forward`` (``features`` when asked); every tensor is a view into the batch's outputs, so a loss over any of them - e.g.
         ``sum(f(out[b]) for b in range(B))`` - back-propagates through ONE library call (toad_mil_multi_bwd_f32), as ONE forward call
@@ -421,7 +423,7 @@ class TOAD_fc_mtl_concat(nn.Module):
         over the concatenated rows - not the per-slide masks. No gradient reaches the bags or the sexes (a bag or sex that requires grad is
         refused), and PreparedBag inputs are not taken. Limits: at most 4,096 slides and 1,048,575 rows per call; split larger batches."""
         if any(getattr(b, "is_prepared_bag", False) for b in bags):
-            raise TypeError("forward_batch concatenates fp32 bags; pass the tensors, not PreparedBag objects")
+            raise TypeError("forward_batch concatenates fp32 / fp16 bags; pass the tensors, not PreparedBag objects")
         if len(bags) != len(sexes):
             raise ValueError(f"forward_batch: one sex entry per bag (got {len(bags)} bags and {len(sexes)} sexes)")
         if len(bags) == 0:
@@ -451,7 +453,7 @@ class TOAD_fc_mtl_concat(nn.Module):
         drop_p, seed = _draw_dropout(self._dropout and self.training)
         w = self._weights()
         _require_cuda(w["w1"], "model parameters")
-        xcat, offsets = ops._concat_bags([b if b.dtype == torch.float32 else b.float() for b in bags])
+        xcat, offsets = ops._concat_bags(bags)              # (all fp16: kept as stored; anything else: fp32)
         sp = [w[k] for k in F_.SLOTS]
         if torch.is_grad_enabled() and any(p.requires_grad for p in sp):
             logits, site_logits, a_raw, feats, y_prob, y_hat, site_prob, site_hat = F_.ToadMILBatch.apply(

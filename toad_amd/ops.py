@@ -709,15 +709,16 @@ def _adjacent_rows(bags):
     """Bags that already lie back to back in ONE allocation (an ingest buffer filled slide after slide, or views cut from a concatenated
     tensor) are their own concatenation: return it as a view, or None. Saves the copy of every bag row that torch.cat would make."""
     first = bags[0]
-    if first.dtype != torch.float32 or first.dim() != 2:
+    if first.dtype not in (torch.float32, torch.float16) or first.dim() != 2:
         return None
+    esz = first.element_size()                   # fp16 landing buffers (BagPrefetcher(arena_dtype=torch.float16)) are joined like fp32 ones
     store = first.untyped_storage().data_ptr()
-    nxt, rows = first.data_ptr() + first.numel() * 4, first.shape[0]
+    nxt, rows = first.data_ptr() + first.numel() * esz, first.shape[0]
     for b in bags[1:]:
-        if b.dtype != torch.float32 or b.dim() != 2 or b.shape[1] != first.shape[1] or not b.is_contiguous() \
+        if b.dtype != first.dtype or b.dim() != 2 or b.shape[1] != first.shape[1] or not b.is_contiguous() \
                 or b.untyped_storage().data_ptr() != store or b.data_ptr() != nxt:
             return None
-        nxt += b.numel() * 4
+        nxt += b.numel() * esz
         rows += b.shape[0]
     return torch.as_strided(first, (rows, first.shape[1]), (first.shape[1], 1))
 
@@ -727,22 +728,15 @@ def mil_multi_step(w, grads, beta: float, bags, sex, label, site, w_cls: float =
     """forward + weighted CE + backward for a BATCH of slides in ONE library call (toad_mil_multi_step_f32): the trunk / attention GEMMs
     run once over the concatenated bags, pooling + heads + loss per slide. ``bags``: a list of fp32 [N_b, 1024] device tensors
     (concatenated here), or ONE already concatenated [sum N_b, 1024] tensor together with ``offsets`` (list of B + 1 row offsets).
+    fp16 bags - a list that is fp16 throughout, or an fp16 concatenation - run as stored (toad_mil_multi_step_x16_f32: no up-cast, no fp32
+    copy); mixed lists and totals toad_mil_multi_x16_ok refuses are up-cast.
     ``sex`` [B] float32, ``label`` / ``site`` [B] int64 device tensors. grads = beta*grads + sum over the batch.
     Returns (loss [B,3], logits [B,C] | None, site_logits [B,2] | None)."""
     import ctypes
-    if offsets is None:
-        bags = [b.contiguous() for b in bags]
-        offsets = [0]
-        for b in bags:
-            offsets.append(offsets[-1] + int(b.shape[0]))
-        xcat = bags[0] if len(bags) == 1 else _adjacent_rows(bags)
-        if xcat is None:
-            xcat = torch.cat(bags, 0)
-    else:
-        xcat = bags
-        offsets = [int(o) for o in offsets]
+    xcat, offsets = _concat_bags(bags, offsets)
     nb = len(offsets) - 1
-    _chk(xcat, "bags"); _chk(sex, "sex"); _chk(label, "label", dtype=torch.int64); _chk(site, "site", dtype=torch.int64)
+    half = _chk_xcat(xcat)
+    _chk(sex, "sex"); _chk(label, "label", dtype=torch.int64); _chk(site, "site", dtype=torch.int64)
     if xcat.dim() != 2 or xcat.shape[0] != offsets[-1] or sex.numel() != nb or label.numel() != nb or site.numel() != nb:
         raise ValueError("mil_multi_step: one sex / label / site entry per slide and offsets[-1] == rows of the concatenation")
     ws_t = [w[k] for k in STEP_SLOTS]
@@ -768,9 +762,10 @@ def mil_multi_step(w, grads, beta: float, bags, sex, label, site, w_cls: float =
         nev = 18 if _TIMING_LEVEL >= 2 else 2
         ev_objs = [_take_event() for _ in range(nev)]
         events = (ctypes.c_void_p * 18)(*([e.cuda_event for e in ev_objs] + [None] * (18 - nev)))
-    _lib.check(lib.toad_mil_multi_step_f32(_ptr_array(ws_t), _ptr_array(gs_t), float(beta), _p(xcat), offs, nb, _p(sex), _p(label), _p(site),
-                                           float(w_cls), float(w_site), c, d, float(drop_p), int(seed), _p(loss), _p(logits), _p(slog),
-                                           _p(ws), ws.numel(), events, _stream()), "toad_mil_multi_step_f32")
+    fn, name = (lib.toad_mil_multi_step_x16_f32, "toad_mil_multi_step_x16_f32") if half else (lib.toad_mil_multi_step_f32, "toad_mil_multi_step_f32")
+    _lib.check(fn(_ptr_array(ws_t), _ptr_array(gs_t), float(beta), _p(xcat), offs, nb, _p(sex), _p(label), _p(site),
+                  float(w_cls), float(w_site), c, d, float(drop_p), int(seed), _p(loss), _p(logits), _p(slog),
+                  _p(ws), ws.numel(), events, _stream()), name)
     if ev_objs is not None:
         _TIMING.setdefault("pool_fwd", []).append((ev_objs[0], ev_objs[1]))
         if len(ev_objs) == 18:
@@ -778,7 +773,7 @@ def mil_multi_step(w, grads, beta: float, bags, sex, label, site, w_cls: float =
                 _TIMING.setdefault(name, []).append((ev_objs[2 + 2 * i], ev_objs[3 + 2 * i]))
             # whole-call bucket from the events the library already records: first GEMM's start .. the deferred weight-gradient reduction's end
             # (the weight split launch in front of the first GEMM, ~6 us, is outside it; no extra event packets on the stream)
-            _TIMING.setdefault("mil_multi_step", []).append((ev_objs[2], ev_objs[17]))
+            _TIMING.setdefault("mil_multi_step_x16" if half else "mil_multi_step", []).append((ev_objs[2], ev_objs[17]))
     return loss, logits, slog
 
 
@@ -919,7 +914,7 @@ MULTI_MAX_ROWS = (1 << 20) - 1             # sum N_b: the concatenation is ONE l
 class MilMultiArena(MilArena):
     """The forward arena of a batch of slides (toad_mil_multi_arena_layout): saved activations of the concatenation, per-slide pooling
     records, the device copy of the offsets and the dense per-slide outputs, as typed views of ONE allocation. Keeps the concatenated bag
-    and the offsets the forward ran on (the backward needs both)."""
+    (fp32, or fp16 as stored: half the bytes held between forward and backward) and the offsets the forward ran on (the backward needs both)."""
 
     def __init__(self, xcat: torch.Tensor, offsets, c: int, d: int, cached: bool = False):
         import ctypes
@@ -946,16 +941,35 @@ class MilMultiArena(MilArena):
 
 
 def _concat_bags(bags, offsets=None):
-    """(xcat, offsets): a list of fp32 [N_b, 1024] bags concatenated once (bags already back to back in one allocation are taken as they are), or
-    an already concatenated tensor with its B + 1 row offsets."""
+    """(xcat, offsets): a list of [N_b, 1024] bags concatenated once (bags already back to back in one allocation are taken as they are), or
+    an already concatenated tensor with its B + 1 row offsets. A list whose bags are ALL fp16 stays fp16 (the x16 multi-slide calls read it as
+    stored) when the library takes the total (toad_mil_multi_x16_ok); any other list is up-cast to fp32, and so is an fp16 total it refuses."""
     if offsets is None:
-        bags = [b.contiguous() for b in bags]
+        half = all(b.dtype == torch.float16 for b in bags) and multi_x16_ok(sum(int(b.shape[0]) for b in bags))
+        bags = [(b if half or b.dtype == torch.float32 else b.float()).contiguous() for b in bags]
         offsets = [0]
         for b in bags:
             offsets.append(offsets[-1] + int(b.shape[0]))
         xcat = bags[0] if len(bags) == 1 else _adjacent_rows(bags)
         return (torch.cat(bags, 0) if xcat is None else xcat), offsets
-    return bags, [int(o) for o in offsets]
+    xcat, offsets = bags, [int(o) for o in offsets]
+    if xcat.dtype == torch.float16 and not multi_x16_ok(int(xcat.shape[0])):
+        xcat = xcat.float()
+    return xcat, offsets
+
+
+def multi_x16_ok(rows: int) -> bool:
+    """The ragged multi-slide calls take fp16 bags of this many concatenated rows as stored (toad_mil_multi_x16_ok); others are up-cast."""
+    return bool(_lib.load().toad_mil_multi_x16_ok(int(rows)))
+
+
+def _chk_xcat(xcat) -> bool:
+    """The concatenated bags of a multi-slide call: fp32 (-> False) or fp16 as stored (toad_mil_multi_*_x16_f32, -> True)."""
+    if xcat.dtype == torch.float16:
+        _chk(xcat, "bags", dtype=torch.float16)
+        return True
+    _chk(xcat, "bags")
+    return False
 
 
 def _multi_scratch(n: int, nb: int, c: int, d: int, dev) -> torch.Tensor:
@@ -968,13 +982,15 @@ def _multi_scratch(n: int, nb: int, c: int, d: int, dev) -> torch.Tensor:
 def mil_multi_fwd(w, bags_or_xcat, sex, drop_p: float = 0.0, seed: int = 0, offsets=None, cached_arena: bool = False):
     """models/model_toad.py:90-116 for a BATCH of slides in ONE library call (toad_mil_multi_fwd_f32): the trunk / attention GEMMs run once over
     the concatenated bags, pooling and heads per slide. ``bags``: a list of fp32 [N_b, 1024] device tensors (concatenated here, once), or ONE
-    concatenated tensor with ``offsets`` (B + 1 row offsets); ``sex`` [B] float32 on the device. Returns (arena, outputs): the MilMultiArena the backward needs
+    concatenated tensor with ``offsets`` (B + 1 row offsets); fp16 bags as for mil_multi_step (toad_mil_multi_fwd_x16_f32: the arena then keeps
+    the fp16 concatenation for the backward); ``sex`` [B] float32 on the device. Returns (arena, outputs): the MilMultiArena the backward needs
     and MilMultiArena.outputs(). Dropout masks are those of mil_multi_step for the same (drop_p, seed). ``cached_arena``: forward-only use (see
     MilArena): clone what you keep."""
     import ctypes
     xcat, offsets = _concat_bags(bags_or_xcat, offsets)
     nb = len(offsets) - 1
-    _chk(xcat, "bags"); _chk(sex, "sex")
+    half = _chk_xcat(xcat)
+    _chk(sex, "sex")
     if xcat.dim() != 2 or nb < 1 or xcat.shape[0] != offsets[-1] or sex.numel() != nb:
         raise ValueError("mil_multi_fwd: one sex entry per slide and offsets[-1] == rows of the concatenation")
     ws_t = [w[k] for k in STEP_SLOTS]
@@ -985,9 +1001,10 @@ def mil_multi_fwd(w, bags_or_xcat, sex, drop_p: float = 0.0, seed: int = 0, offs
     arena = MilMultiArena(xcat, offsets, c, d, cached=cached_arena)
     scratch = _multi_scratch(n, nb, c, d, xcat.device)
     offs = (ctypes.c_int64 * (nb + 1))(*offsets)
-    with _timed("mil_multi_fwd"):
-        _lib.check(lib.toad_mil_multi_fwd_f32(_ptr_array(ws_t), _p(xcat), offs, nb, _p(sex), c, d, float(drop_p), int(seed), _p(arena.buf), arena.buf.numel(),
-                                              _p(scratch), scratch.numel(), _stream()), "toad_mil_multi_fwd_f32")
+    fn, name = (lib.toad_mil_multi_fwd_x16_f32, "toad_mil_multi_fwd_x16_f32") if half else (lib.toad_mil_multi_fwd_f32, "toad_mil_multi_fwd_f32")
+    with _timed("mil_multi_fwd_x16" if half else "mil_multi_fwd"):
+        _lib.check(fn(_ptr_array(ws_t), _p(xcat), offs, nb, _p(sex), c, d, float(drop_p), int(seed), _p(arena.buf), arena.buf.numel(),
+                      _p(scratch), scratch.numel(), _stream()), name)
     return arena, arena.outputs()
 
 
@@ -1004,7 +1021,8 @@ def mil_multi_bwd(w, grads, beta: float, xcat, offsets, arena: MilMultiArena, dl
     nb = len(offsets) - 1
     if tuple(offsets) != arena.offsets or xcat.shape[0] != arena.n:
         raise ValueError("mil_multi_bwd: the offsets / bags must be those of the forward that filled the arena")
-    _chk(xcat, "bags"); _chk(dlogits, "dlogits"); _chk(dsite, "dsite")
+    half = _chk_xcat(xcat)
+    _chk(dlogits, "dlogits"); _chk(dsite, "dsite")
     _chk(da_ext, "da_ext", allow_none=True); _chk(dmcat_ext, "dmcat_ext", allow_none=True)
     ws_t = [w[k] for k in STEP_SLOTS]
     gs_t = [grads[k] for k in STEP_SLOTS]
@@ -1020,10 +1038,11 @@ def mil_multi_bwd(w, grads, beta: float, xcat, offsets, arena: MilMultiArena, dl
     lib = _lib.load()
     scratch = _multi_scratch(n, nb, c, d, xcat.device)
     offs = (ctypes.c_int64 * (nb + 1))(*offsets)
-    with _timed("mil_multi_bwd"):
-        _lib.check(lib.toad_mil_multi_bwd_f32(_ptr_array(ws_t), _ptr_array(gs_t), float(beta), _p(xcat), offs, nb, c, d, float(drop_p), int(seed),
-                                              _p(arena.buf), arena.buf.numel(), _p(dlogits), _p(dsite), _p(da_ext), _p(dmcat_ext), _p(scratch),
-                                              scratch.numel(), _stream()), "toad_mil_multi_bwd_f32")
+    fn, name = (lib.toad_mil_multi_bwd_x16_f32, "toad_mil_multi_bwd_x16_f32") if half else (lib.toad_mil_multi_bwd_f32, "toad_mil_multi_bwd_f32")
+    with _timed("mil_multi_bwd_x16" if half else "mil_multi_bwd"):
+        _lib.check(fn(_ptr_array(ws_t), _ptr_array(gs_t), float(beta), _p(xcat), offs, nb, c, d, float(drop_p), int(seed),
+                      _p(arena.buf), arena.buf.numel(), _p(dlogits), _p(dsite), _p(da_ext), _p(dmcat_ext), _p(scratch),
+                      scratch.numel(), _stream()), name)
 
 
 # ---- feature-extractor pieces (conv.hip) --------------------------------------------------------------------------

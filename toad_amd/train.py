@@ -243,7 +243,8 @@ def validate(model, loader: Iterable, n_classes: int, loss_fn=None, with_auc: bo
 
 def train_loop_dp(epoch: int, dp, loader: Iterable, batch_slides: int) -> Dict[str, object]:
     """One epoch under DATA-PARALLEL semantics: one optimiser step per ``batch_slides`` slides of this rank (times the world size), through
-    ``SlideShardedDP.step`` - small fp32 bags of a batch go through ONE ragged multi-slide library call (toad_mil_multi_step_f32: trunk /
+    ``SlideShardedDP.step`` - small bags of a batch (fp32, or fp16 as an fp16 ingest hands them out: toad_mil_multi_step_x16_f32, no up-cast)
+    go through ONE ragged multi-slide library call (toad_mil_multi_step_f32: trunk /
     attention GEMMs once over the concatenated bags), the gradient is all-reduced once per step. The reference steps once per SLIDE
     (utils/core_utils_mtl_concat.py:200-234, batch size 1, utils/utils.py:51-55); this is the loop to use when its real bags - a few
     hundred to a few thousand patches - should fill a GPU: 77.6k instead of 4.5k slides/s at 256 patches (64 per step). Every rank must
