@@ -307,6 +307,36 @@ size_t toad_resnet50_trunc_ws_bytes(int B, int H, int W);
 int toad_resnet50_trunc_fwd_f32(const float *tiles_nchw, const float *const *weights, const float *const *biases,
                                 float *feat, int B, int H, int W, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- The extractor's front end: uint8 tiles as decoded -> bag rows (an additive extension of ABI 15; the version number does not change) ----
+ * The reference tree has no feature-extraction script: its extractor (models/resnet_custom.py:95-108) is fed tiles that torchvision's ToTensor + Normalize
+ * have already turned into normalised fp32 NCHW on the CPU, with the statistics of the ImageNet weights resnet_custom.py:121-124 loads
+ * (mean 0.485 0.456 0.406, std 0.229 0.224 0.225). The calls below take what an image decoder hands over instead - uint8, RGB, channels last,
+ * [B,H,W,3] on the device - and normalise on the device:
+ *     x = fmaf((float)u, a_c, b_c),   a_c = 1 / (255 std_c),   b_c = -mean_c / std_c          (one rounding per value)
+ * `norm` is a HOST array of six floats, a_R a_G a_B b_R b_G b_B, computed by the caller in double precision and rounded once to fp32; it is read at
+ * call time (the values travel as kernel arguments). Every value must be finite (a std of 0 arrives as an infinite a_c): TOAD_EINVAL otherwise.
+ * Taps outside the image are 0 in NORMALISED space (Normalize, then the convolution's zero padding of resnet_custom.py:62), not b_c.
+ * Each call is bitwise its fp32 twin fed out[b,c,y,x] = fmaf(u[b,y,x,c], a_c, b_c). */
+
+/* ToTensor + Normalize as one kernel: tiles uint8 [B,H,W,3] (any alignment) -> out fp32 [B,3,H,W] (16-byte aligned), the input form of
+ * ResNet_Baseline.forward (resnet_custom.py:95-96). Any B, H, W >= 1 with H*W < 2^31. */
+int toad_tiles_u8_nhwc_to_nchw_f32(const unsigned char *tiles, const float *norm, float *out, int B, int H, int W, void *stream);
+
+/* toad_stem_pool_nchw_f32 (conv1 + bn1 + relu + maxpool, resnet_custom.py:96-99) straight from uint8 tiles [B,H,256,3]: the window loader reads the tiles as
+ * stored and normalises while it converts its window, no fp32 image exists. Shapes, Wf, workspace and Yp as for toad_stem_pool_nchw_f32 (W == 256,
+ * H % 4 == 0; TOAD_ESHAPE otherwise). `tiles` must be 2-byte aligned (a pixel pair is read as a 4-byte and a 2-byte word): TOAD_EALIGN otherwise. */
+int toad_stem_pool_nhwc_u8(const unsigned char *tiles, const float *norm, const float *Wf, const float *bias, float *Yp, int B, int H, int W,
+                           void *ws, size_t ws_bytes, void *stream);
+
+/* ResNet_Baseline.forward (resnet_custom.py:95-108) on uint8 tiles [B,H,W,3]; weights / biases as for toad_resnet50_trunc_fwd_f32, and the shapes it refuses.
+ * feat (fp32 [B,1024]) and feat_f16 (fp16 [B,1024] = the fp32 row rounded to nearest even, stored by the average pool: the form the *_x16 calls read) - either
+ * may be NULL, not both; both 16-byte aligned. Tiles with W == 256 and H % 4 == 0 go through toad_stem_pool_nhwc_u8 (`tiles` 2-byte aligned, TOAD_EALIGN
+ * otherwise); other shapes are converted by toad_tiles_u8_nhwc_to_nchw_f32 into a staging image at the end of the workspace (any alignment) and take the
+ * fp32 call's stem. toad_resnet50_trunc_u8_ws_bytes = the fp32 figure, plus the staging image only for the shapes that need it. */
+size_t toad_resnet50_trunc_u8_ws_bytes(int B, int H, int W);
+int toad_resnet50_trunc_fwd_u8(const unsigned char *tiles, const float *norm, const float *const *weights, const float *const *biases,
+                               float *feat, void *feat_f16, int B, int H, int W, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- Whole-slide calls: forward, backward, training step -------------------------------- */
 
 /* The reference drives this path through three Python statements,

@@ -84,6 +84,11 @@ SIGNATURES = {
     "toad_mil_multi_step_x16_f32": (I, [P, P, F, P, P, I, P, P, P, F, F, I, I, F, U64, P, P, P, P, SZ, P, P]),
     "toad_mil_multi_fwd_x16_f32": (I, [P, P, P, I, P, I, I, F, U64, P, SZ, P, SZ, P]),
     "toad_mil_multi_bwd_x16_f32": (I, [P, P, F, P, P, I, I, I, F, U64, P, SZ, P, P, P, P, P, SZ, P]),
+    # uint8 NHWC tiles into the extractor: additive to ABI 15 as well
+    "toad_tiles_u8_nhwc_to_nchw_f32": (I, [P, P, P, I, I, I, P]),
+    "toad_stem_pool_nhwc_u8": (I, [P, P, P, P, P, I, I, I, P, SZ, P]),
+    "toad_resnet50_trunc_u8_ws_bytes": (SZ, [I, I, I]),
+    "toad_resnet50_trunc_fwd_u8": (I, [P, P, P, P, P, P, I, I, I, P, SZ, P]),
 }
 
 _lib = None

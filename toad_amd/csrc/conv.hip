@@ -11,6 +11,7 @@
 // the NHWC activation); the explicit gathers below (16-B lanes, coalesced on the channel dimension) remain for strided
 // 1x1 convolutions, for small batches of the 256-channel 3x3, and as API entry points.
 #include "common.h"
+#include "stem_u8.h"
 
 namespace toad {
 
@@ -126,7 +127,9 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_nhwc_kernel(const float *__r
 
 // nn.AdaptiveAvgPool2d(1) + flatten (resnet_custom.py:70,104-105): feat[b, c] = mean over the HW pixels of X[b, :, c].
 // Block = (tile b, 256 channels): 4 pixel groups x 64 lanes x 16 B; fixed-order LDS combine -> deterministic.
-__global__ __launch_bounds__(256) void avgpool_nhwc_kernel(const float *__restrict__ X, float *__restrict__ feat, int HW, int C) {
+// H16: the bag row is stored as fp16, rn16 of the fp32 mean (feature stores kept in half precision: the *_x16 calls of the MIL path read it as stored).
+template <bool H16>
+__global__ __launch_bounds__(256) void avgpool_nhwc_kernel(const float *__restrict__ X, void *__restrict__ feat_v, int HW, int C) {
     __shared__ f32x4 part[4][64];
     const int b = blockIdx.y, c0 = blockIdx.x * 256;
     const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
@@ -141,7 +144,52 @@ __global__ __launch_bounds__(256) void avgpool_nhwc_kernel(const float *__restri
     if (grp == 0 && live) {
         const f32x4 s = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
         const float inv = 1.f / (float)HW;
-        st4(feat + (uint64_t)b * C + c0 + 4 * lane, s * inv);
+        const f32x4 m = s * inv;
+        const uint64_t o = (uint64_t)b * C + c0 + 4 * lane;
+        if constexpr (H16) {
+            typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
+            *reinterpret_cast<h16x4 *>(reinterpret_cast<_Float16 *>(feat_v) + o) = h16x4{(_Float16)m[0], (_Float16)m[1], (_Float16)m[2], (_Float16)m[3]};
+        } else {
+            st4(reinterpret_cast<float *>(feat_v) + o, m);
+        }
+    }
+}
+
+// uint8 NHWC tiles [B, H, W, 3] (RGB, as an image decoder hands them over) -> the normalised fp32 NCHW tiles [B, 3, H, W] the reference model is fed:
+// out[b, c, p] = fmaf((float)u[b, p, c], a_c, b_c), a_c = 1 / (255 std_c), b_c = -mean_c / std_c - ToTensor + Normalize in one rounding (the explicit fma:
+// this library is built with -ffp-contract=fast). One thread per group of four pixels of one image: 12 source bytes (three 4-byte loads where the group's
+// address allows it, byte loads otherwise - any base alignment, no read past the group), one 16-byte store per channel plane when HW % 4 == 0 (the
+// planes are then 16-byte aligned like `out`), scalar stores otherwise and in a ragged last group.
+__global__ __launch_bounds__(256) void tiles_u8_nhwc_to_nchw_kernel(const unsigned char *__restrict__ src, float *__restrict__ out, uint64_t B, uint32_t HW,
+                                                                    StemNorm nrm) {
+    const uint32_t gpi = (HW + 3) >> 2;                                   // groups per image
+    const uint64_t total = B * gpi;
+    const bool vec = (HW & 3u) == 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (uint64_t)gridDim.x * 256) {
+        const uint64_t b = i / gpi;
+        const uint32_t p0 = (uint32_t)(i - b * gpi) * 4, np = HW - p0 < 4 ? HW - p0 : 4;
+        const unsigned char *s = src + (b * HW + p0) * 3;
+        unsigned u[12];
+        if (np == 4 && (reinterpret_cast<uintptr_t>(s) & 3u) == 0) {
+            const unsigned w0 = reinterpret_cast<const unsigned *>(s)[0], w1 = reinterpret_cast<const unsigned *>(s)[1], w2 = reinterpret_cast<const unsigned *>(s)[2];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { u[e] = (w0 >> (8 * e)) & 255u; u[4 + e] = (w1 >> (8 * e)) & 255u; u[8 + e] = (w2 >> (8 * e)) & 255u; }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 12; ++e) u[e] = (uint32_t)e < 3 * np ? s[e] : 0u;
+        }
+        float *o = out + b * 3 * HW + p0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            f32x4 v;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf((float)u[3 * e + c], nrm.a[c], nrm.b[c]);
+            float *oc = o + (uint64_t)c * HW;
+            if (vec) st4(oc, v);
+            else
+#pragma unroll
+                for (int e = 0; e < 4; ++e) if ((uint32_t)e < np) oc[e] = v[e];
+        }
     }
 }
 
@@ -247,12 +295,28 @@ extern "C" int toad_maxpool3x3s2_nhwc_f32(const float *X, float *Y, int B, int H
     return check_launch(what);
 }
 
-extern "C" int toad_avgpool_nhwc_f32(const float *X, float *feat, int B, int HW, int C, void *stream) {
-    const char *what = "toad_avgpool_nhwc_f32";
+static int launch_avgpool(const float *X, void *feat, bool h16, int B, int HW, int C, hipStream_t st, const char *what) {
     if (!X || !feat) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
     if (B <= 0 || B > 65535 || HW <= 0 || C <= 0 || C % 4) { set_error("%s: bad shape", what); return TOAD_ESHAPE; }
     if (!aligned16(X) || !aligned16(feat)) { set_error("%s: pointers must be 16-byte aligned", what); return TOAD_EALIGN; }
-    hipLaunchKernelGGL(avgpool_nhwc_kernel, dim3((C + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, X, feat, HW, C);
+    if (h16) hipLaunchKernelGGL(avgpool_nhwc_kernel<true>, dim3((C + 255) / 256, B), dim3(256), 0, st, X, feat, HW, C);
+    else hipLaunchKernelGGL(avgpool_nhwc_kernel<false>, dim3((C + 255) / 256, B), dim3(256), 0, st, X, feat, HW, C);
+    return check_launch(what);
+}
+extern "C" int toad_avgpool_nhwc_f32(const float *X, float *feat, int B, int HW, int C, void *stream) {
+    return launch_avgpool(X, feat, false, B, HW, C, (hipStream_t)stream, "toad_avgpool_nhwc_f32");
+}
+
+extern "C" int toad_tiles_u8_nhwc_to_nchw_f32(const unsigned char *tiles, const float *norm, float *out, int B, int H, int W, void *stream) {
+    const char *what = "toad_tiles_u8_nhwc_to_nchw_f32";
+    if (!tiles || !norm || !out) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (B <= 0 || H <= 0 || W <= 0 || (uint64_t)H * W >= (1ull << 31)) { set_error("%s: bad shape", what); return TOAD_ESHAPE; }
+    if (int rc = check_norm_u8(norm, what)) return rc;
+    if (!aligned16(out)) { set_error("%s: out must be 16-byte aligned (the uint8 source may have any alignment)", what); return TOAD_EALIGN; }
+    StemNorm nrm;
+    for (int c = 0; c < 3; ++c) { nrm.a[c] = norm[c]; nrm.b[c] = norm[3 + c]; }
+    const uint32_t HW = (uint32_t)H * (uint32_t)W;
+    hipLaunchKernelGGL(tiles_u8_nhwc_to_nchw_kernel, dim3(grid_for((uint64_t)B * ((HW + 3) / 4))), dim3(256), 0, (hipStream_t)stream, tiles, out, (uint64_t)B, HW, nrm);
     return check_launch(what);
 }
 
@@ -262,18 +326,22 @@ extern "C" size_t toad_resnet50_trunc_ws_bytes(int B, int H, int W) {
     return 4 * align2m(p.act_max * 4) + align2m(p.cols_max * 4) + align2m(p.gemm_ws) + align2m(4096) + ((size_t)1 << 21);
 }
 
+// The uint8 call's workspace: the fp32 call's, plus - only for tile shapes the one-kernel stem does not take - the staging image of the normalised fp32 NCHW
+// tiles at its end.
+extern "C" size_t toad_resnet50_trunc_u8_ws_bytes(int B, int H, int W) {
+    const size_t base = toad_resnet50_trunc_ws_bytes(B, H, W);
+    if (base == 0) return 0;
+    return base + (stem_nchw_pool_ok(H, W) ? 0 : align2m((size_t)B * 3 * H * W * 4));
+}
+
 // weights[i] : folded conv i as [Cout, K] fp32 (K = kh*kw*Cin in (ky, kx, c) order; the stem is [64, 192] in the space-to-depth
 //              order of toad_stem_conv_s2d_f32),
 // biases[i]  : folded BN shift [Cout]; i runs in execution order (conv1, then per block conv1, conv2, conv3[, downsample]).
-extern "C" int toad_resnet50_trunc_fwd_f32(const float *tiles_nchw, const float *const *weights, const float *const *biases,
-                                            float *feat, int B, int H, int W, void *ws, size_t ws_bytes, void *stream) {
-    const char *what = "toad_resnet50_trunc_fwd_f32";
-    if (!tiles_nchw || !weights || !biases || !feat || !ws) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
-    NetPlan p;
-    if (!make_plan(B, H, W, p)) { set_error("%s: bad shape B=%d H=%d W=%d", what, B, H, W); return TOAD_ESHAPE; }
-    if (ws_bytes < toad_resnet50_trunc_ws_bytes(B, H, W)) { set_error("%s: workspace too small", what); return TOAD_EWORKSPACE; }
-    if (!aligned16(ws) || !aligned16(feat)) { set_error("%s: workspace / output must be 16-byte aligned", what); return TOAD_EALIGN; }
-    for (int i = 0; i < kNumConvs; ++i) if (!weights[i] || !biases[i]) { set_error("%s: null weight/bias slot %d", what, i); return TOAD_EINVAL; }
+// The network behind both entry points. tiles_u8 == NULL: fp32 NCHW tiles (toad_resnet50_trunc_fwd_f32, arguments checked there). Otherwise uint8 NHWC tiles with
+// norm[6]: 256-wide tiles go straight into the stem kernel, others are converted into the staging image and take the fp32 call's three-kernel stem from there.
+// feat / feat16: either may be NULL; each one given receives the bag rows.
+static int trunc_fwd(const float *tiles_nchw, const unsigned char *tiles_u8, const float *norm, const float *const *weights, const float *const *biases, float *feat,
+                     void *feat16, const NetPlan &p, int B, int H, int W, void *ws, void *stream, const char *what) {
     hipStream_t st = (hipStream_t)stream;
     char *base = reinterpret_cast<char *>(ws);
     size_t off = align2m(reinterpret_cast<uintptr_t>(ws)) - reinterpret_cast<uintptr_t>(ws);
@@ -296,7 +364,16 @@ extern "C" int toad_resnet50_trunc_fwd_f32(const float *tiles_nchw, const float 
     // stem: 7x7/2 conv + BN + ReLU (resnet_custom.py:96-98), 3x3/2 max-pool (:99)
     float *g_in = slot();
     float *gx = slot();
-    if (stem_nchw_pool_ok(H, W) && aligned16(tiles_nchw)) {
+    if (tiles_u8 && !stem_nchw_pool_ok(H, W)) {
+        float *stage = reinterpret_cast<float *>(take((size_t)B * 3 * H * W * 4));
+        TOAD_TRY(toad_tiles_u8_nhwc_to_nchw_f32(tiles_u8, norm, stage, B, H, W, st));
+        tiles_nchw = stage;
+        tiles_u8 = nullptr;
+    }
+    if (tiles_u8) {
+        // uint8 tiles, 256 wide: the same kernel body reads them as stored and normalises while it converts its window (stem_halo.inc, uint8 form)
+        TOAD_TRY(ext_stem_nhwc_u8_pool(tiles_u8, norm, weights[0], biases[0], act[1], gx, B, H, W, gws, gcap, st, what));
+    } else if (stem_nchw_pool_ok(H, W) && aligned16(tiles_nchw)) {
         // 256-wide tiles: stem + ReLU + max-pool as ONE kernel reading the NCHW tiles themselves (stem_halo.inc); per-tile operand scales, so not even
         // max |tiles| is measured
         TOAD_TRY(ext_stem_nchw_pool(tiles_nchw, weights[0], biases[0], act[1], gx, B, H, W, gws, gcap, st, what));
@@ -357,6 +434,34 @@ extern "C" int toad_resnet50_trunc_fwd_f32(const float *tiles_nchw, const float 
             ci += b == 0 ? 4 : 3;
             x = y; gx = gy; inpl = 4 * pl; h = ho; w = wo;
         }
+    if (feat) TOAD_TRY(launch_avgpool(x, feat, false, B, h * w, inpl, st, what));
+    if (feat16) TOAD_TRY(launch_avgpool(x, feat16, true, B, h * w, inpl, st, what));
 #undef TOAD_TRY
-    return toad_avgpool_nhwc_f32(x, feat, B, h * w, inpl, st);
+    return TOAD_OK;
+}
+
+extern "C" int toad_resnet50_trunc_fwd_f32(const float *tiles_nchw, const float *const *weights, const float *const *biases,
+                                            float *feat, int B, int H, int W, void *ws, size_t ws_bytes, void *stream) {
+    const char *what = "toad_resnet50_trunc_fwd_f32";
+    if (!tiles_nchw || !weights || !biases || !feat || !ws) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    NetPlan p;
+    if (!make_plan(B, H, W, p)) { set_error("%s: bad shape B=%d H=%d W=%d", what, B, H, W); return TOAD_ESHAPE; }
+    if (ws_bytes < toad_resnet50_trunc_ws_bytes(B, H, W)) { set_error("%s: workspace too small", what); return TOAD_EWORKSPACE; }
+    if (!aligned16(ws) || !aligned16(feat)) { set_error("%s: workspace / output must be 16-byte aligned", what); return TOAD_EALIGN; }
+    for (int i = 0; i < kNumConvs; ++i) if (!weights[i] || !biases[i]) { set_error("%s: null weight/bias slot %d", what, i); return TOAD_EINVAL; }
+    return trunc_fwd(tiles_nchw, nullptr, nullptr, weights, biases, feat, nullptr, p, B, H, W, ws, stream, what);
+}
+
+extern "C" int toad_resnet50_trunc_fwd_u8(const unsigned char *tiles, const float *norm, const float *const *weights, const float *const *biases, float *feat,
+                                           void *feat_f16, int B, int H, int W, void *ws, size_t ws_bytes, void *stream) {
+    const char *what = "toad_resnet50_trunc_fwd_u8";
+    if (!tiles || !norm || !weights || !biases || (!feat && !feat_f16) || !ws) { set_error("%s: null pointer (feat and feat_f16 may not both be NULL)", what); return TOAD_EINVAL; }
+    NetPlan p;
+    if (!make_plan(B, H, W, p)) { set_error("%s: bad shape B=%d H=%d W=%d", what, B, H, W); return TOAD_ESHAPE; }
+    if (int rc = check_norm_u8(norm, what)) return rc;
+    if (ws_bytes < toad_resnet50_trunc_u8_ws_bytes(B, H, W)) { set_error("%s: workspace too small", what); return TOAD_EWORKSPACE; }
+    if (!aligned16(ws) || (feat && !aligned16(feat)) || (feat_f16 && !aligned16(feat_f16))) { set_error("%s: workspace / outputs must be 16-byte aligned", what); return TOAD_EALIGN; }
+    if (stem_nchw_pool_ok(H, W) && (reinterpret_cast<uintptr_t>(tiles) & 1u) != 0) { set_error("%s: 256-wide uint8 tiles must be 2-byte aligned", what); return TOAD_EALIGN; }
+    for (int i = 0; i < kNumConvs; ++i) if (!weights[i] || !biases[i]) { set_error("%s: null weight/bias slot %d", what, i); return TOAD_EINVAL; }
+    return trunc_fwd(nullptr, tiles, norm, weights, biases, feat, feat_f16, p, B, H, W, ws, stream, what);
 }

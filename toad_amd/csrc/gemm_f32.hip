@@ -22,6 +22,7 @@
 // Why not plain bf16: parity with the reference's PyTorch-CPU path is 1e-4 on fp32 outputs and bf16 operands miss it
 // (1e-3..6e-3); gfx950 has no TF32/xf32. DESIGN.md 4 gives the arithmetic and the measurements.
 #include "common.h"
+#include "stem_u8.h"
 
 #include <stdlib.h>
 #include <mutex>
@@ -101,7 +102,8 @@ static void cfg() {
         TOAD_ATTR((gemm_nt_h2_stream_kernel<2, 4, GATHER_CONV>), (StreamCfg<2, 4>::SMEM));
         TOAD_ATTR((gemm_nt_h2_stream_kernel<2, 2, GATHER_STEM>), (StreamCfg<2, 2>::SMEM));
         TOAD_ATTR((gemm_nt_h2_stream_kernel<2, 2, GATHER_STEM_POOL>), (StreamCfg<2, 2>::SMEM + STEM_POOL_LDS));
-        TOAD_ATTR(stem_halo_pool_kernel, SH_SMEM);
+        TOAD_ATTR(stem_halo_pool_kernel<false>, SH_SMEM);
+        TOAD_ATTR(stem_halo_pool_kernel<true>, SH_SMEM);
         TOAD_ATTR(conv3x3_h2_halo_kernel<2>, 160 * 1024);
         TOAD_ATTR(conv3x3_h2_halo_kernel<4>, 160 * 1024);
 #undef TOAD_ATTR
@@ -707,15 +709,22 @@ extern "C" int toad_stem_conv_pool_s2d_f32(const float *Xs, const float *Wf, con
     return ext_stem_conv(Xs, nullptr, Wf, bias, Yp, nullptr, B, Ho, Wo, TOAD_ACT_RELU, ws, ws_bytes, (hipStream_t)stream, "toad_stem_conv_pool_s2d_f32", true);
 }
 
-// The stem + ReLU + 3x3/2 max-pool straight from NCHW tiles (stem_halo.inc): no space-to-depth image, no fragment loads from global memory.
+// The stem + ReLU + 3x3/2 max-pool straight from the tiles (stem_halo.inc): no space-to-depth image, no fragment loads from global memory. norm == NULL: fp32 NCHW
+// tiles; otherwise uint8 NHWC tiles [B, H, 256, 3] and the six normalisation constants (stem_u8.h), checked before any device work.
 bool toad::stem_nchw_pool_ok(int H, int W) { return W == 256 && H >= 4 && H % 4 == 0; }
-int toad::ext_stem_nchw_pool(const float *X, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W, void *ws, size_t ws_bytes,
-                             hipStream_t st, const char *what) {
-    if (!X || !Wf || !Yp || !ws) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
-    if (B <= 0 || !stem_nchw_pool_ok(H, W)) { set_error("%s: needs W = 256 and H %% 4 == 0 (other tiles: toad_stem_s2d_nchw_f32 + toad_stem_conv_s2d_f32 + toad_maxpool3x3s2_nhwc_f32)", what); return TOAD_ESHAPE; }
+static int stem_pool_from_tiles(const void *X, bool u8, const float *norm, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W, void *ws,
+                                size_t ws_bytes, hipStream_t st, const char *what) {
+    if (!X || (u8 && !norm) || !Wf || !Yp || !ws) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (B <= 0 || !stem_nchw_pool_ok(H, W)) {
+        set_error("%s: needs W = 256 and H %% 4 == 0 (other tiles: %stoad_stem_s2d_nchw_f32 + toad_stem_conv_s2d_f32 + toad_maxpool3x3s2_nhwc_f32)", what,
+                  u8 ? "toad_tiles_u8_nhwc_to_nchw_f32 + " : "");
+        return TOAD_ESHAPE;
+    }
     const int64_t M = (int64_t)B * (H / 2) * 128;
     if (M >= (1ll << 31)) { set_error("%s: batch too large for 32-bit offsets (split it)", what); return TOAD_ESHAPE; }
-    if (!aligned16(X) || !aligned16(Wf) || !aligned16(Yp) || (bias && !aligned16(bias))) { set_error("%s: pointers must be 16-byte aligned", what); return TOAD_EALIGN; }
+    if (u8) { if (int rc = check_norm_u8(norm, what)) return rc; }
+    if (u8 && (reinterpret_cast<uintptr_t>(X) & 1u) != 0) { set_error("%s: the uint8 tiles must be 2-byte aligned", what); return TOAD_EALIGN; }
+    if ((!u8 && !aligned16(X)) || !aligned16(Wf) || !aligned16(Yp) || (bias && !aligned16(bias))) { set_error("%s: pointers must be 16-byte aligned", what); return TOAD_EALIGN; }
     if (int rc = check_ws(ws, ws_bytes, M, 64, 192, what)) return rc;
     (void)cfg();
     char *w = reinterpret_cast<char *>(ws) + (size_t)PB_GRID * PB * PB * sizeof(float);
@@ -724,11 +733,30 @@ int toad::ext_stem_nchw_pool(const float *X, const float *Wf, const float *bias,
     hipLaunchKernelGGL(split_planes_narrow_h2_kernel<2>, dim3(16), dim3(256), 0, st, Wf, (int64_t)192, planes, binv, 64, 192, 1, 1, 12, 6);
     if (int rc = check_launch(what)) return rc;
     const int tiles = B * (H / 4);
-    hipLaunchKernelGGL(stem_halo_pool_kernel, dim3(std::min(tiles, 2 * PB_GRID)), dim3(256), SH_SMEM, st, X, planes, binv, bias, Yp, B, H, y_gmax, tiles);      // two workgroups per CU
+    const dim3 grid(std::min(tiles, 2 * PB_GRID));                  // two workgroups per CU
+    if (u8) {
+        StemNorm nrm;
+        for (int c = 0; c < 3; ++c) { nrm.a[c] = norm[c]; nrm.b[c] = norm[3 + c]; }
+        hipLaunchKernelGGL(stem_halo_pool_kernel<true>, grid, dim3(256), SH_SMEM, st, reinterpret_cast<const unsigned char *>(X), planes, binv, bias, Yp, B, H, y_gmax, tiles, nrm);
+    } else {
+        hipLaunchKernelGGL(stem_halo_pool_kernel<false>, grid, dim3(256), SH_SMEM, st, reinterpret_cast<const float *>(X), planes, binv, bias, Yp, B, H, y_gmax, tiles, StemNoNorm{});
+    }
     return check_launch(what);
+}
+int toad::ext_stem_nchw_pool(const float *X, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W, void *ws, size_t ws_bytes,
+                             hipStream_t st, const char *what) {
+    return stem_pool_from_tiles(X, false, nullptr, Wf, bias, Yp, y_gmax, B, H, W, ws, ws_bytes, st, what);
+}
+int toad::ext_stem_nhwc_u8_pool(const unsigned char *X8, const float *norm, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W,
+                                void *ws, size_t ws_bytes, hipStream_t st, const char *what) {
+    return stem_pool_from_tiles(X8, true, norm, Wf, bias, Yp, y_gmax, B, H, W, ws, ws_bytes, st, what);
 }
 extern "C" int toad_stem_pool_nchw_f32(const float *X, const float *Wf, const float *bias, float *Yp, int B, int H, int W, void *ws, size_t ws_bytes, void *stream) {
     return ext_stem_nchw_pool(X, Wf, bias, Yp, nullptr, B, H, W, ws, ws_bytes, (hipStream_t)stream, "toad_stem_pool_nchw_f32");
+}
+extern "C" int toad_stem_pool_nhwc_u8(const unsigned char *tiles, const float *norm, const float *Wf, const float *bias, float *Yp, int B, int H, int W, void *ws,
+                                      size_t ws_bytes, void *stream) {
+    return ext_stem_nhwc_u8_pool(tiles, norm, Wf, bias, Yp, nullptr, B, H, W, ws, ws_bytes, (hipStream_t)stream, "toad_stem_pool_nhwc_u8");
 }
 
 extern "C" int toad_linear_dgrad_f32(const float *dY, const float *WT, const float *addend, const float *relu_src,

@@ -38,11 +38,34 @@ constexpr int SH_SMEM = SH_SCR_OFF + 64;
 static_assert(2 * SH_PLANE >= 64 * 64 * 4 && 2 * SH_SMEM <= 160 * 1024, "two workgroups per CU");
 constexpr int SH_TASKS = (SH_ROWS * SH_WS + 255) / 256;      // space-to-depth pixels per thread and tile: 3 (655 over 256 threads)
 
-__global__ __launch_bounds__(256, 2) void stem_halo_pool_kernel(const float *__restrict__ X, const unsigned short *__restrict__ Bp, const float *__restrict__ binv,
-                                                                const float *__restrict__ bias, float *Yp, int B, int H, float *y_gmax, int tiles) {
+// Input forms of the window loader. The kernel body is one template; what differs is how a lane fetches and holds the 12 values of its space-to-depth pixel:
+//   fp32 NCHW (stem_halo_pool_kernel<false>): six 8-byte loads (2 rows x 3 channel planes), held as 12 floats per task across the matrix loop;
+//   uint8 NHWC (stem_halo_pool_kernel<true>): the tiles as an image decoder hands them over, [B, H, 256, 3] RGB. A pixel pair of one row is 6 contiguous
+//     bytes at ((b H + iy) 256 + ix) 3 - a multiple of 6, so 2-byte aligned relative to the base and not 4-byte aligned in general: one 4-byte and one
+//     2-byte load per row, held RAW (4 registers per task instead of 12) across the matrix loop. store_window converts them once, in front of the abs-max:
+//     x = fmaf((float)u, a_c, b_c) with a_c = 1 / (255 std_c), b_c = -mean_c / std_c rounded to fp32 by the host - ToTensor + Normalize of the tiles the
+//     reference's extractor is fed (the ImageNet statistics of the weights models/resnet_custom.py:121-124 loads). A tap outside the image is 0 in
+//     NORMALISED space (Normalize, then the convolution's zero padding), not b_c: the spare upper half of the 2-byte load's register carries the
+//     "outside" mark. From the abs-max on the two forms run the same code on the same values, so the results are bitwise those of the fp32 form
+//     fed the normalised image.
+constexpr unsigned SH_U8_OUTSIDE = 0xFFFF0000u;              // upper half of a row's 2-byte word: the pixel pair lies outside the image
+typedef unsigned sh_u32_a2 __attribute__((aligned(2)));      // a 4-byte load from a 2-byte aligned address
+
+// (the constants are the LAST kernel argument, an empty struct in the fp32 form: that form's argument layout, registers and code are the ones it had as a
+//  plain kernel - 64 SGPRs, 242 VGPRs, no scratch; the uint8 form: 68 SGPRs, 218 VGPRs, no scratch; both 81,728 B of LDS, two workgroups per CU)
+struct StemNoNorm {};
+template <bool U8>
+__global__ __launch_bounds__(256, 2) void stem_halo_pool_kernel(const typename std::conditional<U8, unsigned char, float>::type *__restrict__ Xv,
+                                                                const unsigned short *__restrict__ Bp, const float *__restrict__ binv,
+                                                                const float *__restrict__ bias, float *Yp, int B, int H, float *y_gmax, int tiles,
+                                                                typename std::conditional<U8, StemNorm, StemNoNorm>::type nrm_arg) {
     using Cfg = StreamCfg<2, 2>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     char *lds = reinterpret_cast<char *>(smem);
+    const float *X = reinterpret_cast<const float *>(Xv);
+    const unsigned char *X8 = reinterpret_cast<const unsigned char *>(Xv);
+    StemNorm nrm{};
+    if constexpr (U8) nrm = nrm_arg;
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, hi = lane >> 5;
@@ -66,8 +89,29 @@ __global__ __launch_bounds__(256, 2) void stem_halo_pool_kernel(const float *__r
         tk[k] = task < SH_ROWS * SH_WS ? (Yl << 8) | (task - Yl * SH_WS) : -1;
     }
     // raw[k][ry * 3 + c] = columns (2 Xs - 4, 2 Xs - 3) of image row 4 t - 4 + 2 Yl + ry, channel c (a local of the caller's scope: loop-local liveness)
-    auto load_window = [&](int q, f2 (&raw)[SH_TASKS][6]) __attribute__((always_inline)) {
+    // what a task holds between its loads and store_window: fp32 - the 12 values; uint8 - per row ry the 4-byte word [2 ry] (c0 c1 c2 of column 0, c0 of
+    // column 1) and the 2-byte word [2 ry + 1] (c1 c2 of column 1; upper half 0, or SH_U8_OUTSIDE)
+    using Raw = typename std::conditional<U8, unsigned[SH_TASKS][4], f2[SH_TASKS][6]>::type;
+    auto load_window = [&](int q, Raw &raw) __attribute__((always_inline)) {
         const int b = q / tpi, t = q - b * tpi;
+        if constexpr (U8) {
+            const unsigned char *img8 = X8 + (int64_t)b * H * W * 3;
+#pragma unroll
+            for (int k = 0; k < SH_TASKS; ++k) {
+                int tc = tk[k];
+                asm volatile("" : "+v"(tc));                     // (laundered per call, as below)
+                const int Yl = tc >> 8, Xs = tc & 255;
+                const int ix = 2 * Xs - 4;
+#pragma unroll
+                for (int ry = 0; ry < 2; ++ry) {
+                    const int iy = 4 * t - 4 + 2 * Yl + ry;
+                    const bool ok = tc >= 0 && iy >= 0 && iy < H && ix >= 0 && ix < W;       // (ix even, W even: both columns or neither; bytes [0, 6) of the pair end inside row iy)
+                    const unsigned char *p = img8 + ((int64_t)iy * W + ix) * 3;
+                    raw[k][2 * ry] = ok ? __builtin_nontemporal_load(reinterpret_cast<const sh_u32_a2 *>(p)) : 0u;
+                    raw[k][2 * ry + 1] = ok ? (unsigned)__builtin_nontemporal_load(reinterpret_cast<const unsigned short *>(p + 4)) : SH_U8_OUTSIDE;
+                }
+            }
+        } else {
         const float *img = X + (int64_t)b * 3 * H * W;
         // (the packed task coordinates are laundered per call: offsets and edge predicates are then formed here, per tile - a few integer instructions - instead
         //  of being hoisted out of the tile loop, where ~25 registers of them lived across the matrix loop and, at 256 registers per wave, were spilled)
@@ -86,10 +130,11 @@ __global__ __launch_bounds__(256, 2) void stem_halo_pool_kernel(const float *__r
                     raw[k][ry * 3 + c] = ok ? __builtin_nontemporal_load(reinterpret_cast<const f2 *>(img + ((int64_t)c * H + iy) * W + ix)) : f2{0.f, 0.f};
             }
         }
+        }
     };
     float *scr = reinterpret_cast<float *>(lds + SH_SCR_OFF);
     // abs-max of the loaded window -> the tile's exponent; split into the two pieces, written in K order (ry, rx, c) per pixel
-    auto store_window = [&](f2 (&raw)[SH_TASKS][6]) __attribute__((always_inline)) {
+    auto store_values = [&](f2 (&raw)[SH_TASKS][6]) __attribute__((always_inline)) {
         float mx = 0.f;
 #pragma unroll
         for (int k = 0; k < SH_TASKS; ++k)
@@ -128,6 +173,28 @@ __global__ __launch_bounds__(256, 2) void stem_halo_pool_kernel(const float *__r
         }
         lds_barrier();
         return ke;
+    };
+    // uint8: the raw words -> the values the fp32 form would have loaded (same [ry * 3 + c][rx] layout), ONE rounding each (an explicit fma: the
+    // library is built with -ffp-contract=fast, and neither contraction nor its absence may decide the bits); then the shared code
+    auto store_window = [&](Raw &raw) __attribute__((always_inline)) {
+        if constexpr (U8) {
+            f2 cv[SH_TASKS][6];
+#pragma unroll
+            for (int k = 0; k < SH_TASKS; ++k)
+#pragma unroll
+                for (int ry = 0; ry < 2; ++ry) {
+                    const unsigned lo = raw[k][2 * ry], hi = raw[k][2 * ry + 1];
+                    const bool in = hi < SH_U8_OUTSIDE;
+                    const unsigned u[2][3] = {{lo & 255u, (lo >> 8) & 255u, (lo >> 16) & 255u}, {lo >> 24, hi & 255u, (hi >> 8) & 255u}};
+#pragma unroll
+                    for (int c = 0; c < 3; ++c)
+#pragma unroll
+                        for (int rx = 0; rx < 2; ++rx) cv[k][ry * 3 + c][rx] = in ? __builtin_fmaf((float)u[rx][c], nrm.a[c], nrm.b[c]) : 0.f;
+                }
+            return store_values(cv);
+        } else {
+            return store_values(raw);
+        }
     };
 
     // ---- fragments. Wave w: conv row w >> 1 of the tile, pixels (w & 1) * 64 + a * 32 + li (a = 0, 1); columns = the 64 channels (2 blocks)
@@ -179,7 +246,7 @@ __global__ __launch_bounds__(256, 2) void stem_halo_pool_kernel(const float *__r
 #pragma unroll
     for (int i = 0; i < 32; ++i) carry_r[i] = 0.f;
     int ke;
-    { f2 raw0[SH_TASKS][6]; load_window(item_tile(0), raw0); ke = store_window(raw0); }                                  // (its first barrier also publishes the weight planes)
+    { Raw raw0; load_window(item_tile(0), raw0); ke = store_window(raw0); }                                  // (its first barrier also publishes the weight planes)
     for (int it = 0; it < n_items; ++it) {
         const int q = item_tile(it);
         zero_acc();
@@ -200,7 +267,7 @@ __global__ __launch_bounds__(256, 2) void stem_halo_pool_kernel(const float *__r
         // combine and the stores (and under the other workgroup's matrix loop), and their 36 registers coexist neither with the two fragment sets of the loop nor
         // with the accumulators - at two workgroups per CU a wave has 256 registers, not 512. (Measured against "in front of the epilogue" and "behind it": 728 /
         // 777 / 754 us and 780 / 790 / 812 us on two boxes - the other workgroup hides most of the latency either way; profiles/r07f_stem_variants.txt.)
-        f2 raw[SH_TASKS][6];
+        Raw raw;
         int li_e = li, hi_e = hi;                             // the epilogue's lane coordinates, laundered (see read_frags)
         asm volatile("" : "+v"(li_e), "+v"(hi_e));
         const bool more = it + 1 < n_items;

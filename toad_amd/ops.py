@@ -1146,6 +1146,61 @@ def stem_pool_nchw(x: torch.Tensor, wf: torch.Tensor, b) -> torch.Tensor:
     return y
 
 
+IMAGENET_MEAN = (0.485, 0.456, 0.406)      # the statistics of the weights the reference loads (models/resnet_custom.py:121-124)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+
+
+def norm_constants_u8(mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """The `norm` argument of the uint8 calls: ctypes float[6] = a_c = 1/(255 std_c) then b_c = -mean_c/std_c, each computed in double precision and
+    rounded once to fp32. The device value of a byte u is fmaf(u, a_c, b_c)."""
+    import ctypes
+    import math
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("mean and std must have three entries (R, G, B)")
+    if any(v == 0.0 or not math.isfinite(v) for v in std) or not all(math.isfinite(v) for v in mean):
+        raise ValueError(f"mean / std must be finite and std non-zero (got mean={mean}, std={std})")
+    vals = [1.0 / (255.0 * sd) for sd in std] + [-m / sd for m, sd in zip(mean, std)]
+    arr = (ctypes.c_float * 6)(*vals)                    # c_float rounds the double to nearest fp32
+    if not all(math.isfinite(v) for v in arr):
+        raise ValueError(f"1/(255 std) or -mean/std is not finite in fp32 (mean={mean}, std={std})")
+    return arr
+
+
+def _chk_tiles_u8(tiles: torch.Tensor, name: str):
+    _chk(tiles, "tiles", dtype=torch.uint8)
+    if tiles.dim() != 4 or tiles.shape[3] != 3:
+        raise ValueError(f"{name}: expected uint8 [B,H,W,3] tiles (RGB, channels last), got {tuple(tiles.shape)}")
+
+
+def tiles_u8_to_f32(tiles: torch.Tensor, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> torch.Tensor:
+    """ToTensor + Normalize(mean, std) on the device in one rounding: uint8 [B,H,W,3] (any alignment) -> fp32 [B,3,H,W],
+    out[b,c,y,x] = fmaf(tiles[b,y,x,c], 1/(255 std_c), -mean_c/std_c)."""
+    _chk_tiles_u8(tiles, "tiles_u8_to_f32")
+    norm = norm_constants_u8(mean, std)
+    b, h, w, _ = tiles.shape
+    out = torch.empty((b, 3, h, w), dtype=torch.float32, device=tiles.device)
+    _lib.check(_lib.load().toad_tiles_u8_nhwc_to_nchw_f32(_p(tiles), norm, _p(out), b, h, w, _stream()), "toad_tiles_u8_nhwc_to_nchw_f32")
+    return out
+
+
+def stem_pool_nhwc_u8(tiles: torch.Tensor, wf: torch.Tensor, b, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> torch.Tensor:
+    """stem_pool_nchw straight from uint8 tiles [B,H,256,3] (H % 4 == 0): bitwise stem_pool_nchw(tiles_u8_to_f32(tiles, mean, std), wf, b), without the
+    fp32 image. A source at an odd address is copied once (the kernel reads 2-byte aligned words)."""
+    _chk_tiles_u8(tiles, "stem_pool_nhwc_u8"); _chk(wf, "wf"); _chk(b, "b", allow_none=True)
+    if tuple(wf.shape) != (64, 192):
+        raise ValueError("stem_pool_nhwc_u8: expected a [64,192] space-to-depth weight")
+    norm = norm_constants_u8(mean, std)
+    bb, h, w, _ = tiles.shape
+    if tiles.data_ptr() % 2:
+        tiles = tiles.clone()
+    y = torch.empty((bb, h // 4, w // 4, 64), dtype=torch.float32, device=tiles.device)
+    lib = _lib.load()
+    ws = _ws(lib.toad_linear_ws_bytes(bb * (h // 2) * (w // 2), 64, 192), tiles.device)
+    _lib.check(lib.toad_stem_pool_nhwc_u8(_p(tiles), norm, _p(wf), _p(b), _p(y), bb, h, w, _p(ws), ws.numel(), _stream()), "toad_stem_pool_nhwc_u8")
+    return y
+
+
 def maxpool3x3s2_nhwc(x: torch.Tensor) -> torch.Tensor:
     _chk(x, "x")
     b, h, w, c = x.shape

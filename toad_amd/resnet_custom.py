@@ -21,8 +21,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .ops import IMAGENET_MEAN, IMAGENET_STD, norm_constants_u8
 
-__all__ = ["Bottleneck_Baseline", "ResNet_Baseline", "resnet50_baseline"]
+__all__ = ["Bottleneck_Baseline", "ResNet_Baseline", "resnet50_baseline", "IMAGENET_MEAN", "IMAGENET_STD"]
 
 STEM_K = 192            # 4 x 4 space-to-depth taps x 12 channels (147 real taps + zero slots)
 MAX_TILES_PER_CALL = 512     # at 256x256 tiles. 32-bit byte offsets inside the kernels: B*(H/4)*(W/4)*128*4 < 2^31 (layer2.0 conv2 input)
@@ -175,6 +176,49 @@ class ResNet_Baseline(nn.Module):
                 self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
             _lib.check(lib.toad_resnet50_trunc_fwd_f32(x[b0:b0 + nb].data_ptr(), wp, bp, out[b0:b0 + nb].data_ptr(), nb, H, W,
                                                        self._ws.data_ptr(), self._ws.numel(), stream), "toad_resnet50_trunc_fwd_f32")
+        return out
+
+    def forward_u8(self, tiles: torch.Tensor, mean=IMAGENET_MEAN, std=IMAGENET_STD, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """[B,H,W,3] uint8 RGB tiles on the HIP device, as an image decoder hands them over -> [B,1024] bag rows, fp32 or fp16.
+
+        ToTensor + Normalize(mean, std) happen on the device in one rounding, x = fmaf(u, 1/(255 std_c), -mean_c/std_c); the result is bitwise
+        ``forward`` of that fp32 NCHW tensor (``out_dtype=torch.float16``: bitwise ``forward(...).half()``, stored by the last kernel). 256-wide tiles with
+        H % 4 == 0 never exist as an fp32 image: the stem kernel reads the bytes. Other shapes are converted into a staging image inside the workspace."""
+        if self.training:
+            raise RuntimeError("the HIP extractor is inference-only: call .eval() (the reference never trains it)")
+        if tiles.dtype != torch.uint8:
+            raise RuntimeError(f"forward_u8 expects uint8 tiles, got {tiles.dtype} (normalised float32 [B,3,H,W] tiles go to forward)")
+        if tiles.dim() != 4 or tiles.shape[3] != 3:
+            raise RuntimeError(f"forward_u8 expects channels-last [B,H,W,3] tiles, got {tuple(tiles.shape)}")
+        if out_dtype not in (torch.float32, torch.float16):
+            raise RuntimeError(f"out_dtype must be torch.float32 or torch.float16, got {out_dtype}")
+        if not tiles.is_cuda:
+            raise RuntimeError("expected a uint8 [B,H,W,3] tensor on the HIP device (no CPU fallback)")
+        if self.conv1.weight.device != tiles.device:
+            raise RuntimeError("model and input are on different devices; call model.relocate()")
+        norm = norm_constants_u8(mean, std)
+        lib = _lib.load()
+        if self._folded is None or self._folded_sig != self._param_signature():
+            self._fold_all()
+        _, _, wp, bp = self._folded
+        tiles = tiles.contiguous()
+        B, H, W, _ = tiles.shape
+        if W == 256 and H >= 4 and H % 4 == 0 and tiles.data_ptr() % 2:
+            tiles = tiles.clone()                       # the stem reads 2-byte aligned words: one copy of a source at an odd address
+        out = torch.empty(B, 1024, device=tiles.device, dtype=out_dtype)
+        half = out_dtype == torch.float16
+        stream = torch.cuda.current_stream(tiles.device).cuda_stream
+        cap = max_tiles_per_call(H, W)
+        for b0 in range(0, B, cap):
+            nb = min(cap, B - b0)
+            need = lib.toad_resnet50_trunc_u8_ws_bytes(nb, H, W)
+            if need == 0:
+                raise RuntimeError(f"unsupported tile shape {H}x{W}")
+            if self._ws is None or self._ws.numel() < need or self._ws.device != tiles.device:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=tiles.device)
+            o = out[b0:b0 + nb].data_ptr()
+            _lib.check(lib.toad_resnet50_trunc_fwd_u8(tiles[b0:b0 + nb].data_ptr(), norm, wp, bp, None if half else o, o if half else None, nb, H, W,
+                                                      self._ws.data_ptr(), self._ws.numel(), stream), "toad_resnet50_trunc_fwd_u8")
         return out
 
 
