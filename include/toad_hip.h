@@ -337,6 +337,36 @@ size_t toad_resnet50_trunc_u8_ws_bytes(int B, int H, int W);
 int toad_resnet50_trunc_fwd_u8(const unsigned char *tiles, const float *norm, const float *const *weights, const float *const *biases,
                                float *feat, void *feat_f16, int B, int H, int W, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- The extractor's front end: tiles by origin from one decoded region (an additive extension of ABI 15; the version number does not change) ----
+ * A slide reader hands over a region, one uint8 image; the calls above want it cut into a [B,H,W,3] copy first. The calls below read the tiles where they
+ * lie: no tile copy exists anywhere.
+ *   region   uint8 [Hr,Wr,3] on the device, RGB, channels last: pixel (x, y), channel c at region + y * pitch + x * 3 + c. `pitch` is the row pitch in BYTES,
+ *            any value >= 3 * Wr (a column crop of a wider image is taken as it is). Any base address and any pitch parity: no alignment requirement.
+ *   origins  DEVICE int32 [B][2], 4-byte aligned: (x, y) - x first, as in the coordinate arrays of the reference's h5 bags - the top-left pixel of tile b in
+ *            region coordinates. Duplicates, overlaps and any order are allowed. Every tile must lie inside the region, 0 <= x, x + W <= Wr, 0 <= y,
+ *            y + H <= Hr: THIS IS THE CALLER'S DUTY - the library cannot see device values without a synchronisation, and an out-of-range origin is an
+ *            out-of-bounds read. The Python layer (toad_amd.ops, ResNet_Baseline.forward_u8_region) takes the origins on the host and checks every one.
+ *   padding  is the TILE's, not the region's: a tap outside the tile is 0 in normalised space even where the region has pixels there. Tile b behaves exactly
+ *            as region[y:y+H, x:x+W] cut out and passed to the tile call; each call is BITWISE its tile twin on those materialised tiles.
+ * norm, Wf, weights, outputs and workspaces as for the tile twins. Refused on the host before any device work: a null pointer or a non-finite norm
+ * (TOAD_EINVAL); pitch < 3 * Wr, H > Hr, W > Wr, Hr or Wr < 1, or H * pitch >= 2^31 - offsets inside a tile are 32-bit - (TOAD_ESHAPE); a workspace too
+ * small (TOAD_EWORKSPACE); and what the twins refuse. */
+
+/* toad_tiles_u8_nhwc_to_nchw_f32 by origin: out fp32 [B,3,H,W] (16-byte aligned). Any B, H, W >= 1 with H*W < 2^31. */
+int toad_tiles_u8_region_to_nchw_f32(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm, float *out,
+                                     int B, int H, int W, void *stream);
+
+/* toad_stem_pool_nhwc_u8 by origin (W == 256, H % 4 == 0; TOAD_ESHAPE otherwise): the window loader forms each tile's base as a 64-bit scalar and reads the
+ * pixel pairs through byte-aligned loads. */
+int toad_stem_pool_region_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm, const float *Wf,
+                             const float *bias, float *Yp, int B, int H, int W, void *ws, size_t ws_bytes, void *stream);
+
+/* toad_resnet50_trunc_fwd_u8 by origin. Workspace: toad_resnet50_trunc_u8_ws_bytes(B, H, W), unchanged (tiles with W != 256 or H % 4 != 0 are converted by
+ * toad_tiles_u8_region_to_nchw_f32 into the staging image at its end). */
+int toad_resnet50_trunc_fwd_u8_region(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm,
+                                      const float *const *weights, const float *const *biases, float *feat, void *feat_f16, int B, int H, int W,
+                                      void *ws, size_t ws_bytes, void *stream);
+
 /* ---- Whole-slide calls: forward, backward, training step -------------------------------- */
 
 /* The reference drives this path through three Python statements,

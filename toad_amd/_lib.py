@@ -89,6 +89,10 @@ SIGNATURES = {
     "toad_stem_pool_nhwc_u8": (I, [P, P, P, P, P, I, I, I, P, SZ, P]),
     "toad_resnet50_trunc_u8_ws_bytes": (SZ, [I, I, I]),
     "toad_resnet50_trunc_fwd_u8": (I, [P, P, P, P, P, P, I, I, I, P, SZ, P]),
+    # ... and tiles read by origin from one decoded uint8 region: additive to ABI 15 too
+    "toad_tiles_u8_region_to_nchw_f32": (I, [P, I64, I, I, P, P, P, I, I, I, P]),
+    "toad_stem_pool_region_u8": (I, [P, I64, I, I, P, P, P, P, P, I, I, I, P, SZ, P]),
+    "toad_resnet50_trunc_fwd_u8_region": (I, [P, I64, I, I, P, P, P, P, P, P, I, I, I, P, SZ, P]),
 }
 
 _lib = None

@@ -160,17 +160,42 @@ __global__ __launch_bounds__(256) void avgpool_nhwc_kernel(const float *__restri
 // this library is built with -ffp-contract=fast). One thread per group of four pixels of one image: 12 source bytes (three 4-byte loads where the group's
 // address allows it, byte loads otherwise - any base alignment, no read past the group), one 16-byte store per channel plane when HW % 4 == 0 (the
 // planes are then 16-byte aligned like `out`), scalar stores otherwise and in a ragged last group.
+// REGION: the tiles are read by origin from one decoded image (src = uint8 [Hr, Wr, 3] with a row pitch in bytes, origins = int32 [B][2] = (x, y) of tile b's
+// top-left pixel): pixel p of tile b is at src + (y_b + p / W) pitch + (x_b + p % W) 3. A group that lies in one tile row is 12 contiguous bytes as above;
+// one that wraps into the next row takes its pixels one by one. Only bytes of the tile are read; the values and the stores are those of the tile form.
+struct TilesNoRegion {};
+struct TilesRegionArg { int64_t pitch; const int *origins; uint32_t W; };
+template <bool REGION>
 __global__ __launch_bounds__(256) void tiles_u8_nhwc_to_nchw_kernel(const unsigned char *__restrict__ src, float *__restrict__ out, uint64_t B, uint32_t HW,
-                                                                    StemNorm nrm) {
+                                                                    StemNorm nrm, typename std::conditional<REGION, TilesRegionArg, TilesNoRegion>::type rg) {
     const uint32_t gpi = (HW + 3) >> 2;                                   // groups per image
     const uint64_t total = B * gpi;
     const bool vec = (HW & 3u) == 0;
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (uint64_t)gridDim.x * 256) {
         const uint64_t b = i / gpi;
         const uint32_t p0 = (uint32_t)(i - b * gpi) * 4, np = HW - p0 < 4 ? HW - p0 : 4;
-        const unsigned char *s = src + (b * HW + p0) * 3;
+        const unsigned char *s, *tile = nullptr;
+        bool one_run = true;                                              // the group's 3 np bytes are contiguous
+        if constexpr (REGION) {
+            const uint32_t y0 = p0 / rg.W, x0 = p0 - y0 * rg.W;
+            tile = src + (uint64_t)(uint32_t)rg.origins[2 * b + 1] * (uint64_t)rg.pitch + (uint64_t)(uint32_t)rg.origins[2 * b] * 3;
+            s = tile + (uint64_t)y0 * (uint64_t)rg.pitch + x0 * 3;
+            one_run = x0 + np <= rg.W;
+        } else {
+            s = src + (b * HW + p0) * 3;
+        }
         unsigned u[12];
-        if (np == 4 && (reinterpret_cast<uintptr_t>(s) & 3u) == 0) {
+        if (!one_run) {
+            if constexpr (REGION) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const uint32_t pe = p0 + e, ye = pe / rg.W, xe = pe - ye * rg.W;
+                    const unsigned char *q = tile + (uint64_t)ye * (uint64_t)rg.pitch + xe * 3;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) u[3 * e + c] = (uint32_t)e < np ? q[c] : 0u;
+                }
+            }
+        } else if (np == 4 && (reinterpret_cast<uintptr_t>(s) & 3u) == 0) {
             const unsigned w0 = reinterpret_cast<const unsigned *>(s)[0], w1 = reinterpret_cast<const unsigned *>(s)[1], w2 = reinterpret_cast<const unsigned *>(s)[2];
 #pragma unroll
             for (int e = 0; e < 4; ++e) { u[e] = (w0 >> (8 * e)) & 255u; u[4 + e] = (w1 >> (8 * e)) & 255u; u[8 + e] = (w2 >> (8 * e)) & 255u; }
@@ -316,8 +341,27 @@ extern "C" int toad_tiles_u8_nhwc_to_nchw_f32(const unsigned char *tiles, const 
     StemNorm nrm;
     for (int c = 0; c < 3; ++c) { nrm.a[c] = norm[c]; nrm.b[c] = norm[3 + c]; }
     const uint32_t HW = (uint32_t)H * (uint32_t)W;
-    hipLaunchKernelGGL(tiles_u8_nhwc_to_nchw_kernel, dim3(grid_for((uint64_t)B * ((HW + 3) / 4))), dim3(256), 0, (hipStream_t)stream, tiles, out, (uint64_t)B, HW, nrm);
+    hipLaunchKernelGGL(tiles_u8_nhwc_to_nchw_kernel<false>, dim3(grid_for((uint64_t)B * ((HW + 3) / 4))), dim3(256), 0, (hipStream_t)stream, tiles, out, (uint64_t)B, HW, nrm,
+                       TilesNoRegion{});
     return check_launch(what);
+}
+
+static int region_to_nchw(const RegionSrc &rg, const float *norm, float *out, int B, int H, int W, hipStream_t st, const char *what) {
+    if (!norm || !out) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (int rc = check_region_u8(rg, H, W, what)) return rc;
+    if (B <= 0 || (uint64_t)H * W >= (1ull << 31)) { set_error("%s: bad shape", what); return TOAD_ESHAPE; }
+    if (int rc = check_norm_u8(norm, what)) return rc;
+    if (!aligned16(out)) { set_error("%s: out must be 16-byte aligned (the region may have any alignment)", what); return TOAD_EALIGN; }
+    StemNorm nrm;
+    for (int c = 0; c < 3; ++c) { nrm.a[c] = norm[c]; nrm.b[c] = norm[3 + c]; }
+    const uint32_t HW = (uint32_t)H * (uint32_t)W;
+    hipLaunchKernelGGL(tiles_u8_nhwc_to_nchw_kernel<true>, dim3(grid_for((uint64_t)B * ((HW + 3) / 4))), dim3(256), 0, st, rg.region, out, (uint64_t)B, HW, nrm,
+                       TilesRegionArg{rg.pitch, rg.origins, (uint32_t)W});
+    return check_launch(what);
+}
+extern "C" int toad_tiles_u8_region_to_nchw_f32(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm, float *out, int B,
+                                                int H, int W, void *stream) {
+    return region_to_nchw(RegionSrc{region, pitch, Hr, Wr, origins}, norm, out, B, H, W, (hipStream_t)stream, "toad_tiles_u8_region_to_nchw_f32");
 }
 
 extern "C" size_t toad_resnet50_trunc_ws_bytes(int B, int H, int W) {
@@ -337,11 +381,12 @@ extern "C" size_t toad_resnet50_trunc_u8_ws_bytes(int B, int H, int W) {
 // weights[i] : folded conv i as [Cout, K] fp32 (K = kh*kw*Cin in (ky, kx, c) order; the stem is [64, 192] in the space-to-depth
 //              order of toad_stem_conv_s2d_f32),
 // biases[i]  : folded BN shift [Cout]; i runs in execution order (conv1, then per block conv1, conv2, conv3[, downsample]).
-// The network behind both entry points. tiles_u8 == NULL: fp32 NCHW tiles (toad_resnet50_trunc_fwd_f32, arguments checked there). Otherwise uint8 NHWC tiles with
+// The network behind the three entry points. tiles_u8 == NULL: fp32 NCHW tiles (toad_resnet50_trunc_fwd_f32, arguments checked there). Otherwise uint8 NHWC tiles with
 // norm[6]: 256-wide tiles go straight into the stem kernel, others are converted into the staging image and take the fp32 call's three-kernel stem from there.
+// rg != NULL: the uint8 tiles are read by origin from rg->region (tiles_u8 == rg->region), by the region forms of the same two kernels.
 // feat / feat16: either may be NULL; each one given receives the bag rows.
 static int trunc_fwd(const float *tiles_nchw, const unsigned char *tiles_u8, const float *norm, const float *const *weights, const float *const *biases, float *feat,
-                     void *feat16, const NetPlan &p, int B, int H, int W, void *ws, void *stream, const char *what) {
+                     void *feat16, const NetPlan &p, int B, int H, int W, void *ws, void *stream, const char *what, const RegionSrc *rg = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     char *base = reinterpret_cast<char *>(ws);
     size_t off = align2m(reinterpret_cast<uintptr_t>(ws)) - reinterpret_cast<uintptr_t>(ws);
@@ -366,11 +411,14 @@ static int trunc_fwd(const float *tiles_nchw, const unsigned char *tiles_u8, con
     float *gx = slot();
     if (tiles_u8 && !stem_nchw_pool_ok(H, W)) {
         float *stage = reinterpret_cast<float *>(take((size_t)B * 3 * H * W * 4));
-        TOAD_TRY(toad_tiles_u8_nhwc_to_nchw_f32(tiles_u8, norm, stage, B, H, W, st));
+        if (rg) TOAD_TRY(region_to_nchw(*rg, norm, stage, B, H, W, st, what));
+        else TOAD_TRY(toad_tiles_u8_nhwc_to_nchw_f32(tiles_u8, norm, stage, B, H, W, st));
         tiles_nchw = stage;
         tiles_u8 = nullptr;
     }
-    if (tiles_u8) {
+    if (tiles_u8 && rg) {
+        TOAD_TRY(ext_stem_region_u8_pool(*rg, norm, weights[0], biases[0], act[1], gx, B, H, W, gws, gcap, st, what));
+    } else if (tiles_u8) {
         // uint8 tiles, 256 wide: the same kernel body reads them as stored and normalises while it converts its window (stem_halo.inc, uint8 form)
         TOAD_TRY(ext_stem_nhwc_u8_pool(tiles_u8, norm, weights[0], biases[0], act[1], gx, B, H, W, gws, gcap, st, what));
     } else if (stem_nchw_pool_ok(H, W) && aligned16(tiles_nchw)) {
@@ -464,4 +512,20 @@ extern "C" int toad_resnet50_trunc_fwd_u8(const unsigned char *tiles, const floa
     if (stem_nchw_pool_ok(H, W) && (reinterpret_cast<uintptr_t>(tiles) & 1u) != 0) { set_error("%s: 256-wide uint8 tiles must be 2-byte aligned", what); return TOAD_EALIGN; }
     for (int i = 0; i < kNumConvs; ++i) if (!weights[i] || !biases[i]) { set_error("%s: null weight/bias slot %d", what, i); return TOAD_EINVAL; }
     return trunc_fwd(nullptr, tiles, norm, weights, biases, feat, feat_f16, p, B, H, W, ws, stream, what);
+}
+
+extern "C" int toad_resnet50_trunc_fwd_u8_region(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm,
+                                                  const float *const *weights, const float *const *biases, float *feat, void *feat_f16, int B, int H, int W, void *ws,
+                                                  size_t ws_bytes, void *stream) {
+    const char *what = "toad_resnet50_trunc_fwd_u8_region";
+    if (!region || !origins || !norm || !weights || !biases || (!feat && !feat_f16) || !ws) { set_error("%s: null pointer (feat and feat_f16 may not both be NULL)", what); return TOAD_EINVAL; }
+    NetPlan p;
+    if (!make_plan(B, H, W, p)) { set_error("%s: bad shape B=%d H=%d W=%d", what, B, H, W); return TOAD_ESHAPE; }
+    const RegionSrc rg{region, pitch, Hr, Wr, origins};
+    if (int rc = check_region_u8(rg, H, W, what)) return rc;
+    if (int rc = check_norm_u8(norm, what)) return rc;
+    if (ws_bytes < toad_resnet50_trunc_u8_ws_bytes(B, H, W)) { set_error("%s: workspace too small", what); return TOAD_EWORKSPACE; }
+    if (!aligned16(ws) || (feat && !aligned16(feat)) || (feat_f16 && !aligned16(feat_f16))) { set_error("%s: workspace / outputs must be 16-byte aligned", what); return TOAD_EALIGN; }
+    for (int i = 0; i < kNumConvs; ++i) if (!weights[i] || !biases[i]) { set_error("%s: null weight/bias slot %d", what, i); return TOAD_EINVAL; }
+    return trunc_fwd(nullptr, region, norm, weights, biases, feat, feat_f16, p, B, H, W, ws, stream, what, &rg);
 }

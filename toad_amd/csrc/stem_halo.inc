@@ -39,8 +39,8 @@ static_assert(2 * SH_PLANE >= 64 * 64 * 4 && 2 * SH_SMEM <= 160 * 1024, "two wor
 constexpr int SH_TASKS = (SH_ROWS * SH_WS + 255) / 256;      // space-to-depth pixels per thread and tile: 3 (655 over 256 threads)
 
 // Input forms of the window loader. The kernel body is one template; what differs is how a lane fetches and holds the 12 values of its space-to-depth pixel:
-//   fp32 NCHW (stem_halo_pool_kernel<false>): six 8-byte loads (2 rows x 3 channel planes), held as 12 floats per task across the matrix loop;
-//   uint8 NHWC (stem_halo_pool_kernel<true>): the tiles as an image decoder hands them over, [B, H, 256, 3] RGB. A pixel pair of one row is 6 contiguous
+//   fp32 NCHW (stem_halo_pool_kernel<SH_F32>): six 8-byte loads (2 rows x 3 channel planes), held as 12 floats per task across the matrix loop;
+//   uint8 NHWC (stem_halo_pool_kernel<SH_U8>): the tiles as an image decoder hands them over, [B, H, 256, 3] RGB. A pixel pair of one row is 6 contiguous
 //     bytes at ((b H + iy) 256 + ix) 3 - a multiple of 6, so 2-byte aligned relative to the base and not 4-byte aligned in general: one 4-byte and one
 //     2-byte load per row, held RAW (4 registers per task instead of 12) across the matrix loop. store_window converts them once, in front of the abs-max:
 //     x = fmaf((float)u, a_c, b_c) with a_c = 1 / (255 std_c), b_c = -mean_c / std_c rounded to fp32 by the host - ToTensor + Normalize of the tiles the
@@ -48,24 +48,44 @@ constexpr int SH_TASKS = (SH_ROWS * SH_WS + 255) / 256;      // space-to-depth p
 //     NORMALISED space (Normalize, then the convolution's zero padding), not b_c: the spare upper half of the 2-byte load's register carries the
 //     "outside" mark. From the abs-max on the two forms run the same code on the same values, so the results are bitwise those of the fp32 form
 //     fed the normalised image.
+//   uint8 region (stem_halo_pool_kernel<SH_U8_REGION>): the tiles are never cut out. One decoded image [Hr, Wr, 3] with a row pitch in bytes, and per tile
+//     its top-left pixel (x_b, y_b) in an int32 array [B][2] on the device. The image index b = q / tpi is uniform over the workgroup, so the tile's base
+//     region + y_b pitch + x_b 3 is a 64-bit SCALAR; the in-tile offset iy pitch + ix 3 stays 32-bit (the launcher refuses H pitch >= 2^31). The edge
+//     predicate is the TILE's (iy in [0, H), ix in [0, 256)), not the region's: a tap outside the tile is 0 in normalised space even where the region has
+//     pixels there, so tile b behaves exactly as region[y:y+H, x:x+256] cut out and given to the uint8 form - and no address outside the tile, hence none
+//     outside the region, is ever read (the origins' bounds are the caller's duty). (y_b + iy) pitch + (x_b + ix) 3 has any parity, and it changes from
+//     row to row with an odd pitch: the 4-byte and the 2-byte word are loaded through types declared aligned(1) - the same two loads per row and the same
+//     4 registers per task as the uint8 form, on global memory the hardware takes a dword at any byte address (six byte loads assembled in registers compile
+//     to the same two loads at -O3: there is no second form to choose from). The loads are plain, not nontemporal:
+//     overlapping tiles (heat-map strides) read the same bytes again. From the raw words on it is the uint8 form's code.
 constexpr unsigned SH_U8_OUTSIDE = 0xFFFF0000u;              // upper half of a row's 2-byte word: the pixel pair lies outside the image
 typedef unsigned sh_u32_a2 __attribute__((aligned(2)));      // a 4-byte load from a 2-byte aligned address
+typedef unsigned sh_u32_a1 __attribute__((aligned(1)));      // region form: the same words from any byte address
+typedef unsigned short sh_u16_a1 __attribute__((aligned(1)));
+constexpr int SH_F32 = 0, SH_U8 = 1, SH_U8_REGION = 2;   // the FORM parameter of the kernel
 
 // (the constants are the LAST kernel argument, an empty struct in the fp32 form: that form's argument layout, registers and code are the ones it had as a
-//  plain kernel - 64 SGPRs, 242 VGPRs, no scratch; the uint8 form: 68 SGPRs, 218 VGPRs, no scratch; both 81,728 B of LDS, two workgroups per CU)
+//  plain kernel - 64 SGPRs, 242 VGPRs, no scratch; the uint8 form: 68 SGPRs, 218 VGPRs, no scratch; the region form, whose last argument also carries the
+//  pitch and the origins: 70 SGPRs, 217 VGPRs, no scratch; all 81,728 B of LDS, two workgroups per CU)
 struct StemNoNorm {};
-template <bool U8>
-__global__ __launch_bounds__(256, 2) void stem_halo_pool_kernel(const typename std::conditional<U8, unsigned char, float>::type *__restrict__ Xv,
+struct StemRegionArg { StemNorm nrm; int pitch; const int *origins; };      // origins: int32 [B][2] = (x, y) of each tile's top-left pixel
+template <int FORM> struct StemLastArg { typedef StemNoNorm type; };
+template <> struct StemLastArg<SH_U8> { typedef StemNorm type; };
+template <> struct StemLastArg<SH_U8_REGION> { typedef StemRegionArg type; };
+template <int FORM>
+__global__ __launch_bounds__(256, 2) void stem_halo_pool_kernel(const typename std::conditional<FORM != SH_F32, unsigned char, float>::type *__restrict__ Xv,
                                                                 const unsigned short *__restrict__ Bp, const float *__restrict__ binv,
                                                                 const float *__restrict__ bias, float *Yp, int B, int H, float *y_gmax, int tiles,
-                                                                typename std::conditional<U8, StemNorm, StemNoNorm>::type nrm_arg) {
+                                                                typename StemLastArg<FORM>::type nrm_arg) {
+    constexpr bool U8 = FORM != SH_F32, REGION = FORM == SH_U8_REGION;
     using Cfg = StreamCfg<2, 2>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     char *lds = reinterpret_cast<char *>(smem);
     const float *X = reinterpret_cast<const float *>(Xv);
     const unsigned char *X8 = reinterpret_cast<const unsigned char *>(Xv);
     StemNorm nrm{};
-    if constexpr (U8) nrm = nrm_arg;
+    if constexpr (REGION) nrm = nrm_arg.nrm;
+    else if constexpr (U8) nrm = nrm_arg;
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, hi = lane >> 5;
@@ -94,7 +114,26 @@ __global__ __launch_bounds__(256, 2) void stem_halo_pool_kernel(const typename s
     using Raw = typename std::conditional<U8, unsigned[SH_TASKS][4], f2[SH_TASKS][6]>::type;
     auto load_window = [&](int q, Raw &raw) __attribute__((always_inline)) {
         const int b = q / tpi, t = q - b * tpi;
-        if constexpr (U8) {
+        if constexpr (REGION) {
+            const int pitch = nrm_arg.pitch;
+            const int x_b = __builtin_amdgcn_readfirstlane(nrm_arg.origins[2 * b]), y_b = __builtin_amdgcn_readfirstlane(nrm_arg.origins[2 * b + 1]);
+            const unsigned char *img8 = X8 + ((int64_t)y_b * pitch + (int64_t)x_b * 3);
+#pragma unroll
+            for (int k = 0; k < SH_TASKS; ++k) {
+                int tc = tk[k];
+                asm volatile("" : "+v"(tc));                     // (laundered per call, as below)
+                const int Yl = tc >> 8, Xs = tc & 255;
+                const int ix = 2 * Xs - 4;
+#pragma unroll
+                for (int ry = 0; ry < 2; ++ry) {
+                    const int iy = 4 * t - 4 + 2 * Yl + ry;
+                    const bool ok = tc >= 0 && iy >= 0 && iy < H && ix >= 0 && ix < W;       // the TILE's edges: bytes [0, 6) of the pair end inside row iy of the tile
+                    const unsigned char *p = img8 + ((unsigned)iy * (unsigned)pitch + (unsigned)(ix * 3));      // (32-bit, unsigned: H pitch < 2^31; only read where ok)
+                    raw[k][2 * ry] = ok ? *reinterpret_cast<const sh_u32_a1 *>(p) : 0u;
+                    raw[k][2 * ry + 1] = ok ? (unsigned)*reinterpret_cast<const sh_u16_a1 *>(p + 4) : SH_U8_OUTSIDE;
+                }
+            }
+        } else if constexpr (U8) {
             const unsigned char *img8 = X8 + (int64_t)b * H * W * 3;
 #pragma unroll
             for (int k = 0; k < SH_TASKS; ++k) {

@@ -21,4 +21,22 @@ static inline int check_norm_u8(const float *norm, const char *what) {
 int ext_stem_nhwc_u8_pool(const unsigned char *X8, const float *norm, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W,
                           void *ws, size_t ws_bytes, hipStream_t st, const char *what);
 
+// Tiles read by origin from one decoded image (include/toad_hip.h, "tiles by origin"): region = uint8 [Hr, Wr, 3] on the device with a row pitch in bytes,
+// origins = DEVICE int32 [B][2], (x, y) of each tile's top-left pixel. What the host can see of it is checked here, by every entry point, before any
+// device work; that every origin keeps its tile inside the region is the caller's duty (the Python layer checks it on the host).
+struct RegionSrc { const unsigned char *region; int64_t pitch; int Hr, Wr; const int *origins; };
+static inline int check_region_u8(const RegionSrc &rg, int H, int W, const char *what) {
+    if (!rg.region || !rg.origins) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (rg.Hr <= 0 || rg.Wr <= 0 || H <= 0 || W <= 0) { set_error("%s: bad shape", what); return TOAD_ESHAPE; }
+    if (rg.pitch < 3 * (int64_t)rg.Wr) { set_error("%s: pitch %lld is less than a row of the region (3 Wr = %lld bytes)", what, (long long)rg.pitch, 3ll * rg.Wr); return TOAD_ESHAPE; }
+    if (H > rg.Hr || W > rg.Wr) { set_error("%s: a %d x %d tile does not fit a %d x %d region", what, H, W, rg.Hr, rg.Wr); return TOAD_ESHAPE; }
+    if ((int64_t)H * rg.pitch >= (1ll << 31)) { set_error("%s: pitch too large: H * pitch must stay below 2^31 (32-bit offsets inside a tile)", what); return TOAD_ESHAPE; }
+    if ((reinterpret_cast<uintptr_t>(rg.origins) & 3u) != 0) { set_error("%s: origins (int32 [B][2]) must be 4-byte aligned", what); return TOAD_EALIGN; }
+    return TOAD_OK;
+}
+
+// ext_stem_nhwc_u8_pool with the tiles read by origin (stem_halo.inc, region form): any base address, any pitch parity.
+int ext_stem_region_u8_pool(const RegionSrc &rg, const float *norm, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W,
+                            void *ws, size_t ws_bytes, hipStream_t st, const char *what);
+
 }  // namespace toad

@@ -196,3 +196,13 @@ def attention_heatmap_scores(model: TOAD_fc_mtl_concat, data: torch.Tensor, perc
     ranks = torch.empty_like(a)
     ranks[order] = torch.arange(a.numel(), device=a.device, dtype=a.dtype)
     return ranks / max(a.numel() - 1, 1)
+
+
+def region_attention_scores(extractor, model: TOAD_fc_mtl_concat, region: torch.Tensor, origins, tile=256, bag_dtype: torch.dtype = torch.float16,
+                            percentile: bool = False) -> torch.Tensor:
+    """Heat-map scores of the tiles at ``origins`` of one decoded uint8 region [Hr,Wr,3], in the order of ``origins``, with no tile tensor at any point:
+    ``extractor.forward_u8_region`` reads the tiles where they lie (overlapping ones - a heat-map stride below the tile size - included) and writes its
+    rows chunk by chunk into one [B,1024] bag of ``bag_dtype``; ``attention_heatmap_scores(model, bag, percentile)`` scores that bag. Equal to scoring
+    ``extractor.forward_u8(stacked tiles, out_dtype=bag_dtype)``. Rasterising the B scores onto a canvas is host work and not done here."""
+    bag = extractor.forward_u8_region(region, origins, tile=tile, out_dtype=bag_dtype)
+    return attention_heatmap_scores(model, bag, percentile)

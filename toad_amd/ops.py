@@ -1201,6 +1201,86 @@ def stem_pool_nhwc_u8(tiles: torch.Tensor, wf: torch.Tensor, b, mean=IMAGENET_ME
     return y
 
 
+def tile_shape(tile):
+    """`tile` of the region calls, an int or (H, W) -> (H, W)."""
+    h, w = (tile, tile) if isinstance(tile, int) else tuple(tile)
+    if not (isinstance(h, int) and isinstance(w, int)) or h < 1 or w < 1:
+        raise ValueError(f"tile must be a positive int or (H, W), got {tile!r}")
+    return h, w
+
+
+def check_origins(origins, hr: int, wr: int, h: int, w: int) -> torch.Tensor:
+    """The `origins` argument of the region calls, checked on the HOST: [B,2] integers (x, y), the top-left pixel of each tile in region coordinates, as a
+    CPU tensor, a numpy array or a list -> a contiguous int32 CPU tensor. Every tile must lie inside the hr x wr region: the kernels read where the origins
+    point, so an origin out of range is an out-of-bounds read. A device tensor is refused for that reason - its values cannot be checked without a
+    synchronisation. Raises before anything is launched."""
+    if isinstance(origins, torch.Tensor) and origins.device.type != "cpu":
+        raise ValueError("origins must be given on the host (a CPU tensor, a numpy array or a list): their bounds are checked before the launch, and "
+                         f"device values cannot be read without a synchronisation (got a tensor on {origins.device})")
+    o = torch.as_tensor(origins)
+    if o.is_floating_point() or o.is_complex() or o.dtype == torch.bool:
+        raise TypeError(f"origins must be integers (pixel coordinates), got {o.dtype}")
+    if o.dim() != 2 or o.shape[1] != 2:
+        raise ValueError(f"origins must be [B,2] = (x, y) per tile, got {tuple(o.shape)}")
+    o = o.to(torch.int64)
+    bad = (o[:, 0] < 0) | (o[:, 0] + w > wr) | (o[:, 1] < 0) | (o[:, 1] + h > hr)
+    if bool(bad.any()):
+        i = int(torch.nonzero(bad)[0])
+        raise ValueError(f"origins[{i}] = (x={int(o[i, 0])}, y={int(o[i, 1])}): a {h} x {w} (H x W) tile there does not lie inside the {hr} x {wr} region")
+    return o.to(torch.int32).contiguous()
+
+
+def region_layout_ok(region: torch.Tensor) -> bool:
+    """[Hr,Wr,3] with stride(2) == 1, stride(1) == 3 and a row pitch stride(0) >= 3 Wr (any pitch: a column crop of a wider image is taken as it is)."""
+    return region.dim() == 3 and region.shape[2] == 3 and region.shape[0] >= 1 and region.shape[1] >= 1 and region.stride(2) == 1 and region.stride(1) == 3 \
+        and (region.stride(0) >= 3 * region.shape[1] or region.shape[0] == 1)
+
+
+def _region_args(region: torch.Tensor, origins, tile, name: str):
+    if not isinstance(region, torch.Tensor) or not region.is_cuda:
+        raise RuntimeError(f"{name}: region must be a CUDA(HIP) tensor: toad_amd has no CPU path")
+    if region.dtype != torch.uint8:
+        raise TypeError(f"{name}: region must be torch.uint8, got {region.dtype}")
+    if not region_layout_ok(region):
+        raise ValueError(f"{name}: expected a uint8 [Hr,Wr,3] region (RGB, channels last) with stride(2) == 1, stride(1) == 3 and a row pitch >= 3 Wr, got "
+                         f"shape {tuple(region.shape)} strides {tuple(region.stride())}")
+    h, w = tile_shape(tile)
+    hr, wr = region.shape[0], region.shape[1]
+    o = check_origins(origins, hr, wr, h, w)
+    if o.shape[0] == 0:
+        raise ValueError(f"{name}: no origins")
+    pitch = region.stride(0) if hr > 1 else max(region.stride(0), 3 * wr)
+    return pitch, hr, wr, h, w, o.to(region.device)
+
+
+def tiles_u8_region_to_f32(region: torch.Tensor, origins, tile=256, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> torch.Tensor:
+    """tiles_u8_to_f32 with the tiles read by origin from one decoded uint8 region [Hr,Wr,3] (any row pitch, any alignment): bitwise
+    tiles_u8_to_f32(torch.stack([region[y:y+H, x:x+W] for x, y in origins]), mean, std), and no such stack exists. origins: check_origins."""
+    pitch, hr, wr, h, w, o = _region_args(region, origins, tile, "tiles_u8_region_to_f32")
+    norm = norm_constants_u8(mean, std)
+    out = torch.empty((o.shape[0], 3, h, w), dtype=torch.float32, device=region.device)
+    _lib.check(_lib.load().toad_tiles_u8_region_to_nchw_f32(_p(region), pitch, hr, wr, _p(o), norm, _p(out), o.shape[0], h, w, _stream()),
+               "toad_tiles_u8_region_to_nchw_f32")
+    return out
+
+
+def stem_pool_region_u8(region: torch.Tensor, origins, wf: torch.Tensor, b, tile=256, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> torch.Tensor:
+    """stem_pool_nhwc_u8 with the tiles (H, 256), H % 4 == 0, read by origin from one decoded uint8 region: bitwise stem_pool_nhwc_u8 on the stacked
+    tiles. Padding is the tile's, not the region's; the region is read in place whatever its address and pitch."""
+    pitch, hr, wr, h, w, o = _region_args(region, origins, tile, "stem_pool_region_u8")
+    _chk(wf, "wf"); _chk(b, "b", allow_none=True)
+    if tuple(wf.shape) != (64, 192):
+        raise ValueError("stem_pool_region_u8: expected a [64,192] space-to-depth weight")
+    norm = norm_constants_u8(mean, std)
+    bb = o.shape[0]
+    y = torch.empty((bb, h // 4, w // 4, 64), dtype=torch.float32, device=region.device)
+    lib = _lib.load()
+    ws = _ws(lib.toad_linear_ws_bytes(bb * (h // 2) * (w // 2), 64, 192), region.device)
+    _lib.check(lib.toad_stem_pool_region_u8(_p(region), pitch, hr, wr, _p(o), norm, _p(wf), _p(b), _p(y), bb, h, w, _p(ws), ws.numel(), _stream()),
+               "toad_stem_pool_region_u8")
+    return y
+
+
 def maxpool3x3s2_nhwc(x: torch.Tensor) -> torch.Tensor:
     _chk(x, "x")
     b, h, w, c = x.shape

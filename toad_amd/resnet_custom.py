@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .ops import IMAGENET_MEAN, IMAGENET_STD, norm_constants_u8
+from .ops import IMAGENET_MEAN, IMAGENET_STD, check_origins, norm_constants_u8, region_layout_ok, tile_shape
 
 __all__ = ["Bottleneck_Baseline", "ResNet_Baseline", "resnet50_baseline", "IMAGENET_MEAN", "IMAGENET_STD"]
 
@@ -220,6 +220,61 @@ class ResNet_Baseline(nn.Module):
             _lib.check(lib.toad_resnet50_trunc_fwd_u8(tiles[b0:b0 + nb].data_ptr(), norm, wp, bp, None if half else o, o if half else None, nb, H, W,
                                                       self._ws.data_ptr(), self._ws.numel(), stream), "toad_resnet50_trunc_fwd_u8")
         return out
+
+    def forward_u8_region(self, region: torch.Tensor, origins, tile=256, mean=IMAGENET_MEAN, std=IMAGENET_STD, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """Tiles read by origin from one decoded region -> [B,1024] bag rows, fp32 or fp16; no tile copy exists at any point.
+
+        ``region``: uint8 [Hr,Wr,3] RGB on the HIP device with stride(2) == 1, stride(1) == 3 and any row pitch stride(0) >= 3 Wr (a column crop of a
+        wider image is read in place; any base address). ``origins``: [B,2] integers (x, y), the top-left pixel of each tile in region coordinates, given
+        on the HOST (CPU tensor, numpy array or list) - every tile must lie inside the region, which is checked here before anything is launched
+        (``ValueError`` naming the first offender); duplicates, overlaps and any order are fine. ``tile``: an int or (H, W). Padding is the tile's, not the
+        region's: the result is bitwise ``forward_u8(torch.stack([region[y:y+H, x:x+W] for x, y in origins]), mean, std, out_dtype)``. More than
+        ``max_tiles_per_call`` origins are run in chunks that write into the one [B,1024] result."""
+        if self.training:
+            raise RuntimeError("the HIP extractor is inference-only: call .eval() (the reference never trains it)")
+        if region.dtype != torch.uint8:
+            raise RuntimeError(f"forward_u8_region expects a uint8 region, got {region.dtype}")
+        if region.dim() != 3 or region.shape[2] != 3:
+            raise RuntimeError(f"forward_u8_region expects a channels-last [Hr,Wr,3] region, got {tuple(region.shape)}")
+        if out_dtype not in (torch.float32, torch.float16):
+            raise RuntimeError(f"out_dtype must be torch.float32 or torch.float16, got {out_dtype}")
+        if not region.is_cuda:
+            raise RuntimeError("expected a uint8 [Hr,Wr,3] tensor on the HIP device (no CPU fallback)")
+        if not region_layout_ok(region):
+            raise RuntimeError(f"forward_u8_region expects a region with stride(2) == 1, stride(1) == 3 and a row pitch stride(0) >= 3 Wr (rows are read in "
+                               f"place, there is no hidden copy), got strides {tuple(region.stride())} for shape {tuple(region.shape)}")
+        if self.conv1.weight.device != region.device:
+            raise RuntimeError("model and input are on different devices; call model.relocate()")
+        H, W = tile_shape(tile)
+        Hr, Wr = region.shape[0], region.shape[1]
+        org = check_origins(origins, Hr, Wr, H, W)
+        B = org.shape[0]
+        norm = norm_constants_u8(mean, std)
+        out = torch.empty(B, 1024, device=region.device, dtype=out_dtype)
+        if B == 0:
+            return out
+        lib = _lib.load()
+        if self._folded is None or self._folded_sig != self._param_signature():
+            self._fold_all()
+        _, _, wp, bp = self._folded
+        pitch = region.stride(0) if Hr > 1 else max(region.stride(0), 3 * Wr)
+        org = org.to(region.device)                         # int32 [B,2]: the one small copy of the call
+        half = out_dtype == torch.float16
+        stream = torch.cuda.current_stream(region.device).cuda_stream
+        cap = max_tiles_per_call(H, W)
+        for b0 in range(0, B, cap):                         # the origins are sliced, never the region
+            nb = min(cap, B - b0)
+            need = lib.toad_resnet50_trunc_u8_ws_bytes(nb, H, W)
+            if need == 0:
+                raise RuntimeError(f"unsupported tile shape {H}x{W}")
+            if self._ws is None or self._ws.numel() < need or self._ws.device != region.device:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=region.device)
+            o = out[b0:b0 + nb].data_ptr()
+            _lib.check(lib.toad_resnet50_trunc_fwd_u8_region(region.data_ptr(), pitch, Hr, Wr, org[b0:b0 + nb].data_ptr(), norm, wp, bp, None if half else o,
+                                                             o if half else None, nb, H, W, self._ws.data_ptr(), self._ws.numel(), stream),
+                       "toad_resnet50_trunc_fwd_u8_region")
+        return out
+
 
 
 def resnet50_baseline(pretrained: bool = False) -> ResNet_Baseline:

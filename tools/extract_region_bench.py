@@ -1,0 +1,160 @@
+"""What reading tiles by origin costs: ResNet_Baseline.forward_u8_region against forward_u8 on the same tiles cut out beforehand. A sibling of
+extract_u8_bench.py (its event timing, its alternation of the arms inside one process and its two interleaved halves of arm A as the noise figure).
+
+  resident: 512 tiles of 256 x 256 per call, everything on the device before the clock starts:
+      arm A  forward_u8 on the materialised tiles [512,256,256,3] (the existing route), reported as two interleaved halves A1 / A2;
+      arm B  forward_u8_region on the region those tiles were cut from: a 16 x 32 grid of non-overlapping tiles, 4096 x 8192 pixels (the same bytes);
+      arm C  forward_u8_region at stride 64: a 16 x 32 grid of overlapping tiles from a 1216 x 2240 region (the heat-map case; other pixels than A and B).
+    The origins are a CPU tensor, checked and copied to the device inside the clock on every call of arms B and C.
+  host_fed: 512 tiles per step from a region in page-locked host memory, the steps run one after another (nothing overlapped), wall-clock:
+      arm D1  the host cuts the tiles with numpy into a page-locked [512,256,256,3] buffer, one H2D copy of it, forward_u8;
+      arm D2  one H2D copy of the region, forward_u8_region.
+    Per arm: tiles/s, link GB/s over the whole step, and the host seconds per step spent before the copy is issued (the cutting; for D2 nothing).
+    --stride 64 runs the same pair on the overlapping grid, where the tiles are 12 times the region.
+  launches: four calls of ONE resident arm (--arm A | B | C) for a `rocprofv3 --kernel-trace --stats` run of its own: the stem instantiations' times.
+
+Prints one JSON line per result; --out FILE keeps them.
+usage: extract_region_bench.py [--resident] [--host-fed] [--launches --arm A|B|C] [--stride S] [--seconds S] [--steps K] [--out FILE]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import torch                                   # noqa: E402
+
+from extract_u8_bench import alternate, make_model, median      # noqa: E402
+
+GRID = (16, 32)                                # 512 tiles
+TILE = 256
+
+
+def grid_region(stride, dev):
+    """(region [Hr,Wr,3] of random bytes, origins [512,2] (x, y) as a CPU tensor) of the 16 x 32 grid at `stride` pixels."""
+    gy, gx = GRID
+    hr, wr = (gy - 1) * stride + TILE, (gx - 1) * stride + TILE
+    g = torch.Generator(device=dev).manual_seed(1)
+    region = torch.randint(0, 256, (hr, wr, 3), device=dev, dtype=torch.uint8, generator=g)
+    origins = torch.tensor([(x * stride, y * stride) for y in range(gy) for x in range(gx)], dtype=torch.int32)
+    return region, origins
+
+
+def cut(region, origins):
+    return torch.stack([region[y:y + TILE, x:x + TILE] for x, y in origins.tolist()])
+
+
+def resident(seconds):
+    dev = torch.device("cuda:0")
+    model = make_model()
+    region, origins = grid_region(TILE, dev)
+    tiles = cut(region, origins)
+    region64, origins64 = grid_region(64, dev)
+    same = bool(torch.equal(model.forward_u8_region(region, origins), model.forward_u8(tiles)))
+    same64 = bool(torch.equal(model.forward_u8_region(region64, origins64, out_dtype=torch.float16),
+                              model.forward_u8(cut(region64, origins64), out_dtype=torch.float16)))
+    arms = {"A_u8_tiles": lambda: model.forward_u8(tiles), "B_region_grid": lambda: model.forward_u8_region(region, origins),
+            "C_region_stride64": lambda: model.forward_u8_region(region64, origins64)}
+    t, iters = alternate(arms, seconds)
+    a = t["A_u8_tiles"]
+    a1, a2 = median(a[0::2]), median(a[1::2])
+    n = origins.shape[0]
+    return [dict(kind="resident_region", tiles=n, tile="256x256", region=list(region.shape[:2]), region_stride64=list(region64.shape[:2]), rounds=len(a),
+                 iters_per_round=iters, ms={k: round(median(v), 4) for k, v in t.items()}, ms_min={k: round(min(v), 4) for k, v in t.items()},
+                 ms_max={k: round(max(v), 4) for k, v in t.items()}, tiles_per_s={k: round(n / median(v) * 1e3, 1) for k, v in t.items()},
+                 arm_a_halves_ms=[round(a1, 4), round(a2, 4)], arm_a_spread=round(abs(a1 - a2) / median(a), 4),
+                 b_over_a=round(median(t["B_region_grid"]) / median(a), 4), c_over_a=round(median(t["C_region_stride64"]) / median(a), 4),
+                 b_within_1p02_a=bool(median(t["B_region_grid"]) <= 1.02 * median(a)), region_bitwise_tiles=same, region_stride64_fp16_bitwise_tiles=same64)]
+
+
+def host_fed(stride, steps):
+    dev = torch.device("cuda:0")
+    model = make_model()
+    region_d, origins = grid_region(stride, dev)
+    n = origins.shape[0]
+    region_h = torch.empty(region_d.shape, dtype=torch.uint8, pin_memory=True)
+    region_h.copy_(region_d)
+    del region_d
+    region_np = region_h.numpy()
+    tiles_h = torch.empty((n, TILE, TILE, 3), dtype=torch.uint8, pin_memory=True)
+    tiles_np = tiles_h.numpy()
+    tiles_d = torch.empty(tiles_h.shape, dtype=torch.uint8, device=dev)
+    region_dst = torch.empty(region_h.shape, dtype=torch.uint8, device=dev)
+    xy = origins.tolist()
+
+    def step_cut():
+        t0 = time.perf_counter()
+        for i, (x, y) in enumerate(xy):
+            tiles_np[i] = region_np[y:y + TILE, x:x + TILE]
+        host = time.perf_counter() - t0
+        tiles_d.copy_(tiles_h, non_blocking=True)
+        model.forward_u8(tiles_d)
+        return host
+
+    def step_region():
+        region_dst.copy_(region_h, non_blocking=True)
+        model.forward_u8_region(region_dst, origins)
+        return 0.0
+
+    res = []
+    for arm, step, nbytes in (("D1_host_cuts_tiles", step_cut, tiles_h.numel()), ("D2_region_by_origin", step_region, region_h.numel())):
+        for _ in range(2):
+            step()
+        torch.cuda.synchronize()
+        host = 0.0
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            host += step()
+            torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        res.append(dict(kind="host_fed_region", arm=arm, stride=stride, tiles_per_step=n, steps=steps, h2d_bytes_per_step=nbytes,
+                        tiles_per_s=round(steps * n / dt, 1), ms_per_step=round(dt / steps * 1e3, 3), link_gbps=round(steps * nbytes / dt / 1e9, 2),
+                        host_s_per_step=round(host / steps, 5), host_cut_gbps=round(steps * nbytes / host / 1e9, 2) if host > 0 else None,
+                        host_threads=torch.get_num_threads()))
+    return res
+
+
+def launches(arm, calls=4):
+    """`calls` calls of one arm, no warm-up (run under rocprofv3 --kernel-trace --stats: every count divides by `calls`)."""
+    dev = torch.device("cuda:0")
+    model = make_model()
+    region, origins = grid_region(64 if arm == "C" else TILE, dev)
+    tiles = cut(region, origins) if arm == "A" else None
+    for _ in range(calls):
+        if arm == "A":
+            model.forward_u8(tiles)
+        else:
+            model.forward_u8_region(region, origins)
+    torch.cuda.synchronize()
+    return [dict(kind="launches_region", tiles=origins.shape[0], calls=calls, arm=arm)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--resident", action="store_true")
+    ap.add_argument("--host-fed", action="store_true")
+    ap.add_argument("--launches", action="store_true")
+    ap.add_argument("--arm", default="B", choices=("A", "B", "C"))
+    ap.add_argument("--stride", type=int, default=TILE)
+    ap.add_argument("--seconds", type=float, default=3.0)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    every = not (a.resident or a.host_fed or a.launches)
+    res = []
+    if a.launches:
+        res += launches(a.arm)
+    if a.resident or every:
+        res += resident(a.seconds)
+    if a.host_fed or every:
+        res += host_fed(a.stride, a.steps)
+    lines = [json.dumps(r) for r in res]
+    print("\n".join(lines), flush=True)
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
