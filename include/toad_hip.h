@@ -367,6 +367,37 @@ int toad_resnet50_trunc_fwd_u8_region(const unsigned char *region, int64_t pitch
                                       const float *const *weights, const float *const *biases, float *feat, void *feat_f16, int B, int H, int W,
                                       void *ws, size_t ws_bytes, void *stream);
 
+/* ---- Tissue selection: which tiles of a decoded region to read (an additive extension of ABI 15; the version number does not change) ----
+ * The reference tree has no patching script: its bags come from CLAM's, which thresholds HSV saturation and keeps the tiles that hold tissue. The two
+ * calls below produce the per-tile tissue-pixel counts from which the caller forms the `origins` of the region calls above; csrc/tissue.hip.
+ *   predicate  integers only, no rounding anywhere. For a pixel (r, g, b), mx = max(r, g, b), mn = min(r, g, b):
+ *                  tissue  <=>  mx >= val_min  and  255 * (mx - mn) > sat_thresh * mx
+ *              i.e. HSV saturation (mx - mn) / mx above sat_thresh on the 8-bit scale, written without the division. It is NOT OpenCV's rounded S
+ *              channel (round(255 * (mx - mn) / mx) > sat_thresh). mx == 0 is never tissue. val_min removes black scanner margins, whose JPEG noise -
+ *              (1, 0, 0) for example - is fully saturated. sat_thresh and val_min in [0, 255], TOAD_EINVAL otherwise.
+ *   cells      the region is partitioned into cell x cell pixel cells anchored at its (0, 0), cell in {4, 8, 16, 32, 64} (TOAD_ESHAPE otherwise):
+ *              Gy = ceil(Hr / cell) rows of Gx = ceil(Wr / cell) cells; a partial cell at the right or the bottom edge counts the pixels that exist.
+ * Both calls are asynchronous on `stream`, allocate nothing and do not synchronise; every refusal comes before any device access. */
+
+/* counts int32 [Gy][Gx] (4-byte aligned, TOAD_EALIGN otherwise) = the tissue pixels of every cell. EVERY element is written by the call, whatever it held:
+ * nothing has to be zeroed first. region and pitch as for the region calls above: any base address, any pitch >= 3 * Wr; the row base y * pitch is 64-bit,
+ * the byte offset inside a row 32-bit (3 * Wr >= 2^31: TOAD_ESHAPE). No byte outside region + y * pitch + [0, 3 * Wr), 0 <= y < Hr, is read - the last row
+ * of a pitched view may be the end of its allocation. Hr or Wr < 1, pitch < 3 * Wr: TOAD_ESHAPE. One streaming pass over the region. */
+int toad_region_tissue_cells_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, int cell, int sat_thresh, int val_min, int *counts,
+                                void *stream);
+
+/* tile_counts int32 [ny][nx] = the tissue pixels of every tile of a lattice: tile (j, i) has its top-left pixel at (x0 + i * sx, y0 + j * sy) and H x W
+ * pixels (rows x columns). `counts` [Gy][Gx] and `cell` are those of a toad_region_tissue_cells_u8 call. x0, y0, H, W, sx, sy must be non-negative multiples
+ * of cell, so that a tile is an exact union of whole cells; strides below the tile size (heat-map lattices) just re-read cells. Gy, Gx, H, W, sx, sy, nx, ny
+ * >= 1 and H * W < 2^31 (TOAD_ESHAPE otherwise).
+ * Bounds: every tile must lie inside the region the cells were counted on, x0 + (nx - 1) * sx + W <= Wr and y0 + (ny - 1) * sy + H <= Hr, where the caller
+ * used exactly Gy = ceil(Hr / cell) and Gx = ceil(Wr / cell). The library sees Gy and Gx only: it refuses (TOAD_ESHAPE) a lattice whose last tile ends
+ * beyond Gx * cell columns or Gy * cell rows - that would read outside `counts`. A tile that passes this test but reaches beyond Wr or Hr, into a partial
+ * edge cell, reads inside `counts` and is counted over the pixels that exist; keeping tiles inside Hr x Wr is the caller's duty (toad_amd.tissue.lattice).
+ * counts and tile_counts 4-byte aligned (TOAD_EALIGN). */
+int toad_tissue_tile_counts(const int *counts, int Gy, int Gx, int cell, int x0, int y0, int H, int W, int sx, int sy, int nx, int ny, int *tile_counts,
+                            void *stream);
+
 /* ---- Whole-slide calls: forward, backward, training step -------------------------------- */
 
 /* The reference drives this path through three Python statements,

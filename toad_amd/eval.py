@@ -206,3 +206,16 @@ def region_attention_scores(extractor, model: TOAD_fc_mtl_concat, region: torch.
     ``extractor.forward_u8(stacked tiles, out_dtype=bag_dtype)``. Rasterising the B scores onto a canvas is host work and not done here."""
     bag = extractor.forward_u8_region(region, origins, tile=tile, out_dtype=bag_dtype)
     return attention_heatmap_scores(model, bag, percentile)
+
+
+def region_tissue_attention_scores(extractor, model: TOAD_fc_mtl_concat, region: torch.Tensor, tile=256, stride=None, min_fraction: float = 0.25,
+                                   sat_thresh: int = 8, val_min: int = 0, bag_dtype: torch.dtype = torch.float16, percentile: bool = False):
+    """``(origins, scores)`` of the tissue tiles of one decoded uint8 region [Hr,Wr,3]: ``tissue.tissue_origins`` picks the lattice tiles that hold tissue
+    from the pixels (two launches and one small read-back, on the region where it lies), ``region_attention_scores`` scores exactly those. ``origins`` is
+    the int64 [B,2] host array of (x, y), row-major over the lattice; ``scores`` its B scores on the device. A region without a tissue tile returns an
+    empty [0,2] array and an empty score tensor, and the extractor is not called. Selection arguments and their defaults: ``tissue.tissue_origins``."""
+    from .tissue import tissue_origins
+    origins = tissue_origins(region, tile=tile, stride=stride, min_fraction=min_fraction, sat_thresh=sat_thresh, val_min=val_min)
+    if origins.shape[0] == 0:
+        return origins, torch.empty(0, dtype=torch.float32, device=region.device)
+    return origins, region_attention_scores(extractor, model, region, origins, tile=tile, bag_dtype=bag_dtype, percentile=percentile)

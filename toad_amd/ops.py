@@ -1236,7 +1236,8 @@ def region_layout_ok(region: torch.Tensor) -> bool:
         and (region.stride(0) >= 3 * region.shape[1] or region.shape[0] == 1)
 
 
-def _region_args(region: torch.Tensor, origins, tile, name: str):
+def _region_pitch(region: torch.Tensor, name: str):
+    """The device / dtype / layout checks every region call makes -> (pitch in bytes, Hr, Wr)."""
     if not isinstance(region, torch.Tensor) or not region.is_cuda:
         raise RuntimeError(f"{name}: region must be a CUDA(HIP) tensor: toad_amd has no CPU path")
     if region.dtype != torch.uint8:
@@ -1244,12 +1245,16 @@ def _region_args(region: torch.Tensor, origins, tile, name: str):
     if not region_layout_ok(region):
         raise ValueError(f"{name}: expected a uint8 [Hr,Wr,3] region (RGB, channels last) with stride(2) == 1, stride(1) == 3 and a row pitch >= 3 Wr, got "
                          f"shape {tuple(region.shape)} strides {tuple(region.stride())}")
-    h, w = tile_shape(tile)
     hr, wr = region.shape[0], region.shape[1]
+    return (region.stride(0) if hr > 1 else max(region.stride(0), 3 * wr)), hr, wr
+
+
+def _region_args(region: torch.Tensor, origins, tile, name: str):
+    pitch, hr, wr = _region_pitch(region, name)
+    h, w = tile_shape(tile)
     o = check_origins(origins, hr, wr, h, w)
     if o.shape[0] == 0:
         raise ValueError(f"{name}: no origins")
-    pitch = region.stride(0) if hr > 1 else max(region.stride(0), 3 * wr)
     return pitch, hr, wr, h, w, o.to(region.device)
 
 
@@ -1279,6 +1284,44 @@ def stem_pool_region_u8(region: torch.Tensor, origins, wf: torch.Tensor, b, tile
     _lib.check(lib.toad_stem_pool_region_u8(_p(region), pitch, hr, wr, _p(o), norm, _p(wf), _p(b), _p(y), bb, h, w, _p(ws), ws.numel(), _stream()),
                "toad_stem_pool_region_u8")
     return y
+
+
+TISSUE_CELLS = (64, 32, 16, 8, 4)      # the cell sizes of csrc/tissue.hip
+
+
+def region_tissue_cells(region: torch.Tensor, cell: int, sat_thresh: int, val_min: int) -> torch.Tensor:
+    """Tissue pixels per cell x cell cell of one decoded uint8 region [Hr,Wr,3] (any row pitch, any alignment; read in place): int32 [Gy,Gx] on the device,
+    Gy = ceil(Hr / cell), Gx = ceil(Wr / cell), cells anchored at the region's (0, 0), partial edge cells counting the pixels that exist. A pixel is tissue
+    iff mx >= val_min and 255 (mx - mn) > sat_thresh mx, mx / mn = max / min of (r, g, b): HSV saturation above sat_thresh on the 8-bit scale in exact
+    integers - not OpenCV's rounded S channel. cell in TISSUE_CELLS; sat_thresh, val_min ints in [0, 255]. One launch, no synchronisation."""
+    name = "region_tissue_cells"
+    pitch, hr, wr = _region_pitch(region, name)
+    if cell not in TISSUE_CELLS:
+        raise ValueError(f"{name}: cell must be one of {TISSUE_CELLS}, got {cell!r}")
+    for k, v in (("sat_thresh", sat_thresh), ("val_min", val_min)):
+        if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= 255:
+            raise ValueError(f"{name}: {k} must be an int in [0, 255] (the 8-bit scale), got {v!r}")
+    counts = torch.empty((-(-hr // cell), -(-wr // cell)), dtype=torch.int32, device=region.device)
+    _lib.check(_lib.load().toad_region_tissue_cells_u8(_p(region), pitch, hr, wr, cell, sat_thresh, val_min, _p(counts), _stream()),
+               "toad_region_tissue_cells_u8")
+    return counts
+
+
+def tissue_tile_counts(cells: torch.Tensor, cell: int, origin, tile, stride, n) -> torch.Tensor:
+    """Tissue pixels per tile of a lattice, from the cell counts of region_tissue_cells(region, cell, ...): int32 [ny,nx] on the device. origin = (x0, y0)
+    of tile (0, 0), tile = (H, W), stride = (sy, sx), n = (nx, ny); tile (j, i) has its top-left pixel at (x0 + i sx, y0 + j sy). All six lattice numbers
+    must be multiples of `cell` (a tile is then an exact union of whole cells) and every tile must lie inside the region the cells were counted on
+    (toad_amd.tissue.lattice gives the largest such extent). One launch, no synchronisation."""
+    _chk(cells, "cells", dtype=torch.int32)
+    if cells.dim() != 2:
+        raise ValueError(f"tissue_tile_counts: expected int32 [Gy,Gx] cell counts, got {tuple(cells.shape)}")
+    (x0, y0), (h, w), (sy, sx), (nx, ny) = origin, tile, stride, n
+    if nx < 1 or ny < 1:
+        raise ValueError(f"tissue_tile_counts: an empty lattice (nx = {nx}, ny = {ny})")
+    out = torch.empty((ny, nx), dtype=torch.int32, device=cells.device)
+    _lib.check(_lib.load().toad_tissue_tile_counts(_p(cells), cells.shape[0], cells.shape[1], cell, x0, y0, h, w, sx, sy, nx, ny, _p(out), _stream()),
+               "toad_tissue_tile_counts")
+    return out
 
 
 def maxpool3x3s2_nhwc(x: torch.Tensor) -> torch.Tensor:
