@@ -398,6 +398,35 @@ int toad_region_tissue_cells_u8(const unsigned char *region, int64_t pitch, int 
 int toad_tissue_tile_counts(const int *counts, int Gy, int Gx, int cell, int x0, int y0, int H, int W, int sx, int sy, int nx, int ny, int *tile_counts,
                             void *stream);
 
+/* ---- Attention heat map: the scores of the tiles of a region, rendered onto the region where it lies (an additive extension of ABI 15 as well) ----
+ * The reference tree draws its heat maps with CLAM's host loop (overlay[y:y+h, x:x+w] += score; counter += 1; divide; colour-map; addWeighted). The two
+ * calls below are that loop defined in integers, on the device; csrc/heatmap.hip.
+ *   tile table  tile_q int32 [ny][nx] over a lattice as in toad_tissue_tile_counts: -1 = the tile is absent (not selected), otherwise its score
+ *               quantised to 0 .. 65535 (toad_amd.heatmap.quantise_scores). Values above 65535 count as 65535.
+ *   cell value  cells of cell x cell pixels anchored at the region's (0, 0), Gy = ceil(Hr / cell), Gx = ceil(Wr / cell). With n the present tiles that
+ *               cover a cell and S the sum of their q:  idx = (2 * S + 257 * n) / (514 * n) if n > 0, else -1. That is 255 * mean(q) / 65535 rounded
+ *               half up (65535 = 255 * 257), in 0 .. 255.
+ *   canvas      down in {1, 2, 4}: Ho = Hr / down, Wo = Wr / down (partial boxes at the right and the bottom edge are dropped). Per channel
+ *               m = (sum of the down x down box + down * down / 2) / (down * down); the output byte is m where the box's cell has idx = -1, elsewhere
+ *                   (alpha * lut[idx][c] + (256 - alpha) * m + 128) >> 8,    alpha an integer in [0, 256], lut uint8 [256][3].
+ *               down divides every cell size, so a box lies in one cell. alpha = 0 gives the box-filtered region, alpha = 256 flat colour on covered cells.
+ * Both calls are asynchronous on `stream`, allocate nothing and do not synchronise; every refusal comes before any device access. */
+
+/* cells int32 [Gy][Gx] = the cell values of the lattice x0, y0, H, W, sx, sy, nx, ny (pixels; tile (j, i) at (x0 + i * sx, y0 + j * sy), H rows x W
+ * columns). EVERY element is written by the call, whatever it held. All six lattice numbers non-negative multiples of cell, Gy, Gx, nx, ny, H, W, sx, sy
+ * >= 1, the last tile inside Gx * cell columns and Gy * cell rows, and a coverage ceil(H / sy) * ceil(W / sx) of at most 4096 tiles per cell (then
+ * 2 * S + 257 * n < 2^31): TOAD_ESHAPE otherwise. tile_q and cells 4-byte aligned (TOAD_EALIGN). */
+int toad_heat_cells(const int *tile_q, int nx, int ny, int cell, int x0, int y0, int H, int W, int sx, int sy, int Gy, int Gx, int *cells, void *stream);
+
+/* out uint8 [Ho][Wo][3] with row pitch out_pitch >= 3 * Wo bytes = the canvas of `region` under `cells` [Gy][Gx] (Gy = ceil(Hr / cell), Gx = ceil(Wr /
+ * cell) exactly; values -1 .. 255), `lut` [256][3], `alpha` in [0, 256] and `down` in {1, 2, 4}: TOAD_ESHAPE otherwise. region and pitch as for
+ * toad_region_tissue_cells_u8: any base address, any pitch >= 3 * Wr, 64-bit row bases, 32-bit offsets inside a row (3 * Wr >= 2^31: TOAD_ESHAPE). out
+ * may have any base address and pitch as well, so it can be a window of a larger canvas; it must not overlap region. No byte outside region + y * pitch +
+ * [0, 3 * Wr), 0 <= y < Hr, is read, no byte outside out + y * out_pitch + [0, 3 * Wo), 0 <= y < Ho, is written. cells 4-byte aligned (TOAD_EALIGN).
+ * Ho == 0 or Wo == 0: returns TOAD_OK and launches nothing. One streaming pass: 3 * Hr * Wr bytes read, 3 * Ho * Wo written. */
+int toad_region_heat_blend_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx, int cell,
+                              const unsigned char *lut, int alpha, int down, unsigned char *out, int64_t out_pitch, void *stream);
+
 /* ---- Whole-slide calls: forward, backward, training step -------------------------------- */
 
 /* The reference drives this path through three Python statements,

@@ -96,6 +96,9 @@ SIGNATURES = {
     # ... and the stage in front of them, tissue-pixel counts per cell and per lattice tile of a region: additive to ABI 15
     "toad_region_tissue_cells_u8": (I, [P, I64, I, I, I, I, I, P, P]),
     "toad_tissue_tile_counts": (I, [P, I, I, I, I, I, I, I, I, I, I, I, P, P]),
+    # ... and the stage behind them, the tiles' scores rendered onto the region as a heat map: additive to ABI 15
+    "toad_heat_cells": (I, [P, I, I, I, I, I, I, I, I, I, I, I, P, P]),
+    "toad_region_heat_blend_u8": (I, [P, I64, I, I, P, I, I, I, P, I, I, P, I64, P]),
 }
 
 _lib = None

@@ -203,7 +203,8 @@ def region_attention_scores(extractor, model: TOAD_fc_mtl_concat, region: torch.
     """Heat-map scores of the tiles at ``origins`` of one decoded uint8 region [Hr,Wr,3], in the order of ``origins``, with no tile tensor at any point:
     ``extractor.forward_u8_region`` reads the tiles where they lie (overlapping ones - a heat-map stride below the tile size - included) and writes its
     rows chunk by chunk into one [B,1024] bag of ``bag_dtype``; ``attention_heatmap_scores(model, bag, percentile)`` scores that bag. Equal to scoring
-    ``extractor.forward_u8(stacked tiles, out_dtype=bag_dtype)``. Rasterising the B scores onto a canvas is host work and not done here."""
+    ``extractor.forward_u8(stacked tiles, out_dtype=bag_dtype)``. Putting the B scores on a canvas: ``heatmap.attention_canvas``, or
+    ``region_tissue_attention_heatmap`` for selection, scores and canvas in one call."""
     bag = extractor.forward_u8_region(region, origins, tile=tile, out_dtype=bag_dtype)
     return attention_heatmap_scores(model, bag, percentile)
 
@@ -219,3 +220,16 @@ def region_tissue_attention_scores(extractor, model: TOAD_fc_mtl_concat, region:
     if origins.shape[0] == 0:
         return origins, torch.empty(0, dtype=torch.float32, device=region.device)
     return origins, region_attention_scores(extractor, model, region, origins, tile=tile, bag_dtype=bag_dtype, percentile=percentile)
+
+
+def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region: torch.Tensor, tile=256, stride=None, min_fraction: float = 0.25,
+                                    sat_thresh: int = 8, val_min: int = 0, bag_dtype: torch.dtype = torch.float16, alpha=102, down: int = 1, lut=None,
+                                    out=None):
+    """``(origins, scores, canvas)`` of one decoded uint8 region [Hr,Wr,3]: ``region_tissue_attention_scores(..., percentile=True)`` selects and scores the
+    tissue tiles, ``heatmap.attention_canvas`` renders those percentile scores onto the region on the same lattice, on the device - uint8
+    [Hr // down, Wr // down, 3]; the tiles that were not selected keep the (box-filtered) pixels of the region. ``alpha``, ``down``, ``lut`` and ``out``:
+    ``heatmap.attention_canvas``. Gaussian smoothing, CLAM's vis-level pyramid and saving the image are not done here."""
+    from .heatmap import attention_canvas
+    origins, scores = region_tissue_attention_scores(extractor, model, region, tile=tile, stride=stride, min_fraction=min_fraction, sat_thresh=sat_thresh,
+                                                     val_min=val_min, bag_dtype=bag_dtype, percentile=True)
+    return origins, scores, attention_canvas(region, origins, scores, tile=tile, stride=stride, alpha=alpha, down=down, lut=lut, out=out)

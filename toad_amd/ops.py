@@ -1324,6 +1324,65 @@ def tissue_tile_counts(cells: torch.Tensor, cell: int, origin, tile, stride, n) 
     return out
 
 
+HEAT_DOWNS = (1, 2, 4)                 # the box filters of csrc/heatmap.hip
+
+
+def heat_cells(tile_q: torch.Tensor, cell: int, origin, tile, stride, n, region_hw) -> torch.Tensor:
+    """The heat-map value of every cell x cell cell of an (Hr, Wr) = region_hw region: int32 [Gy,Gx] on the device, Gy = ceil(Hr / cell), Gx = ceil(Wr /
+    cell). tile_q int32 [ny,nx] holds -1 for an absent tile and otherwise its score quantised to 0 .. 65535 (toad_amd.heatmap); the lattice arguments are
+    those of tissue_tile_counts. With n the present tiles that cover a cell and S the sum of their q the value is (2 S + 257 n) // (514 n) - that is
+    255 mean(q) / 65535 rounded half up, in 0 .. 255 - and -1 where no present tile covers the cell. One launch, no synchronisation."""
+    _chk(tile_q, "tile_q", dtype=torch.int32)
+    (x0, y0), (h, w), (sy, sx), (nx, ny), (hr, wr) = origin, tile, stride, n, region_hw
+    if tile_q.dim() != 2 or tuple(tile_q.shape) != (ny, nx) or nx < 1 or ny < 1:
+        raise ValueError(f"heat_cells: expected a non-empty int32 [ny,nx] = [{ny},{nx}] tile table, got {tuple(tile_q.shape)}")
+    if hr < 1 or wr < 1:
+        raise ValueError(f"heat_cells: bad region shape (Hr, Wr) = {region_hw!r}")
+    if cell not in TISSUE_CELLS:
+        raise ValueError(f"heat_cells: cell must be one of {TISSUE_CELLS}, got {cell!r}")
+    cells = torch.empty((-(-hr // cell), -(-wr // cell)), dtype=torch.int32, device=tile_q.device)
+    _lib.check(_lib.load().toad_heat_cells(_p(tile_q), nx, ny, cell, x0, y0, h, w, sx, sy, cells.shape[0], cells.shape[1], _p(cells), _stream()),
+               "toad_heat_cells")
+    return cells
+
+
+def region_heat_blend(region: torch.Tensor, cells: torch.Tensor, cell: int, lut: torch.Tensor, alpha: int, down: int, out=None) -> torch.Tensor:
+    """The heat-map canvas of one decoded uint8 region [Hr,Wr,3] (any row pitch, any alignment; read in place): uint8 [Hr // down, Wr // down, 3] on the
+    device. Per channel m = the down x down box mean rounded half up (partial boxes at the right and the bottom edge are dropped); the output is m where
+    the box's cell has cells = -1 and (alpha lut[cells][c] + (256 - alpha) m + 128) >> 8 elsewhere. cells int32 [ceil(Hr / cell), ceil(Wr / cell)] with
+    values -1 .. 255 (heat_cells), lut uint8 [256,3], alpha an int in [0, 256], down in HEAT_DOWNS. `out` may be a [Ho,Wo,3] uint8 view with strides
+    (pitch, 3, 1), a window of a larger canvas; it must not share storage with region. One launch, no synchronisation; an empty canvas launches nothing."""
+    name = "region_heat_blend"
+    pitch, hr, wr = _region_pitch(region, name)
+    if cell not in TISSUE_CELLS:
+        raise ValueError(f"{name}: cell must be one of {TISSUE_CELLS}, got {cell!r}")
+    if down not in HEAT_DOWNS:
+        raise ValueError(f"{name}: down must be one of {HEAT_DOWNS}, got {down!r}")
+    if not isinstance(alpha, int) or isinstance(alpha, bool) or not 0 <= alpha <= 256:
+        raise ValueError(f"{name}: alpha must be an int in [0, 256], got {alpha!r}")
+    _chk(cells, "cells", dtype=torch.int32)
+    if tuple(cells.shape) != (-(-hr // cell), -(-wr // cell)):
+        raise ValueError(f"{name}: expected int32 [Gy,Gx] = [{-(-hr // cell)},{-(-wr // cell)}] cells, got {tuple(cells.shape)}")
+    if not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3) or not lut.is_contiguous() or lut.device != region.device:
+        raise ValueError(f"{name}: lut must be a contiguous uint8 [256,3] tensor on the region's device")
+    ho, wo = hr // down, wr // down
+    if out is None:
+        out = torch.empty((ho, wo, 3), dtype=torch.uint8, device=region.device)
+    else:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != region.device or tuple(out.shape) != (ho, wo, 3):
+            raise ValueError(f"{name}: out must be a uint8 [{ho},{wo},3] tensor on the region's device")
+        if ho and wo and not region_layout_ok(out):
+            raise ValueError(f"{name}: out must have strides (pitch, 3, 1) with pitch >= 3 Wo, got {tuple(out.stride())}")
+        if out.untyped_storage().data_ptr() == region.untyped_storage().data_ptr():
+            raise ValueError(f"{name}: out must not share storage with region (the canvas is written while the region is read)")
+    if ho == 0 or wo == 0:
+        return out
+    out_pitch = out.stride(0) if ho > 1 else max(out.stride(0), 3 * wo)
+    _lib.check(_lib.load().toad_region_heat_blend_u8(_p(region), pitch, hr, wr, _p(cells), cells.shape[0], cells.shape[1], cell, _p(lut), alpha, down,
+                                                     _p(out), out_pitch, _stream()), "toad_region_heat_blend_u8")
+    return out
+
+
 def maxpool3x3s2_nhwc(x: torch.Tensor) -> torch.Tensor:
     _chk(x, "x")
     b, h, w, c = x.shape
