@@ -427,6 +427,50 @@ int toad_heat_cells(const int *tile_q, int nx, int ny, int cell, int x0, int y0,
 int toad_region_heat_blend_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx, int cell,
                               const unsigned char *lut, int alpha, int down, unsigned char *out, int64_t out_pitch, void *stream);
 
+/* ---- Segmented tissue selection: CLAM's recipe - a median-filtered saturation channel of a low-resolution level, thresholded by a fixed value or by
+ * Otsu's - defined in integers (additive to ABI 15 too). A second selector next to the per-pixel predicate above, which does not change; csrc/tissue_seg.hip.
+ *   1 box filter  down in {1, 2, 4, 8, 16, 32} (TOAD_ESHAPE otherwise): Hp = Hr / down, Wp = Wr / down, partial boxes at the right and the bottom edge are
+ *                 dropped, as for the canvas above. The mean pixel of box (y, x), per channel: (sum + down * down / 2) / (down * down).
+ *   2 saturation  on the mean pixel, mx = max(r, g, b), mn = min(r, g, b):  S = (255 * (mx - mn) + (mx >> 1)) / mx, which is 255 * (mx - mn) / mx rounded
+ *                 half up; S = 0 where mx == 0 or mx < val_min. Exact for all 32,896 (mx, mn) pairs. NOT claimed to be bit-equal to OpenCV's
+ *                 COLOR_RGB2HSV S channel.
+ *   3 median      k in {1, 3, 5, 7} (TOAD_ESHAPE otherwise): the (k * k) / 2-th of the sorted k * k values of the k x k window around each plane pixel,
+ *                 coordinates clamped to the plane (replicate border, as cv2.medianBlur does); k = 1 is the identity. Any Hp, Wp >= 1.
+ *   4 histogram   hist[v] = the number of pixels of the median plane equal to v: int32 [256].
+ *   5 Otsu        on the host (toad_amd.tissue.otsu_threshold): with N = sum h, MT = sum i * h[i], W0(t) = sum_{i <= t} h[i], M0(t) = sum_{i <= t} i * h[i],
+ *                 W1 = N - W0, the smallest t in 0 .. 254 that maximises (MT * W0 - M0 * N)^2 / (W0 * W1) over the t with W0 > 0 and W1 > 0 - the
+ *                 between-class variance up to the constant N^2 - and 0 if there is no such t. Fractions compared by cross-multiplication in unbounded
+ *                 integers (the squares reach 2^116). First maximum, and 0 when degenerate, is what OpenCV's Otsu gives as well.
+ *   6 tissue      a plane pixel is tissue iff its median-filtered S > t (THRESH_BINARY), t the caller's value in 0 .. 255 or Otsu's.
+ *   7 tiles       the lattice is given at the region's level; all six numbers multiples of 4 * down, so that in plane units it is a lattice of multiples
+ *                 of 4 and toad_tissue_tile_counts sums the cells of toad_plane_cells_u8 unchanged. A tile is kept iff its count >=
+ *                 ceil(min_fraction * (H / down) * (W / down)).
+ * Morphological closing, contour and hole area filters and several regions per call are not done. All three calls are asynchronous on `stream`, allocate
+ * nothing and do not synchronise; every refusal comes before any device access. */
+
+/* plane uint8 [Hp][Wp] with row pitch plane_pitch >= Wp bytes (TOAD_ESHAPE otherwise), any base address = steps 1 and 2. region and pitch as for
+ * toad_region_tissue_cells_u8: any base address, any pitch >= 3 * Wr, 64-bit row bases, 32-bit offsets inside a row (3 * Wr >= 2^31: TOAD_ESHAPE). No byte
+ * outside region + y * pitch + [0, 3 * Wr), 0 <= y < Hr, is read, and the pixels of a dropped partial box are not read at all; no byte outside plane +
+ * y * plane_pitch + [0, Wp), 0 <= y < Hp, is written, and every byte inside is written exactly once. val_min in [0, 255] (TOAD_EINVAL). Hp == 0 or Wp == 0:
+ * returns TOAD_OK and launches nothing. One streaming pass: 3 * Hr * Wr bytes read, Hp * Wp written. */
+int toad_region_saturation_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, int down, int val_min, unsigned char *plane,
+                              int64_t plane_pitch, void *stream);
+
+/* dst uint8 [Hp][Wp] = the k x k median of src [Hp][Wp] (step 3); both with any base address and any pitch >= Wp, Hp, Wp >= 1 (TOAD_ESHAPE otherwise). src
+ * and dst must not overlap (TOAD_EINVAL). hist may be NULL; otherwise int32 [256], 4-byte aligned (TOAD_EALIGN), and after the call hist = the histogram
+ * of dst (step 4): the call zeroes it on the stream itself, whatever it held, and the kernel adds to it with integer atomics only, so the result does not
+ * depend on the order of the workgroups. No byte outside src + y * src_pitch + [0, Wp) is read, none outside dst + y * dst_pitch + [0, Wp) written. k = 1
+ * is the copy-plus-histogram case. */
+int toad_plane_median_u8(const unsigned char *src, int64_t src_pitch, int Hp, int Wp, int k, unsigned char *dst, int64_t dst_pitch, int *hist,
+                         void *stream);
+
+/* counts int32 [Gy][Gx] (4-byte aligned, TOAD_EALIGN otherwise) = the pixels > thresh of every cell x cell cell of plane [Hp][Wp] (step 6 summed per cell):
+ * Gy = ceil(Hp / cell), Gx = ceil(Wp / cell), cells anchored at (0, 0), partial edge cells counting the pixels that exist; cell in {4, 8, 16, 32, 64}
+ * (TOAD_ESHAPE), thresh in [0, 255] (TOAD_EINVAL). EVERY element is written by the call, whatever it held: nothing is zeroed, nothing is atomic. plane has
+ * any base address and any pitch >= Wp; no byte outside plane + y * pitch + [0, Wp), 0 <= y < Hp, is read. The tile sums are toad_tissue_tile_counts on
+ * these counts, with the lattice in plane units. */
+int toad_plane_cells_u8(const unsigned char *plane, int64_t pitch, int Hp, int Wp, int cell, int thresh, int *counts, void *stream);
+
 /* ---- Whole-slide calls: forward, backward, training step -------------------------------- */
 
 /* The reference drives this path through three Python statements,

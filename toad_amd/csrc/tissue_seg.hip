@@ -1,0 +1,420 @@
+// tissue_seg.hip — tissue selection as CLAM does it: a saturation plane of a box-filtered level, median-filtered, thresholded (by the caller's value or by
+// Otsu's, which the host takes from the histogram this file counts), summed per cell (include/toad_hip.h, "segmented tissue selection"). The second
+// selector next to tissue.hip, which stays as it is. Everything is integer arithmetic, so every plane, histogram and count has one right answer.
+//
+//   box filter  down in {1, 2, 4, 8, 16, 32}; Hp = Hr / down, Wp = Wr / down, partial boxes at the right and the bottom edge are dropped (as in
+//               heat_blend_kernel). Per channel m = (sum of the down x down box + down^2 / 2) / down^2.
+//   saturation  on the mean pixel, mx = max(r, g, b), mn = min(r, g, b):  S = (255 (mx - mn) + (mx >> 1)) / mx, that is 255 (mx - mn) / mx rounded half
+//               up, and S = 0 where mx == 0 or mx < val_min. It is NOT claimed to be bit-equal to OpenCV's COLOR_RGB2HSV S channel (OpenCV rounds
+//               a table-driven fixed-point quotient of its own).
+//   median      k in {1, 3, 5, 7}: the (k k) / 2-th of the sorted k x k window around each plane pixel, coordinates clamped to the plane (replicate
+//               border, as cv2.medianBlur); k = 1 is the identity. Any Hp, Wp >= 1, planes smaller than the window included.
+//   histogram   hist[v] = the number of pixels of the median plane equal to v, int32 [256].
+//   cells       counts[gy][gx] = the pixels > thresh (THRESH_BINARY) of every cell x cell cell of a plane, cells anchored at (0, 0), partial edge cells
+//               counting the pixels that exist - the table toad_tissue_tile_counts sums over a lattice given in plane units.
+//
+// Three kernels:
+//   sat_plane_kernel<DOWN>    one streaming pass over the region (the 100 MB one) -> the uint8 saturation plane.
+//   plane_median_kernel<K>    a 64 x 4 output tile and its K - 1 halo staged in LDS as bytes, the rank taken by bisection over the 8 value bits.
+//   plane_cells_kernel<CELL>  tissue_cells_kernel's work split on one byte per pixel.
+#include "common.h"
+
+namespace toad {
+
+typedef unsigned sg_u32_a1 __attribute__((aligned(1)));            // a dword / a half word at any byte address: bases and pitches have any parity
+typedef unsigned short sg_u16_a1 __attribute__((aligned(1)));
+
+template <int CTRL>
+__device__ __forceinline__ int sg_dpp_mov(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false); }
+// tissue.hip's all-reduce: every lane of each aligned group of LANES lanes (1 .. 16: inside a 16-lane DPP row) ends with the group's sum; all 64 lanes active
+template <int LANES>
+__device__ __forceinline__ int sg_lanes_allreduce_sum(int v) {
+    if constexpr (LANES >= 2) v += sg_dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
+    if constexpr (LANES >= 4) v += sg_dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
+    if constexpr (LANES >= 8) v += sg_dpp_mov<0x141>(v);   // row_half_mirror
+    if constexpr (LANES >= 16) v += sg_dpp_mov<0x140>(v);  // row_mirror
+    return v;
+}
+
+// S = (255 (mx - mn) + (mx >> 1)) / mx exactly, for all 32,896 pairs mn <= mx: the numerator n is below 2^16 and the divisor below 2^8, so the float
+// quotient n * rcp(mx) is off by less than 2^-6 and its truncation by at most one in either direction; one remainder test each way corrects it. mx == 0
+// divides 0 by 1. val_min: S = 0 below it.
+__device__ __forceinline__ unsigned sat_byte(int r, int g, int b, int vmin) {
+    const int mx = max(r, max(g, b)), mn = min(r, min(g, b));
+    const int d = max(mx, 1), n = __mul24(255, mx - mn) + (mx >> 1);
+    int q = (int)((float)n * __builtin_amdgcn_rcpf((float)d));
+    const int rem = n - __mul24(q, d);
+    q += (rem >= d) - (rem < 0);
+    return mx >= vmin ? (unsigned)q : 0u;
+}
+
+// byte k of the 12 bytes of 4 pixels held as three little-endian dwords: r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+__device__ __forceinline__ int sg_byte(const unsigned (&w)[3], int k) { return (int)((w[k >> 2] >> (8 * (k & 3))) & 255u); }
+
+// Work split, as in tissue_cells_kernel: lanes run along x, a lane takes 4 pixels = 12 contiguous bytes of a row as three dwords, a wave 256 pixels = 768
+// contiguous bytes; a workgroup of 4 waves takes one 256-pixel column chunk of RB = max(DOWN, 16) rows, RB / 4 consecutive rows per wave, unrolled (12 or
+// 24 dwords a lane in flight). It carries three channel sums where tissue_cells_kernel carries one count:
+//   DOWN = 1, 2   a lane owns its boxes: 4 outputs a row, or 2 outputs every second row, stored as a dword / a half word at any byte address;
+//   DOWN = 4      a lane's 4 x 4 pixels are one box: one byte a lane;
+//   DOWN >= 8     the DOWN / 4 lanes of a box are summed by DPP moves, the 2 or 4 waves of a box row meet in 3 KB of LDS, one lane per box stores.
+// Hi = DOWN Hp and Wi = DOWN Wp are the rows and columns some box consumes: nothing outside them is read (a dropped partial box needs no reading at all),
+// so no byte outside y pitch + [0, 3 Wr), y < Hr, is. Addresses: row bases are 64-bit, offsets inside a row 32-bit (the launcher refuses 3 Wr >= 2^31). A
+// wave whose 768 bytes end inside 3 Wi over rows that all lie above Hi loads plainly; any other wave takes, row by row, the three dwords only where
+// x + 4 <= Wi, byte loads for the 1 to 3 pixels of the lane the row ends in (DOWN <= 2 only: Wi is a multiple of DOWN), zeros elsewhere. Zeros are
+// harmless: a box lies wholly inside Hi x Wi or wholly outside. Every plane byte is written by exactly one lane, once; nothing outside
+// y plane_pitch + [0, Wp), y < Hp, is written.
+template <int DOWN>
+__global__ __launch_bounds__(256) void sat_plane_kernel(const unsigned char *__restrict__ region, int64_t pitch, int Hi, int Wi, int vmin,
+                                                        unsigned char *__restrict__ plane, int64_t ppitch, unsigned nchunks) {
+    constexpr int RB = DOWN > 16 ? DOWN : 16, RW = RB / 4;         // rows per workgroup, per wave
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned chunk = blockIdx.x % nchunks, rb = blockIdx.x / nchunks;
+    const unsigned x = chunk * 256u + (unsigned)lane * 4u, off = 3u * x;
+    const int64_t y0 = (int64_t)rb * RB + wave * RW;               // first row of this wave (may lie below Hi: then it reads and writes nothing)
+    const unsigned char *src = region + y0 * pitch + off;
+    unsigned w[RW][3];
+    int rows = RW, npx = 4;                                        // rows of this wave and pixels of this lane that are consumed
+    if (chunk * 256u + 256u <= (unsigned)Wi && y0 + RW <= Hi) {    // wave-uniform: all 768 bytes of all RW rows are consumed
+#pragma unroll
+        for (int r = 0; r < RW; ++r)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) w[r][k] = *reinterpret_cast<const sg_u32_a1 *>(src + r * pitch + 4 * k);
+    } else {
+        rows = (int)max((int64_t)0, min((int64_t)RW, (int64_t)Hi - y0));
+        npx = x < (unsigned)Wi ? min(4, Wi - (int)x) : 0;
+#pragma unroll
+        for (int r = 0; r < RW; ++r) {
+            w[r][0] = w[r][1] = w[r][2] = 0;
+            if (r < rows) {
+                const unsigned char *p = src + r * pitch;
+                if (npx == 4) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) w[r][k] = *reinterpret_cast<const sg_u32_a1 *>(p + 4 * k);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 9; ++k)
+                        if (k < 3 * npx) w[r][k >> 2] |= (unsigned)p[k] << (8 * (k & 3));
+                }
+            }
+        }
+    }
+    if constexpr (DOWN == 1) {
+        unsigned char *dst = plane + y0 * ppitch + x;
+#pragma unroll
+        for (int r = 0; r < RW; ++r) {
+            unsigned o = 0;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) o |= sat_byte(sg_byte(w[r], 3 * p), sg_byte(w[r], 3 * p + 1), sg_byte(w[r], 3 * p + 2), vmin) << (8 * p);
+            if (r < rows) {
+                unsigned char *d = dst + r * ppitch;
+                if (npx == 4) {
+                    *reinterpret_cast<sg_u32_a1 *>(d) = o;
+                } else {
+#pragma unroll
+                    for (int p = 0; p < 3; ++p)
+                        if (p < npx) d[p] = (unsigned char)(o >> (8 * p));
+                }
+            }
+        }
+    } else if constexpr (DOWN == 2) {
+        unsigned char *dst = plane + (y0 >> 1) * ppitch + (x >> 1);
+#pragma unroll
+        for (int q = 0; q < RW / 2; ++q) {
+            unsigned o = 0;
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                int s[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    s[c] = (sg_byte(w[2 * q], 6 * p + c) + sg_byte(w[2 * q], 6 * p + 3 + c) + sg_byte(w[2 * q + 1], 6 * p + c) +
+                            sg_byte(w[2 * q + 1], 6 * p + 3 + c) + 2) >> 2;
+                o |= sat_byte(s[0], s[1], s[2], vmin) << (8 * p);
+            }
+            if (2 * q < rows) {                                    // rows is even: Hi and y0 are
+                unsigned char *d = dst + q * ppitch;
+                if (npx == 4) *reinterpret_cast<sg_u16_a1 *>(d) = (unsigned short)o;
+                else if (npx == 2) d[0] = (unsigned char)o;
+            }
+        }
+    } else {
+        constexpr int LANES = DOWN / 4, SH = DOWN == 4 ? 4 : DOWN == 8 ? 6 : DOWN == 16 ? 8 : 10;      // lanes per box, log2(DOWN^2)
+        unsigned b[12];                                            // the 12 column sums over the wave's rows, each at most 8 * 255: two to a dword
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            unsigned ev = 0, od = 0;
+#pragma unroll
+            for (int r = 0; r < RW; ++r) { ev += w[r][k] & 0x00FF00FFu; od += (w[r][k] >> 8) & 0x00FF00FFu; }
+            b[4 * k] = ev & 0xFFFFu; b[4 * k + 1] = od & 0xFFFFu; b[4 * k + 2] = ev >> 16; b[4 * k + 3] = od >> 16;
+        }
+        int s[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s[c] = sg_lanes_allreduce_sum<LANES>((int)(b[c] + b[c + 3] + b[c + 6] + b[c + 9]));
+        if constexpr (DOWN == 4) {
+            if (rows > 0 && npx == 4)
+                plane[(y0 >> 2) * ppitch + (x >> 2)] = (unsigned char)sat_byte((s[0] + 8) >> 4, (s[1] + 8) >> 4, (s[2] + 8) >> 4, vmin);
+        } else {
+            constexpr int NB = RB / DOWN, WPB = 4 / NB, CPR = 64 / LANES;      // box rows per workgroup, waves per box row, boxes per chunk
+            __shared__ int part[3][4][64];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) part[c][wave][lane] = s[c];
+            __syncthreads();
+            if (tid < NB * CPR) {
+                const int band = tid / CPR, bx = tid - band * CPR;
+                int m[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    int t = 0;
+#pragma unroll
+                    for (int k = 0; k < WPB; ++k) t += part[c][band * WPB + k][bx * LANES];
+                    m[c] = (t + (1 << (SH - 1))) >> SH;
+                }
+                const int64_t oy = (int64_t)rb * NB + band;
+                const unsigned ox = chunk * CPR + bx;
+                if (oy * DOWN < Hi && ox * DOWN < (unsigned)Wi) plane[oy * ppitch + ox] = (unsigned char)sat_byte(m[0], m[1], m[2], vmin);
+            }
+        }
+    }
+}
+
+// Per byte of x: bit 7 of the result is set iff the byte >= the byte of t at that place (unsigned); the other bits are garbage. d compares the low 7
+// bits - (x | 0x80) - (t & 0x7f) cannot borrow across bytes - and where the top bits differ (e) the top bit of x decides: a bit-field insert.
+__device__ __forceinline__ unsigned bytes_ge(unsigned x, unsigned t, unsigned t7) {
+    const unsigned d = (x | 0x80808080u) - t7, e = x ^ t;
+    return (e & x) | (~e & d);
+}
+
+// A workgroup of 4 waves takes a 64 x 4 tile of outputs, one row a wave, one output a lane (a small plane - 512 x 256 at down = 16 - still fills the
+// chip). The tile and its halo, (3 + K) rows of 72 bytes = plane columns [x0 - 4, x0 + 68), are staged in LDS as bytes with CLAMPED coordinates, one dword
+// a thread, so nothing afterwards branches on the border: a dword load at any byte address where its 4 columns lie inside the plane, 4 clamped byte loads
+// elsewhere - no byte outside y src_pitch + [0, Wp), y < Hp, is read. A lane then reads its window as K rows of three neighbouring DWORDS (not bytes: no
+// 4-way same-dword traffic), and a byte alignment turns them into the 8 bytes that start at its window's first column. LDS banks: the 32 lanes of a
+// ds_read_b32 group read at most 11 consecutive dwords of one row - distinct banks, equal addresses broadcast; the staging stores are 32 consecutive
+// dwords of a 19-dword-pitch array but for one wrap, so at most 2-way on a handful of banks.
+// The rank: bisection over the 8 value bits. With m = K K / 2 the median is the largest v with #(window < v) <= m, built from the top bit down; a
+// candidate is kept iff #(window >= candidate) >= K K - m. The count is a byte-parallel compare (bytes_ge) and a popcount per dword, masked to the
+// window's K bytes: about 6 K ceil(K / 4) operations a bit, no scratch, the window held in 2 K registers.
+// The histogram: each workgroup counts its outputs in 1 KB of LDS and adds its non-zero bins to hist with INTEGER atomics - integer adds commute, so the
+// result does not depend on the order in which workgroups arrive. No float atomics anywhere.
+template <int K>
+__global__ __launch_bounds__(256) void plane_median_kernel(const unsigned char *__restrict__ src, int64_t spitch, int Hp, int Wp,
+                                                           unsigned char *__restrict__ dst, int64_t dpitch, int *__restrict__ hist, unsigned ntx) {
+    constexpr int R = K / 2, ROWS = 4 + K - 1, ROWDW = 19;         // 18 dwords of pixels and one of zeros, which the last lanes' third read lands in
+    __shared__ unsigned tile[ROWS * ROWDW];
+    __shared__ int lhist[256];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned tx = blockIdx.x % ntx, ty = blockIdx.x / ntx;
+    const int x0 = (int)(tx * 64u);
+    const int64_t y0 = (int64_t)ty * 4;
+    if (hist) lhist[tid] = 0;
+    if (tid < ROWS * ROWDW) {
+        const int r = tid / ROWDW, c = tid - r * ROWDW;
+        unsigned v = 0;
+        if (c < 18) {
+            const int64_t y = min(max(y0 + r - R, (int64_t)0), (int64_t)Hp - 1);
+            const unsigned char *row = src + y * spitch;
+            const int xs = x0 - 4 + 4 * c;
+            if (xs >= 0 && xs + 4 <= Wp) {
+                v = *reinterpret_cast<const sg_u32_a1 *>(row + xs);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v |= (unsigned)row[min(max(xs + k, 0), Wp - 1)] << (8 * k);
+            }
+        }
+        tile[tid] = v;
+    }
+    __syncthreads();
+    const int bx = lane + 4 - R, d0 = bx >> 2, sh = bx & 3;        // the window's first column as a byte of the LDS row: dword and byte inside it
+    unsigned lo[K], hi[K];
+#pragma unroll
+    for (int r = 0; r < K; ++r) {
+        const unsigned *p = tile + (wave + r) * ROWDW + d0;
+        const unsigned w0 = p[0], w1 = p[1], w2 = p[2];
+        lo[r] = __builtin_amdgcn_alignbyte(w1, w0, sh);
+        hi[r] = __builtin_amdgcn_alignbyte(w2, w1, sh);
+    }
+    unsigned med;
+    if constexpr (K == 1) {
+        med = lo[0] & 255u;
+    } else {
+        constexpr unsigned MLO = K >= 4 ? 0x80808080u : 0x00808080u;                               // the window's K bytes of the 8
+        constexpr unsigned MHI = K == 7 ? 0x00808080u : K == 5 ? 0x00000080u : 0u;
+        constexpr int NEED = K * K - (K * K) / 2;
+        med = 0;
+#pragma unroll
+        for (int bit = 7; bit >= 0; --bit) {
+            const unsigned cand = med | (1u << bit), t = cand * 0x01010101u, t7 = t & 0x7F7F7F7Fu;
+            int cnt = 0;
+#pragma unroll
+            for (int r = 0; r < K; ++r) {
+                cnt += __builtin_popcount(bytes_ge(lo[r], t, t7) & MLO);
+                if constexpr (MHI != 0u) cnt += __builtin_popcount(bytes_ge(hi[r], t, t7) & MHI);
+            }
+            if (cnt >= NEED) med = cand;
+        }
+    }
+    const int64_t y = y0 + wave;
+    const int xo = x0 + lane;
+    const bool live = y < Hp && xo < Wp;
+    if (live) dst[y * dpitch + xo] = (unsigned char)med;
+    if (hist) {                                                    // workgroup-uniform
+        if (live) atomicAdd(&lhist[med], 1);
+        __syncthreads();
+        const int n = lhist[tid];
+        if (n) atomicAdd(hist + tid, n);
+    }
+}
+
+// tissue_cells_kernel's work split on a one-byte plane: a lane takes 4 plane bytes of a row as one dword, a wave 256 bytes, a workgroup of 4 waves one
+// 256-column chunk of RB = max(CELL, 16) rows; a cell is CELL / 4 adjacent lanes, summed by DPP moves, and the waves of a band meet in 1 KB of LDS. The
+// bytes > thresh of a dword are its bytes >= thresh + 1 (t1, in 1 .. 255; the launcher passes on = 0 for thresh = 255, where nothing counts): one
+// byte-parallel compare and a popcount. Every element of counts is written by exactly one lane: nothing is zeroed, nothing is atomic. No byte outside
+// y pitch + [0, Wp), y < Hp, is read: the lane the row ends in takes its 1 to 3 bytes one by one; absent bytes are 0, below every t1.
+template <int CELL>
+__global__ __launch_bounds__(256) void plane_cells_kernel(const unsigned char *__restrict__ plane, int64_t pitch, int Hp, int Wp, unsigned t1, int on,
+                                                          int *__restrict__ counts, int Gy, int Gx, unsigned nchunks) {
+    constexpr int RB = CELL > 16 ? CELL : 16, RW = RB / 4;
+    constexpr int NB = RB / CELL, WPB = 4 / NB;
+    constexpr int LANES = CELL / 4, CPR = 64 / LANES;
+    __shared__ int part[4][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned chunk = blockIdx.x % nchunks, rb = blockIdx.x / nchunks;
+    const unsigned off = chunk * 256u + (unsigned)lane * 4u;
+    const int64_t y0 = (int64_t)rb * RB + wave * RW;
+    const unsigned char *base = plane + y0 * pitch + off;
+    const unsigned t = t1 * 0x01010101u, t7 = t & 0x7F7F7F7Fu;
+    int cnt = 0;
+    if (chunk * 256u + 256u <= (unsigned)Wp && y0 + RW <= Hp) {    // wave-uniform: all 256 bytes of all RW rows exist
+#pragma unroll
+        for (int r = 0; r < RW; ++r) cnt += __builtin_popcount(bytes_ge(*reinterpret_cast<const sg_u32_a1 *>(base + r * pitch), t, t7) & 0x80808080u);
+    } else {
+        const int rows = (int)min((int64_t)RW, (int64_t)Hp - y0);  // <= 0 below the plane
+        const int nb = off < (unsigned)Wp ? min(4, Wp - (int)off) : 0;
+        for (int r = 0; r < rows; ++r) {
+            const unsigned char *p = base + r * pitch;
+            unsigned v = 0;
+            if (nb == 4) {
+                v = *reinterpret_cast<const sg_u32_a1 *>(p);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    if (k < nb) v |= (unsigned)p[k] << (8 * k);
+            }
+            cnt += __builtin_popcount(bytes_ge(v, t, t7) & 0x80808080u);
+        }
+    }
+    cnt = sg_lanes_allreduce_sum<LANES>(on ? cnt : 0);
+    part[wave][lane] = cnt;
+    __syncthreads();
+    if (tid < NB * CPR) {
+        const int band = tid / CPR, c = tid - band * CPR;
+        int s = 0;
+#pragma unroll
+        for (int k = 0; k < WPB; ++k) s += part[band * WPB + k][c * LANES];
+        const int64_t gy = (int64_t)rb * NB + band;
+        const unsigned gx = chunk * CPR + c;
+        if (gy < Gy && gx < (unsigned)Gx) counts[gy * Gx + gx] = s;
+    }
+}
+
+static bool seg_cell_ok(int cell) { return cell == 4 || cell == 8 || cell == 16 || cell == 32 || cell == 64; }
+static bool seg_down_ok(int d) { return d == 1 || d == 2 || d == 4 || d == 8 || d == 16 || d == 32; }
+static bool seg_aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+}  // namespace toad
+
+using namespace toad;
+
+extern "C" int toad_region_saturation_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, int down, int val_min, unsigned char *plane,
+                                         int64_t plane_pitch, void *stream) {
+    const char *what = "toad_region_saturation_u8";
+    if (!region || !plane) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (val_min < 0 || val_min > 255) { set_error("%s: val_min = %d must lie in [0, 255] (the 8-bit scale)", what, val_min); return TOAD_EINVAL; }
+    if (!seg_down_ok(down)) { set_error("%s: down = %d is not one of 1, 2, 4, 8, 16, 32", what, down); return TOAD_ESHAPE; }
+    if (Hr <= 0 || Wr <= 0) { set_error("%s: bad shape (Hr = %d, Wr = %d)", what, Hr, Wr); return TOAD_ESHAPE; }
+    if (pitch < 3 * (int64_t)Wr) { set_error("%s: pitch %lld is less than a row of the region (3 Wr = %lld bytes)", what, (long long)pitch, 3ll * Wr); return TOAD_ESHAPE; }
+    if (3 * (int64_t)Wr >= (1ll << 31)) { set_error("%s: region too wide: 3 Wr must stay below 2^31 (32-bit offsets inside a row)", what); return TOAD_ESHAPE; }
+    const int Hp = Hr / down, Wp = Wr / down;
+    if (plane_pitch < (int64_t)Wp) {
+        set_error("%s: plane_pitch %lld is less than a row of the plane (Wp = %d bytes)", what, (long long)plane_pitch, Wp);
+        return TOAD_ESHAPE;
+    }
+    const int Hi = Hp * down, Wi = Wp * down, rb = down > 16 ? down : 16;
+    const int64_t nchunks = ((int64_t)Wi + 255) / 256, blocks = nchunks * (((int64_t)Hi + rb - 1) / rb);
+    if (blocks >= (1ll << 31)) { set_error("%s: region too large: %lld workgroups", what, (long long)blocks); return TOAD_ESHAPE; }
+    if (Hp == 0 || Wp == 0) return TOAD_OK;
+    hipStream_t st = (hipStream_t)stream;
+#define TOAD_SAT_LAUNCH(D) \
+    hipLaunchKernelGGL(sat_plane_kernel<D>, dim3((unsigned)blocks), dim3(256), 0, st, region, pitch, Hi, Wi, val_min, plane, plane_pitch, (unsigned)nchunks)
+    switch (down) {
+        case 1: TOAD_SAT_LAUNCH(1); break;
+        case 2: TOAD_SAT_LAUNCH(2); break;
+        case 4: TOAD_SAT_LAUNCH(4); break;
+        case 8: TOAD_SAT_LAUNCH(8); break;
+        case 16: TOAD_SAT_LAUNCH(16); break;
+        default: TOAD_SAT_LAUNCH(32); break;
+    }
+#undef TOAD_SAT_LAUNCH
+    return check_launch(what);
+}
+
+extern "C" int toad_plane_median_u8(const unsigned char *src, int64_t src_pitch, int Hp, int Wp, int k, unsigned char *dst, int64_t dst_pitch, int *hist,
+                                    void *stream) {
+    const char *what = "toad_plane_median_u8";
+    if (!src || !dst) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (k != 1 && k != 3 && k != 5 && k != 7) { set_error("%s: k = %d is not one of 1, 3, 5, 7", what, k); return TOAD_ESHAPE; }
+    if (Hp <= 0 || Wp <= 0) { set_error("%s: bad shape (Hp = %d, Wp = %d)", what, Hp, Wp); return TOAD_ESHAPE; }
+    if (src_pitch < (int64_t)Wp || dst_pitch < (int64_t)Wp) {
+        set_error("%s: src_pitch %lld or dst_pitch %lld is less than a row of the plane (Wp = %d bytes)", what, (long long)src_pitch, (long long)dst_pitch, Wp);
+        return TOAD_ESHAPE;
+    }
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), s1 = s0 + (uintptr_t)(Hp - 1) * (uintptr_t)src_pitch + (uintptr_t)Wp;
+    const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), d1 = d0 + (uintptr_t)(Hp - 1) * (uintptr_t)dst_pitch + (uintptr_t)Wp;
+    if (s0 < d1 && d0 < s1) { set_error("%s: src and dst overlap (a window reads what a neighbour has written)", what); return TOAD_EINVAL; }
+    const int64_t ntx = ((int64_t)Wp + 63) / 64, blocks = ntx * (((int64_t)Hp + 3) / 4);
+    if (blocks >= (1ll << 31)) { set_error("%s: plane too large: %lld workgroups", what, (long long)blocks); return TOAD_ESHAPE; }
+    if (hist && !seg_aligned4(hist)) { set_error("%s: hist (int32 [256]) must be 4-byte aligned (the planes may have any alignment)", what); return TOAD_EALIGN; }
+    hipStream_t st = (hipStream_t)stream;
+    if (hist && hipMemsetAsync(hist, 0, 256 * sizeof(int), st) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("%s: zeroing hist failed", what);
+        return TOAD_EINVAL;
+    }
+#define TOAD_MEDIAN_LAUNCH(KK) \
+    hipLaunchKernelGGL(plane_median_kernel<KK>, dim3((unsigned)blocks), dim3(256), 0, st, src, src_pitch, Hp, Wp, dst, dst_pitch, hist, (unsigned)ntx)
+    switch (k) {
+        case 1: TOAD_MEDIAN_LAUNCH(1); break;
+        case 3: TOAD_MEDIAN_LAUNCH(3); break;
+        case 5: TOAD_MEDIAN_LAUNCH(5); break;
+        default: TOAD_MEDIAN_LAUNCH(7); break;
+    }
+#undef TOAD_MEDIAN_LAUNCH
+    return check_launch(what);
+}
+
+extern "C" int toad_plane_cells_u8(const unsigned char *plane, int64_t pitch, int Hp, int Wp, int cell, int thresh, int *counts, void *stream) {
+    const char *what = "toad_plane_cells_u8";
+    if (!plane || !counts) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (thresh < 0 || thresh > 255) { set_error("%s: thresh = %d must lie in [0, 255] (the 8-bit scale)", what, thresh); return TOAD_EINVAL; }
+    if (!seg_cell_ok(cell)) { set_error("%s: cell = %d is not one of 4, 8, 16, 32, 64", what, cell); return TOAD_ESHAPE; }
+    if (Hp <= 0 || Wp <= 0) { set_error("%s: bad shape (Hp = %d, Wp = %d)", what, Hp, Wp); return TOAD_ESHAPE; }
+    if (pitch < (int64_t)Wp) { set_error("%s: pitch %lld is less than a row of the plane (Wp = %d bytes)", what, (long long)pitch, Wp); return TOAD_ESHAPE; }
+    const int rb = cell > 16 ? cell : 16;
+    const int64_t nchunks = ((int64_t)Wp + 255) / 256, blocks = nchunks * (((int64_t)Hp + rb - 1) / rb);
+    if (blocks >= (1ll << 31)) { set_error("%s: plane too large: %lld workgroups", what, (long long)blocks); return TOAD_ESHAPE; }
+    if (!seg_aligned4(counts)) { set_error("%s: counts (int32 [Gy][Gx]) must be 4-byte aligned (the plane may have any alignment)", what); return TOAD_EALIGN; }
+    const int Gy = (int)(((int64_t)Hp + cell - 1) / cell), Gx = (int)(((int64_t)Wp + cell - 1) / cell);
+    const unsigned t1 = thresh < 255 ? (unsigned)thresh + 1u : 255u;
+    const int on = thresh < 255;
+    hipStream_t st = (hipStream_t)stream;
+#define TOAD_PCELLS_LAUNCH(C) \
+    hipLaunchKernelGGL(plane_cells_kernel<C>, dim3((unsigned)blocks), dim3(256), 0, st, plane, pitch, Hp, Wp, t1, on, counts, Gy, Gx, (unsigned)nchunks)
+    switch (cell) {
+        case 4: TOAD_PCELLS_LAUNCH(4); break;
+        case 8: TOAD_PCELLS_LAUNCH(8); break;
+        case 16: TOAD_PCELLS_LAUNCH(16); break;
+        case 32: TOAD_PCELLS_LAUNCH(32); break;
+        default: TOAD_PCELLS_LAUNCH(64); break;
+    }
+#undef TOAD_PCELLS_LAUNCH
+    return check_launch(what);
+}

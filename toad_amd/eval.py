@@ -209,14 +209,33 @@ def region_attention_scores(extractor, model: TOAD_fc_mtl_concat, region: torch.
     return attention_heatmap_scores(model, bag, percentile)
 
 
+_SEGMENT_KEYS = ("down", "median", "sat_thresh", "val_min")
+
+
+def _select_origins(region, tile, stride, min_fraction, sat_thresh, val_min, segment):
+    from .tissue import segmented_tissue_origins, tissue_origins
+    if segment is None:
+        return tissue_origins(region, tile=tile, stride=stride, min_fraction=min_fraction, sat_thresh=sat_thresh, val_min=val_min)
+    if not isinstance(segment, dict) or any(k not in _SEGMENT_KEYS for k in segment):
+        bad = segment if not isinstance(segment, dict) else sorted(k for k in segment if k not in _SEGMENT_KEYS)
+        raise ValueError(f"segment must be None or a dict with keys among {_SEGMENT_KEYS}, got {bad!r}")
+    kw = dict(sat_thresh=sat_thresh, val_min=val_min)
+    kw.update(segment)
+    return segmented_tissue_origins(region, tile=tile, stride=stride, min_fraction=min_fraction, **kw)
+
+
 def region_tissue_attention_scores(extractor, model: TOAD_fc_mtl_concat, region: torch.Tensor, tile=256, stride=None, min_fraction: float = 0.25,
-                                   sat_thresh: int = 8, val_min: int = 0, bag_dtype: torch.dtype = torch.float16, percentile: bool = False):
+                                   sat_thresh: int = 8, val_min: int = 0, bag_dtype: torch.dtype = torch.float16, percentile: bool = False,
+                                   segment: Optional[dict] = None):
     """``(origins, scores)`` of the tissue tiles of one decoded uint8 region [Hr,Wr,3]: ``tissue.tissue_origins`` picks the lattice tiles that hold tissue
     from the pixels (two launches and one small read-back, on the region where it lies), ``region_attention_scores`` scores exactly those. ``origins`` is
     the int64 [B,2] host array of (x, y), row-major over the lattice; ``scores`` its B scores on the device. A region without a tissue tile returns an
-    empty [0,2] array and an empty score tensor, and the extractor is not called. Selection arguments and their defaults: ``tissue.tissue_origins``."""
-    from .tissue import tissue_origins
-    origins = tissue_origins(region, tile=tile, stride=stride, min_fraction=min_fraction, sat_thresh=sat_thresh, val_min=val_min)
+    empty [0,2] array and an empty score tensor, and the extractor is not called. Selection arguments and their defaults: ``tissue.tissue_origins``.
+
+    ``segment``: None selects with ``tissue_origins``; a dict of ``tissue.segmented_tissue_origins`` keywords - any of ``down``, ``median``,
+    ``sat_thresh``, ``val_min`` - selects with that function instead (CLAM's median-filtered saturation of a box-filtered level, ``sat_thresh`` an int
+    or ``"otsu"``). Keys it does not give take this call's ``sat_thresh`` / ``val_min`` and that function's ``down`` / ``median`` defaults."""
+    origins = _select_origins(region, tile, stride, min_fraction, sat_thresh, val_min, segment)
     if origins.shape[0] == 0:
         return origins, torch.empty(0, dtype=torch.float32, device=region.device)
     return origins, region_attention_scores(extractor, model, region, origins, tile=tile, bag_dtype=bag_dtype, percentile=percentile)
@@ -224,12 +243,13 @@ def region_tissue_attention_scores(extractor, model: TOAD_fc_mtl_concat, region:
 
 def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region: torch.Tensor, tile=256, stride=None, min_fraction: float = 0.25,
                                     sat_thresh: int = 8, val_min: int = 0, bag_dtype: torch.dtype = torch.float16, alpha=102, down: int = 1, lut=None,
-                                    out=None):
+                                    out=None, segment: Optional[dict] = None):
     """``(origins, scores, canvas)`` of one decoded uint8 region [Hr,Wr,3]: ``region_tissue_attention_scores(..., percentile=True)`` selects and scores the
     tissue tiles, ``heatmap.attention_canvas`` renders those percentile scores onto the region on the same lattice, on the device - uint8
     [Hr // down, Wr // down, 3]; the tiles that were not selected keep the (box-filtered) pixels of the region. ``alpha``, ``down``, ``lut`` and ``out``:
-    ``heatmap.attention_canvas``. Gaussian smoothing, CLAM's vis-level pyramid and saving the image are not done here."""
+    ``heatmap.attention_canvas``. ``segment``: as for ``region_tissue_attention_scores`` - None or a dict that selects the tiles with
+    ``tissue.segmented_tissue_origins``. Gaussian smoothing, CLAM's vis-level pyramid and saving the image are not done here."""
     from .heatmap import attention_canvas
     origins, scores = region_tissue_attention_scores(extractor, model, region, tile=tile, stride=stride, min_fraction=min_fraction, sat_thresh=sat_thresh,
-                                                     val_min=val_min, bag_dtype=bag_dtype, percentile=True)
+                                                     val_min=val_min, bag_dtype=bag_dtype, percentile=True, segment=segment)
     return origins, scores, attention_canvas(region, origins, scores, tile=tile, stride=stride, alpha=alpha, down=down, lut=lut, out=out)

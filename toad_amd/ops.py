@@ -1324,6 +1324,89 @@ def tissue_tile_counts(cells: torch.Tensor, cell: int, origin, tile, stride, n) 
     return out
 
 
+SEG_DOWNS = (1, 2, 4, 8, 16, 32)       # the box filters of csrc/tissue_seg.hip
+SEG_MEDIANS = (1, 3, 5, 7)             # ... and its median windows
+
+
+def _plane_pitch(plane: torch.Tensor, name: str):
+    """The device / dtype / layout checks of the plane calls -> (pitch in bytes, Hp, Wp). A plane is uint8 [Hp,Wp] with stride(1) == 1 and any row pitch
+    >= Wp (a window of a wider plane is taken as it is); either extent may be 0."""
+    if not isinstance(plane, torch.Tensor) or not plane.is_cuda:
+        raise RuntimeError(f"{name}: plane must be a CUDA(HIP) tensor: toad_amd has no CPU path")
+    if plane.dtype != torch.uint8:
+        raise TypeError(f"{name}: plane must be torch.uint8, got {plane.dtype}")
+    if plane.dim() != 2:
+        raise ValueError(f"{name}: expected a uint8 [Hp,Wp] plane, got shape {tuple(plane.shape)}")
+    hp, wp = plane.shape
+    if hp and wp and not ((plane.stride(1) == 1 or wp == 1) and (plane.stride(0) >= wp or hp == 1)):
+        raise ValueError(f"{name}: expected a uint8 [Hp,Wp] plane with stride(1) == 1 and a row pitch >= Wp, got shape {tuple(plane.shape)} strides "
+                         f"{tuple(plane.stride())}")
+    return (plane.stride(0) if hp > 1 else max(plane.stride(0), wp)), hp, wp
+
+
+def region_saturation(region: torch.Tensor, down: int, val_min: int = 0, out=None) -> torch.Tensor:
+    """The saturation plane of one decoded uint8 region [Hr,Wr,3] (any row pitch, any alignment; read in place): uint8 [Hr // down, Wr // down] on the
+    device. Per channel m = the down x down box mean rounded half up, (sum + down^2 / 2) // down^2 (partial boxes at the right and the bottom edge are
+    dropped); with mx / mn = max / min of the mean pixel, S = (255 (mx - mn) + (mx >> 1)) // mx - 255 (mx - mn) / mx rounded half up - and S = 0 where
+    mx == 0 or mx < val_min. Exact integers; not claimed to be bit-equal to OpenCV's COLOR_RGB2HSV. down in SEG_DOWNS, val_min an int in [0, 255]. `out`
+    may be a uint8 [Hp,Wp] view with stride(1) == 1 and any pitch >= Wp. One launch, no synchronisation; an empty plane launches nothing."""
+    name = "region_saturation"
+    pitch, hr, wr = _region_pitch(region, name)
+    if down not in SEG_DOWNS:
+        raise ValueError(f"{name}: down must be one of {SEG_DOWNS}, got {down!r}")
+    if not isinstance(val_min, int) or isinstance(val_min, bool) or not 0 <= val_min <= 255:
+        raise ValueError(f"{name}: val_min must be an int in [0, 255] (the 8-bit scale), got {val_min!r}")
+    hp, wp = hr // down, wr // down
+    if out is None:
+        out = torch.empty((hp, wp), dtype=torch.uint8, device=region.device)
+    else:
+        if not isinstance(out, torch.Tensor) or out.device != region.device or tuple(out.shape) != (hp, wp):
+            raise ValueError(f"{name}: out must be a uint8 [{hp},{wp}] tensor on the region's device")
+        _plane_pitch(out, name)
+        if out.untyped_storage().data_ptr() == region.untyped_storage().data_ptr():
+            raise ValueError(f"{name}: out must not share storage with region (the plane is written while the region is read)")
+    if hp == 0 or wp == 0:
+        return out
+    out_pitch = out.stride(0) if hp > 1 else max(out.stride(0), wp)
+    _lib.check(_lib.load().toad_region_saturation_u8(_p(region), pitch, hr, wr, down, val_min, _p(out), out_pitch, _stream()), "toad_region_saturation_u8")
+    return out
+
+
+def plane_median(plane: torch.Tensor, k: int, want_hist: bool = False):
+    """The k x k median of a uint8 [Hp,Wp] plane (stride(1) == 1, any pitch >= Wp, any alignment): a new contiguous uint8 [Hp,Wp] on the device. The
+    output is the (k k) // 2-th of the sorted k k values of the window around each pixel, coordinates clamped to the plane (replicate border, as
+    cv2.medianBlur); k in SEG_MEDIANS, k = 1 the identity; planes smaller than the window are fine. With want_hist -> (median, hist): hist int32 [256] on
+    the device, hist[v] = the pixels of the median plane equal to v (integer atomics: the same on every run). One launch (and one 1 KB memset with
+    want_hist), no synchronisation; an empty plane launches nothing and has a zero histogram."""
+    name = "plane_median"
+    pitch, hp, wp = _plane_pitch(plane, name)
+    if k not in SEG_MEDIANS:
+        raise ValueError(f"{name}: k must be one of {SEG_MEDIANS}, got {k!r}")
+    out = torch.empty((hp, wp), dtype=torch.uint8, device=plane.device)
+    if hp == 0 or wp == 0:
+        return (out, torch.zeros(256, dtype=torch.int32, device=plane.device)) if want_hist else out
+    hist = torch.empty(256, dtype=torch.int32, device=plane.device) if want_hist else None
+    _lib.check(_lib.load().toad_plane_median_u8(_p(plane), pitch, hp, wp, k, _p(out), wp, _p(hist), _stream()), "toad_plane_median_u8")
+    return (out, hist) if want_hist else out
+
+
+def plane_cells(plane: torch.Tensor, cell: int, thresh: int) -> torch.Tensor:
+    """Pixels > thresh per cell x cell cell of a uint8 [Hp,Wp] plane (stride(1) == 1, any pitch >= Wp, any alignment): int32 [Gy,Gx] on the device,
+    Gy = ceil(Hp / cell), Gx = ceil(Wp / cell), cells anchored at (0, 0), partial edge cells counting the pixels that exist. cell in TISSUE_CELLS, thresh
+    an int in [0, 255]. tissue_tile_counts sums these over a lattice given in plane units. One launch, no synchronisation."""
+    name = "plane_cells"
+    pitch, hp, wp = _plane_pitch(plane, name)
+    if cell not in TISSUE_CELLS:
+        raise ValueError(f"{name}: cell must be one of {TISSUE_CELLS}, got {cell!r}")
+    if not isinstance(thresh, int) or isinstance(thresh, bool) or not 0 <= thresh <= 255:
+        raise ValueError(f"{name}: thresh must be an int in [0, 255] (the 8-bit scale), got {thresh!r}")
+    counts = torch.empty((-(-hp // cell), -(-wp // cell)), dtype=torch.int32, device=plane.device)
+    if hp == 0 or wp == 0:
+        return counts
+    _lib.check(_lib.load().toad_plane_cells_u8(_p(plane), pitch, hp, wp, cell, thresh, _p(counts), _stream()), "toad_plane_cells_u8")
+    return counts
+
+
 HEAT_DOWNS = (1, 2, 4)                 # the box filters of csrc/heatmap.hip
 
 

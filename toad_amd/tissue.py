@@ -2,12 +2,34 @@
 (``ResNet_Baseline.forward_u8_region``, ``eval.region_attention_scores``).
 
 The reference tree has no patching script; its bags come from CLAM's, which thresholds HSV saturation and keeps the tiles that hold tissue.
-Here the region is already resident when the extractor is called, so the decision is one streaming pass over its bytes (csrc/tissue.hip):
-tissue pixels per ``cell x cell`` cell, then per tile of a lattice whose origin, tile shape and strides are multiples of the cell.
+Here the region is already resident when the extractor is called, so the decision is made where it lies. There are two selectors.
 
-The pixel predicate is exact integer arithmetic: with ``mx = max(r, g, b)`` and ``mn = min(r, g, b)`` a pixel is tissue iff
-``mx >= val_min and 255 * (mx - mn) > sat_thresh * mx`` - HSV saturation above ``sat_thresh`` on the 8-bit scale, written without the division.
-It is not OpenCV's rounded ``S`` channel. ``val_min`` removes black scanner margins, whose JPEG noise is fully saturated; ``mx == 0`` is never tissue.
+``tissue_origins`` (csrc/tissue.hip) - one streaming pass over the region's bytes: tissue pixels per ``cell x cell`` cell, then per tile of a lattice
+whose origin, tile shape and strides are multiples of the cell. The pixel predicate is exact integer arithmetic: with ``mx = max(r, g, b)`` and
+``mn = min(r, g, b)`` a pixel is tissue iff ``mx >= val_min and 255 * (mx - mn) > sat_thresh * mx`` - HSV saturation above ``sat_thresh`` on the 8-bit
+scale, written without the division. It is not OpenCV's rounded ``S`` channel. ``val_min`` removes black scanner margins, whose JPEG noise is fully
+saturated; ``mx == 0`` is never tissue.
+
+``segmented_tissue_origins`` (csrc/tissue_seg.hip) - CLAM's recipe, defined in integers:
+
+1. box filter: ``down`` in 1, 2, 4, 8, 16, 32; ``Hp = Hr // down``, ``Wp = Wr // down``, partial boxes at the right and the bottom edge dropped; the
+   mean pixel of a box is ``(sum + down * down // 2) // (down * down)`` per channel. An empty plane launches nothing.
+2. saturation byte: on the mean pixel ``S = (255 * (mx - mn) + (mx >> 1)) // mx`` - ``255 (mx - mn) / mx`` rounded half up - and ``S = 0`` where
+   ``mx == 0`` or ``mx < val_min``. Exact for every ``(mx, mn)``; not claimed to be bit-equal to OpenCV's ``COLOR_RGB2HSV``.
+3. median: ``median`` = k in 1, 3, 5, 7; the ``(k * k) // 2``-th of the sorted ``k * k`` values of the window around each plane pixel, coordinates
+   clamped to the plane (replicate border, as ``cv2.medianBlur``); k = 1 is the identity; planes smaller than the window are fine.
+4. histogram: ``hist[v]`` = the pixels of the median plane equal to ``v``, int32 [256].
+5. Otsu (``otsu_threshold``, on the host): with ``N = sum h``, ``MT = sum i h[i]``, ``W0(t) = sum_{i<=t} h[i]``, ``M0(t) = sum_{i<=t} i h[i]``,
+   ``W1 = N - W0``, the smallest ``t`` in 0..254 that maximises ``(MT W0 - M0 N)^2 / (W0 W1)`` over the ``t`` with ``W0 > 0`` and ``W1 > 0`` - the
+   between-class variance up to the constant ``N^2`` - and 0 if there is none. Fractions are compared by cross-multiplication in Python ints. First
+   maximum, and 0 when degenerate, is what OpenCV's Otsu gives too.
+6. tissue: a plane pixel is tissue iff its median-filtered ``S > t`` (``THRESH_BINARY``), ``t`` the caller's ``sat_thresh`` in 0..255 or Otsu's.
+7. tiles: the lattice is given at the region's level and all six numbers must be multiples of ``4 * down``; in plane units it is then a lattice of
+   multiples of 4 and ``lattice_cell`` applies unchanged. The extent is ``lattice(Hr, Wr, ...)``; a tile is kept iff its tissue count
+   ``>= ceil(min_fraction * (H // down) * (W // down))``.
+
+Dust, JPEG speckle and single saturated pixels on glass are tissue for the first selector and vanish under the median of the second. Not done:
+morphological closing, contour and hole area filters, several regions per call.
 
 Conventions: ``tile`` = int or (H, W) as in ``ops.tile_shape``; ``stride`` = int or (sy, sx), the same order, default the tile shape;
 ``origin`` = (x, y) of the lattice's first tile, x first as in ``origins``.
@@ -75,7 +97,8 @@ def tissue_origins(region: torch.Tensor, tile=256, stride=None, min_fraction: fl
     [0,2] result, not an error.
 
     The defaults are API defaults in CLAM's units (its ``sthresh = 8``; min_fraction and val_min have no CLAM counterpart), not tuned values: CLAM
-    thresholds a median-blurred, OpenCV-rounded saturation channel of a downsampled level, this is the exact per-pixel predicate at the region's level."""
+    thresholds a median-blurred, OpenCV-rounded saturation channel of a downsampled level, this is the exact per-pixel predicate at the region's level.
+    ``segmented_tissue_origins`` is the selector that follows CLAM's recipe (box filter, median, fixed or Otsu threshold)."""
     if not isinstance(min_fraction, (int, float)) or isinstance(min_fraction, bool) or not 0.0 <= min_fraction <= 1.0:
         raise ValueError(f"min_fraction must lie in [0, 1], got {min_fraction!r}")
     counts, nx, ny = tissue_tile_fraction(region, tile, stride, origin, sat_thresh, val_min)
@@ -87,3 +110,99 @@ def tissue_origins(region: torch.Tensor, tile=256, stride=None, min_fraction: fl
     j, i = np.nonzero(c >= math.ceil(min_fraction * h * w))         # row-major: j (y) outer, i (x) inner
     origins = np.stack([x0 + i * sx, y0 + j * sy], axis=1).astype(np.int64)
     return (origins, c[j, i]) if return_counts else origins
+
+
+def otsu_threshold(hist) -> int:
+    """Otsu's threshold of a 256-bin histogram (any 256-long integer sequence, numpy array or CPU tensor), in Python ints: with N = sum h,
+    MT = sum i h[i], W0(t) = sum_{i<=t} h[i], M0(t) = sum_{i<=t} i h[i] and W1 = N - W0, the smallest t in 0..254 that maximises
+    (MT W0 - M0 N)^2 / (W0 W1) over the t with W0 > 0 and W1 > 0; 0 if there is no such t (an empty or a one-bin histogram). The fractions are compared
+    by cross-multiplication - the squares reach about 2^116, beyond float and int64. A pixel is then tissue iff its value > t."""
+    if isinstance(hist, torch.Tensor):
+        hist = hist.tolist()
+    h = [int(v) for v in hist]
+    if len(h) != 256 or any(v < 0 for v in h):
+        raise ValueError(f"otsu_threshold: expected 256 non-negative counts, got {len(h)} values" + ("" if len(h) != 256 else ", some negative"))
+    n, mt = sum(h), sum(i * v for i, v in enumerate(h))
+    best, num, den = 0, -1, 1
+    w0 = m0 = 0
+    for t in range(255):
+        w0 += h[t]
+        m0 += t * h[t]
+        w1 = n - w0
+        if w0 <= 0 or w1 <= 0:
+            continue
+        a, d = (mt * w0 - m0 * n) ** 2, w0 * w1
+        if a * den > num * d:                                       # strictly above the best so far: the FIRST maximum stays
+            best, num, den = t, a, d
+    return best
+
+
+def _seg_args(down, median, sat_thresh, val_min):
+    if down not in ops.SEG_DOWNS:
+        raise ValueError(f"down must be one of {ops.SEG_DOWNS}, got {down!r}")
+    if median not in ops.SEG_MEDIANS:
+        raise ValueError(f"median must be one of {ops.SEG_MEDIANS}, got {median!r}")
+    if sat_thresh != "otsu" and (not isinstance(sat_thresh, int) or isinstance(sat_thresh, bool) or not 0 <= sat_thresh <= 255):
+        raise ValueError(f"sat_thresh must be 'otsu' or an int in [0, 255] (the 8-bit scale), got {sat_thresh!r}")
+    if not isinstance(val_min, int) or isinstance(val_min, bool) or not 0 <= val_min <= 255:
+        raise ValueError(f"val_min must be an int in [0, 255] (the 8-bit scale), got {val_min!r}")
+
+
+def segment_tissue(region: torch.Tensor, down: int = 16, median: int = 7, sat_thresh=8, val_min: int = 0):
+    """(plane, t): the median-filtered saturation plane of the region, uint8 [Hr // down, Wr // down] ON THE DEVICE (steps 1 to 3 of the module's
+    definition), and the threshold used - a plane pixel is tissue iff it is > t. With an int ``sat_thresh`` t is that int and the call is two launches
+    without any synchronisation. ``sat_thresh="otsu"`` also counts the plane's histogram and takes Otsu's threshold of it on the host
+    (``otsu_threshold``): ONE extra device-to-host copy of 1 KB and its synchronisation. An empty plane gives t = 0 under "otsu"."""
+    _seg_args(down, median, sat_thresh, val_min)
+    sat = ops.region_saturation(region, down, val_min)
+    if sat_thresh == "otsu":
+        plane, hist = ops.plane_median(sat, median, want_hist=True)
+        return plane, otsu_threshold(hist.cpu())                    # the 1 KB copy, the synchronisation
+    return ops.plane_median(sat, median), sat_thresh
+
+
+def _seg_lattice(tile, stride, origin, down):
+    """The lattice in plane units, after the 4 * down divisibility rule."""
+    h, w, sy, sx, x0, y0 = _lattice_args(tile, stride, origin)
+    for name, v in (("tile height", h), ("tile width", w), ("stride y", sy), ("stride x", sx), ("origin x", x0), ("origin y", y0)):
+        if v % (4 * down):
+            raise ValueError(f"{name} = {v} is not a multiple of 4 * down = {4 * down} (down = {down}): on the plane the tile shape, the strides and the "
+                             "origin of a tissue lattice must all be multiples of 4")
+    return h // down, w // down, sy // down, sx // down, x0 // down, y0 // down
+
+
+def segmented_tissue_origins(region: torch.Tensor, tile=256, stride=None, min_fraction: float = 0.25, down: int = 16, median: int = 7, sat_thresh=8,
+                             val_min: int = 0, origin=(0, 0), return_counts: bool = False, return_threshold: bool = False):
+    """``tissue_origins`` with CLAM's tissue decision (the module's steps 1 to 7): the region is box-filtered by ``down``, its saturation plane
+    median-filtered (``median`` x ``median``), a plane pixel is tissue iff it is > ``sat_thresh`` - an int in 0..255 or ``"otsu"`` - and a lattice tile
+    is kept iff its tissue count >= ceil(min_fraction (H // down) (W // down)). Result as for ``tissue_origins``: np.ndarray int64 [B,2] of (x, y) at the
+    region's level ON THE HOST, row-major over the lattice; with ``return_counts`` also the kept tiles' counts (plane pixels), int64 [B]; with
+    ``return_threshold`` also the threshold used, last. The tile shape, the strides and the origin must be multiples of ``4 * down``.
+
+    Four launches and ONE device-to-host copy of ny nx int32, its one synchronisation; ``"otsu"`` adds a 1 KB memset and one more 1 KB copy with its
+    synchronisation. An empty region or lattice gives an empty [0,2] result, not an error (and launches nothing; the threshold is then ``sat_thresh``,
+    0 for ``"otsu"``).
+
+    The defaults are CLAM's: ``sthresh = 8``, ``mthresh = 7``, a low-resolution level (``down = 16``); ``use_otsu`` is ``sat_thresh="otsu"``.
+    Morphological closing and the contour and hole area filters of CLAM are not done."""
+    if not isinstance(min_fraction, (int, float)) or isinstance(min_fraction, bool) or not 0.0 <= min_fraction <= 1.0:
+        raise ValueError(f"min_fraction must lie in [0, 1], got {min_fraction!r}")
+    _seg_args(down, median, sat_thresh, val_min)
+    _, hr, wr = ops._region_pitch(region, "segmented_tissue_origins")
+    h, w, sy, sx, x0, y0 = _lattice_args(tile, stride, origin)
+    ph, pw, psy, psx, px0, py0 = _seg_lattice((h, w), (sy, sx), (x0, y0), down)
+    nx, ny = lattice(hr, wr, (h, w), (sy, sx), (x0, y0))
+
+    def result(origins, counts, t):
+        out = (origins,) + ((counts,) if return_counts else ()) + ((t,) if return_threshold else ())
+        return out if len(out) > 1 else origins
+
+    if nx == 0 or ny == 0:
+        return result(np.zeros((0, 2), dtype=np.int64), np.zeros((0,), dtype=np.int64), 0 if sat_thresh == "otsu" else sat_thresh)
+    plane, t = segment_tissue(region, down, median, sat_thresh, val_min)
+    cell = lattice_cell((ph, pw), (psy, psx), (px0, py0))
+    cells = ops.plane_cells(plane, cell, t)
+    c = ops.tissue_tile_counts(cells, cell, (px0, py0), (ph, pw), (psy, psx), (nx, ny)).cpu().numpy().astype(np.int64)      # the one copy
+    j, i = np.nonzero(c >= math.ceil(min_fraction * ph * pw))       # row-major: j (y) outer, i (x) inner
+    origins = np.stack([x0 + i * sx, y0 + j * sy], axis=1).astype(np.int64)
+    return result(origins, c[j, i], t)
