@@ -445,8 +445,20 @@ int toad_region_heat_blend_u8(const unsigned char *region, int64_t pitch, int Hr
  *   7 tiles       the lattice is given at the region's level; all six numbers multiples of 4 * down, so that in plane units it is a lattice of multiples
  *                 of 4 and toad_tissue_tile_counts sums the cells of toad_plane_cells_u8 unchanged. A tile is kept iff its count >=
  *                 ceil(min_fraction * (H / down) * (W / down)).
- * Morphological closing, contour and hole area filters and several regions per call are not done. All three calls are asynchronous on `stream`, allocate
- * nothing and do not synchronise; every refusal comes before any device access. */
+ * Between steps 6 and 7 the mask M0 of step 6 may pass through the remaining steps of CLAM's segmentTissue (csrc/tissue_morph.hip, further below):
+ *   6a closing    close = c in 0 .. 8, 0 and 1 the identity; lo = c / 2, hi = c - 1 - c / 2. Dilation: D[y][x] = OR of M0[y + dy][x + dx] over
+ *                 -lo <= dy, dx <= hi, the window clipped to the plane. Erosion: M1[y][x] = AND of D over the same offsets, clipped the same way. This is
+ *                 cv2.morphologyEx(m, MORPH_CLOSE, np.ones((c, c))) as OpenCV defines it - the default anchor (c / 2, c / 2) for both halves, which is why an
+ *                 even c shifts by a pixel, border pixels ignored - stated from OpenCV's documentation: not claimed bit-equal to OpenCV.
+ *   6b components min_area = a >= 0 plane pixels: label the 8-connected components of M1; a component of fewer than a pixels is removed (kept iff
+ *                 count >= a; CLAM keeps area > a_t). This gives M2. 0 and 1 remove nothing.
+ *   6c holes      min_hole = h >= 0 plane pixels: label the 4-connected components of the complement of M2; one is a hole iff none of its pixels lies in
+ *                 row 0, row Hp - 1, column 0 or column Wp - 1; a hole of fewer than h pixels becomes tissue. This gives M3, on which step 7 runs.
+ *   The order is closing, components, holes: after 6b every remaining component is kept, so a hole never needs to know its enclosing component, and an
+ *   island removed in 6b merges into the hole around it before 6c counts that hole. Areas are pixel counts of the unfilled component - CLAM's
+ *   contourArea(outer) - sum(contourArea(holes)) but for the polygon-versus-pixel difference; from CLAM's units: a_t * 512^2 / (level downsample * down)^2.
+ * max_n_holes, polygon areas and several regions per call are not done. All calls are asynchronous on `stream`, allocate nothing and do not synchronise;
+ * every refusal comes before any device access. */
 
 /* plane uint8 [Hp][Wp] with row pitch plane_pitch >= Wp bytes (TOAD_ESHAPE otherwise), any base address = steps 1 and 2. region and pitch as for
  * toad_region_tissue_cells_u8: any base address, any pitch >= 3 * Wr, 64-bit row bases, 32-bit offsets inside a row (3 * Wr >= 2^31: TOAD_ESHAPE). No byte
@@ -470,6 +482,27 @@ int toad_plane_median_u8(const unsigned char *src, int64_t src_pitch, int Hp, in
  * any base address and any pitch >= Wp; no byte outside plane + y * pitch + [0, Wp), 0 <= y < Hp, is read. The tile sums are toad_tissue_tile_counts on
  * these counts, with the lattice in plane units. */
 int toad_plane_cells_u8(const unsigned char *plane, int64_t pitch, int Hp, int Wp, int cell, int thresh, int *counts, void *stream);
+
+/* ---- Steps 6a to 6c (additive to ABI 15 too; csrc/tissue_morph.hip). Planes uint8 [Hp][Wp] at any base address and any pitch >= Wp; nothing is read or
+ * written outside [0, Wp) of each row. Hp, Wp >= 1 (TOAD_ESHAPE otherwise). */
+
+/* dst = 255 where M1 (step 6a with M0 = src > thresh) is set, 0 elsewhere; c in 0 .. 8 (TOAD_ESHAPE), c = 0 or 1 binarises only; thresh in [0, 255]
+ * (TOAD_EINVAL). src and dst must not overlap (TOAD_EINVAL). One kernel: a 64 x 16 tile and its halo of 2 * lo rows and columns on the low side, 2 * hi on
+ * the high side, in LDS; separable row and column passes; the windows are clipped to the plane, not to the tile. */
+int toad_plane_close_u8(const unsigned char *src, int64_t src_pitch, int Hp, int Wp, int thresh, int c, unsigned char *dst, int64_t dst_pitch, void *stream);
+
+/* Connected components of the selected pixels, (plane > thresh) != background; background 0 or 1, thresh in [0, 255] (TOAD_EINVAL). Connectivity is 8
+ * when background == 0 and 4 when background == 1. labels int32 [Hp][Wp], dense: -1 on unselected pixels, otherwise the smallest y * Wp + x of the pixel's
+ * component - a canonical labelling, independent of scheduling. area int32 [Hp * Wp]: at a component's label index its pixel count, plus 1 << 30 iff the
+ * component touches row 0, row Hp - 1, column 0 or column Wp - 1; 0 everywhere else. EVERY element of both arrays is written, whatever it held.
+ * 1 <= Hp * Wp < 2^30 (TOAD_ESHAPE); both arrays 4-byte aligned (TOAD_EALIGN). Union-find in three launches (two where the plane is one 64 x 16 tile):
+ * tiles in LDS, tile seams with returned device-scope atomic mins, then roots and counts (integer atomics only: the same on every run). */
+int toad_plane_components_u8(const unsigned char *plane, int64_t pitch, int Hp, int Wp, int thresh, int background, int *labels, int *area, void *stream);
+
+/* dst from the labels and areas of toad_plane_components_u8, with count = area[label] & (2^30 - 1). mode 0 (drop small): dst = 255 iff label >= 0 and
+ * count >= limit. mode 1 (fill small holes; the labels are those of the background): dst = 255 iff label < 0, or count < limit and the border bit is clear.
+ * 0 otherwise. mode 0 or 1, limit >= 0 (TOAD_EINVAL); Hp * Wp < 2^30 (TOAD_ESHAPE); labels and area 4-byte aligned (TOAD_EALIGN). */
+int toad_plane_area_select_u8(const int *labels, const int *area, int Hp, int Wp, int mode, int limit, unsigned char *dst, int64_t dst_pitch, void *stream);
 
 /* ---- Whole-slide calls: forward, backward, training step -------------------------------- */
 

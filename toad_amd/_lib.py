@@ -103,6 +103,10 @@ SIGNATURES = {
     "toad_region_saturation_u8": (I, [P, I64, I, I, I, I, P, I64, P]),
     "toad_plane_median_u8": (I, [P, I64, I, I, I, P, I64, P, P]),
     "toad_plane_cells_u8": (I, [P, I64, I, I, I, I, P, P]),
+    # ... and what follows its threshold, closing and the component / hole area filters (csrc/tissue_morph.hip): additive to ABI 15
+    "toad_plane_close_u8": (I, [P, I64, I, I, I, I, P, I64, P]),
+    "toad_plane_components_u8": (I, [P, I64, I, I, I, I, P, P, P]),
+    "toad_plane_area_select_u8": (I, [P, P, I, I, I, I, P, I64, P]),
 }
 
 _lib = None

@@ -209,7 +209,7 @@ def region_attention_scores(extractor, model: TOAD_fc_mtl_concat, region: torch.
     return attention_heatmap_scores(model, bag, percentile)
 
 
-_SEGMENT_KEYS = ("down", "median", "sat_thresh", "val_min")
+_SEGMENT_KEYS = ("down", "median", "sat_thresh", "val_min", "close", "min_area", "min_hole")
 
 
 def _select_origins(region, tile, stride, min_fraction, sat_thresh, val_min, segment):
@@ -233,7 +233,7 @@ def region_tissue_attention_scores(extractor, model: TOAD_fc_mtl_concat, region:
     empty [0,2] array and an empty score tensor, and the extractor is not called. Selection arguments and their defaults: ``tissue.tissue_origins``.
 
     ``segment``: None selects with ``tissue_origins``; a dict of ``tissue.segmented_tissue_origins`` keywords - any of ``down``, ``median``,
-    ``sat_thresh``, ``val_min`` - selects with that function instead (CLAM's median-filtered saturation of a box-filtered level, ``sat_thresh`` an int
+    ``sat_thresh``, ``val_min``, ``close``, ``min_area``, ``min_hole`` - selects with that function instead (CLAM's median-filtered saturation of a box-filtered level, ``sat_thresh`` an int
     or ``"otsu"``). Keys it does not give take this call's ``sat_thresh`` / ``val_min`` and that function's ``down`` / ``median`` defaults."""
     origins = _select_origins(region, tile, stride, min_fraction, sat_thresh, val_min, segment)
     if origins.shape[0] == 0:

@@ -1407,6 +1407,85 @@ def plane_cells(plane: torch.Tensor, cell: int, thresh: int) -> torch.Tensor:
     return counts
 
 
+SEG_CLOSES = tuple(range(9))           # the closing windows of csrc/tissue_morph.hip (0 and 1: the identity)
+
+
+def _thresh_arg(name: str, thresh):
+    if not isinstance(thresh, int) or isinstance(thresh, bool) or not 0 <= thresh <= 255:
+        raise ValueError(f"{name}: thresh must be an int in [0, 255] (the 8-bit scale), got {thresh!r}")
+
+
+def plane_close(plane: torch.Tensor, close: int, thresh: int) -> torch.Tensor:
+    """The morphological closing of the mask plane > thresh of a uint8 [Hp,Wp] plane (stride(1) == 1, any pitch >= Wp, any alignment): a new contiguous
+    uint8 [Hp,Wp] on the device, 255 where the closed mask is set and 0 elsewhere. close = c in SEG_CLOSES; with lo = c // 2 and hi = c - 1 - c // 2 the
+    mask is dilated - OR over -lo <= dy, dx <= hi, the window clipped to the plane - and the result eroded - AND over the same offsets, clipped the same
+    way: cv2.morphologyEx(m, MORPH_CLOSE, np.ones((c, c))) as OpenCV defines it, not claimed bit-equal to OpenCV. c = 0 or 1 binarises only. One launch,
+    no synchronisation; an empty plane launches nothing."""
+    name = "plane_close"
+    pitch, hp, wp = _plane_pitch(plane, name)
+    if not isinstance(close, int) or isinstance(close, bool) or close not in SEG_CLOSES:
+        raise ValueError(f"{name}: close must be one of {SEG_CLOSES}, got {close!r}")
+    _thresh_arg(name, thresh)
+    out = torch.empty((hp, wp), dtype=torch.uint8, device=plane.device)
+    if hp == 0 or wp == 0:
+        return out
+    _lib.check(_lib.load().toad_plane_close_u8(_p(plane), pitch, hp, wp, thresh, close, _p(out), wp, _stream()), "toad_plane_close_u8")
+    return out
+
+
+def plane_components(plane: torch.Tensor, thresh: int, background: int = 0, workspace: bool = False):
+    """(labels, area): the connected components of the selected pixels, (plane > thresh) != background, of a uint8 [Hp,Wp] plane (stride(1) == 1, any pitch
+    >= Wp, any alignment). background = 0 labels the pixels above the threshold with connectivity 8, background = 1 the others with connectivity 4.
+    labels int32 [Hp,Wp]: -1 on unselected pixels, otherwise the smallest y * Wp + x of the pixel's component - canonical, the same on every run. area int32
+    [Hp * Wp]: at a component's label its pixel count, plus 2^30 iff it touches row 0, row Hp - 1, column 0 or column Wp - 1; 0 elsewhere. Hp * Wp < 2^30.
+    With `workspace` both are views of per-stream scratch (``_ws``), valid until the next such call on the stream. Three launches (two where the plane is
+    one 64 x 16 tile), no synchronisation; an empty plane launches nothing."""
+    name = "plane_components"
+    pitch, hp, wp = _plane_pitch(plane, name)
+    _thresh_arg(name, thresh)
+    if not isinstance(background, int) or isinstance(background, bool) or background not in (0, 1):
+        raise ValueError(f"{name}: background must be 0 or 1, got {background!r}")
+    if hp * wp >= 1 << 30:
+        raise ValueError(f"{name}: plane too large: Hp * Wp = {hp * wp} must stay below 2^30")
+    n = hp * wp
+    if workspace and n:
+        labels = _ws(4 * n, plane.device, "cc_labels")[:4 * n].view(torch.int32).view(hp, wp)
+        area = _ws(4 * n, plane.device, "cc_area")[:4 * n].view(torch.int32)
+    else:
+        labels = torch.empty((hp, wp), dtype=torch.int32, device=plane.device)
+        area = torch.empty((n,), dtype=torch.int32, device=plane.device)
+    if n == 0:
+        return labels, area
+    _lib.check(_lib.load().toad_plane_components_u8(_p(plane), pitch, hp, wp, thresh, background, _p(labels), _p(area), _stream()),
+               "toad_plane_components_u8")
+    return labels, area
+
+
+def plane_area_select(labels: torch.Tensor, area: torch.Tensor, mode: int, limit: int) -> torch.Tensor:
+    """A mask from the (labels, area) of plane_components: a new contiguous uint8 [Hp,Wp] on the device, 255 or 0. With count = area[label] & (2^30 - 1):
+    mode 0 (drop small components) sets a pixel iff label >= 0 and count >= limit; mode 1 (fill small holes; labels of the background) iff label < 0, or
+    count < limit and the component does not touch the plane's border. limit a non-negative int. One launch, no synchronisation."""
+    name = "plane_area_select"
+    for t, what in ((labels, "labels"), (area, "area")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{name}: {what} must be a CUDA(HIP) tensor: toad_amd has no CPU path")
+        if t.dtype != torch.int32:
+            raise TypeError(f"{name}: {what} must be torch.int32, got {t.dtype}")
+    if labels.dim() != 2 or area.dim() != 1 or area.numel() != labels.numel() or not labels.is_contiguous() or not area.is_contiguous():
+        raise ValueError(f"{name}: expected contiguous labels int32 [Hp,Wp] and area int32 [Hp * Wp], got shapes {tuple(labels.shape)} and {tuple(area.shape)}")
+    if not isinstance(mode, int) or isinstance(mode, bool) or mode not in (0, 1):
+        raise ValueError(f"{name}: mode must be 0 (drop small components) or 1 (fill small holes), got {mode!r}")
+    if not isinstance(limit, int) or isinstance(limit, bool) or limit < 0:
+        raise ValueError(f"{name}: limit must be a non-negative int, got {limit!r}")
+    hp, wp = labels.shape
+    out = torch.empty((hp, wp), dtype=torch.uint8, device=labels.device)
+    if hp == 0 or wp == 0:
+        return out
+    _lib.check(_lib.load().toad_plane_area_select_u8(_p(labels), _p(area), hp, wp, mode, min(limit, 1 << 30), _p(out), wp, _stream()),
+               "toad_plane_area_select_u8")
+    return out
+
+
 HEAT_DOWNS = (1, 2, 4)                 # the box filters of csrc/heatmap.hip
 
 

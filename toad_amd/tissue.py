@@ -28,8 +28,26 @@ saturated; ``mx == 0`` is never tissue.
    multiples of 4 and ``lattice_cell`` applies unchanged. The extent is ``lattice(Hr, Wr, ...)``; a tile is kept iff its tissue count
    ``>= ceil(min_fraction * (H // down) * (W // down))``.
 
+Between steps 6 and 7 the mask ``M0`` of step 6 may pass through the remaining steps of CLAM's ``segmentTissue`` (csrc/tissue_morph.hip), each switched
+on by its keyword and skipped entirely at its default:
+
+6a. closing: ``close`` = c in 0..8, 0 and 1 the identity; ``lo = c // 2``, ``hi = c - 1 - c // 2``. Dilation: ``D[y,x]`` is the OR of ``M0[y+dy, x+dx]``
+    over ``-lo <= dy, dx <= hi``, the window clipped to the plane; erosion: ``M1[y,x]`` is the AND of ``D`` over the same offsets, clipped the same way.
+    This is ``cv2.morphologyEx(m, MORPH_CLOSE, np.ones((c, c)))`` as OpenCV defines it - the default anchor ``(c // 2, c // 2)`` for both halves, which is
+    why an even c shifts by a pixel; border pixels ignored - stated, not tested: not claimed bit-equal to OpenCV.
+6b. small components: ``min_area`` = a >= 0 plane pixels. The 8-connected components of ``M1`` with fewer than a pixels are removed (kept iff
+    ``count >= min_area``; CLAM keeps ``a > a_t``). This gives ``M2``. 0 and 1 remove nothing and launch nothing.
+6c. small holes: ``min_hole`` = h >= 0 plane pixels. The 4-connected components of the complement of ``M2`` are labelled; one is a hole iff none of its
+    pixels lies in row 0, row ``Hp - 1``, column 0 or column ``Wp - 1``; a hole with fewer than h pixels becomes tissue. This gives ``M3``, on which step
+    7 runs unchanged. 0 launches nothing.
+
+The order is closing, components, holes: after 6b every remaining component is kept, so a hole never needs to know its enclosing component, and an island
+removed in 6b merges into the hole around it before 6c counts that hole. The areas are pixel counts of the unfilled component - CLAM's
+``contourArea(outer) - sum(contourArea(holes))`` but for the polygon-versus-pixel difference. From CLAM's units (multiples of a 512 x 512 reference patch at
+level 0): ``min_area = a_t * 512^2 / (level downsample * down)^2``, and ``min_hole`` from ``a_h`` alike.
+
 Dust, JPEG speckle and single saturated pixels on glass are tissue for the first selector and vanish under the median of the second. Not done:
-morphological closing, contour and hole area filters, several regions per call.
+``max_n_holes``, polygon areas, several regions per call.
 
 Conventions: ``tile`` = int or (H, W) as in ``ops.tile_shape``; ``stride`` = int or (sy, sx), the same order, default the tile shape;
 ``origin`` = (x, y) of the lattice's first tile, x first as in ``origins``.
@@ -148,17 +166,50 @@ def _seg_args(down, median, sat_thresh, val_min):
         raise ValueError(f"val_min must be an int in [0, 255] (the 8-bit scale), got {val_min!r}")
 
 
-def segment_tissue(region: torch.Tensor, down: int = 16, median: int = 7, sat_thresh=8, val_min: int = 0):
+def _morph_args(close, min_area, min_hole):
+    if not isinstance(close, int) or isinstance(close, bool) or close not in ops.SEG_CLOSES:
+        raise ValueError(f"close must be one of {ops.SEG_CLOSES}, got {close!r}")
+    for name, v in (("min_area", min_area), ("min_hole", min_hole)):
+        if not isinstance(v, int) or isinstance(v, bool) or v < 0:
+            raise ValueError(f"{name} must be a non-negative int (plane pixels), got {v!r}")
+    return close > 1 or min_area > 1 or min_hole > 0
+
+
+def _morph(plane: torch.Tensor, t: int, close: int, min_area: int, min_hole: int) -> torch.Tensor:
+    """Steps 6a to 6c on the median plane: the 0 / 255 plane of M3. Only the active stages launch; the first of them reads the plane with t directly."""
+    mask, th = plane, t
+    if close > 1:
+        mask, th = ops.plane_close(mask, close, th), 0
+    if min_area > 1:
+        labels, area = ops.plane_components(mask, th, 0, workspace=True)
+        mask, th = ops.plane_area_select(labels, area, 0, min_area), 0
+    if min_hole > 0:
+        labels, area = ops.plane_components(mask, th, 1, workspace=True)
+        mask, th = ops.plane_area_select(labels, area, 1, min_hole), 0
+    return mask
+
+
+def segment_tissue(region: torch.Tensor, down: int = 16, median: int = 7, sat_thresh=8, val_min: int = 0, close: int = 0, min_area: int = 0,
+                   min_hole: int = 0, return_threshold: bool = False):
     """(plane, t): the median-filtered saturation plane of the region, uint8 [Hr // down, Wr // down] ON THE DEVICE (steps 1 to 3 of the module's
     definition), and the threshold used - a plane pixel is tissue iff it is > t. With an int ``sat_thresh`` t is that int and the call is two launches
     without any synchronisation. ``sat_thresh="otsu"`` also counts the plane's histogram and takes Otsu's threshold of it on the host
-    (``otsu_threshold``): ONE extra device-to-host copy of 1 KB and its synchronisation. An empty plane gives t = 0 under "otsu"."""
+    (``otsu_threshold``): ONE extra device-to-host copy of 1 KB and its synchronisation. An empty plane gives t = 0 under "otsu".
+
+    With ``close`` > 1, ``min_area`` > 1 or ``min_hole`` > 0 (steps 6a to 6c; the other values are the identity and launch nothing) the result is
+    (mask, 0): mask = the 0 / 255 plane of M3, so "tissue iff > t" still holds for the pair. ``return_threshold`` appends the threshold that was applied
+    to the median plane (``sat_thresh`` or Otsu's). Launches on top of the two: ``close`` 1; ``min_area`` 4 (3 labelling launches - 2 where the plane is
+    one 64 x 16 tile - and the selection); ``min_hole`` 4 likewise; all three 9. No further synchronisation. An empty plane still launches nothing."""
     _seg_args(down, median, sat_thresh, val_min)
+    active = _morph_args(close, min_area, min_hole)
     sat = ops.region_saturation(region, down, val_min)
     if sat_thresh == "otsu":
         plane, hist = ops.plane_median(sat, median, want_hist=True)
-        return plane, otsu_threshold(hist.cpu())                    # the 1 KB copy, the synchronisation
-    return ops.plane_median(sat, median), sat_thresh
+        t = otsu_threshold(hist.cpu())                               # the 1 KB copy, the synchronisation
+    else:
+        plane, t = ops.plane_median(sat, median), sat_thresh
+    out = (_morph(plane, t, close, min_area, min_hole), 0) if active and plane.numel() else (plane, t)
+    return out + (t,) if return_threshold else out
 
 
 def _seg_lattice(tile, stride, origin, down):
@@ -172,7 +223,8 @@ def _seg_lattice(tile, stride, origin, down):
 
 
 def segmented_tissue_origins(region: torch.Tensor, tile=256, stride=None, min_fraction: float = 0.25, down: int = 16, median: int = 7, sat_thresh=8,
-                             val_min: int = 0, origin=(0, 0), return_counts: bool = False, return_threshold: bool = False):
+                             val_min: int = 0, origin=(0, 0), return_counts: bool = False, return_threshold: bool = False, close: int = 0,
+                             min_area: int = 0, min_hole: int = 0):
     """``tissue_origins`` with CLAM's tissue decision (the module's steps 1 to 7): the region is box-filtered by ``down``, its saturation plane
     median-filtered (``median`` x ``median``), a plane pixel is tissue iff it is > ``sat_thresh`` - an int in 0..255 or ``"otsu"`` - and a lattice tile
     is kept iff its tissue count >= ceil(min_fraction (H // down) (W // down)). Result as for ``tissue_origins``: np.ndarray int64 [B,2] of (x, y) at the
@@ -183,11 +235,16 @@ def segmented_tissue_origins(region: torch.Tensor, tile=256, stride=None, min_fr
     synchronisation. An empty region or lattice gives an empty [0,2] result, not an error (and launches nothing; the threshold is then ``sat_thresh``,
     0 for ``"otsu"``).
 
+    ``close``, ``min_area``, ``min_hole`` (the module's steps 6a to 6c: CLAM's ``close``, ``a_t`` and ``a_h`` in plane pixels) filter the mask before the
+    tiles are counted; each is skipped entirely at 0 (``close`` and ``min_area`` at 1 as well). They add 1, 4 and 4 launches (9 together; a labelling is 2
+    launches, not 3, where the plane is one 64 x 16 tile) and no synchronisation; ``return_threshold`` still gives the threshold applied to the median plane.
+
     The defaults are CLAM's: ``sthresh = 8``, ``mthresh = 7``, a low-resolution level (``down = 16``); ``use_otsu`` is ``sat_thresh="otsu"``.
-    Morphological closing and the contour and hole area filters of CLAM are not done."""
+    CLAM's ``max_n_holes`` and its polygon areas are not done."""
     if not isinstance(min_fraction, (int, float)) or isinstance(min_fraction, bool) or not 0.0 <= min_fraction <= 1.0:
         raise ValueError(f"min_fraction must lie in [0, 1], got {min_fraction!r}")
     _seg_args(down, median, sat_thresh, val_min)
+    active = _morph_args(close, min_area, min_hole)
     _, hr, wr = ops._region_pitch(region, "segmented_tissue_origins")
     h, w, sy, sx, x0, y0 = _lattice_args(tile, stride, origin)
     ph, pw, psy, psx, px0, py0 = _seg_lattice((h, w), (sy, sx), (x0, y0), down)
@@ -201,7 +258,7 @@ def segmented_tissue_origins(region: torch.Tensor, tile=256, stride=None, min_fr
         return result(np.zeros((0, 2), dtype=np.int64), np.zeros((0,), dtype=np.int64), 0 if sat_thresh == "otsu" else sat_thresh)
     plane, t = segment_tissue(region, down, median, sat_thresh, val_min)
     cell = lattice_cell((ph, pw), (psy, psx), (px0, py0))
-    cells = ops.plane_cells(plane, cell, t)
+    cells = ops.plane_cells(_morph(plane, t, close, min_area, min_hole), cell, 0) if active else ops.plane_cells(plane, cell, t)
     c = ops.tissue_tile_counts(cells, cell, (px0, py0), (ph, pw), (psy, psx), (nx, ny)).cpu().numpy().astype(np.int64)      # the one copy
     j, i = np.nonzero(c >= math.ceil(min_fraction * ph * pw))       # row-major: j (y) outer, i (x) inner
     origins = np.stack([x0 + i * sx, y0 + j * sy], axis=1).astype(np.int64)
