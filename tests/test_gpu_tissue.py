@@ -43,7 +43,7 @@ def embedded(region: np.ndarray, top, left, bottom, right, dev):
 
 # ---- 1. cells, exact ----------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("hr,wr", [(1, 1), (7, 5), (64, 64), (67, 131), (131, 67), (300, 520)])
+@pytest.mark.parametrize("hr,wr", [(1, 1), (7, 5), (7, 6), (64, 64), (67, 131), (131, 67), (66, 134), (300, 520)])
 def test_cell_counts_equal_the_reference_and_every_element_is_written(cuda, hr, wr):
     from toad_amd import ops
     s = ref.slide(hr, wr, 1)

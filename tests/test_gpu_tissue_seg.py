@@ -96,7 +96,7 @@ def test_saturation_on_every_max_min_pair(cuda):
 
 # ---- 2. shapes, every box filter ------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("hr,wr", [(1, 1), (7, 5), (31, 33), (67, 131), (131, 67), (300, 520), (70, 1037)])
+@pytest.mark.parametrize("hr,wr", [(1, 1), (7, 5), (7, 6), (31, 33), (67, 131), (131, 67), (66, 134), (300, 520), (70, 1037)])
 def test_saturation_planes_equal_the_reference_and_nothing_else_is_written(cuda, hr, wr):
     """(70, 1037) is the last-lane case beyond four 256-pixel chunks. The plane lies in a parent poisoned with 0x7f, at an odd pitch and offset."""
     from toad_amd import ops

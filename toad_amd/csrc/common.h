@@ -20,19 +20,34 @@ int check_launch(const char *what);
 void note_fallback_launch();      // an exact-fp32 fallback GEMM kernel was launched (toad_fallback_launches, capi.hip)
 
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+// a dword / a half word at ANY byte address (the uint8 region and plane kernels: bases, pitches and 3 x have any parity). On global memory the hardware
+// takes either at any byte address; the type only stops the compiler from assuming more.
+typedef unsigned u32_a1 __attribute__((aligned(1)));
+typedef unsigned short u16_a1 __attribute__((aligned(1)));
 
 // ---- 16-lane ("DPP row") all-reduce: every lane of each 16-lane row ends with the row's sum.
 // quad_perm[1,0,3,2] -> quad_perm[2,3,0,1] -> row_half_mirror -> row_mirror. All four are
 // single-instruction DPP modifiers on gfx9, no LDS traffic.
 template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
+__device__ __forceinline__ int dpp_mov(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false); }
+template <int CTRL>
+__device__ __forceinline__ float dpp_mov(float v) { return __builtin_bit_cast(float, dpp_mov<CTRL>(__builtin_bit_cast(int, v))); }
 __device__ __forceinline__ float row16_allreduce_sum(float v) {
     v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
     v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
     v += dpp_mov<0x141>(v);  // row_half_mirror
     v += dpp_mov<0x140>(v);  // row_mirror
+    return v;
+}
+// the integer form over 1, 2, 4, 8 or 16 lanes: every lane of each aligned group of LANES lanes ends with the group's sum; all 64 lanes must be active
+template <int LANES>
+__device__ __forceinline__ int lanes_allreduce_sum(int v) {
+    if constexpr (LANES >= 2) v += dpp_mov<0xB1>(v);
+    if constexpr (LANES >= 4) v += dpp_mov<0x4E>(v);
+    if constexpr (LANES >= 8) v += dpp_mov<0x141>(v);
+    if constexpr (LANES >= 16) v += dpp_mov<0x140>(v);
     return v;
 }
 

@@ -11,12 +11,9 @@
 // Two kernels:
 //   heat_cells_kernel         one thread per cell: the covering tiles' index ranges in closed form from the lattice in cell units, a loop over them.
 //   heat_blend_kernel<DOWN>   one streaming pass over the region: read uint8, write uint8.
-#include "common.h"
+#include "region_u8.h"
 
 namespace toad {
-
-typedef unsigned hm_u32_a1 __attribute__((aligned(1)));           // a dword / a half word at any byte address: base, pitch and 3 x have any parity
-typedef unsigned short hm_u16_a1 __attribute__((aligned(1)));
 
 // All lattice arguments in cell units. Tile j covers cell row gy iff cy0 + j csy <= gy < cy0 + j csy + ch: with t = gy - cy0 >= 0 that is
 // j in [t >= ch ? (t - ch) / csy + 1 : 0,  min(t / csy, ny - 1)], and the same along x. The launcher bounds ceil(ch / csy) ceil(cw / csx) by 4096, so
@@ -57,13 +54,7 @@ __device__ __forceinline__ void heat_px4(const unsigned (&w)[DOWN][3], const uns
     } else {
         constexpr int SH = DOWN == 2 ? 2 : 4;                        // log2(DOWN^2)
         unsigned b[12];                                              // the 12 column sums over the DOWN rows, each at most 4 * 255
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            unsigned ev = 0, od = 0;
-#pragma unroll
-            for (int r = 0; r < DOWN; ++r) { ev += w[r][k] & 0x00FF00FFu; od += (w[r][k] >> 8) & 0x00FF00FFu; }
-            b[4 * k] = ev & 0xFFFFu; b[4 * k + 1] = od & 0xFFFFu; b[4 * k + 2] = ev >> 16; b[4 * k + 3] = od >> 16;
-        }
+        column_sums<DOWN>(w, b);
         o[0] = o[1] = o[2] = 0;
 #pragma unroll
         for (int p = 0; p < 4 / DOWN; ++p)
@@ -82,24 +73,20 @@ __device__ __forceinline__ void heat_px4(const unsigned (&w)[DOWN][3], const uns
 template <int DOWN>
 __device__ __forceinline__ void heat_store4(unsigned char *d, const unsigned (&o)[3]) {
     if constexpr (DOWN == 1) {
-        *reinterpret_cast<hm_u32_a1 *>(d) = o[0]; *reinterpret_cast<hm_u32_a1 *>(d + 4) = o[1]; *reinterpret_cast<hm_u32_a1 *>(d + 8) = o[2];
+        *reinterpret_cast<u32_a1 *>(d) = o[0]; *reinterpret_cast<u32_a1 *>(d + 4) = o[1]; *reinterpret_cast<u32_a1 *>(d + 8) = o[2];
     } else if constexpr (DOWN == 2) {
-        *reinterpret_cast<hm_u32_a1 *>(d) = o[0]; *reinterpret_cast<hm_u16_a1 *>(d + 4) = (unsigned short)o[1];
+        *reinterpret_cast<u32_a1 *>(d) = o[0]; *reinterpret_cast<u16_a1 *>(d + 4) = (unsigned short)o[1];
     } else {
-        *reinterpret_cast<hm_u16_a1 *>(d) = (unsigned short)o[0]; d[2] = (unsigned char)(o[0] >> 16);
+        *reinterpret_cast<u16_a1 *>(d) = (unsigned short)o[0]; d[2] = (unsigned char)(o[0] >> 16);
     }
 }
 
-// Work split, as in tissue_cells_kernel: lanes run along x, a lane takes 4 pixels = 12 contiguous bytes of a row as three dwords, a wave 256 pixels = 768
-// contiguous bytes; a workgroup of 4 waves takes one 256-pixel column chunk of 16 rows, 4 consecutive rows per wave, unrolled (12 dwords a lane in flight).
-// A lane owns a 4-pixel-wide, DOWN-row-high block and writes its 4 / DOWN output pixels - 12, 6 or 3 bytes - as dword, half-word and byte stores at any
-// byte address. x is a multiple of 4 and the wave's first row one too, so with cell >= 4 a lane's 4 x 4 pixels lie in ONE cell: one cells load per lane,
-// one lookup in the 256 colours the workgroup has packed into 1 KB of LDS.
-//
-// Hi = DOWN Ho and Wi = DOWN Wo are the rows and columns of the region that some output pixel consumes; nothing outside them is touched. Addresses: the
-// row bases y pitch and oy out_pitch are 64-bit, the in-row byte offsets 32-bit (the launcher refuses 3 Wr >= 2^31). A wave whose 768 bytes end inside
-// 3 Wi, over 4 rows that all lie above Hi, runs the plain path. Any other wave loops over the output rows that exist and per lane takes the three dwords
-// and the wide stores only where x + 4 <= Wi, byte loads and byte stores for the 1 to 3 pixels of the lane the row ends in, and nothing beyond.
+// The work split and its addresses are region_u8.h's, on strips of 16 rows (4 a wave, 12 dwords a lane in flight) over the Hi = DOWN Ho rows and
+// Wi = DOWN Wo columns of the region that some output pixel consumes; nothing outside them is touched. What differs here: a lane owns a 4-pixel-wide,
+// DOWN-row-high block and writes its 4 / DOWN output pixels - 12, 6 or 3 bytes - as dword, half-word and byte stores at any byte address (the row base
+// oy out_pitch is 64-bit like y pitch); off the plain path it takes the wide stores only where x + 4 <= Wi and byte stores for the 1 to 3 pixels of the
+// lane the row ends in. x is a multiple of 4 and the wave's first row one too, so with cell >= 4 a lane's 4 x 4 pixels lie in ONE cell: one cells load per
+// lane, one lookup in the 256 colours the workgroup has packed into 1 KB of LDS.
 template <int DOWN>
 __global__ __launch_bounds__(256) void heat_blend_kernel(const unsigned char *__restrict__ region, int64_t pitch, int Hi, int Wi, const int *__restrict__ cells,
                                                          int Gx, int shift, const unsigned char *__restrict__ lut, int alpha, unsigned char *__restrict__ out,
@@ -123,7 +110,7 @@ __global__ __launch_bounds__(256) void heat_blend_kernel(const unsigned char *__
 #pragma unroll
         for (int r = 0; r < RW; ++r)
 #pragma unroll
-            for (int k = 0; k < 3; ++k) w[r / DOWN][r % DOWN][k] = *reinterpret_cast<const hm_u32_a1 *>(src + r * pitch + 4 * k);
+            for (int k = 0; k < 3; ++k) w[r / DOWN][r % DOWN][k] = *reinterpret_cast<const u32_a1 *>(src + r * pitch + 4 * k);
 #pragma unroll
         for (int q = 0; q < ORW; ++q) {
             unsigned o[3];
@@ -133,22 +120,11 @@ __global__ __launch_bounds__(256) void heat_blend_kernel(const unsigned char *__
     } else {
         const int rows = (int)min((int64_t)ORW, (Hi - y0) / DOWN);   // output rows of this wave that exist: Hi and y0 are multiples of DOWN
         const int npx = x < (unsigned)Wi ? min(4, Wi - (int)x) : 0;  // pixels of this lane that are consumed: 0, DOWN, .., 4
-        const int nin = 3 * npx, nout = nin / DOWN;                  // bytes to read per row, bytes to write per output row
+        const int nout = 3 * npx / DOWN;                             // bytes to write per output row
         for (int q = 0; q < rows; ++q) {
             unsigned w[DOWN][3];
 #pragma unroll
-            for (int r = 0; r < DOWN; ++r) {
-                const unsigned char *p = src + (q * DOWN + r) * pitch;
-                if (npx == 4) {
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) w[r][k] = *reinterpret_cast<const hm_u32_a1 *>(p + 4 * k);
-                } else {                                             // the lane the row ends in: 1 to 3 pixels byte by byte, or none
-                    w[r][0] = w[r][1] = w[r][2] = 0;
-#pragma unroll
-                    for (int k = 0; k < 9; ++k)
-                        if (k < nin) w[r][k >> 2] |= (unsigned)p[k] << (8 * (k & 3));
-                }
-            }
+            for (int r = 0; r < DOWN; ++r) load_px4(src + (q * DOWN + r) * pitch, npx, w[r]);
             unsigned o[3];
             heat_px4<DOWN>(w, a, beta, o);
             unsigned char *d = dst + q * out_pitch;
@@ -163,9 +139,6 @@ __global__ __launch_bounds__(256) void heat_blend_kernel(const unsigned char *__
     }
 }
 
-static bool heat_cell_ok(int cell) { return cell == 4 || cell == 8 || cell == 16 || cell == 32 || cell == 64; }
-static bool heat_aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
 }  // namespace toad
 
 using namespace toad;
@@ -174,30 +147,15 @@ extern "C" int toad_heat_cells(const int *tile_q, int nx, int ny, int cell, int 
                                void *stream) {
     const char *what = "toad_heat_cells";
     if (!tile_q || !cells) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
-    if (!heat_cell_ok(cell)) { set_error("%s: cell = %d is not one of 4, 8, 16, 32, 64", what, cell); return TOAD_ESHAPE; }
-    if (Gy <= 0 || Gx <= 0 || nx <= 0 || ny <= 0 || H <= 0 || W <= 0 || sx <= 0 || sy <= 0) {
-        set_error("%s: bad shape (Gy, Gx, nx, ny, H, W, sx, sy must all be positive)", what);
-        return TOAD_ESHAPE;
-    }
-    const int vals[6] = {x0, y0, H, W, sx, sy};
-    const char *names[6] = {"x0", "y0", "H", "W", "sx", "sy"};
-    for (int k = 0; k < 6; ++k)
-        if (vals[k] < 0 || vals[k] % cell) {
-            set_error("%s: %s = %d is negative or not a multiple of cell = %d (a tile must be a union of whole cells)", what, names[k], vals[k], cell);
-            return TOAD_ESHAPE;
-        }
+    if (int rc = check_cell(what, cell)) return rc;
+    if (int rc = check_lattice_units(what, cell, x0, y0, H, W, sx, sy, nx, ny, Gy, Gx)) return rc;
     const int64_t cover = (((int64_t)H + sy - 1) / sy) * (((int64_t)W + sx - 1) / sx);
     if (cover > 4096) {
         set_error("%s: coverage ceil(H / sy) * ceil(W / sx) = %lld exceeds 4096 tiles per cell (the int32 sum of their scores)", what, (long long)cover);
         return TOAD_ESHAPE;
     }
-    const int64_t x_end = x0 + (int64_t)(nx - 1) * sx + W, y_end = y0 + (int64_t)(ny - 1) * sy + H;
-    if (x_end > (int64_t)Gx * cell || y_end > (int64_t)Gy * cell) {
-        set_error("%s: the lattice's last tile ends at (x, y) = (%lld, %lld), outside the %d x %d cells of %d pixels (Gy x Gx)", what, (long long)x_end,
-                  (long long)y_end, Gy, Gx, cell);
-        return TOAD_ESHAPE;
-    }
-    if (!heat_aligned4(tile_q) || !heat_aligned4(cells)) { set_error("%s: tile_q and cells (int32) must be 4-byte aligned", what); return TOAD_EALIGN; }
+    if (int rc = check_lattice_extent(what, cell, x0, y0, H, W, sx, sy, nx, ny, Gy, Gx)) return rc;
+    if (!aligned4(tile_q) || !aligned4(cells)) { set_error("%s: tile_q and cells (int32) must be 4-byte aligned", what); return TOAD_EALIGN; }
     const uint64_t g = ((uint64_t)Gy * Gx + 255) / 256;
     hipLaunchKernelGGL(heat_cells_kernel, dim3((unsigned)(g > 8192 ? 8192 : g)), dim3(256), 0, (hipStream_t)stream, tile_q, nx, ny, x0 / cell, y0 / cell,
                        H / cell, W / cell, sx / cell, sy / cell, Gy, Gx, cells);
@@ -208,12 +166,11 @@ extern "C" int toad_region_heat_blend_u8(const unsigned char *region, int64_t pi
                                          const unsigned char *lut, int alpha, int down, unsigned char *out, int64_t out_pitch, void *stream) {
     const char *what = "toad_region_heat_blend_u8";
     if (!region || !cells || !lut || !out) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
-    if (!heat_cell_ok(cell)) { set_error("%s: cell = %d is not one of 4, 8, 16, 32, 64", what, cell); return TOAD_ESHAPE; }
-    if (Hr <= 0 || Wr <= 0) { set_error("%s: bad shape (Hr = %d, Wr = %d)", what, Hr, Wr); return TOAD_ESHAPE; }
+    if (int rc = check_cell(what, cell)) return rc;
+    if (int rc = check_hw(what, "Hr", Hr, "Wr", Wr)) return rc;
     if (alpha < 0 || alpha > 256) { set_error("%s: alpha = %d must lie in [0, 256] (256 = the colour alone)", what, alpha); return TOAD_ESHAPE; }
     if (down != 1 && down != 2 && down != 4) { set_error("%s: down = %d is not one of 1, 2, 4", what, down); return TOAD_ESHAPE; }
-    if (pitch < 3 * (int64_t)Wr) { set_error("%s: pitch %lld is less than a row of the region (3 Wr = %lld bytes)", what, (long long)pitch, 3ll * Wr); return TOAD_ESHAPE; }
-    if (3 * (int64_t)Wr >= (1ll << 31)) { set_error("%s: region too wide: 3 Wr must stay below 2^31 (32-bit offsets inside a row)", what); return TOAD_ESHAPE; }
+    if (int rc = check_region_pitch(what, pitch, Wr)) return rc;
     const int Ho = Hr / down, Wo = Wr / down;
     if (out_pitch < 3 * (int64_t)Wo) {
         set_error("%s: out_pitch %lld is less than a row of the canvas (3 Wo = %lld bytes)", what, (long long)out_pitch, 3ll * Wo);
@@ -226,8 +183,8 @@ extern "C" int toad_region_heat_blend_u8(const unsigned char *region, int64_t pi
     }
     const int Hi = Ho * down, Wi = Wo * down;
     const int64_t nchunks = ((int64_t)Wi + 255) / 256, blocks = nchunks * (((int64_t)Hi + 15) / 16);
-    if (blocks >= (1ll << 31)) { set_error("%s: region too large: %lld workgroups", what, (long long)blocks); return TOAD_ESHAPE; }
-    if (!heat_aligned4(cells)) { set_error("%s: cells (int32 [Gy][Gx]) must be 4-byte aligned (the region and the canvas may have any alignment)", what); return TOAD_EALIGN; }
+    if (int rc = check_blocks(what, "region", blocks)) return rc;
+    if (!aligned4(cells)) { set_error("%s: cells (int32 [Gy][Gx]) must be 4-byte aligned (the region and the canvas may have any alignment)", what); return TOAD_EALIGN; }
     if (Ho == 0 || Wo == 0) return TOAD_OK;
     int shift = 2;
     while ((1 << shift) < cell) ++shift;

@@ -54,14 +54,12 @@ constexpr int SH_TASKS = (SH_ROWS * SH_WS + 255) / 256;      // space-to-depth p
 //     predicate is the TILE's (iy in [0, H), ix in [0, 256)), not the region's: a tap outside the tile is 0 in normalised space even where the region has
 //     pixels there, so tile b behaves exactly as region[y:y+H, x:x+256] cut out and given to the uint8 form - and no address outside the tile, hence none
 //     outside the region, is ever read (the origins' bounds are the caller's duty). (y_b + iy) pitch + (x_b + ix) 3 has any parity, and it changes from
-//     row to row with an odd pitch: the 4-byte and the 2-byte word are loaded through types declared aligned(1) - the same two loads per row and the same
+//     row to row with an odd pitch: the 4-byte and the 2-byte word are loaded through common.h's u32_a1 / u16_a1 - the same two loads per row and the same
 //     4 registers per task as the uint8 form, on global memory the hardware takes a dword at any byte address (six byte loads assembled in registers compile
 //     to the same two loads at -O3: there is no second form to choose from). The loads are plain, not nontemporal:
 //     overlapping tiles (heat-map strides) read the same bytes again. From the raw words on it is the uint8 form's code.
 constexpr unsigned SH_U8_OUTSIDE = 0xFFFF0000u;              // upper half of a row's 2-byte word: the pixel pair lies outside the image
 typedef unsigned sh_u32_a2 __attribute__((aligned(2)));      // a 4-byte load from a 2-byte aligned address
-typedef unsigned sh_u32_a1 __attribute__((aligned(1)));      // region form: the same words from any byte address
-typedef unsigned short sh_u16_a1 __attribute__((aligned(1)));
 constexpr int SH_F32 = 0, SH_U8 = 1, SH_U8_REGION = 2;   // the FORM parameter of the kernel
 
 // (the constants are the LAST kernel argument, an empty struct in the fp32 form: that form's argument layout, registers and code are the ones it had as a
@@ -129,8 +127,8 @@ __global__ __launch_bounds__(256, 2) void stem_halo_pool_kernel(const typename s
                     const int iy = 4 * t - 4 + 2 * Yl + ry;
                     const bool ok = tc >= 0 && iy >= 0 && iy < H && ix >= 0 && ix < W;       // the TILE's edges: bytes [0, 6) of the pair end inside row iy of the tile
                     const unsigned char *p = img8 + ((unsigned)iy * (unsigned)pitch + (unsigned)(ix * 3));      // (32-bit, unsigned: H pitch < 2^31; only read where ok)
-                    raw[k][2 * ry] = ok ? *reinterpret_cast<const sh_u32_a1 *>(p) : 0u;
-                    raw[k][2 * ry + 1] = ok ? (unsigned)*reinterpret_cast<const sh_u16_a1 *>(p + 4) : SH_U8_OUTSIDE;
+                    raw[k][2 * ry] = ok ? *reinterpret_cast<const u32_a1 *>(p) : 0u;
+                    raw[k][2 * ry + 1] = ok ? (unsigned)*reinterpret_cast<const u16_a1 *>(p + 4) : SH_U8_OUTSIDE;
                 }
             }
         } else if constexpr (U8) {

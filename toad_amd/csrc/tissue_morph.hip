@@ -30,7 +30,7 @@
 // Hang safety: every loop strictly decreases an index (find: x <- parent[x] < x; union: max(a, b) decreases with every lost race), no lane waits for another
 // workgroup, there is no grid-wide barrier, no cooperative launch and no float atomic. Counts and the border bit reach area[] by integer add and or, which
 // commute: the result does not depend on the order of arrival.
-#include "common.h"
+#include "region_u8.h"
 
 namespace toad {
 
@@ -298,8 +298,6 @@ __global__ __launch_bounds__(256) void area_select_kernel(const int *__restrict_
     }
 }
 
-static bool morph_aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
 }  // namespace toad
 
 using namespace toad;
@@ -308,18 +306,13 @@ extern "C" int toad_plane_close_u8(const unsigned char *src, int64_t src_pitch, 
                                    void *stream) {
     const char *what = "toad_plane_close_u8";
     if (!src || !dst) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
-    if (thresh < 0 || thresh > 255) { set_error("%s: thresh = %d must lie in [0, 255] (the 8-bit scale)", what, thresh); return TOAD_EINVAL; }
+    if (int rc = check_u8(what, "thresh", thresh)) return rc;
     if (c < 0 || c > 8) { set_error("%s: c = %d is not one of 0 .. 8", what, c); return TOAD_ESHAPE; }
-    if (Hp <= 0 || Wp <= 0) { set_error("%s: bad shape (Hp = %d, Wp = %d)", what, Hp, Wp); return TOAD_ESHAPE; }
-    if (src_pitch < (int64_t)Wp || dst_pitch < (int64_t)Wp) {
-        set_error("%s: src_pitch %lld or dst_pitch %lld is less than a row of the plane (Wp = %d bytes)", what, (long long)src_pitch, (long long)dst_pitch, Wp);
-        return TOAD_ESHAPE;
-    }
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), s1 = s0 + (uintptr_t)(Hp - 1) * (uintptr_t)src_pitch + (uintptr_t)Wp;
-    const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), d1 = d0 + (uintptr_t)(Hp - 1) * (uintptr_t)dst_pitch + (uintptr_t)Wp;
-    if (s0 < d1 && d0 < s1) { set_error("%s: src and dst overlap (a window reads what a neighbour has written)", what); return TOAD_EINVAL; }
+    if (int rc = check_hw(what, "Hp", Hp, "Wp", Wp)) return rc;
+    if (int rc = check_plane_pitches(what, Wp, src_pitch, dst_pitch)) return rc;
+    if (int rc = check_no_overlap(what, src, src_pitch, dst, dst_pitch, Hp, Wp)) return rc;
     const int64_t ntx = ((int64_t)Wp + MT_W - 1) / MT_W, blocks = ntx * (((int64_t)Hp + MT_H - 1) / MT_H);
-    if (blocks >= (1ll << 31)) { set_error("%s: plane too large: %lld workgroups", what, (long long)blocks); return TOAD_ESHAPE; }
+    if (int rc = check_blocks(what, "plane", blocks)) return rc;
     hipStream_t st = (hipStream_t)stream;
 #define TOAD_CLOSE_LAUNCH(CC) \
     hipLaunchKernelGGL(plane_close_kernel<CC>, dim3((unsigned)blocks), dim3(256), 0, st, src, src_pitch, Hp, Wp, thresh, dst, dst_pitch, (unsigned)ntx)
@@ -341,18 +334,11 @@ extern "C" int toad_plane_components_u8(const unsigned char *plane, int64_t pitc
                                         void *stream) {
     const char *what = "toad_plane_components_u8";
     if (!plane || !labels || !area) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
-    if (thresh < 0 || thresh > 255) { set_error("%s: thresh = %d must lie in [0, 255] (the 8-bit scale)", what, thresh); return TOAD_EINVAL; }
+    if (int rc = check_u8(what, "thresh", thresh)) return rc;
     if (background != 0 && background != 1) { set_error("%s: background = %d must be 0 or 1", what, background); return TOAD_EINVAL; }
-    if (Hp <= 0 || Wp <= 0) { set_error("%s: bad shape (Hp = %d, Wp = %d)", what, Hp, Wp); return TOAD_ESHAPE; }
-    if (pitch < (int64_t)Wp) { set_error("%s: pitch %lld is less than a row of the plane (Wp = %d bytes)", what, (long long)pitch, Wp); return TOAD_ESHAPE; }
-    if ((int64_t)Hp * Wp >= (1ll << 30)) {
-        set_error("%s: plane too large: Hp * Wp = %lld must stay below 2^30 (int32 labels, the border bit of area)", what, (long long)Hp * Wp);
-        return TOAD_ESHAPE;
-    }
-    if (!morph_aligned4(labels) || !morph_aligned4(area)) {
-        set_error("%s: labels (int32 [Hp][Wp]) and area (int32 [Hp * Wp]) must be 4-byte aligned (the plane may have any alignment)", what);
-        return TOAD_EALIGN;
-    }
+    if (int rc = check_hw(what, "Hp", Hp, "Wp", Wp)) return rc;
+    if (int rc = check_plane_pitch(what, Wp, "pitch", pitch)) return rc;
+    if (int rc = check_labels(what, Hp, Wp, labels, area, "the plane")) return rc;
     const int ntx = (Wp + MT_W - 1) / MT_W, nty = (Hp + MT_H - 1) / MT_H, blocks = ntx * nty;      // < 2^20
     const int nvl = (ntx - 1) * Hp, total = nvl + (nty - 1) * Wp;                                   // < 2^30 / 8
     hipStream_t st = (hipStream_t)stream;
@@ -369,16 +355,9 @@ extern "C" int toad_plane_area_select_u8(const int *labels, const int *area, int
     if (!labels || !area || !dst) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
     if (mode != 0 && mode != 1) { set_error("%s: mode = %d must be 0 (drop small components) or 1 (fill small holes)", what, mode); return TOAD_EINVAL; }
     if (limit < 0) { set_error("%s: limit = %d must not be negative", what, limit); return TOAD_EINVAL; }
-    if (Hp <= 0 || Wp <= 0) { set_error("%s: bad shape (Hp = %d, Wp = %d)", what, Hp, Wp); return TOAD_ESHAPE; }
-    if (dst_pitch < (int64_t)Wp) { set_error("%s: dst_pitch %lld is less than a row of the plane (Wp = %d bytes)", what, (long long)dst_pitch, Wp); return TOAD_ESHAPE; }
-    if ((int64_t)Hp * Wp >= (1ll << 30)) {
-        set_error("%s: plane too large: Hp * Wp = %lld must stay below 2^30 (int32 labels, the border bit of area)", what, (long long)Hp * Wp);
-        return TOAD_ESHAPE;
-    }
-    if (!morph_aligned4(labels) || !morph_aligned4(area)) {
-        set_error("%s: labels (int32 [Hp][Wp]) and area (int32 [Hp * Wp]) must be 4-byte aligned (dst may have any alignment)", what);
-        return TOAD_EALIGN;
-    }
+    if (int rc = check_hw(what, "Hp", Hp, "Wp", Wp)) return rc;
+    if (int rc = check_plane_pitch(what, Wp, "dst_pitch", dst_pitch)) return rc;
+    if (int rc = check_labels(what, Hp, Wp, labels, area, "dst")) return rc;
     const int ntx = (Wp + MT_W - 1) / MT_W, nty = (Hp + MT_H - 1) / MT_H;
     hipLaunchKernelGGL(area_select_kernel, dim3((unsigned)(ntx * nty)), dim3(256), 0, (hipStream_t)stream, labels, area, Hp, Wp, mode, limit, dst, dst_pitch,
                        (unsigned)ntx);

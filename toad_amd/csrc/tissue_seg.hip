@@ -17,24 +17,9 @@
 //   sat_plane_kernel<DOWN>    one streaming pass over the region (the 100 MB one) -> the uint8 saturation plane.
 //   plane_median_kernel<K>    a 64 x 4 output tile and its K - 1 halo staged in LDS as bytes, the rank taken by bisection over the 8 value bits.
 //   plane_cells_kernel<CELL>  tissue_cells_kernel's work split on one byte per pixel.
-#include "common.h"
+#include "region_u8.h"
 
 namespace toad {
-
-typedef unsigned sg_u32_a1 __attribute__((aligned(1)));            // a dword / a half word at any byte address: bases and pitches have any parity
-typedef unsigned short sg_u16_a1 __attribute__((aligned(1)));
-
-template <int CTRL>
-__device__ __forceinline__ int sg_dpp_mov(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false); }
-// tissue.hip's all-reduce: every lane of each aligned group of LANES lanes (1 .. 16: inside a 16-lane DPP row) ends with the group's sum; all 64 lanes active
-template <int LANES>
-__device__ __forceinline__ int sg_lanes_allreduce_sum(int v) {
-    if constexpr (LANES >= 2) v += sg_dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
-    if constexpr (LANES >= 4) v += sg_dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
-    if constexpr (LANES >= 8) v += sg_dpp_mov<0x141>(v);   // row_half_mirror
-    if constexpr (LANES >= 16) v += sg_dpp_mov<0x140>(v);  // row_mirror
-    return v;
-}
 
 // S = (255 (mx - mn) + (mx >> 1)) / mx exactly, for all 32,896 pairs mn <= mx: the numerator n is below 2^16 and the divisor below 2^8, so the float
 // quotient n * rcp(mx) is off by less than 2^-6 and its truncation by at most one in either direction; one remainder test each way corrects it. mx == 0
@@ -51,22 +36,24 @@ __device__ __forceinline__ unsigned sat_byte(int r, int g, int b, int vmin) {
 // byte k of the 12 bytes of 4 pixels held as three little-endian dwords: r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
 __device__ __forceinline__ int sg_byte(const unsigned (&w)[3], int k) { return (int)((w[k >> 2] >> (8 * (k & 3))) & 255u); }
 
-// Work split, as in tissue_cells_kernel: lanes run along x, a lane takes 4 pixels = 12 contiguous bytes of a row as three dwords, a wave 256 pixels = 768
-// contiguous bytes; a workgroup of 4 waves takes one 256-pixel column chunk of RB = max(DOWN, 16) rows, RB / 4 consecutive rows per wave, unrolled (12 or
-// 24 dwords a lane in flight). It carries three channel sums where tissue_cells_kernel carries one count:
+// The work split and its addresses are region_u8.h's, on strips of RB = strip_rows(DOWN) rows (12 or 24 dwords a lane in flight). The kernel carries three
+// channel sums where tissue_cells_kernel carries one count:
 //   DOWN = 1, 2   a lane owns its boxes: 4 outputs a row, or 2 outputs every second row, stored as a dword / a half word at any byte address;
 //   DOWN = 4      a lane's 4 x 4 pixels are one box: one byte a lane;
 //   DOWN >= 8     the DOWN / 4 lanes of a box are summed by DPP moves, the 2 or 4 waves of a box row meet in 3 KB of LDS, one lane per box stores.
 // Hi = DOWN Hp and Wi = DOWN Wp are the rows and columns some box consumes: nothing outside them is read (a dropped partial box needs no reading at all),
-// so no byte outside y pitch + [0, 3 Wr), y < Hr, is. Addresses: row bases are 64-bit, offsets inside a row 32-bit (the launcher refuses 3 Wr >= 2^31). A
-// wave whose 768 bytes end inside 3 Wi over rows that all lie above Hi loads plainly; any other wave takes, row by row, the three dwords only where
-// x + 4 <= Wi, byte loads for the 1 to 3 pixels of the lane the row ends in (DOWN <= 2 only: Wi is a multiple of DOWN), zeros elsewhere. Zeros are
-// harmless: a box lies wholly inside Hi x Wi or wholly outside. Every plane byte is written by exactly one lane, once; nothing outside
-// y plane_pitch + [0, Wp), y < Hp, is written.
+// so no byte outside y pitch + [0, 3 Wr), y < Hr, is. A wave off the plain path holds zeros for the rows and pixels that are not consumed (a lane has
+// 1 to 3 pixels with DOWN <= 2 only: Wi is a multiple of DOWN). Zeros are harmless: a box lies wholly inside Hi x Wi or wholly outside. Every plane byte is
+// written by exactly one lane, once; nothing outside y plane_pitch + [0, Wp), y < Hp, is written.
+// The one exception to "edge loads go through load_px4": the loop below is load_px4's body, statement for statement, but for the zeroing of w[r], which
+// stands in front of the r < rows test (rows that do not exist must be zeros too) and not in the byte-load arm. With the helper called instead, hipcc
+// lays sat_plane_kernel<1> out differently and its PLAIN path - the same instructions - ran 0.8 % slower on a 4096 x 8192 region in 6 of 6 alternating
+// runs, the parent's own runs spreading by 0.2 % (profiles/r13a_region_refactor_ab.md, "sat_plane_kernel through load_px4"). Written out, DOWN = 1 and 2
+// compile to the parent's code.
 template <int DOWN>
 __global__ __launch_bounds__(256) void sat_plane_kernel(const unsigned char *__restrict__ region, int64_t pitch, int Hi, int Wi, int vmin,
                                                         unsigned char *__restrict__ plane, int64_t ppitch, unsigned nchunks) {
-    constexpr int RB = DOWN > 16 ? DOWN : 16, RW = RB / 4;         // rows per workgroup, per wave
+    constexpr int RB = strip_rows(DOWN), RW = RB / 4;              // rows per workgroup, per wave
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned chunk = blockIdx.x % nchunks, rb = blockIdx.x / nchunks;
     const unsigned x = chunk * 256u + (unsigned)lane * 4u, off = 3u * x;
@@ -78,18 +65,18 @@ __global__ __launch_bounds__(256) void sat_plane_kernel(const unsigned char *__r
 #pragma unroll
         for (int r = 0; r < RW; ++r)
 #pragma unroll
-            for (int k = 0; k < 3; ++k) w[r][k] = *reinterpret_cast<const sg_u32_a1 *>(src + r * pitch + 4 * k);
+            for (int k = 0; k < 3; ++k) w[r][k] = *reinterpret_cast<const u32_a1 *>(src + r * pitch + 4 * k);
     } else {
         rows = (int)max((int64_t)0, min((int64_t)RW, (int64_t)Hi - y0));
         npx = x < (unsigned)Wi ? min(4, Wi - (int)x) : 0;
 #pragma unroll
         for (int r = 0; r < RW; ++r) {
             w[r][0] = w[r][1] = w[r][2] = 0;
-            if (r < rows) {
+            if (r < rows) {                                        // load_px4(src + r * pitch, npx, w[r]), written out: see above
                 const unsigned char *p = src + r * pitch;
                 if (npx == 4) {
 #pragma unroll
-                    for (int k = 0; k < 3; ++k) w[r][k] = *reinterpret_cast<const sg_u32_a1 *>(p + 4 * k);
+                    for (int k = 0; k < 3; ++k) w[r][k] = *reinterpret_cast<const u32_a1 *>(p + 4 * k);
                 } else {
 #pragma unroll
                     for (int k = 0; k < 9; ++k)
@@ -108,7 +95,7 @@ __global__ __launch_bounds__(256) void sat_plane_kernel(const unsigned char *__r
             if (r < rows) {
                 unsigned char *d = dst + r * ppitch;
                 if (npx == 4) {
-                    *reinterpret_cast<sg_u32_a1 *>(d) = o;
+                    *reinterpret_cast<u32_a1 *>(d) = o;
                 } else {
 #pragma unroll
                     for (int p = 0; p < 3; ++p)
@@ -132,23 +119,17 @@ __global__ __launch_bounds__(256) void sat_plane_kernel(const unsigned char *__r
             }
             if (2 * q < rows) {                                    // rows is even: Hi and y0 are
                 unsigned char *d = dst + q * ppitch;
-                if (npx == 4) *reinterpret_cast<sg_u16_a1 *>(d) = (unsigned short)o;
+                if (npx == 4) *reinterpret_cast<u16_a1 *>(d) = (unsigned short)o;
                 else if (npx == 2) d[0] = (unsigned char)o;
             }
         }
     } else {
         constexpr int LANES = DOWN / 4, SH = DOWN == 4 ? 4 : DOWN == 8 ? 6 : DOWN == 16 ? 8 : 10;      // lanes per box, log2(DOWN^2)
-        unsigned b[12];                                            // the 12 column sums over the wave's rows, each at most 8 * 255: two to a dword
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            unsigned ev = 0, od = 0;
-#pragma unroll
-            for (int r = 0; r < RW; ++r) { ev += w[r][k] & 0x00FF00FFu; od += (w[r][k] >> 8) & 0x00FF00FFu; }
-            b[4 * k] = ev & 0xFFFFu; b[4 * k + 1] = od & 0xFFFFu; b[4 * k + 2] = ev >> 16; b[4 * k + 3] = od >> 16;
-        }
+        unsigned b[12];                                            // the 12 column sums over the wave's rows, each at most 8 * 255
+        column_sums<RW>(w, b);
         int s[3];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) s[c] = sg_lanes_allreduce_sum<LANES>((int)(b[c] + b[c + 3] + b[c + 6] + b[c + 9]));
+        for (int c = 0; c < 3; ++c) s[c] = lanes_allreduce_sum<LANES>((int)(b[c] + b[c + 3] + b[c + 6] + b[c + 9]));
         if constexpr (DOWN == 4) {
             if (rows > 0 && npx == 4)
                 plane[(y0 >> 2) * ppitch + (x >> 2)] = (unsigned char)sat_byte((s[0] + 8) >> 4, (s[1] + 8) >> 4, (s[2] + 8) >> 4, vmin);
@@ -214,7 +195,7 @@ __global__ __launch_bounds__(256) void plane_median_kernel(const unsigned char *
             const unsigned char *row = src + y * spitch;
             const int xs = x0 - 4 + 4 * c;
             if (xs >= 0 && xs + 4 <= Wp) {
-                v = *reinterpret_cast<const sg_u32_a1 *>(row + xs);
+                v = *reinterpret_cast<const u32_a1 *>(row + xs);
             } else {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) v |= (unsigned)row[min(max(xs + k, 0), Wp - 1)] << (8 * k);
@@ -264,17 +245,13 @@ __global__ __launch_bounds__(256) void plane_median_kernel(const unsigned char *
     }
 }
 
-// tissue_cells_kernel's work split on a one-byte plane: a lane takes 4 plane bytes of a row as one dword, a wave 256 bytes, a workgroup of 4 waves one
-// 256-column chunk of RB = max(CELL, 16) rows; a cell is CELL / 4 adjacent lanes, summed by DPP moves, and the waves of a band meet in 1 KB of LDS. The
-// bytes > thresh of a dword are its bytes >= thresh + 1 (t1, in 1 .. 255; the launcher passes on = 0 for thresh = 255, where nothing counts): one
-// byte-parallel compare and a popcount. Every element of counts is written by exactly one lane: nothing is zeroed, nothing is atomic. No byte outside
-// y pitch + [0, Wp), y < Hp, is read: the lane the row ends in takes its 1 to 3 bytes one by one; absent bytes are 0, below every t1.
+// tissue_cells_kernel on a one-byte plane (region_u8.h's work split with a dword a lane, and its cell-count tail). The bytes > thresh of a dword are its
+// bytes >= thresh + 1 (t1, in 1 .. 255; the launcher passes on = 0 for thresh = 255, where nothing counts): one byte-parallel compare and a popcount. No
+// byte outside y pitch + [0, Wp), y < Hp, is read: the lane the row ends in takes its 1 to 3 bytes one by one; absent bytes are 0, below every t1.
 template <int CELL>
 __global__ __launch_bounds__(256) void plane_cells_kernel(const unsigned char *__restrict__ plane, int64_t pitch, int Hp, int Wp, unsigned t1, int on,
                                                           int *__restrict__ counts, int Gy, int Gx, unsigned nchunks) {
-    constexpr int RB = CELL > 16 ? CELL : 16, RW = RB / 4;
-    constexpr int NB = RB / CELL, WPB = 4 / NB;
-    constexpr int LANES = CELL / 4, CPR = 64 / LANES;
+    constexpr int RB = CellStrip<CELL>::RB, RW = CellStrip<CELL>::RW;
     __shared__ int part[4][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned chunk = blockIdx.x % nchunks, rb = blockIdx.x / nchunks;
@@ -285,7 +262,7 @@ __global__ __launch_bounds__(256) void plane_cells_kernel(const unsigned char *_
     int cnt = 0;
     if (chunk * 256u + 256u <= (unsigned)Wp && y0 + RW <= Hp) {    // wave-uniform: all 256 bytes of all RW rows exist
 #pragma unroll
-        for (int r = 0; r < RW; ++r) cnt += __builtin_popcount(bytes_ge(*reinterpret_cast<const sg_u32_a1 *>(base + r * pitch), t, t7) & 0x80808080u);
+        for (int r = 0; r < RW; ++r) cnt += __builtin_popcount(bytes_ge(*reinterpret_cast<const u32_a1 *>(base + r * pitch), t, t7) & 0x80808080u);
     } else {
         const int rows = (int)min((int64_t)RW, (int64_t)Hp - y0);  // <= 0 below the plane
         const int nb = off < (unsigned)Wp ? min(4, Wp - (int)off) : 0;
@@ -293,7 +270,7 @@ __global__ __launch_bounds__(256) void plane_cells_kernel(const unsigned char *_
             const unsigned char *p = base + r * pitch;
             unsigned v = 0;
             if (nb == 4) {
-                v = *reinterpret_cast<const sg_u32_a1 *>(p);
+                v = *reinterpret_cast<const u32_a1 *>(p);
             } else {
 #pragma unroll
                 for (int k = 0; k < 3; ++k)
@@ -302,23 +279,10 @@ __global__ __launch_bounds__(256) void plane_cells_kernel(const unsigned char *_
             cnt += __builtin_popcount(bytes_ge(v, t, t7) & 0x80808080u);
         }
     }
-    cnt = sg_lanes_allreduce_sum<LANES>(on ? cnt : 0);
-    part[wave][lane] = cnt;
-    __syncthreads();
-    if (tid < NB * CPR) {
-        const int band = tid / CPR, c = tid - band * CPR;
-        int s = 0;
-#pragma unroll
-        for (int k = 0; k < WPB; ++k) s += part[band * WPB + k][c * LANES];
-        const int64_t gy = (int64_t)rb * NB + band;
-        const unsigned gx = chunk * CPR + c;
-        if (gy < Gy && gx < (unsigned)Gx) counts[gy * Gx + gx] = s;
-    }
+    store_cell_counts<CELL>(on ? cnt : 0, part, rb, chunk, counts, Gy, Gx);
 }
 
-static bool seg_cell_ok(int cell) { return cell == 4 || cell == 8 || cell == 16 || cell == 32 || cell == 64; }
 static bool seg_down_ok(int d) { return d == 1 || d == 2 || d == 4 || d == 8 || d == 16 || d == 32; }
-static bool seg_aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 }  // namespace toad
 
@@ -328,19 +292,15 @@ extern "C" int toad_region_saturation_u8(const unsigned char *region, int64_t pi
                                          int64_t plane_pitch, void *stream) {
     const char *what = "toad_region_saturation_u8";
     if (!region || !plane) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
-    if (val_min < 0 || val_min > 255) { set_error("%s: val_min = %d must lie in [0, 255] (the 8-bit scale)", what, val_min); return TOAD_EINVAL; }
+    if (int rc = check_u8(what, "val_min", val_min)) return rc;
     if (!seg_down_ok(down)) { set_error("%s: down = %d is not one of 1, 2, 4, 8, 16, 32", what, down); return TOAD_ESHAPE; }
-    if (Hr <= 0 || Wr <= 0) { set_error("%s: bad shape (Hr = %d, Wr = %d)", what, Hr, Wr); return TOAD_ESHAPE; }
-    if (pitch < 3 * (int64_t)Wr) { set_error("%s: pitch %lld is less than a row of the region (3 Wr = %lld bytes)", what, (long long)pitch, 3ll * Wr); return TOAD_ESHAPE; }
-    if (3 * (int64_t)Wr >= (1ll << 31)) { set_error("%s: region too wide: 3 Wr must stay below 2^31 (32-bit offsets inside a row)", what); return TOAD_ESHAPE; }
+    if (int rc = check_hw(what, "Hr", Hr, "Wr", Wr)) return rc;
+    if (int rc = check_region_pitch(what, pitch, Wr)) return rc;
     const int Hp = Hr / down, Wp = Wr / down;
-    if (plane_pitch < (int64_t)Wp) {
-        set_error("%s: plane_pitch %lld is less than a row of the plane (Wp = %d bytes)", what, (long long)plane_pitch, Wp);
-        return TOAD_ESHAPE;
-    }
-    const int Hi = Hp * down, Wi = Wp * down, rb = down > 16 ? down : 16;
+    if (int rc = check_plane_pitch(what, Wp, "plane_pitch", plane_pitch)) return rc;
+    const int Hi = Hp * down, Wi = Wp * down, rb = strip_rows(down);
     const int64_t nchunks = ((int64_t)Wi + 255) / 256, blocks = nchunks * (((int64_t)Hi + rb - 1) / rb);
-    if (blocks >= (1ll << 31)) { set_error("%s: region too large: %lld workgroups", what, (long long)blocks); return TOAD_ESHAPE; }
+    if (int rc = check_blocks(what, "region", blocks)) return rc;
     if (Hp == 0 || Wp == 0) return TOAD_OK;
     hipStream_t st = (hipStream_t)stream;
 #define TOAD_SAT_LAUNCH(D) \
@@ -362,17 +322,12 @@ extern "C" int toad_plane_median_u8(const unsigned char *src, int64_t src_pitch,
     const char *what = "toad_plane_median_u8";
     if (!src || !dst) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
     if (k != 1 && k != 3 && k != 5 && k != 7) { set_error("%s: k = %d is not one of 1, 3, 5, 7", what, k); return TOAD_ESHAPE; }
-    if (Hp <= 0 || Wp <= 0) { set_error("%s: bad shape (Hp = %d, Wp = %d)", what, Hp, Wp); return TOAD_ESHAPE; }
-    if (src_pitch < (int64_t)Wp || dst_pitch < (int64_t)Wp) {
-        set_error("%s: src_pitch %lld or dst_pitch %lld is less than a row of the plane (Wp = %d bytes)", what, (long long)src_pitch, (long long)dst_pitch, Wp);
-        return TOAD_ESHAPE;
-    }
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), s1 = s0 + (uintptr_t)(Hp - 1) * (uintptr_t)src_pitch + (uintptr_t)Wp;
-    const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), d1 = d0 + (uintptr_t)(Hp - 1) * (uintptr_t)dst_pitch + (uintptr_t)Wp;
-    if (s0 < d1 && d0 < s1) { set_error("%s: src and dst overlap (a window reads what a neighbour has written)", what); return TOAD_EINVAL; }
+    if (int rc = check_hw(what, "Hp", Hp, "Wp", Wp)) return rc;
+    if (int rc = check_plane_pitches(what, Wp, src_pitch, dst_pitch)) return rc;
+    if (int rc = check_no_overlap(what, src, src_pitch, dst, dst_pitch, Hp, Wp)) return rc;
     const int64_t ntx = ((int64_t)Wp + 63) / 64, blocks = ntx * (((int64_t)Hp + 3) / 4);
-    if (blocks >= (1ll << 31)) { set_error("%s: plane too large: %lld workgroups", what, (long long)blocks); return TOAD_ESHAPE; }
-    if (hist && !seg_aligned4(hist)) { set_error("%s: hist (int32 [256]) must be 4-byte aligned (the planes may have any alignment)", what); return TOAD_EALIGN; }
+    if (int rc = check_blocks(what, "plane", blocks)) return rc;
+    if (hist && !aligned4(hist)) { set_error("%s: hist (int32 [256]) must be 4-byte aligned (the planes may have any alignment)", what); return TOAD_EALIGN; }
     hipStream_t st = (hipStream_t)stream;
     if (hist && hipMemsetAsync(hist, 0, 256 * sizeof(int), st) != hipSuccess) {
         (void)hipGetLastError();
@@ -394,14 +349,14 @@ extern "C" int toad_plane_median_u8(const unsigned char *src, int64_t src_pitch,
 extern "C" int toad_plane_cells_u8(const unsigned char *plane, int64_t pitch, int Hp, int Wp, int cell, int thresh, int *counts, void *stream) {
     const char *what = "toad_plane_cells_u8";
     if (!plane || !counts) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
-    if (thresh < 0 || thresh > 255) { set_error("%s: thresh = %d must lie in [0, 255] (the 8-bit scale)", what, thresh); return TOAD_EINVAL; }
-    if (!seg_cell_ok(cell)) { set_error("%s: cell = %d is not one of 4, 8, 16, 32, 64", what, cell); return TOAD_ESHAPE; }
-    if (Hp <= 0 || Wp <= 0) { set_error("%s: bad shape (Hp = %d, Wp = %d)", what, Hp, Wp); return TOAD_ESHAPE; }
-    if (pitch < (int64_t)Wp) { set_error("%s: pitch %lld is less than a row of the plane (Wp = %d bytes)", what, (long long)pitch, Wp); return TOAD_ESHAPE; }
-    const int rb = cell > 16 ? cell : 16;
+    if (int rc = check_u8(what, "thresh", thresh)) return rc;
+    if (int rc = check_cell(what, cell)) return rc;
+    if (int rc = check_hw(what, "Hp", Hp, "Wp", Wp)) return rc;
+    if (int rc = check_plane_pitch(what, Wp, "pitch", pitch)) return rc;
+    const int rb = strip_rows(cell);
     const int64_t nchunks = ((int64_t)Wp + 255) / 256, blocks = nchunks * (((int64_t)Hp + rb - 1) / rb);
-    if (blocks >= (1ll << 31)) { set_error("%s: plane too large: %lld workgroups", what, (long long)blocks); return TOAD_ESHAPE; }
-    if (!seg_aligned4(counts)) { set_error("%s: counts (int32 [Gy][Gx]) must be 4-byte aligned (the plane may have any alignment)", what); return TOAD_EALIGN; }
+    if (int rc = check_blocks(what, "plane", blocks)) return rc;
+    if (!aligned4(counts)) { set_error("%s: counts (int32 [Gy][Gx]) must be 4-byte aligned (the plane may have any alignment)", what); return TOAD_EALIGN; }
     const int Gy = (int)(((int64_t)Hp + cell - 1) / cell), Gx = (int)(((int64_t)Wp + cell - 1) / cell);
     const unsigned t1 = thresh < 255 ? (unsigned)thresh + 1u : 255u;
     const int on = thresh < 255;

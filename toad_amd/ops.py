@@ -1236,6 +1236,11 @@ def region_layout_ok(region: torch.Tensor) -> bool:
         and (region.stride(0) >= 3 * region.shape[1] or region.shape[0] == 1)
 
 
+# the row pitch in bytes of a uint8 view whose rows hold row_bytes bytes; the stride of a single row says nothing, so it counts as at least one row
+def _row_pitch(t: torch.Tensor, row_bytes: int) -> int:
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), row_bytes)
+
+
 def _region_pitch(region: torch.Tensor, name: str):
     """The device / dtype / layout checks every region call makes -> (pitch in bytes, Hr, Wr)."""
     if not isinstance(region, torch.Tensor) or not region.is_cuda:
@@ -1246,7 +1251,7 @@ def _region_pitch(region: torch.Tensor, name: str):
         raise ValueError(f"{name}: expected a uint8 [Hr,Wr,3] region (RGB, channels last) with stride(2) == 1, stride(1) == 3 and a row pitch >= 3 Wr, got "
                          f"shape {tuple(region.shape)} strides {tuple(region.stride())}")
     hr, wr = region.shape[0], region.shape[1]
-    return (region.stride(0) if hr > 1 else max(region.stride(0), 3 * wr)), hr, wr
+    return _row_pitch(region, 3 * wr), hr, wr
 
 
 def _region_args(region: torch.Tensor, origins, tile, name: str):
@@ -1289,6 +1294,16 @@ def stem_pool_region_u8(region: torch.Tensor, origins, wf: torch.Tensor, b, tile
 TISSUE_CELLS = (64, 32, 16, 8, 4)      # the cell sizes of csrc/tissue.hip
 
 
+def _cell_arg(name: str, cell):
+    if cell not in TISSUE_CELLS:
+        raise ValueError(f"{name}: cell must be one of {TISSUE_CELLS}, got {cell!r}")
+
+
+def _u8_arg(name: str, arg: str, v):
+    if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= 255:
+        raise ValueError(f"{name}: {arg} must be an int in [0, 255] (the 8-bit scale), got {v!r}")
+
+
 def region_tissue_cells(region: torch.Tensor, cell: int, sat_thresh: int, val_min: int) -> torch.Tensor:
     """Tissue pixels per cell x cell cell of one decoded uint8 region [Hr,Wr,3] (any row pitch, any alignment; read in place): int32 [Gy,Gx] on the device,
     Gy = ceil(Hr / cell), Gx = ceil(Wr / cell), cells anchored at the region's (0, 0), partial edge cells counting the pixels that exist. A pixel is tissue
@@ -1296,11 +1311,9 @@ def region_tissue_cells(region: torch.Tensor, cell: int, sat_thresh: int, val_mi
     integers - not OpenCV's rounded S channel. cell in TISSUE_CELLS; sat_thresh, val_min ints in [0, 255]. One launch, no synchronisation."""
     name = "region_tissue_cells"
     pitch, hr, wr = _region_pitch(region, name)
-    if cell not in TISSUE_CELLS:
-        raise ValueError(f"{name}: cell must be one of {TISSUE_CELLS}, got {cell!r}")
-    for k, v in (("sat_thresh", sat_thresh), ("val_min", val_min)):
-        if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= 255:
-            raise ValueError(f"{name}: {k} must be an int in [0, 255] (the 8-bit scale), got {v!r}")
+    _cell_arg(name, cell)
+    _u8_arg(name, "sat_thresh", sat_thresh)
+    _u8_arg(name, "val_min", val_min)
     counts = torch.empty((-(-hr // cell), -(-wr // cell)), dtype=torch.int32, device=region.device)
     _lib.check(_lib.load().toad_region_tissue_cells_u8(_p(region), pitch, hr, wr, cell, sat_thresh, val_min, _p(counts), _stream()),
                "toad_region_tissue_cells_u8")
@@ -1341,7 +1354,7 @@ def _plane_pitch(plane: torch.Tensor, name: str):
     if hp and wp and not ((plane.stride(1) == 1 or wp == 1) and (plane.stride(0) >= wp or hp == 1)):
         raise ValueError(f"{name}: expected a uint8 [Hp,Wp] plane with stride(1) == 1 and a row pitch >= Wp, got shape {tuple(plane.shape)} strides "
                          f"{tuple(plane.stride())}")
-    return (plane.stride(0) if hp > 1 else max(plane.stride(0), wp)), hp, wp
+    return _row_pitch(plane, wp), hp, wp
 
 
 def region_saturation(region: torch.Tensor, down: int, val_min: int = 0, out=None) -> torch.Tensor:
@@ -1354,8 +1367,7 @@ def region_saturation(region: torch.Tensor, down: int, val_min: int = 0, out=Non
     pitch, hr, wr = _region_pitch(region, name)
     if down not in SEG_DOWNS:
         raise ValueError(f"{name}: down must be one of {SEG_DOWNS}, got {down!r}")
-    if not isinstance(val_min, int) or isinstance(val_min, bool) or not 0 <= val_min <= 255:
-        raise ValueError(f"{name}: val_min must be an int in [0, 255] (the 8-bit scale), got {val_min!r}")
+    _u8_arg(name, "val_min", val_min)
     hp, wp = hr // down, wr // down
     if out is None:
         out = torch.empty((hp, wp), dtype=torch.uint8, device=region.device)
@@ -1367,8 +1379,8 @@ def region_saturation(region: torch.Tensor, down: int, val_min: int = 0, out=Non
             raise ValueError(f"{name}: out must not share storage with region (the plane is written while the region is read)")
     if hp == 0 or wp == 0:
         return out
-    out_pitch = out.stride(0) if hp > 1 else max(out.stride(0), wp)
-    _lib.check(_lib.load().toad_region_saturation_u8(_p(region), pitch, hr, wr, down, val_min, _p(out), out_pitch, _stream()), "toad_region_saturation_u8")
+    _lib.check(_lib.load().toad_region_saturation_u8(_p(region), pitch, hr, wr, down, val_min, _p(out), _row_pitch(out, wp), _stream()),
+               "toad_region_saturation_u8")
     return out
 
 
@@ -1396,10 +1408,8 @@ def plane_cells(plane: torch.Tensor, cell: int, thresh: int) -> torch.Tensor:
     an int in [0, 255]. tissue_tile_counts sums these over a lattice given in plane units. One launch, no synchronisation."""
     name = "plane_cells"
     pitch, hp, wp = _plane_pitch(plane, name)
-    if cell not in TISSUE_CELLS:
-        raise ValueError(f"{name}: cell must be one of {TISSUE_CELLS}, got {cell!r}")
-    if not isinstance(thresh, int) or isinstance(thresh, bool) or not 0 <= thresh <= 255:
-        raise ValueError(f"{name}: thresh must be an int in [0, 255] (the 8-bit scale), got {thresh!r}")
+    _cell_arg(name, cell)
+    _u8_arg(name, "thresh", thresh)
     counts = torch.empty((-(-hp // cell), -(-wp // cell)), dtype=torch.int32, device=plane.device)
     if hp == 0 or wp == 0:
         return counts
@@ -1408,11 +1418,6 @@ def plane_cells(plane: torch.Tensor, cell: int, thresh: int) -> torch.Tensor:
 
 
 SEG_CLOSES = tuple(range(9))           # the closing windows of csrc/tissue_morph.hip (0 and 1: the identity)
-
-
-def _thresh_arg(name: str, thresh):
-    if not isinstance(thresh, int) or isinstance(thresh, bool) or not 0 <= thresh <= 255:
-        raise ValueError(f"{name}: thresh must be an int in [0, 255] (the 8-bit scale), got {thresh!r}")
 
 
 def plane_close(plane: torch.Tensor, close: int, thresh: int) -> torch.Tensor:
@@ -1425,7 +1430,7 @@ def plane_close(plane: torch.Tensor, close: int, thresh: int) -> torch.Tensor:
     pitch, hp, wp = _plane_pitch(plane, name)
     if not isinstance(close, int) or isinstance(close, bool) or close not in SEG_CLOSES:
         raise ValueError(f"{name}: close must be one of {SEG_CLOSES}, got {close!r}")
-    _thresh_arg(name, thresh)
+    _u8_arg(name, "thresh", thresh)
     out = torch.empty((hp, wp), dtype=torch.uint8, device=plane.device)
     if hp == 0 or wp == 0:
         return out
@@ -1442,7 +1447,7 @@ def plane_components(plane: torch.Tensor, thresh: int, background: int = 0, work
     one 64 x 16 tile), no synchronisation; an empty plane launches nothing."""
     name = "plane_components"
     pitch, hp, wp = _plane_pitch(plane, name)
-    _thresh_arg(name, thresh)
+    _u8_arg(name, "thresh", thresh)
     if not isinstance(background, int) or isinstance(background, bool) or background not in (0, 1):
         raise ValueError(f"{name}: background must be 0 or 1, got {background!r}")
     if hp * wp >= 1 << 30:
@@ -1500,8 +1505,7 @@ def heat_cells(tile_q: torch.Tensor, cell: int, origin, tile, stride, n, region_
         raise ValueError(f"heat_cells: expected a non-empty int32 [ny,nx] = [{ny},{nx}] tile table, got {tuple(tile_q.shape)}")
     if hr < 1 or wr < 1:
         raise ValueError(f"heat_cells: bad region shape (Hr, Wr) = {region_hw!r}")
-    if cell not in TISSUE_CELLS:
-        raise ValueError(f"heat_cells: cell must be one of {TISSUE_CELLS}, got {cell!r}")
+    _cell_arg("heat_cells", cell)
     cells = torch.empty((-(-hr // cell), -(-wr // cell)), dtype=torch.int32, device=tile_q.device)
     _lib.check(_lib.load().toad_heat_cells(_p(tile_q), nx, ny, cell, x0, y0, h, w, sx, sy, cells.shape[0], cells.shape[1], _p(cells), _stream()),
                "toad_heat_cells")
@@ -1516,8 +1520,7 @@ def region_heat_blend(region: torch.Tensor, cells: torch.Tensor, cell: int, lut:
     (pitch, 3, 1), a window of a larger canvas; it must not share storage with region. One launch, no synchronisation; an empty canvas launches nothing."""
     name = "region_heat_blend"
     pitch, hr, wr = _region_pitch(region, name)
-    if cell not in TISSUE_CELLS:
-        raise ValueError(f"{name}: cell must be one of {TISSUE_CELLS}, got {cell!r}")
+    _cell_arg(name, cell)
     if down not in HEAT_DOWNS:
         raise ValueError(f"{name}: down must be one of {HEAT_DOWNS}, got {down!r}")
     if not isinstance(alpha, int) or isinstance(alpha, bool) or not 0 <= alpha <= 256:
@@ -1539,9 +1542,8 @@ def region_heat_blend(region: torch.Tensor, cells: torch.Tensor, cell: int, lut:
             raise ValueError(f"{name}: out must not share storage with region (the canvas is written while the region is read)")
     if ho == 0 or wo == 0:
         return out
-    out_pitch = out.stride(0) if ho > 1 else max(out.stride(0), 3 * wo)
     _lib.check(_lib.load().toad_region_heat_blend_u8(_p(region), pitch, hr, wr, _p(cells), cells.shape[0], cells.shape[1], cell, _p(lut), alpha, down,
-                                                     _p(out), out_pitch, _stream()), "toad_region_heat_blend_u8")
+                                                     _p(out), _row_pitch(out, 3 * wo), _stream()), "toad_region_heat_blend_u8")
     return out
 
 

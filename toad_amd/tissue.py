@@ -105,6 +105,21 @@ def tissue_tile_fraction(region: torch.Tensor, tile=256, stride=None, origin=(0,
     return ops.tissue_tile_counts(cells, cell, (x0, y0), (h, w), (sy, sx), (nx, ny)), nx, ny
 
 
+def _min_fraction_arg(min_fraction):
+    if not isinstance(min_fraction, (int, float)) or isinstance(min_fraction, bool) or not 0.0 <= min_fraction <= 1.0:
+        raise ValueError(f"min_fraction must lie in [0, 1], got {min_fraction!r}")
+
+
+def _kept(counts, need: int, x0: int, y0: int, sx: int, sy: int):
+    """(origins, counts) of the lattice tiles whose count is >= need, from the device table int32 [ny,nx] (None: an empty lattice, nothing is copied).
+    Origins int64 [B,2] of (x, y), row-major over the lattice - j (y) outer, i (x) inner; counts int64 [B]. The call's one copy and synchronisation."""
+    if counts is None:
+        return np.zeros((0, 2), dtype=np.int64), np.zeros((0,), dtype=np.int64)
+    c = counts.cpu().numpy().astype(np.int64)
+    j, i = np.nonzero(c >= need)
+    return np.stack([x0 + i * sx, y0 + j * sy], axis=1).astype(np.int64), c[j, i]
+
+
 def tissue_origins(region: torch.Tensor, tile=256, stride=None, min_fraction: float = 0.25, sat_thresh: int = 8, val_min: int = 0, origin=(0, 0),
                    return_counts: bool = False):
     """The origins of the lattice tiles that hold tissue: np.ndarray int64 [B,2] of (x, y) ON THE HOST (``ops.check_origins`` wants them there), in
@@ -117,17 +132,11 @@ def tissue_origins(region: torch.Tensor, tile=256, stride=None, min_fraction: fl
     The defaults are API defaults in CLAM's units (its ``sthresh = 8``; min_fraction and val_min have no CLAM counterpart), not tuned values: CLAM
     thresholds a median-blurred, OpenCV-rounded saturation channel of a downsampled level, this is the exact per-pixel predicate at the region's level.
     ``segmented_tissue_origins`` is the selector that follows CLAM's recipe (box filter, median, fixed or Otsu threshold)."""
-    if not isinstance(min_fraction, (int, float)) or isinstance(min_fraction, bool) or not 0.0 <= min_fraction <= 1.0:
-        raise ValueError(f"min_fraction must lie in [0, 1], got {min_fraction!r}")
+    _min_fraction_arg(min_fraction)
     counts, nx, ny = tissue_tile_fraction(region, tile, stride, origin, sat_thresh, val_min)
     h, w, sy, sx, x0, y0 = _lattice_args(tile, stride, origin)
-    if nx == 0 or ny == 0:
-        empty = np.zeros((0, 2), dtype=np.int64)
-        return (empty, np.zeros((0,), dtype=np.int64)) if return_counts else empty
-    c = counts.cpu().numpy().astype(np.int64)                       # the one copy, the one synchronisation
-    j, i = np.nonzero(c >= math.ceil(min_fraction * h * w))         # row-major: j (y) outer, i (x) inner
-    origins = np.stack([x0 + i * sx, y0 + j * sy], axis=1).astype(np.int64)
-    return (origins, c[j, i]) if return_counts else origins
+    origins, kept = _kept(counts if nx and ny else None, math.ceil(min_fraction * h * w), x0, y0, sx, sy)
+    return (origins, kept) if return_counts else origins
 
 
 def otsu_threshold(hist) -> int:
@@ -241,8 +250,7 @@ def segmented_tissue_origins(region: torch.Tensor, tile=256, stride=None, min_fr
 
     The defaults are CLAM's: ``sthresh = 8``, ``mthresh = 7``, a low-resolution level (``down = 16``); ``use_otsu`` is ``sat_thresh="otsu"``.
     CLAM's ``max_n_holes`` and its polygon areas are not done."""
-    if not isinstance(min_fraction, (int, float)) or isinstance(min_fraction, bool) or not 0.0 <= min_fraction <= 1.0:
-        raise ValueError(f"min_fraction must lie in [0, 1], got {min_fraction!r}")
+    _min_fraction_arg(min_fraction)
     _seg_args(down, median, sat_thresh, val_min)
     active = _morph_args(close, min_area, min_hole)
     _, hr, wr = ops._region_pitch(region, "segmented_tissue_origins")
@@ -250,16 +258,12 @@ def segmented_tissue_origins(region: torch.Tensor, tile=256, stride=None, min_fr
     ph, pw, psy, psx, px0, py0 = _seg_lattice((h, w), (sy, sx), (x0, y0), down)
     nx, ny = lattice(hr, wr, (h, w), (sy, sx), (x0, y0))
 
-    def result(origins, counts, t):
-        out = (origins,) + ((counts,) if return_counts else ()) + ((t,) if return_threshold else ())
-        return out if len(out) > 1 else origins
-
-    if nx == 0 or ny == 0:
-        return result(np.zeros((0, 2), dtype=np.int64), np.zeros((0,), dtype=np.int64), 0 if sat_thresh == "otsu" else sat_thresh)
-    plane, t = segment_tissue(region, down, median, sat_thresh, val_min)
-    cell = lattice_cell((ph, pw), (psy, psx), (px0, py0))
-    cells = ops.plane_cells(_morph(plane, t, close, min_area, min_hole), cell, 0) if active else ops.plane_cells(plane, cell, t)
-    c = ops.tissue_tile_counts(cells, cell, (px0, py0), (ph, pw), (psy, psx), (nx, ny)).cpu().numpy().astype(np.int64)      # the one copy
-    j, i = np.nonzero(c >= math.ceil(min_fraction * ph * pw))       # row-major: j (y) outer, i (x) inner
-    origins = np.stack([x0 + i * sx, y0 + j * sy], axis=1).astype(np.int64)
-    return result(origins, c[j, i], t)
+    counts, t = None, 0 if sat_thresh == "otsu" else sat_thresh
+    if nx and ny:
+        plane, t = segment_tissue(region, down, median, sat_thresh, val_min)
+        cell = lattice_cell((ph, pw), (psy, psx), (px0, py0))
+        cells = ops.plane_cells(_morph(plane, t, close, min_area, min_hole), cell, 0) if active else ops.plane_cells(plane, cell, t)
+        counts = ops.tissue_tile_counts(cells, cell, (px0, py0), (ph, pw), (psy, psx), (nx, ny))
+    origins, kept = _kept(counts, math.ceil(min_fraction * ph * pw), x0, y0, sx, sy)
+    out = (origins,) + ((kept,) if return_counts else ()) + ((t,) if return_threshold else ())
+    return out if len(out) > 1 else origins

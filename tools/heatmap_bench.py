@@ -23,6 +23,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch                                   # noqa: E402
 
+import tools.ab.select_lib                     # noqa: E402,F401  (TOAD_HIP_LIB=<variant.so> is honoured HERE, not by the product's loader)
+
 from extract_u8_bench import alternate, median      # noqa: E402
 from tissue_bench import HR, WR, TILE, Rotating, make_slide      # noqa: E402
 from toad_amd import ops                            # noqa: E402
