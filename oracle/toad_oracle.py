@@ -9,7 +9,9 @@ Parity status: PINNED.  ``oracle/pin_against_reference.py`` imports the unmodifi
 reference model in the build container, checks this restatement against it
 (forward dict, all 14 parameter gradients, ``attention_only``/``return_features``
 for N in {0,1,2,63,64,65,256,777,1024 (x30, saturated softmax),300 (all rows equal),10000,100000}, C in {2,18}) and writes the golden vectors committed under
-``tests/golden/``.  The reference has no tests or golden vectors of its own
+``tests/golden/``.  Its second case table pins the ``masks=`` branches (train-mode Dropout(0.25), with the
+reference's own draws captured by forward hooks), dropout=True in eval mode and size_arg="small" the same way
+(``tests/golden/toad_dropout_golden.npz``).  The reference has no tests or golden vectors of its own
 (SURVEY.md §4), so the imported reference is the pin.
 
 Every function cites the reference lines it restates (paths relative to
@@ -38,6 +40,27 @@ PARAM_KEYS = (
     "classifier.weight", "classifier.bias",
     "site_classifier.weight", "site_classifier.bias",
 )
+
+
+# With dropout=True the reference's nn.Sequential gains a Dropout after each ReLU (models/model_toad.py:60-64), so the second Linear and the
+# attention block move from positions 2, 4 to 3, 6: its state dict then says attention_net.{0,3,6.*}.
+DROPOUT_KEY_PREFIX = {"attention_net.2.": "attention_net.3.", "attention_net.4.": "attention_net.6."}
+
+
+def dropout_key(key: str) -> str:
+    """The dropout=True state-dict name of a dropout=False key."""
+    for a, b in DROPOUT_KEY_PREFIX.items():
+        if key.startswith(a):
+            return b + key[len(a):]
+    return key
+
+
+def plain_key(key: str) -> str:
+    """The dropout=False state-dict name (PARAM_KEYS) of a dropout=True key."""
+    for a, b in DROPOUT_KEY_PREFIX.items():
+        if key.startswith(b):
+            return a + key[len(b):]
+    return key
 
 
 def param_shapes(n_classes: int, size_arg: str = "big") -> Dict[str, Tuple[int, ...]]:

@@ -9,14 +9,29 @@ SLOT2KEY = dict(zip(
     orc.PARAM_KEYS))
 
 
+MASK_WIDTHS = {"big": (("h1", 512), ("h", 512), ("a", 384), ("b", 384)), "small": (("h1", 512), ("h", 512), ("a", 256), ("b", 256))}
+
+
 def case_inputs(golden, name):
-    n, c, sex, label, site, scale, equal = golden[name + "/meta"]
+    """Inputs of a golden case, rebuilt from its meta row. toad_golden.npz has seven fields (every case is size_arg="big", dropout=False,
+    train mode); toad_dropout_golden.npz appends three flags - size_arg == "small", dropout, train mode - and, for the train-mode dropout
+    cases, carries the reference's captured masks as packed bits of "kept" (oracle/pin_against_reference.py DROPOUT_CASES)."""
+    meta = golden[name + "/meta"]
+    n, c, sex, label, site, scale, equal = meta[:7]
+    small, dropout, train = (bool(v) for v in meta[7:10]) if len(meta) > 7 else (False, False, True)
+    size_arg = "small" if small else "big"
     n, c = int(n), int(c)
     kind = {0: "wave", 1: "equal", 2: "randn"}[int(round(float(equal)))]        # meta[6]: bag family (oracle/pin_against_reference.py KIND_CODE)
     x = orc.random_bag(n, 1000 + n) if kind == "randn" else orc.closed_form_bag(n, 1024, float(scale), kind)
-    params = orc.random_params(c, 2000 + n) if kind == "randn" else orc.closed_form_params(c)
+    params = orc.random_params(c, 2000 + n, size_arg) if kind == "randn" else orc.closed_form_params(c, size_arg)
+    masks = None
+    if name + "/mask_kept/h1" in golden.files:
+        keep_scale = float(np.float32(1.0) / np.float32(0.75))                  # nn.Dropout(0.25)'s multiplier of a kept element, in fp32
+        masks = {k: torch.from_numpy(np.unpackbits(golden[f"{name}/mask_kept/{k}"], count=n * w).reshape(n, w).astype(np.float32)) * keep_scale
+                 for k, w in MASK_WIDTHS[size_arg]}
     return dict(n=n, c=c, params=params, x=x, sex=torch.tensor([float(sex)]),
-                label=torch.tensor([int(label)]), site=torch.tensor([int(site)]))
+                label=torch.tensor([int(label)]), site=torch.tensor([int(site)]),
+                size_arg=size_arg, dropout=dropout, train=train, masks=masks)
 
 
 def strided_sample(t, k=64):
@@ -49,9 +64,11 @@ def oracle_fp32_noise(golden, name):
     itself, measured here on the CPU restatement, not the size of the (vanishing) result."""
     if name not in _ORACLE_DEV:
         ci = case_inputs(golden, name)
-        _, _, g32 = orc.fwd_bwd(ci["params"], ci["x"], ci["sex"], ci["label"], ci["site"])
+        mk = ci["masks"]                            # the reference's captured dropout multipliers (train-mode dropout cases), else None
+        _, _, g32 = orc.fwd_bwd(ci["params"], ci["x"], ci["sex"], ci["label"], ci["site"], masks=mk)
         p64 = {k: v.double() for k, v in ci["params"].items()}
-        _, _, g64 = orc.fwd_bwd(p64, ci["x"].double(), ci["sex"].double(), ci["label"], ci["site"])
+        _, _, g64 = orc.fwd_bwd(p64, ci["x"].double(), ci["sex"].double(), ci["label"], ci["site"],
+                                masks=None if mk is None else {k: v.double() for k, v in mk.items()})
         _ORACLE_DEV[name] = {k: float((g32[k].double() - g64[k]).abs().max()) for k in orc.PARAM_KEYS}
     return _ORACLE_DEV[name]
 
