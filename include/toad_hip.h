@@ -427,6 +427,32 @@ int toad_heat_cells(const int *tile_q, int nx, int ny, int cell, int x0, int y0,
 int toad_region_heat_blend_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx, int cell,
                               const unsigned char *lut, int alpha, int down, unsigned char *out, int64_t out_pitch, void *stream);
 
+/* The same canvas with the colour index and the alpha decided per canvas pixel (additive to ABI 15 too; toad_region_heat_blend_u8 does not change). Integers
+ * only. Inputs as above plus `smooth` in {0, 1} and an optional mask plane. For canvas pixel (ox, oy): m per channel as above; gy_own = (down * oy) / cell,
+ * gx_own = (down * ox) / cell, own = cells[gy_own][gx_own] (values above 255 read as 255, as above).
+ *   colour index  smooth = 0: idx_px = own. smooth = 1: the bilinear tent between cell centres, in doubled coordinates. Along x:
+ *                     p = 2 * down * ox + down - cell,  g0 = floor(p / (2 * cell)) (may be -1),  f = p - 2 * cell * g0 in [0, 2 * cell),
+ *                     weights w0 = 2 * cell - f for cell g0 and w1 = f for cell g0 + 1;
+ *                 the same along y. Each of the four neighbours (gy, gx) contributes v = cells[gy][gx] if it lies inside the table and is >= 0, and
+ *                 `own` otherwise;  idx_px = (sum wy * wx * v + 2 * cell * cell) >> (2 * log2(cell) + 2). The weights sum to 4 * cell * cell, so a
+ *                 constant field is reproduced exactly; the sum is at most 255 * 4 * 64 * 64 < 2^23; there is no division. Where a canvas pixel is a whole
+ *                 cell (down == cell == 4) the tent is exactly `own`.
+ *   tissue        mask == NULL: every pixel is tissue (Hm, Wm, mask_pitch, mask_down, mask_thresh are then ignored). Otherwise mask is a uint8 [Hm][Wm]
+ *                 plane with row pitch mask_pitch >= Wm, Hm = Hr / mask_down, Wm = Wr / mask_down, mask_down in {1, 2, 4, 8, 16, 32} and a multiple of
+ *                 down (a canvas box then lies in one mask pixel), mask_thresh in 0 .. 255. With mx = (down * ox) / mask_down, my = (down * oy) /
+ *                 mask_down the pixel is tissue iff mx < Wm, my < Hm and mask[my][mx] > mask_thresh: the pixels of the partial boxes the plane dropped are
+ *                 not tissue. This is the (plane, t) pair of the segmented tissue selection below, read as it lies.
+ *   output byte   (alpha * lut[idx_px][c] + (256 - alpha) * m + 128) >> 8 where own >= 0 and the pixel is tissue, m elsewhere. Coverage edges and mask
+ *                 edges stay sharp; only the colour inside them is interpolated.
+ * This is not CLAM's Gaussian `blur` and does not claim to be: the smoothing width is one cell. Seams between separately rendered regions (a neighbour
+ * outside the table counts as `own`), wider kernels and cell-level pre-smoothing passes are not done.
+ * Refusals as for toad_region_heat_blend_u8, and: smooth not 0 or 1, mask_thresh outside 0 .. 255 (TOAD_EINVAL); a mask_down not in the list or not a
+ * multiple of down, Hm or Wm not the floor quotients, mask_pitch < Wm (TOAD_ESHAPE). No byte outside mask + y * mask_pitch + [0, Wm), 0 <= y < Hm, is read;
+ * the mask may have any base address. Ho == 0 or Wo == 0: returns TOAD_OK and launches nothing. One streaming pass. */
+int toad_region_heat_blend_px_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx, int cell,
+                                 const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm,
+                                 int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream);
+
 /* ---- Segmented tissue selection: CLAM's recipe - a median-filtered saturation channel of a low-resolution level, thresholded by a fixed value or by
  * Otsu's - defined in integers (additive to ABI 15 too). A second selector next to the per-pixel predicate above, which does not change; csrc/tissue_seg.hip.
  *   1 box filter  down in {1, 2, 4, 8, 16, 32} (TOAD_ESHAPE otherwise): Hp = Hr / down, Wp = Wr / down, partial boxes at the right and the bottom edge are

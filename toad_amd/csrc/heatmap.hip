@@ -8,9 +8,17 @@
 //               m = (sum of the down x down box + down^2 / 2) / down^2;  the output byte is m where the box's cell has idx = -1, elsewhere
 //               (alpha lut[idx][c] + (256 - alpha) m + 128) >> 8  with alpha in [0, 256]. down divides every cell size: a box lies in one cell.
 //
-// Two kernels:
-//   heat_cells_kernel         one thread per cell: the covering tiles' index ranges in closed form from the lattice in cell units, a loop over them.
-//   heat_blend_kernel<DOWN>   one streaming pass over the region: read uint8, write uint8.
+//   per pixel   (toad_region_heat_blend_px_u8) the same canvas with the colour index and the alpha decided per canvas pixel: with smooth = 1 the index is
+//               the bilinear tent between cell centres, in doubled coordinates so that it stays in integers - along x  p = 2 down ox + down - cell,
+//               g0 = floor(p / (2 cell)), f = p - 2 cell g0, weights 2 cell - f for cell g0 and f for g0 + 1, the same along y; a neighbour outside the
+//               table or without a value counts as the pixel's own cell;  idx_px = (sum wy wx v + 2 cell^2) >> (2 log2(cell) + 2). With a mask plane
+//               [Hm][Wm] of mask_down x mask_down boxes a pixel is blended only where mask[(down oy) / mask_down][(down ox) / mask_down] > mask_thresh;
+//               the pixels of the partial boxes the plane dropped are not. Coverage and mask edges stay sharp: only the colour inside is interpolated.
+//
+// Three kernels:
+//   heat_cells_kernel                       one thread per cell: the covering tiles' index ranges in closed form from the lattice in cell units, a loop over them.
+//   heat_blend_kernel<DOWN>                 one streaming pass over the region: read uint8, write uint8.
+//   heat_blend_px_kernel<DOWN,SMOOTH,MASK>  the same pass with the index, the colour lookup and the alpha per canvas pixel.
 #include "region_u8.h"
 
 namespace toad {
@@ -139,6 +147,219 @@ __global__ __launch_bounds__(256) void heat_blend_kernel(const unsigned char *__
     }
 }
 
+// ---- the per-pixel pass: toad_region_heat_blend_px_u8 ----
+struct HeatPxArgs {
+    const unsigned char *region; int64_t pitch; int Hi, Wi;
+    const int *cells; int Gy, Gx, shift;
+    int alpha;
+    const unsigned char *mask; int64_t mask_pitch; int Hm, Wm, mshift, mask_thresh;
+    unsigned char *out; int64_t out_pitch; unsigned nchunks;
+};
+
+// heat_px4 with a colour col[p] (0x00bbggrr, as in the LDS table) and an alpha al[p] of its own for each of the row's NP = 4 / DOWN output pixels. At
+// DOWN == 1 a pixel's r and b go through one multiply-add as 0x00bb00rr and its g through another: alpha c + 128 + (256 - alpha) m < 2^16 as before, and
+// the three output dwords are put together from the second byte of every half.
+template <int DOWN>
+__device__ __forceinline__ void heat_px4_each(const unsigned (&w)[DOWN][3], const unsigned (&col)[4 / DOWN], const unsigned (&al)[4 / DOWN], unsigned (&o)[3]) {
+    if constexpr (DOWN == 1) {
+        const unsigned w0 = w[0][0], w1 = w[0][1], w2 = w[0][2];
+        const unsigned rb[4] = {w0 & 0x00FF00FFu, (w0 >> 24) | ((w1 << 8) & 0x00FF0000u), ((w1 >> 16) & 0xFFu) | ((w2 & 0xFFu) << 16), (w2 >> 8) & 0x00FF00FFu};
+        const unsigned g[4] = {(w0 >> 8) & 0xFFu, w1 & 0xFFu, w1 >> 24, (w2 >> 16) & 0xFFu};
+        unsigned RB[4], G[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const unsigned beta = 256u - al[p];
+            RB[p] = rb[p] * beta + (col[p] & 0x00FF00FFu) * al[p] + 0x00800080u;
+            G[p] = g[p] * beta + ((col[p] >> 8) & 0xFFu) * al[p] + 128u;
+        }
+        o[0] = ((RB[0] >> 8) & 0x00FF00FFu) | (G[0] & 0xFF00u) | ((RB[1] << 16) & 0xFF000000u);                              // r0 g0 b0 r1
+        o[1] = ((G[1] >> 8) & 0xFFu) | ((RB[1] >> 16) & 0xFF00u) | ((RB[2] << 8) & 0x00FF0000u) | ((G[2] << 16) & 0xFF000000u);      // g1 b1 r2 g2
+        o[2] = (RB[2] >> 24) | (RB[3] & 0xFF00FF00u) | ((G[3] << 8) & 0x00FF0000u);                                          // b2 r3 g3 b3
+    } else {
+        constexpr int SH = DOWN == 2 ? 2 : 4;                        // log2(DOWN^2)
+        unsigned b[12];
+        column_sums<DOWN>(w, b);
+        o[0] = o[1] = o[2] = 0;
+#pragma unroll
+        for (int p = 0; p < 4 / DOWN; ++p) {
+            const unsigned beta = 256u - al[p];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                unsigned s = 0;
+#pragma unroll
+                for (int d = 0; d < DOWN; ++d) s += b[3 * (p * DOWN + d) + c];
+                const unsigned m = (s + (1u << (SH - 1))) >> SH;
+                o[(3 * p + c) >> 2] |= ((al[p] * ((col[p] >> (8 * c)) & 255u) + 128u + beta * m) >> 8) << (8 * ((3 * p + c) & 3));
+            }
+        }
+    }
+}
+
+// n of the NB = 4, 2 or 1 mask bytes at p exist: those bytes as a little-endian word, 0 for the others (0 is above no threshold: not tissue). Touches
+// nothing beyond the n bytes.
+template <int NB>
+__device__ __forceinline__ unsigned load_mask(const unsigned char *p, int n) {
+    if (n == NB) {
+        if constexpr (NB == 4) return *reinterpret_cast<const u32_a1 *>(p);
+        else if constexpr (NB == 2) return *reinterpret_cast<const u16_a1 *>(p);
+        else return p[0];
+    }
+    unsigned v = 0;
+#pragma unroll
+    for (int k = 0; k < NB - 1; ++k)
+        if (k < n) v |= (unsigned)p[k] << (8 * k);
+    return v;
+}
+
+// One lane of heat_blend_px_kernel: the strip split, the addresses, the plain and the edge path and the stores are heat_blend_kernel's; what is new is
+// decided per canvas pixel of the lane's 4 x 4 region pixels (x and y0 are multiples of 4, so they lie in one cell):
+//   index   SMOOTH 0: the cell's own. SMOOTH 1 (cell >= 8): the 4 x 4 pixels also lie in one QUADRANT of the cell - 2 x .. 2 x + 8 holds no cell centre,
+//           those are multiples of 8 in doubled coordinates - so g0 is the lane's: four neighbour loads, f steps by 2 DOWN from pixel to pixel. SMOOTH 2
+//           (cell == 4): the lane's pixels are the whole width of the cell and straddle its centre: nine loads, g0 and f compile-time constants of the
+//           pixel. Either way the tent is separable: H[r][j] = 2 cell v[r][0] + fx_j (v[r][1] - v[r][0]) per neighbour row and pixel column, then
+//           S = 2 cell H[0][j] + fy_i (H[1][j] - H[0][j]). A neighbour outside the table or without a value is replaced by the own cell; where that has none
+//           either the pixel is not blended, and max(own, 0) only keeps the lookup inside the table.
+//   tissue  tis[r] = the mask bytes of region row y0 + r under the lane's 4 pixels, one byte a pixel: mask_down >= 4 is ONE byte for the whole block
+//           (mask_down is a power of two and x, y0 are multiples of 4), 2 two rows of two bytes, 1 four dwords. Outside Hm x Wm the byte is 0.
+//   alpha   al = alpha where own >= 0 and the byte is above the threshold, else 0: no branch.
+// lut_s: the workgroup's 256 packed colours. No barrier in here: the caller has filled lut_s.
+template <int DOWN, int SMOOTH, bool MASK>
+__device__ __forceinline__ void heat_px_lane(const HeatPxArgs &a, const unsigned *lut_s, unsigned chunk, unsigned rb, int wave, int lane) {
+    constexpr int RW = 4, ORW = RW / DOWN, NP = 4 / DOWN, OB = 12 / DOWN;
+    const unsigned x = chunk * 256u + (unsigned)lane * 4u, off = 3u * x, ooff = off / DOWN;
+    const int64_t y0 = (int64_t)rb * 16 + wave * RW;
+    if (y0 >= a.Hi) return;
+    const bool live = x < (unsigned)a.Wi;
+    const int gy = (int)(y0 >> a.shift), gx = (int)(x >> a.shift);
+    const int own = live ? min(a.cells[(int64_t)gy * a.Gx + gx], 255) : -1;
+
+    int idx[NP][NP];
+    if constexpr (SMOOTH == 0) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+#pragma unroll
+            for (int j = 0; j < NP; ++j) idx[i][j] = max(own, 0);
+    } else {
+        constexpr int NB = SMOOTH == 2 ? 3 : 2;                      // the neighbourhood: NB x NB cells from (by, bx)
+        const int cell = 1 << a.shift, c2 = 2 * cell;
+        int bx, by, fx0 = 0, fy0 = 0;
+        if constexpr (SMOOTH == 1) {
+            const int px = 2 * (int)x + DOWN - cell;                 // 3 Wr < 2^31, so 2 x fits
+            const int64_t py = 2 * y0 + DOWN - cell;
+            bx = px >> (a.shift + 1); fx0 = px & (c2 - 1);
+            by = (int)(py >> (a.shift + 1)); fy0 = (int)(py & (c2 - 1));
+        } else {
+            bx = gx - 1; by = gy - 1;
+        }
+        int v[NB][NB];
+#pragma unroll
+        for (int r = 0; r < NB; ++r)
+#pragma unroll
+            for (int c = 0; c < NB; ++c) {
+                const int yy = by + r, xx = bx + c;
+                const bool in = live && yy >= 0 && yy < a.Gy && xx >= 0 && xx < a.Gx;
+                const int t = in ? a.cells[(int64_t)yy * a.Gx + xx] : -1;
+                v[r][c] = t >= 0 ? min(t, 255) : max(own, 0);
+            }
+        int H[NB][NP];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            const int pj = 2 * DOWN * j + DOWN - 4;                  // SMOOTH 2: the pixel's doubled offset from the cell's centre
+            const int ca = SMOOTH == 2 && pj >= 0 ? 1 : 0, fx = SMOOTH == 2 ? (pj & 7) : fx0 + 2 * DOWN * j;
+#pragma unroll
+            for (int r = 0; r < NB; ++r) H[r][j] = c2 * v[r][ca] + fx * (v[r][ca + 1] - v[r][ca]);
+        }
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int pi = 2 * DOWN * i + DOWN - 4;
+            const int ra = SMOOTH == 2 && pi >= 0 ? 1 : 0, fy = SMOOTH == 2 ? (pi & 7) : fy0 + 2 * DOWN * i;
+#pragma unroll
+            for (int j = 0; j < NP; ++j) idx[i][j] = (c2 * H[ra][j] + fy * (H[ra + 1][j] - H[ra][j]) + 2 * cell * cell) >> (2 * a.shift + 2);
+        }
+    }
+
+    unsigned tis[RW] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    int thr = -1;                                                    // without a mask every byte is above it
+    if constexpr (MASK) {
+        thr = a.mask_thresh;
+        const unsigned mx = x >> a.mshift;
+        const int64_t my = y0 >> a.mshift;
+        const int have = live && mx < (unsigned)a.Wm ? a.Wm - (int)mx : 0;      // mask columns from mx on that exist
+        const unsigned char *mp = a.mask + my * a.mask_pitch + mx;
+        if (a.mshift >= 2) {
+            const unsigned t = load_mask<1>(mp, my < a.Hm ? min(have, 1) : 0) * 0x01010101u;
+#pragma unroll
+            for (int r = 0; r < RW; ++r) tis[r] = t;
+        } else if (DOWN <= 2 && a.mshift == 1) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const unsigned t = load_mask<2>(mp + r * a.mask_pitch, my + r < a.Hm ? min(have, 2) : 0);
+                tis[2 * r] = tis[2 * r + 1] = (t & 0xFFu) * 0x0101u | (t >> 8) * 0x01010000u;
+            }
+        } else if (DOWN == 1) {
+#pragma unroll
+            for (int r = 0; r < RW; ++r) tis[r] = load_mask<4>(mp + r * a.mask_pitch, my + r < a.Hm ? min(have, 4) : 0);
+        }
+    }
+
+    const unsigned char *src = a.region + y0 * a.pitch + off;
+    unsigned char *dst = a.out + (y0 / DOWN) * a.out_pitch + ooff;
+    // output row q of the lane from its DOWN region rows
+    auto blend_row = [&](int q, const unsigned (&w)[DOWN][3], unsigned (&o)[3]) {
+        unsigned col[NP], al[NP];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            col[j] = lut_s[idx[q][j]];
+            al[j] = own >= 0 && (int)((tis[DOWN * q] >> (8 * DOWN * j)) & 0xFFu) > thr ? (unsigned)a.alpha : 0u;
+        }
+        heat_px4_each<DOWN>(w, col, al, o);
+    };
+    if (chunk * 256u + 256u <= (unsigned)a.Wi && y0 + RW <= a.Hi) {  // wave-uniform: all 768 bytes of all 4 rows are consumed
+        unsigned w[ORW][DOWN][3];
+#pragma unroll
+        for (int r = 0; r < RW; ++r)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) w[r / DOWN][r % DOWN][k] = *reinterpret_cast<const u32_a1 *>(src + r * a.pitch + 4 * k);
+#pragma unroll
+        for (int q = 0; q < ORW; ++q) {
+            unsigned o[3];
+            blend_row(q, w[q], o);
+            heat_store4<DOWN>(dst + q * a.out_pitch, o);
+        }
+    } else {
+        const int rows = (int)min((int64_t)ORW, (a.Hi - y0) / DOWN);  // output rows of this wave that exist: Hi and y0 are multiples of DOWN
+        const int npx = live ? min(4, a.Wi - (int)x) : 0;            // pixels of this lane that are consumed: 0, DOWN, .., 4
+        const int nout = 3 * npx / DOWN;                             // bytes to write per output row
+#pragma unroll
+        for (int q = 0; q < ORW; ++q) {                              // unrolled, so that q indexes registers
+            if (q >= rows) break;
+            unsigned w[DOWN][3];
+#pragma unroll
+            for (int r = 0; r < DOWN; ++r) load_px4(src + (q * DOWN + r) * a.pitch, npx, w[r]);
+            unsigned o[3];
+            blend_row(q, w, o);
+            unsigned char *d = dst + q * a.out_pitch;
+            if (npx == 4) {
+                heat_store4<DOWN>(d, o);
+            } else {
+#pragma unroll
+                for (int k = 0; k < OB; ++k)
+                    if (k < nout) d[k] = (unsigned char)(o[k >> 2] >> (8 * (k & 3)));
+            }
+        }
+    }
+}
+
+// Bounded to 8 waves per SIMD: left alone, the two tent variants with a mask at DOWN == 1 take 65 registers and lose a wave for one register.
+template <int DOWN, int SMOOTH, bool MASK>
+__global__ __launch_bounds__(256, 8) void heat_blend_px_kernel(const HeatPxArgs a, const unsigned char *__restrict__ lut) {
+    __shared__ unsigned lut_s[256];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    lut_s[tid] = (unsigned)lut[3 * tid] | ((unsigned)lut[3 * tid + 1] << 8) | ((unsigned)lut[3 * tid + 2] << 16);
+    __syncthreads();
+    heat_px_lane<DOWN, SMOOTH, MASK>(a, lut_s, blockIdx.x % a.nchunks, blockIdx.x / a.nchunks, wave, lane);
+}
+
 }  // namespace toad
 
 using namespace toad;
@@ -197,5 +418,78 @@ extern "C" int toad_region_heat_blend_u8(const unsigned char *region, int64_t pi
         default: TOAD_HEAT_LAUNCH(4); break;
     }
 #undef TOAD_HEAT_LAUNCH
+    return check_launch(what);
+}
+
+extern "C" int toad_region_heat_blend_px_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx, int cell,
+                                            const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch,
+                                            int Hm, int Wm, int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream) {
+    const char *what = "toad_region_heat_blend_px_u8";
+    if (!region || !cells || !lut || !out) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (int rc = check_cell(what, cell)) return rc;
+    if (int rc = check_hw(what, "Hr", Hr, "Wr", Wr)) return rc;
+    if (alpha < 0 || alpha > 256) { set_error("%s: alpha = %d must lie in [0, 256] (256 = the colour alone)", what, alpha); return TOAD_ESHAPE; }
+    if (down != 1 && down != 2 && down != 4) { set_error("%s: down = %d is not one of 1, 2, 4", what, down); return TOAD_ESHAPE; }
+    if (smooth != 0 && smooth != 1) { set_error("%s: smooth = %d must be 0 or 1", what, smooth); return TOAD_EINVAL; }
+    if (int rc = check_region_pitch(what, pitch, Wr)) return rc;
+    int mshift = 0;
+    if (mask) {
+        if (mask_down != 1 && mask_down != 2 && mask_down != 4 && mask_down != 8 && mask_down != 16 && mask_down != 32) {
+            set_error("%s: mask_down = %d is not one of 1, 2, 4, 8, 16, 32", what, mask_down);
+            return TOAD_ESHAPE;
+        }
+        if (mask_down % down) {
+            set_error("%s: mask_down = %d is not a multiple of down = %d (a canvas box must lie in one mask pixel)", what, mask_down, down);
+            return TOAD_ESHAPE;
+        }
+        if (Hm != Hr / mask_down || Wm != Wr / mask_down) {
+            set_error("%s: Hm x Wm = %d x %d is not (Hr / mask_down) x (Wr / mask_down) = %d x %d", what, Hm, Wm, Hr / mask_down, Wr / mask_down);
+            return TOAD_ESHAPE;
+        }
+        if (int rc = check_plane_pitch(what, Wm, "mask_pitch", mask_pitch)) return rc;
+        if (int rc = check_u8(what, "mask_thresh", mask_thresh)) return rc;
+        while ((1 << mshift) < mask_down) ++mshift;
+    }
+    const int Ho = Hr / down, Wo = Wr / down;
+    if (out_pitch < 3 * (int64_t)Wo) {
+        set_error("%s: out_pitch %lld is less than a row of the canvas (3 Wo = %lld bytes)", what, (long long)out_pitch, 3ll * Wo);
+        return TOAD_ESHAPE;
+    }
+    if (Gy != (int)(((int64_t)Hr + cell - 1) / cell) || Gx != (int)(((int64_t)Wr + cell - 1) / cell)) {
+        set_error("%s: Gy x Gx = %d x %d is not ceil(Hr / cell) x ceil(Wr / cell) = %lld x %lld", what, Gy, Gx, ((long long)Hr + cell - 1) / cell,
+                  ((long long)Wr + cell - 1) / cell);
+        return TOAD_ESHAPE;
+    }
+    const int Hi = Ho * down, Wi = Wo * down;
+    const int64_t nchunks = ((int64_t)Wi + 255) / 256, blocks = nchunks * (((int64_t)Hi + 15) / 16);
+    if (int rc = check_blocks(what, "region", blocks)) return rc;
+    if (!aligned4(cells)) { set_error("%s: cells (int32 [Gy][Gx]) must be 4-byte aligned (the region, the mask and the canvas may have any alignment)", what); return TOAD_EALIGN; }
+    if (Ho == 0 || Wo == 0) return TOAD_OK;
+    int shift = 2;
+    while ((1 << shift) < cell) ++shift;
+    // the tent's variant: none; one quadrant per lane (cell >= 8); cell == 4, where at down == 4 a canvas pixel is a whole cell and the tent is the own value
+    const int sm = !smooth || cell == down ? 0 : cell == 4 ? 2 : 1;
+    const HeatPxArgs a = {region, pitch, Hi, Wi, cells, Gy, Gx, shift, alpha, mask, mask_pitch, Hm, Wm, mshift, mask_thresh, out, out_pitch, (unsigned)nchunks};
+    hipStream_t st = (hipStream_t)stream;
+#define TOAD_HEAT_PX(D, S, M) hipLaunchKernelGGL((heat_blend_px_kernel<D, S, M>), dim3((unsigned)blocks), dim3(256), 0, st, a, lut)
+#define TOAD_HEAT_PX_S(D, M) \
+    switch (sm) {            \
+        case 0: TOAD_HEAT_PX(D, 0, M); break; \
+        case 1: TOAD_HEAT_PX(D, 1, M); break; \
+        default: TOAD_HEAT_PX(D, 2, M); break; \
+    }
+#define TOAD_HEAT_PX_M(D) \
+    if (mask) { TOAD_HEAT_PX_S(D, true) } else { TOAD_HEAT_PX_S(D, false) }
+    switch (down) {
+        case 1: TOAD_HEAT_PX_M(1); break;
+        case 2: TOAD_HEAT_PX_M(2); break;
+        default:                                                      // down == 4: variant 2 does not occur (cell == down)
+            if (mask) { if (sm) TOAD_HEAT_PX(4, 1, true); else TOAD_HEAT_PX(4, 0, true); }
+            else { if (sm) TOAD_HEAT_PX(4, 1, false); else TOAD_HEAT_PX(4, 0, false); }
+            break;
+    }
+#undef TOAD_HEAT_PX_M
+#undef TOAD_HEAT_PX_S
+#undef TOAD_HEAT_PX
     return check_launch(what);
 }

@@ -13,6 +13,7 @@ raise ``NameError`` for ``n_classes == 2`` (the reference's ``topk`` is only bou
 """
 from __future__ import annotations
 
+import inspect
 from typing import Dict, Iterable, Optional, Sequence
 
 import numpy as np
@@ -212,8 +213,17 @@ def region_attention_scores(extractor, model: TOAD_fc_mtl_concat, region: torch.
 _SEGMENT_KEYS = ("down", "median", "sat_thresh", "val_min", "close", "min_area", "min_hole")
 
 
-def _select_origins(region, tile, stride, min_fraction, sat_thresh, val_min, segment):
+def _segment_down(segment: dict):
+    """The ``down`` a segment dict selects with: its own, or the default of ``tissue.segmented_tissue_origins``."""
+    from .tissue import segmented_tissue_origins
+    return segment.get("down", inspect.signature(segmented_tissue_origins).parameters["down"].default)
+
+
+def _select_origins(region, tile, stride, min_fraction, sat_thresh, val_min, segment, return_mask=False):
+    """The tissue tiles' origins; with ``return_mask`` (a ``segment`` dict only) -> (origins, (plane, t, mask_down)), the mask they were counted on."""
     from .tissue import segmented_tissue_origins, tissue_origins
+    if return_mask and segment is None:
+        raise ValueError("tissue_mask=True needs a segment dict: only tissue.segmented_tissue_origins leaves a mask plane on the device")
     if segment is None:
         return tissue_origins(region, tile=tile, stride=stride, min_fraction=min_fraction, sat_thresh=sat_thresh, val_min=val_min)
     if not isinstance(segment, dict) or any(k not in _SEGMENT_KEYS for k in segment):
@@ -221,7 +231,11 @@ def _select_origins(region, tile, stride, min_fraction, sat_thresh, val_min, seg
         raise ValueError(f"segment must be None or a dict with keys among {_SEGMENT_KEYS}, got {bad!r}")
     kw = dict(sat_thresh=sat_thresh, val_min=val_min)
     kw.update(segment)
-    return segmented_tissue_origins(region, tile=tile, stride=stride, min_fraction=min_fraction, **kw)
+    if not return_mask:
+        return segmented_tissue_origins(region, tile=tile, stride=stride, min_fraction=min_fraction, **kw)
+    kw["down"] = _segment_down(kw)
+    origins, (plane, t) = segmented_tissue_origins(region, tile=tile, stride=stride, min_fraction=min_fraction, return_mask=True, **kw)
+    return origins, (plane, t, kw["down"])
 
 
 def region_tissue_attention_scores(extractor, model: TOAD_fc_mtl_concat, region: torch.Tensor, tile=256, stride=None, min_fraction: float = 0.25,
@@ -235,21 +249,41 @@ def region_tissue_attention_scores(extractor, model: TOAD_fc_mtl_concat, region:
     ``segment``: None selects with ``tissue_origins``; a dict of ``tissue.segmented_tissue_origins`` keywords - any of ``down``, ``median``,
     ``sat_thresh``, ``val_min``, ``close``, ``min_area``, ``min_hole`` - selects with that function instead (CLAM's median-filtered saturation of a box-filtered level, ``sat_thresh`` an int
     or ``"otsu"``). Keys it does not give take this call's ``sat_thresh`` / ``val_min`` and that function's ``down`` / ``median`` defaults."""
-    origins = _select_origins(region, tile, stride, min_fraction, sat_thresh, val_min, segment)
+    return _tissue_scores(extractor, model, region, tile, stride, min_fraction, sat_thresh, val_min, bag_dtype, percentile, segment)[:2]
+
+
+def _tissue_scores(extractor, model, region, tile, stride, min_fraction, sat_thresh, val_min, bag_dtype, percentile, segment, return_mask=False):
+    """``region_tissue_attention_scores`` -> (origins, scores, mask): mask = None, or with ``return_mask`` the (plane, t, mask_down) of the selection."""
+    origins, mask = _select_origins(region, tile, stride, min_fraction, sat_thresh, val_min, segment, return_mask), None
+    if return_mask:
+        origins, mask = origins
     if origins.shape[0] == 0:
-        return origins, torch.empty(0, dtype=torch.float32, device=region.device)
-    return origins, region_attention_scores(extractor, model, region, origins, tile=tile, bag_dtype=bag_dtype, percentile=percentile)
+        return origins, torch.empty(0, dtype=torch.float32, device=region.device), mask
+    return origins, region_attention_scores(extractor, model, region, origins, tile=tile, bag_dtype=bag_dtype, percentile=percentile), mask
 
 
 def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region: torch.Tensor, tile=256, stride=None, min_fraction: float = 0.25,
                                     sat_thresh: int = 8, val_min: int = 0, bag_dtype: torch.dtype = torch.float16, alpha=102, down: int = 1, lut=None,
-                                    out=None, segment: Optional[dict] = None):
+                                    out=None, segment: Optional[dict] = None, smooth: bool = False, tissue_mask: bool = False, thresh=None,
+                                    binarize: bool = False):
     """``(origins, scores, canvas)`` of one decoded uint8 region [Hr,Wr,3]: ``region_tissue_attention_scores(..., percentile=True)`` selects and scores the
     tissue tiles, ``heatmap.attention_canvas`` renders those percentile scores onto the region on the same lattice, on the device - uint8
     [Hr // down, Wr // down, 3]; the tiles that were not selected keep the (box-filtered) pixels of the region. ``alpha``, ``down``, ``lut`` and ``out``:
     ``heatmap.attention_canvas``. ``segment``: as for ``region_tissue_attention_scores`` - None or a dict that selects the tiles with
-    ``tissue.segmented_tissue_origins``. Gaussian smoothing, CLAM's vis-level pyramid and saving the image are not done here."""
+    ``tissue.segmented_tissue_origins``.
+
+    ``smooth``, ``thresh``, ``binarize``: ``heatmap.attention_canvas`` (the colour index interpolated between cell centres; tiles below a percentile
+    score dropped; present tiles saturated). ``tissue_mask=True`` (CLAM's ``segment=True``) colours only the tissue pixels of a selected tile: it needs
+    a ``segment`` dict, whose mask plane - the one the tiles were counted on, nothing is recomputed - goes to the renderer with its threshold and its
+    ``down``; that ``down`` must be a multiple of the canvas ``down`` (ValueError otherwise, before anything is launched). CLAM's Gaussian ``blur``, its
+    vis-level pyramid and saving the image are not done here."""
     from .heatmap import attention_canvas
-    origins, scores = region_tissue_attention_scores(extractor, model, region, tile=tile, stride=stride, min_fraction=min_fraction, sat_thresh=sat_thresh,
-                                                     val_min=val_min, bag_dtype=bag_dtype, percentile=True, segment=segment)
-    return origins, scores, attention_canvas(region, origins, scores, tile=tile, stride=stride, alpha=alpha, down=down, lut=lut, out=out)
+    if tissue_mask and isinstance(segment, dict):                   # (without a dict _select_origins refuses)
+        seg_down = _segment_down(segment)
+        if down not in (1, 2, 4) or not isinstance(seg_down, int) or seg_down % down:
+            raise ValueError(f"tissue_mask=True: the segment down = {seg_down!r} must be a multiple of the canvas down = {down!r} (a canvas box must lie "
+                             "in one mask pixel)")
+    origins, scores, mask = _tissue_scores(extractor, model, region, tile, stride, min_fraction, sat_thresh, val_min, bag_dtype, True, segment,
+                                           return_mask=tissue_mask)
+    return origins, scores, attention_canvas(region, origins, scores, tile=tile, stride=stride, alpha=alpha, down=down, lut=lut, out=out, smooth=smooth,
+                                             mask=mask, thresh=thresh, binarize=binarize)

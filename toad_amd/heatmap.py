@@ -10,8 +10,25 @@ integers so that the canvas has one right answer:
 * the canvas is the region box-filtered by ``down`` in 1, 2, 4 (mean rounded half up, partial boxes at the right and the bottom edge dropped), and on the
   cells with a colour ``(alpha lut[idx][c] + (256 - alpha) m + 128) >> 8`` with an integer ``alpha`` in [0, 256].
 
+With ``smooth`` or a ``mask`` the colour index and the alpha are decided per canvas pixel (``ops.region_heat_blend_px``), still in integers. For canvas
+pixel (ox, oy), ``own`` being the value of the cell that holds it:
+
+* ``smooth``: ``idx_px`` is the bilinear tent between cell centres, in doubled coordinates. Along x ``p = 2 down ox + down - cell``,
+  ``g0 = floor(p / (2 cell))`` (may be -1), ``f = p - 2 cell g0`` in [0, 2 cell), weights ``2 cell - f`` for cell g0 and ``f`` for g0 + 1; the same
+  along y. A neighbour outside the table or without a value contributes ``own``; ``idx_px = (sum wy wx v + 2 cell^2) >> (2 log2(cell) + 2)``. The
+  weights sum to ``4 cell^2``: a constant field is reproduced, and where a canvas pixel is a whole cell (``down = cell = 4``) nothing changes.
+* ``mask`` = (plane, t, mask_down), a uint8 [Hr // mask_down, Wr // mask_down] plane with ``mask_down`` in 1, 2, 4, 8, 16, 32 and a multiple of ``down``:
+  the pixel is tissue iff ``mx = (down ox) // mask_down`` and ``my = (down oy) // mask_down`` lie inside the plane and ``plane[my, mx] > t`` - the
+  (plane, t) of ``tissue.segment_tissue`` read as it lies; the partial boxes the plane dropped are not tissue. Without a mask every pixel is tissue.
+* the byte is ``(alpha lut[idx_px][c] + (256 - alpha) m + 128) >> 8`` where ``own >= 0`` and the pixel is tissue, ``m`` elsewhere: coverage edges and
+  mask edges stay sharp, only the colour inside them is interpolated.
+
+This is CLAM's ``segment=True`` and a one-cell-wide stand-in for its ``blur``; it is NOT CLAM's Gaussian and does not claim to be. ``thresh`` and
+``binarize`` (CLAM's ``thresh``, ``binarize``) act on the tiles' scores before the table is built.
+
 Conventions as in ``toad_amd.tissue``: ``tile`` = int or (H, W), ``stride`` = int or (sy, sx), ``origin`` = (x, y) of the lattice's first tile.
-Gaussian smoothing, CLAM's vis-level pyramid and saving images are not done here."""
+Seams between separately rendered regions (a neighbour outside the table counts as ``own``), smoothing kernels wider than one cell, cell-level
+pre-smoothing passes, CLAM's Gaussian, its vis-level pyramid and saving images are not done here."""
 from __future__ import annotations
 
 import numpy as np
@@ -91,12 +108,36 @@ def _alpha_arg(alpha) -> int:
     raise ValueError(f"alpha must be an int in [0, 256] or a float in [0, 1] (meaning round(256 alpha)), got {alpha!r}")
 
 
+def select_scores(scores: torch.Tensor, scores_q: torch.Tensor, thresh=None, binarize: bool = False) -> torch.Tensor:
+    """CLAM's ``thresh`` and ``binarize`` on quantised scores, int32 [B]: a tile whose raw score is below ``thresh`` becomes absent (-1; CLAM keeps
+    ``score >= threshold``, and a NaN score, which is >= nothing, stays absent), and with ``binarize`` every present tile gets q = 65535. Torch ops only,
+    no synchronisation."""
+    q = scores_q
+    if thresh is not None:
+        q = torch.where(scores.reshape(-1) >= thresh, q, torch.full_like(q, -1))
+    if binarize:
+        q = torch.where(q >= 0, torch.full_like(q, 65535), q)
+    return q
+
+
+def _mask_arg(mask):
+    if mask is None:
+        return None, None, 0
+    if not isinstance(mask, (tuple, list)) or len(mask) != 3:
+        raise ValueError("mask must be None or a (plane, t, mask_down) triple: the plane and the threshold of tissue.segment_tissue and its down")
+    return mask
+
+
 def attention_canvas(region: torch.Tensor, origins, scores: torch.Tensor, tile=256, stride=None, origin=(0, 0), alpha=102, down: int = 1, lut=None,
-                     score_range=(0, 1), out=None) -> torch.Tensor:
+                     score_range=(0, 1), out=None, smooth: bool = False, mask=None, thresh=None, binarize: bool = False) -> torch.Tensor:
     """The heat map of one decoded uint8 region [Hr,Wr,3]: uint8 [Hr // down, Wr // down, 3] ON THE DEVICE. ``origins`` [B,2] of (x, y) on the host are
     tiles of the lattice (tile, stride, origin) inside the region - ``tissue.tissue_origins`` with the same arguments gives such - and ``scores`` their B
     scores on the device, in that order. The definition is the module's. ``alpha`` an int in [0, 256] or a float in [0, 1] (the default 102 is CLAM's
     0.4), ``lut`` uint8 [256,3] on the device (default ``jet_lut``), ``out`` as in ``ops.region_heat_blend``.
+
+    ``smooth`` interpolates the colour index between cell centres and ``mask`` = (plane, t, mask_down) blends only tissue pixels (the module's per-pixel
+    definition; ``ops.region_heat_blend_px`` then takes the place of ``ops.region_heat_blend``). ``thresh`` makes a tile absent whose raw score is below
+    it, ``binarize`` gives every present tile the top colour (``select_scores``).
 
     Two launches and a few small torch ops, no synchronisation. Empty ``origins`` give the box-filtered region."""
     _, hr, wr = ops._region_pitch(region, "attention_canvas")
@@ -107,9 +148,18 @@ def attention_canvas(region: torch.Tensor, origins, scores: torch.Tensor, tile=2
         raise ValueError(f"attention_canvas: scores must be a tensor on the region's device ({region.device}), got "
                          f"{scores.device if isinstance(scores, torch.Tensor) else type(scores).__name__}")
     nx, ny = lattice(hr, wr, (h, w), (sy, sx), (x0, y0))
-    table = tile_table(origins, quantise_scores(scores, score_range), (h, w), (sy, sx), (x0, y0), (nx, ny))
+    if not isinstance(smooth, bool) or not isinstance(binarize, bool):
+        raise ValueError(f"attention_canvas: smooth and binarize must be bools, got {smooth!r} and {binarize!r}")
+    if thresh is not None and (isinstance(thresh, bool) or not isinstance(thresh, (int, float)) or thresh != thresh):
+        raise ValueError(f"attention_canvas: thresh must be None or a number (a raw score), got {thresh!r}")
+    plane, t, mask_down = _mask_arg(mask)
+    table = tile_table(origins, select_scores(scores, quantise_scores(scores, score_range), thresh, binarize), (h, w), (sy, sx), (x0, y0), (nx, ny))
     if table.numel() and len(origins):
         cells = ops.heat_cells(table, cell, (x0, y0), (h, w), (sy, sx), (nx, ny), (hr, wr))
     else:
         cells = torch.full((-(-hr // cell), -(-wr // cell)), -1, dtype=torch.int32, device=region.device)
-    return ops.region_heat_blend(region, cells, cell, jet_lut(region.device) if lut is None else lut, a, down, out=out)
+    lut = jet_lut(region.device) if lut is None else lut
+    if not smooth and plane is None:
+        return ops.region_heat_blend(region, cells, cell, lut, a, down, out=out)
+    return ops.region_heat_blend_px(region, cells, cell, lut, a, down, smooth=smooth, mask=plane, mask_down=mask_down if plane is not None else None,
+                                    mask_thresh=t if plane is not None else 0, out=out)

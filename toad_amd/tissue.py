@@ -233,7 +233,7 @@ def _seg_lattice(tile, stride, origin, down):
 
 def segmented_tissue_origins(region: torch.Tensor, tile=256, stride=None, min_fraction: float = 0.25, down: int = 16, median: int = 7, sat_thresh=8,
                              val_min: int = 0, origin=(0, 0), return_counts: bool = False, return_threshold: bool = False, close: int = 0,
-                             min_area: int = 0, min_hole: int = 0):
+                             min_area: int = 0, min_hole: int = 0, return_mask: bool = False):
     """``tissue_origins`` with CLAM's tissue decision (the module's steps 1 to 7): the region is box-filtered by ``down``, its saturation plane
     median-filtered (``median`` x ``median``), a plane pixel is tissue iff it is > ``sat_thresh`` - an int in 0..255 or ``"otsu"`` - and a lattice tile
     is kept iff its tissue count >= ceil(min_fraction (H // down) (W // down)). Result as for ``tissue_origins``: np.ndarray int64 [B,2] of (x, y) at the
@@ -248,6 +248,10 @@ def segmented_tissue_origins(region: torch.Tensor, tile=256, stride=None, min_fr
     tiles are counted; each is skipped entirely at 0 (``close`` and ``min_area`` at 1 as well). They add 1, 4 and 4 launches (9 together; a labelling is 2
     launches, not 3, where the plane is one 64 x 16 tile) and no synchronisation; ``return_threshold`` still gives the threshold applied to the median plane.
 
+    ``return_mask`` appends ``(mask_plane, t)`` last: the uint8 [Hr // down, Wr // down] plane ON THE DEVICE the tile counts were taken from and the
+    threshold it was read with (a plane pixel is tissue iff it is > t) - the median plane and the threshold applied, or the 0 / 255 plane of the filters
+    and 0. Nothing is recomputed for it; with ``down`` it is the mask ``heatmap.attention_canvas`` takes. An empty lattice has no plane: ``(None, t)``.
+
     The defaults are CLAM's: ``sthresh = 8``, ``mthresh = 7``, a low-resolution level (``down = 16``); ``use_otsu`` is ``sat_thresh="otsu"``.
     CLAM's ``max_n_holes`` and its polygon areas are not done."""
     _min_fraction_arg(min_fraction)
@@ -259,11 +263,13 @@ def segmented_tissue_origins(region: torch.Tensor, tile=256, stride=None, min_fr
     nx, ny = lattice(hr, wr, (h, w), (sy, sx), (x0, y0))
 
     counts, t = None, 0 if sat_thresh == "otsu" else sat_thresh
+    mask = (None, t)
     if nx and ny:
         plane, t = segment_tissue(region, down, median, sat_thresh, val_min)
         cell = lattice_cell((ph, pw), (psy, psx), (px0, py0))
-        cells = ops.plane_cells(_morph(plane, t, close, min_area, min_hole), cell, 0) if active else ops.plane_cells(plane, cell, t)
+        mask = (_morph(plane, t, close, min_area, min_hole), 0) if active else (plane, t)
+        cells = ops.plane_cells(mask[0], cell, mask[1])
         counts = ops.tissue_tile_counts(cells, cell, (px0, py0), (ph, pw), (psy, psx), (nx, ny))
     origins, kept = _kept(counts, math.ceil(min_fraction * ph * pw), x0, y0, sx, sy)
-    out = (origins,) + ((kept,) if return_counts else ()) + ((t,) if return_threshold else ())
+    out = (origins,) + ((kept,) if return_counts else ()) + ((t,) if return_threshold else ()) + ((mask,) if return_mask else ())
     return out if len(out) > 1 else origins

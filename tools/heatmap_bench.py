@@ -11,9 +11,17 @@ its alternation of the arms inside one process, warm-up of every arm, its four s
     calls walk round FOUR different slides (403 MB, every call finds its region evicted: the HBM figure, the one to quote) and `_same` calls repeat on
     one slide (the cache-resident figure). bytes/s = 3 Hr Wr read + 3 Ho Wo written over the call's time: the bytes the canvas NEEDS, for arm B too.
   launches: four calls of arm A (or B) on rotating slides, no warm-up, for a `rocprofv3 --kernel-trace --stats` run of its own.
+  px (--px): what the per-pixel pass (ops.region_heat_blend_px: heat_blend_px_kernel) costs over the flat one. Same slides, table and canvas; the mask of
+    each slide is the (plane, t) of tissue.segment_tissue at down 16, median 7, threshold 8. Arms, alternated in one process on the rotating slides:
+      flat      heat_cells_kernel + heat_blend_kernel<down> - arm A above, code this tool has always timed;
+      px_smooth / px_mask / px_both   heat_cells_kernel + heat_blend_px_kernel<down> with smooth, with the mask, with both;
+      B_torch   px_both's definition in torch ops (gathers of the four neighbours, int64 canvas-sized intermediates), checked bit-equal to px_both on
+                every slide before anything is timed.
+    All arms move the same 3 Hr Wr + 3 Ho Wo bytes (the mask plane is 1 / 768 of the region). px_over_flat = median over median; flat_spread = the flat
+    arm's own interleaved-halves spread, the yardstick for "no cost".
 
 Prints one JSON line per result; --out FILE keeps them.
-usage: heatmap_bench.py [--launches --arm A|B --down D] [--seconds S] [--out FILE]"""
+usage: heatmap_bench.py [--launches --arm A|B --down D] [--px] [--seconds S] [--out FILE]"""
 import argparse
 import json
 import os
@@ -29,7 +37,7 @@ from extract_u8_bench import alternate, median      # noqa: E402
 from tissue_bench import HR, WR, TILE, Rotating, make_slide      # noqa: E402
 from toad_amd import ops                            # noqa: E402
 from toad_amd.heatmap import jet_lut                # noqa: E402
-from toad_amd.tissue import lattice, lattice_cell   # noqa: E402
+from toad_amd.tissue import lattice, lattice_cell, segment_tissue   # noqa: E402
 
 STRIDE, ALPHA = 64, 102
 CELL = lattice_cell(TILE, STRIDE)
@@ -105,6 +113,85 @@ def resident(seconds):
     return res
 
 
+MASK_DOWN = 16
+
+
+def hip_canvas_px(region, table, lut, down, out, smooth, mask):
+    cells = ops.heat_cells(table, CELL, (0, 0), (TILE, TILE), (STRIDE, STRIDE), (NX, NY), (HR, WR))
+    plane, t = mask if mask is not None else (None, 0)
+    return ops.region_heat_blend_px(region, cells, CELL, lut, ALPHA, down, smooth=smooth, mask=plane, mask_down=MASK_DOWN if mask is not None else None,
+                                    mask_thresh=t, out=out)
+
+
+def torch_canvas_px(region, table, lut, down, smooth, mask):
+    """The per-pixel definition of include/toad_hip.h in torch ops, uint8 [HR // down, WR // down, 3]."""
+    dev = region.device
+    c = ops.heat_cells(table, CELL, (0, 0), (TILE, TILE), (STRIDE, STRIDE), (NX, NY), (HR, WR)).to(torch.int64).clamp(max=255)
+    ho, wo = HR // down, WR // down
+    oy, ox = torch.arange(ho, device=dev) * down, torch.arange(wo, device=dev) * down
+    own = c[oy // CELL][:, ox // CELL]
+    idx = own
+    if smooth:
+        def axis(n):
+            p = 2 * down * torch.arange(n, device=dev) + down - CELL
+            g0 = torch.div(p, 2 * CELL, rounding_mode="floor")
+            f = p - 2 * CELL * g0
+            return g0, 2 * CELL - f, f
+        (gy0, wy0, wy1), (gx0, wx0, wx1) = axis(ho), axis(wo)
+        acc = torch.zeros(ho, wo, dtype=torch.int64, device=dev)
+        for gy, wy in ((gy0, wy0), (gy0 + 1, wy1)):
+            for gx, wx in ((gx0, wx0), (gx0 + 1, wx1)):
+                inside = ((gy >= 0) & (gy < GY))[:, None] & ((gx >= 0) & (gx < GX))[None, :]
+                v = c[gy.clamp(0, GY - 1)][:, gx.clamp(0, GX - 1)]
+                acc += wy[:, None] * wx[None, :] * torch.where(inside & (v >= 0), v, own)
+        idx = (acc + 2 * CELL * CELL) >> (2 * (CELL.bit_length() - 1) + 2)
+    blend = own >= 0
+    if mask is not None:
+        plane, t = mask
+        hm, wm = plane.shape
+        my, mx = oy // MASK_DOWN, ox // MASK_DOWN
+        blend = blend & ((my < hm)[:, None] & (mx < wm)[None, :]) & (plane[my.clamp(max=hm - 1)][:, mx.clamp(max=wm - 1)] > t)
+    col = lut.to(torch.int32)[idx.clamp(min=0)]
+    if down == 1:
+        m = region.to(torch.int32)
+    else:
+        m = (region[:ho * down, :wo * down].view(ho, down, wo, down, 3).sum(dim=(1, 3), dtype=torch.int32) + down * down // 2) // (down * down)
+    return torch.where(blend.unsqueeze(2), (ALPHA * col + (256 - ALPHA) * m + 128) >> 8, m).to(torch.uint8)
+
+
+def resident_px(seconds):
+    dev = torch.device("cuda:0")
+    slides, table, lut = setup(dev)
+    masks = {s.data_ptr(): segment_tissue(s, MASK_DOWN, 7, 8) for s in slides}
+    res = []
+    for down in (1, 4):
+        out = torch.empty((HR // down, WR // down, 3), dtype=torch.uint8, device=dev)
+        flat = lambda r: hip_canvas(r, table, lut, down, out)                                           # noqa: E731
+        px = lambda smooth, masked: (lambda r: hip_canvas_px(r, table, lut, down, out, smooth, masks[r.data_ptr()] if masked else None))      # noqa: E731
+        tor = lambda r: torch_canvas_px(r, table, lut, down, True, masks[r.data_ptr()])                 # noqa: E731
+        same = all(bool(torch.equal(px(True, True)(s), tor(s))) for s in slides)
+        same_flat = all(bool(torch.equal(px(False, False)(s).clone(), flat(s))) for s in slides)
+        if not (same and same_flat):                                           # a wrong arm must not produce a quoted ratio
+            raise SystemExit(f"heatmap_bench: px_both differs from its torch arm ({same}) or px without keywords from the flat pass ({same_flat}) at down = "
+                             f"{down}: nothing is timed")
+        changed = float((px(True, True)(slides[0]).clone() != flat(slides[0])).any(dim=2).float().mean())
+        arms = {"flat": Rotating(flat, slides), "px_smooth": Rotating(px(True, False), slides), "px_mask": Rotating(px(False, True), slides),
+                "px_both": Rotating(px(True, True), slides), "B_torch": Rotating(tor, slides)}
+        t, iters = alternate(arms, seconds)
+        nbytes = 3 * HR * WR + 3 * (HR // down) * (WR // down)
+        a = t["flat"]
+        a1, a2 = median(a[0::2]), median(a[1::2])
+        res.append(dict(kind="resident_heatmap_px", region=[HR, WR], tile=TILE, stride=STRIDE, cell=CELL, down=down, alpha=ALPHA, mask_down=MASK_DOWN,
+                        moved_bytes=nbytes, slides_rotated=len(slides), pixels_changed_vs_flat=round(changed, 4), rounds=len(a), iters_per_round=iters,
+                        ms={k: round(median(v), 5) for k, v in t.items()}, ms_min={k: round(min(v), 5) for k, v in t.items()},
+                        ms_max={k: round(max(v), 5) for k, v in t.items()}, moved_tbps={k: round(nbytes / median(v) / 1e9, 3) for k, v in t.items()},
+                        flat_halves_ms=[round(a1, 5), round(a2, 5)], flat_spread=round(abs(a1 - a2) / median(a), 4),
+                        px_over_flat={k: round(median(t[k]) / median(a), 4) for k in ("px_smooth", "px_mask", "px_both")},
+                        torch_over_px_both=round(median(t["B_torch"]) / median(t["px_both"]), 2), px_equals_torch=same, px_plain_equals_flat=same_flat))
+        del out
+    return res
+
+
 def launches(arm, down, calls=4):
     """`calls` calls of one arm on rotating slides, no warm-up (run under rocprofv3 --kernel-trace --stats: every count divides by `calls`)."""
     dev = torch.device("cuda:0")
@@ -122,10 +209,11 @@ def main():
     ap.add_argument("--launches", action="store_true")
     ap.add_argument("--arm", default="A", choices=("A", "B"))
     ap.add_argument("--down", type=int, default=1, choices=(1, 2, 4))
+    ap.add_argument("--px", action="store_true")
     ap.add_argument("--seconds", type=float, default=3.0)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    res = launches(a.arm, a.down) if a.launches else resident(a.seconds)
+    res = launches(a.arm, a.down) if a.launches else resident_px(a.seconds) if a.px else resident(a.seconds)
     lines = [json.dumps(r) for r in res]
     print("\n".join(lines), flush=True)
     if a.out:
