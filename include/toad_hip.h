@@ -427,8 +427,8 @@ int toad_heat_cells(const int *tile_q, int nx, int ny, int cell, int x0, int y0,
 int toad_region_heat_blend_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx, int cell,
                               const unsigned char *lut, int alpha, int down, unsigned char *out, int64_t out_pitch, void *stream);
 
-/* The same canvas with the colour index and the alpha decided per canvas pixel (additive to ABI 15 too; toad_region_heat_blend_u8 does not change). Integers
- * only. Inputs as above plus `smooth` in {0, 1} and an optional mask plane. For canvas pixel (ox, oy): m per channel as above; gy_own = (down * oy) / cell,
+/* The same canvas with the colour index and the alpha decided per canvas pixel (additive to ABI 15 too; toad_region_heat_blend_u8 is this call with smooth = 0 and
+ * mask = NULL: the same kernel). Integers only. Inputs as above plus `smooth` in {0, 1} and an optional mask plane. For canvas pixel (ox, oy): m per channel as above; gy_own = (down * oy) / cell,
  * gx_own = (down * ox) / cell, own = cells[gy_own][gx_own] (values above 255 read as 255, as above).
  *   colour index  smooth = 0: idx_px = own. smooth = 1: the bilinear tent between cell centres, in doubled coordinates. Along x:
  *                     p = 2 * down * ox + down - cell,  g0 = floor(p / (2 * cell)) (may be -1),  f = p - 2 * cell * g0 in [0, 2 * cell),

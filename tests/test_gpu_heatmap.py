@@ -1,4 +1,4 @@
-"""GPU: attention heat maps of a decoded uint8 region (csrc/heatmap.hip heat_cells_kernel, heat_blend_kernel<DOWN>; toad_amd/heatmap.py;
+"""GPU: attention heat maps of a decoded uint8 region (csrc/heatmap.hip heat_cells_kernel, heat_blend_px_kernel<DOWN,0,false>; toad_amd/heatmap.py;
 eval.region_tissue_attention_heatmap). The canvas is defined in integers, so every comparison is exact, against the numpy reference of tests/heat_ref.py
 (tested on its own, by hand and on these very inputs, in test_heatmap_host.py - that the cases have covered and uncovered cells, overlap and several
 colours is asserted there)."""

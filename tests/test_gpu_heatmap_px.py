@@ -1,7 +1,7 @@
 """GPU: the per-pixel heat-map blend (csrc/heatmap.hip heat_blend_px_kernel<DOWN,SMOOTH,MASK>, toad_region_heat_blend_px_u8; the smooth / mask / thresh /
 binarize keywords of toad_amd/heatmap.py; eval.region_tissue_attention_heatmap(tissue_mask=True)). The canvas is defined in integers, so every comparison
-is == on whole arrays: against today's kernel where the two must agree, and against the numpy reference of tests/heat_px_ref.py (tested on its own, by hand,
-in test_heatmap_px_host.py) everywhere else."""
+is == on whole arrays: against the flat call (ops.region_heat_blend, itself held to tests/heat_ref.py) where the two must agree, and against the numpy
+reference of tests/heat_px_ref.py (tested on its own, by hand, in test_heatmap_px_host.py) everywhere else."""
 import functools
 
 import numpy as np
@@ -31,7 +31,7 @@ def random_mask(hr, wr, mask_down, seed, grey=False):
     return m
 
 
-# ---- 1. against today's kernel --------------------------------------------------------------------------------------------------------------------------
+# ---- 1. against the flat call ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("down", DOWNS)
 def test_flat_index_and_full_mask_equal_todays_kernel(cuda, down):
@@ -42,6 +42,7 @@ def test_flat_index_and_full_mask_equal_todays_kernel(cuda, down):
             region, cells, lut_d = dev(px, cuda), dev(idx, cuda, torch.int32), dev(lut, cuda)
             for alpha in (102, 0, 256):
                 flat = ops.region_heat_blend(region, cells, cell, lut_d, alpha, down)
+                assert same_px(flat, heat_ref.canvas(px, idx, cell, lut, alpha, down)), (hr, wr, cell, alpha)      # both calls below launch flat's kernel
                 assert torch.equal(ops.region_heat_blend_px(region, cells, cell, lut_d, alpha, down), flat), (hr, wr, cell, alpha)
                 for md in [m for m in MASK_DOWNS if m % down == 0]:
                     full = torch.full((hr // md, wr // md), 255, dtype=torch.uint8, device=cuda)
@@ -219,14 +220,17 @@ def test_attention_canvas_keywords_equal_the_reference(cuda, k):
     base = want(1)
     for other in (want(1, smooth=True), want(1, masked=True), want(1, thresh=0.5), want(1, binarize=True)):
         assert not np.array_equal(other, base)                      # every keyword does something on these inputs
-    # smooth=False and mask=None: exactly today's two launches - the per-pixel entry point is not reached
+    # one blend call with or without the keywords (smooth=False and mask=None launch the flat kernel behind it), and it is what region_heat_blend gives
     called = []
     real = ops.region_heat_blend_px
-    ops.region_heat_blend_px = lambda *a, **kw: called.append(1) or real(*a, **kw)
+    ops.region_heat_blend_px = lambda *a, **kw: called.append((a, kw)) or real(*a, **kw)
     try:
-        assert same_px(attention_canvas(region, origins, sd, thresh=0.5, binarize=True, **lat), want(1, thresh=0.5, binarize=True)) and not called
+        got = attention_canvas(region, origins, sd, thresh=0.5, binarize=True, **lat)
+        assert same_px(got, want(1, thresh=0.5, binarize=True)) and len(called) == 1
+        (a, kw), = called
+        assert len(a) == 6 and kw["smooth"] is False and kw["mask"] is None and torch.equal(got, ops.region_heat_blend(*a))
         attention_canvas(region, origins, sd, smooth=True, **lat)
-        assert called == [1]
+        assert len(called) == 2 and called[1][1]["smooth"] is True
     finally:
         ops.region_heat_blend_px = real
 

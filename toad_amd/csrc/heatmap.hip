@@ -15,10 +15,10 @@
 //               [Hm][Wm] of mask_down x mask_down boxes a pixel is blended only where mask[(down oy) / mask_down][(down ox) / mask_down] > mask_thresh;
 //               the pixels of the partial boxes the plane dropped are not. Coverage and mask edges stay sharp: only the colour inside is interpolated.
 //
-// Three kernels:
+// Two kernels:
 //   heat_cells_kernel                       one thread per cell: the covering tiles' index ranges in closed form from the lattice in cell units, a loop over them.
-//   heat_blend_kernel<DOWN>                 one streaming pass over the region: read uint8, write uint8.
-//   heat_blend_px_kernel<DOWN,SMOOTH,MASK>  the same pass with the index, the colour lookup and the alpha per canvas pixel.
+//   heat_blend_px_kernel<DOWN,SMOOTH,MASK>  one streaming pass over the region: read uint8, write uint8. <DOWN,0,false> is the flat canvas (one colour and one
+//                                           alpha per cell: both entry points launch it); the others decide the index, the colour and the alpha per canvas pixel.
 #include "region_u8.h"
 
 namespace toad {
@@ -89,65 +89,7 @@ __device__ __forceinline__ void heat_store4(unsigned char *d, const unsigned (&o
     }
 }
 
-// The work split and its addresses are region_u8.h's, on strips of 16 rows (4 a wave, 12 dwords a lane in flight) over the Hi = DOWN Ho rows and
-// Wi = DOWN Wo columns of the region that some output pixel consumes; nothing outside them is touched. What differs here: a lane owns a 4-pixel-wide,
-// DOWN-row-high block and writes its 4 / DOWN output pixels - 12, 6 or 3 bytes - as dword, half-word and byte stores at any byte address (the row base
-// oy out_pitch is 64-bit like y pitch); off the plain path it takes the wide stores only where x + 4 <= Wi and byte stores for the 1 to 3 pixels of the
-// lane the row ends in. x is a multiple of 4 and the wave's first row one too, so with cell >= 4 a lane's 4 x 4 pixels lie in ONE cell: one cells load per
-// lane, one lookup in the 256 colours the workgroup has packed into 1 KB of LDS.
-template <int DOWN>
-__global__ __launch_bounds__(256) void heat_blend_kernel(const unsigned char *__restrict__ region, int64_t pitch, int Hi, int Wi, const int *__restrict__ cells,
-                                                         int Gx, int shift, const unsigned char *__restrict__ lut, int alpha, unsigned char *__restrict__ out,
-                                                         int64_t out_pitch, unsigned nchunks) {
-    constexpr int RW = 4, ORW = RW / DOWN, OB = 12 / DOWN;         // rows per wave, output rows per wave, output bytes per lane and output row
-    __shared__ unsigned lut_s[256];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    lut_s[tid] = (unsigned)lut[3 * tid] | ((unsigned)lut[3 * tid + 1] << 8) | ((unsigned)lut[3 * tid + 2] << 16);
-    __syncthreads();
-    const unsigned chunk = blockIdx.x % nchunks, rb = blockIdx.x / nchunks;
-    const unsigned x = chunk * 256u + (unsigned)lane * 4u, off = 3u * x, ooff = off / DOWN;
-    const int64_t y0 = (int64_t)rb * 16 + wave * RW;               // first row of this wave (may lie below Hi: then it writes nothing)
-    if (y0 >= Hi) return;
-    const int idx = x < (unsigned)Wi ? cells[(y0 >> shift) * Gx + (x >> shift)] : -1;
-    const unsigned col = lut_s[min(max(idx, 0), 255)], al = idx >= 0 ? (unsigned)alpha : 0u, beta = 256u - al;
-    const unsigned a[3] = {al * (col & 255u) + 128u, al * ((col >> 8) & 255u) + 128u, al * ((col >> 16) & 255u) + 128u};
-    const unsigned char *src = region + y0 * pitch + off;
-    unsigned char *dst = out + (y0 / DOWN) * out_pitch + ooff;
-    if (chunk * 256u + 256u <= (unsigned)Wi && y0 + RW <= Hi) {    // wave-uniform: all 768 bytes of all 4 rows are consumed
-        unsigned w[ORW][DOWN][3];
-#pragma unroll
-        for (int r = 0; r < RW; ++r)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) w[r / DOWN][r % DOWN][k] = *reinterpret_cast<const u32_a1 *>(src + r * pitch + 4 * k);
-#pragma unroll
-        for (int q = 0; q < ORW; ++q) {
-            unsigned o[3];
-            heat_px4<DOWN>(w[q], a, beta, o);
-            heat_store4<DOWN>(dst + q * out_pitch, o);
-        }
-    } else {
-        const int rows = (int)min((int64_t)ORW, (Hi - y0) / DOWN);   // output rows of this wave that exist: Hi and y0 are multiples of DOWN
-        const int npx = x < (unsigned)Wi ? min(4, Wi - (int)x) : 0;  // pixels of this lane that are consumed: 0, DOWN, .., 4
-        const int nout = 3 * npx / DOWN;                             // bytes to write per output row
-        for (int q = 0; q < rows; ++q) {
-            unsigned w[DOWN][3];
-#pragma unroll
-            for (int r = 0; r < DOWN; ++r) load_px4(src + (q * DOWN + r) * pitch, npx, w[r]);
-            unsigned o[3];
-            heat_px4<DOWN>(w, a, beta, o);
-            unsigned char *d = dst + q * out_pitch;
-            if (npx == 4) {
-                heat_store4<DOWN>(d, o);
-            } else {
-#pragma unroll
-                for (int k = 0; k < OB; ++k)
-                    if (k < nout) d[k] = (unsigned char)(o[k >> 2] >> (8 * (k & 3)));
-            }
-        }
-    }
-}
-
-// ---- the per-pixel pass: toad_region_heat_blend_px_u8 ----
+// ---- the blend pass: toad_region_heat_blend_u8 (no tent, no mask) and toad_region_heat_blend_px_u8 ----
 struct HeatPxArgs {
     const unsigned char *region; int64_t pitch; int Hi, Wi;
     const int *cells; int Gy, Gx, shift;
@@ -211,8 +153,14 @@ __device__ __forceinline__ unsigned load_mask(const unsigned char *p, int n) {
     return v;
 }
 
-// One lane of heat_blend_px_kernel: the strip split, the addresses, the plain and the edge path and the stores are heat_blend_kernel's; what is new is
-// decided per canvas pixel of the lane's 4 x 4 region pixels (x and y0 are multiples of 4, so they lie in one cell):
+// The work split and its addresses are region_u8.h's, on strips of 16 rows (4 a wave, 12 dwords a lane in flight) over the Hi = DOWN Ho rows and
+// Wi = DOWN Wo columns of the region that some output pixel consumes; nothing outside them is touched. What differs here: a lane owns a 4-pixel-wide,
+// DOWN-row-high block and writes its 4 / DOWN output pixels - 12, 6 or 3 bytes - as dword, half-word and byte stores at any byte address (the row base
+// oy out_pitch is 64-bit like y pitch); off the plain path it takes the wide stores only where x + 4 <= Wi and byte stores for the 1 to 3 pixels of the
+// lane the row ends in. x is a multiple of 4 and the wave's first row one too, so with cell >= 4 a lane's 4 x 4 pixels lie in ONE cell: one load of the
+// own cell per lane, lookups in the 256 colours the workgroup has packed into 1 KB of LDS. The variants differ only in blend_row, in how a row's colours
+// and alphas come about. SMOOTH 0 without a mask is the flat canvas: the own cell's colour and alpha for all of the lane's pixels, through heat_px4. The
+// others decide per canvas pixel, through heat_px4_each:
 //   index   SMOOTH 0: the cell's own. SMOOTH 1 (cell >= 8): the 4 x 4 pixels also lie in one QUADRANT of the cell - 2 x .. 2 x + 8 holds no cell centre,
 //           those are multiples of 8 in doubled coordinates - so g0 is the lane's: four neighbour loads, f steps by 2 DOWN from pixel to pixel. SMOOTH 2
 //           (cell == 4): the lane's pixels are the whole width of the cell and straddle its centre: nine loads, g0 and f compile-time constants of the
@@ -225,16 +173,23 @@ __device__ __forceinline__ unsigned load_mask(const unsigned char *p, int n) {
 // lut_s: the workgroup's 256 packed colours. No barrier in here: the caller has filled lut_s.
 template <int DOWN, int SMOOTH, bool MASK>
 __device__ __forceinline__ void heat_px_lane(const HeatPxArgs &a, const unsigned *lut_s, unsigned chunk, unsigned rb, int wave, int lane) {
-    constexpr int RW = 4, ORW = RW / DOWN, NP = 4 / DOWN, OB = 12 / DOWN;
+    constexpr int RW = 4, ORW = RW / DOWN, NP = 4 / DOWN, OB = 12 / DOWN;      // rows per wave, output rows per wave, output pixels and bytes per lane and output row
+    constexpr bool FLAT = SMOOTH == 0 && !MASK;
     const unsigned x = chunk * 256u + (unsigned)lane * 4u, off = 3u * x, ooff = off / DOWN;
-    const int64_t y0 = (int64_t)rb * 16 + wave * RW;
+    const int64_t y0 = (int64_t)rb * 16 + wave * RW;               // first row of this wave (may lie below Hi: then it writes nothing)
     if (y0 >= a.Hi) return;
     const bool live = x < (unsigned)a.Wi;
     const int gy = (int)(y0 >> a.shift), gx = (int)(x >> a.shift);
     const int own = live ? min(a.cells[(int64_t)gy * a.Gx + gx], 255) : -1;
 
-    int idx[NP][NP];
-    if constexpr (SMOOTH == 0) {
+    unsigned ua[3], ubeta;                                         // FLAT: heat_px4's a[] and beta, alpha' = 0 on a cell without a value
+    int idx[NP][NP];                                                 // otherwise: the colour index of each of the lane's canvas pixels
+    if constexpr (FLAT) {
+        const unsigned col = lut_s[max(own, 0)], al = own >= 0 ? (unsigned)a.alpha : 0u;
+        ubeta = 256u - al;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) ua[c] = al * ((col >> (8 * c)) & 255u) + 128u;
+    } else if constexpr (SMOOTH == 0) {
 #pragma unroll
         for (int i = 0; i < NP; ++i)
 #pragma unroll
@@ -306,13 +261,17 @@ __device__ __forceinline__ void heat_px_lane(const HeatPxArgs &a, const unsigned
     unsigned char *dst = a.out + (y0 / DOWN) * a.out_pitch + ooff;
     // output row q of the lane from its DOWN region rows
     auto blend_row = [&](int q, const unsigned (&w)[DOWN][3], unsigned (&o)[3]) {
-        unsigned col[NP], al[NP];
+        if constexpr (FLAT) {
+            heat_px4<DOWN>(w, ua, ubeta, o);
+        } else {
+            unsigned col[NP], al[NP];
 #pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            col[j] = lut_s[idx[q][j]];
-            al[j] = own >= 0 && (int)((tis[DOWN * q] >> (8 * DOWN * j)) & 0xFFu) > thr ? (unsigned)a.alpha : 0u;
+            for (int j = 0; j < NP; ++j) {
+                col[j] = lut_s[idx[q][j]];
+                al[j] = own >= 0 && (int)((tis[DOWN * q] >> (8 * DOWN * j)) & 0xFFu) > thr ? (unsigned)a.alpha : 0u;
+            }
+            heat_px4_each<DOWN>(w, col, al, o);
         }
-        heat_px4_each<DOWN>(w, col, al, o);
     };
     if (chunk * 256u + 256u <= (unsigned)a.Wi && y0 + RW <= a.Hi) {  // wave-uniform: all 768 bytes of all 4 rows are consumed
         unsigned w[ORW][DOWN][3];
@@ -330,8 +289,9 @@ __device__ __forceinline__ void heat_px_lane(const HeatPxArgs &a, const unsigned
         const int rows = (int)min((int64_t)ORW, (a.Hi - y0) / DOWN);  // output rows of this wave that exist: Hi and y0 are multiples of DOWN
         const int npx = live ? min(4, a.Wi - (int)x) : 0;            // pixels of this lane that are consumed: 0, DOWN, .., 4
         const int nout = 3 * npx / DOWN;                             // bytes to write per output row
-#pragma unroll
-        for (int q = 0; q < ORW; ++q) {                              // unrolled, so that q indexes registers
+        constexpr int UNROLL = FLAT ? 1 : ORW;                       // unrolled where blend_row uses q, so that it indexes registers
+#pragma unroll UNROLL
+        for (int q = 0; q < ORW; ++q) {
             if (q >= rows) break;
             unsigned w[DOWN][3];
 #pragma unroll
@@ -383,48 +343,11 @@ extern "C" int toad_heat_cells(const int *tile_q, int nx, int ny, int cell, int 
     return check_launch(what);
 }
 
-extern "C" int toad_region_heat_blend_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx, int cell,
-                                         const unsigned char *lut, int alpha, int down, unsigned char *out, int64_t out_pitch, void *stream) {
-    const char *what = "toad_region_heat_blend_u8";
-    if (!region || !cells || !lut || !out) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
-    if (int rc = check_cell(what, cell)) return rc;
-    if (int rc = check_hw(what, "Hr", Hr, "Wr", Wr)) return rc;
-    if (alpha < 0 || alpha > 256) { set_error("%s: alpha = %d must lie in [0, 256] (256 = the colour alone)", what, alpha); return TOAD_ESHAPE; }
-    if (down != 1 && down != 2 && down != 4) { set_error("%s: down = %d is not one of 1, 2, 4", what, down); return TOAD_ESHAPE; }
-    if (int rc = check_region_pitch(what, pitch, Wr)) return rc;
-    const int Ho = Hr / down, Wo = Wr / down;
-    if (out_pitch < 3 * (int64_t)Wo) {
-        set_error("%s: out_pitch %lld is less than a row of the canvas (3 Wo = %lld bytes)", what, (long long)out_pitch, 3ll * Wo);
-        return TOAD_ESHAPE;
-    }
-    if (Gy != (int)(((int64_t)Hr + cell - 1) / cell) || Gx != (int)(((int64_t)Wr + cell - 1) / cell)) {
-        set_error("%s: Gy x Gx = %d x %d is not ceil(Hr / cell) x ceil(Wr / cell) = %lld x %lld", what, Gy, Gx, ((long long)Hr + cell - 1) / cell,
-                  ((long long)Wr + cell - 1) / cell);
-        return TOAD_ESHAPE;
-    }
-    const int Hi = Ho * down, Wi = Wo * down;
-    const int64_t nchunks = ((int64_t)Wi + 255) / 256, blocks = nchunks * (((int64_t)Hi + 15) / 16);
-    if (int rc = check_blocks(what, "region", blocks)) return rc;
-    if (!aligned4(cells)) { set_error("%s: cells (int32 [Gy][Gx]) must be 4-byte aligned (the region and the canvas may have any alignment)", what); return TOAD_EALIGN; }
-    if (Ho == 0 || Wo == 0) return TOAD_OK;
-    int shift = 2;
-    while ((1 << shift) < cell) ++shift;
-    hipStream_t st = (hipStream_t)stream;
-#define TOAD_HEAT_LAUNCH(D) \
-    hipLaunchKernelGGL(heat_blend_kernel<D>, dim3((unsigned)blocks), dim3(256), 0, st, region, pitch, Hi, Wi, cells, Gx, shift, lut, alpha, out, out_pitch, (unsigned)nchunks)
-    switch (down) {
-        case 1: TOAD_HEAT_LAUNCH(1); break;
-        case 2: TOAD_HEAT_LAUNCH(2); break;
-        default: TOAD_HEAT_LAUNCH(4); break;
-    }
-#undef TOAD_HEAT_LAUNCH
-    return check_launch(what);
-}
-
-extern "C" int toad_region_heat_blend_px_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx, int cell,
-                                            const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch,
-                                            int Hm, int Wm, int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream) {
-    const char *what = "toad_region_heat_blend_px_u8";
+// Both blend entry points: every check in the order in which the first failing one wins, the geometry, the choice of the kernel. The flat entry passes
+// smooth = 0 and mask = NULL, for which the smooth and mask checks are no-ops; `unaligned` names the planes its alignment message lets lie anywhere.
+static int launch_heat_blend(const char *what, const char *unaligned, const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx,
+                             int cell, const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm,
+                             int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream) {
     if (!region || !cells || !lut || !out) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
     if (int rc = check_cell(what, cell)) return rc;
     if (int rc = check_hw(what, "Hr", Hr, "Wr", Wr)) return rc;
@@ -463,33 +386,33 @@ extern "C" int toad_region_heat_blend_px_u8(const unsigned char *region, int64_t
     const int Hi = Ho * down, Wi = Wo * down;
     const int64_t nchunks = ((int64_t)Wi + 255) / 256, blocks = nchunks * (((int64_t)Hi + 15) / 16);
     if (int rc = check_blocks(what, "region", blocks)) return rc;
-    if (!aligned4(cells)) { set_error("%s: cells (int32 [Gy][Gx]) must be 4-byte aligned (the region, the mask and the canvas may have any alignment)", what); return TOAD_EALIGN; }
+    if (!aligned4(cells)) { set_error("%s: cells (int32 [Gy][Gx]) must be 4-byte aligned (%s may have any alignment)", what, unaligned); return TOAD_EALIGN; }
     if (Ho == 0 || Wo == 0) return TOAD_OK;
     int shift = 2;
     while ((1 << shift) < cell) ++shift;
     // the tent's variant: none; one quadrant per lane (cell >= 8); cell == 4, where at down == 4 a canvas pixel is a whole cell and the tent is the own value
     const int sm = !smooth || cell == down ? 0 : cell == 4 ? 2 : 1;
     const HeatPxArgs a = {region, pitch, Hi, Wi, cells, Gy, Gx, shift, alpha, mask, mask_pitch, Hm, Wm, mshift, mask_thresh, out, out_pitch, (unsigned)nchunks};
-    hipStream_t st = (hipStream_t)stream;
-#define TOAD_HEAT_PX(D, S, M) hipLaunchKernelGGL((heat_blend_px_kernel<D, S, M>), dim3((unsigned)blocks), dim3(256), 0, st, a, lut)
-#define TOAD_HEAT_PX_S(D, M) \
-    switch (sm) {            \
-        case 0: TOAD_HEAT_PX(D, 0, M); break; \
-        case 1: TOAD_HEAT_PX(D, 1, M); break; \
-        default: TOAD_HEAT_PX(D, 2, M); break; \
+#define TOAD_HEAT(D, S, M) \
+    case 8 * D + 2 * S + M: hipLaunchKernelGGL((heat_blend_px_kernel<D, S, M != 0>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, lut); break;
+    switch (8 * down + 2 * sm + (mask ? 1 : 0)) {                    // <D, 0, 0> is the flat canvas; variant 2 does not occur at down == 4 (cell == down)
+        TOAD_HEAT(1, 0, 0) TOAD_HEAT(1, 0, 1) TOAD_HEAT(1, 1, 0) TOAD_HEAT(1, 1, 1) TOAD_HEAT(1, 2, 0) TOAD_HEAT(1, 2, 1)
+        TOAD_HEAT(2, 0, 0) TOAD_HEAT(2, 0, 1) TOAD_HEAT(2, 1, 0) TOAD_HEAT(2, 1, 1) TOAD_HEAT(2, 2, 0) TOAD_HEAT(2, 2, 1)
+        TOAD_HEAT(4, 0, 0) TOAD_HEAT(4, 0, 1) TOAD_HEAT(4, 1, 0) TOAD_HEAT(4, 1, 1)
     }
-#define TOAD_HEAT_PX_M(D) \
-    if (mask) { TOAD_HEAT_PX_S(D, true) } else { TOAD_HEAT_PX_S(D, false) }
-    switch (down) {
-        case 1: TOAD_HEAT_PX_M(1); break;
-        case 2: TOAD_HEAT_PX_M(2); break;
-        default:                                                      // down == 4: variant 2 does not occur (cell == down)
-            if (mask) { if (sm) TOAD_HEAT_PX(4, 1, true); else TOAD_HEAT_PX(4, 0, true); }
-            else { if (sm) TOAD_HEAT_PX(4, 1, false); else TOAD_HEAT_PX(4, 0, false); }
-            break;
-    }
-#undef TOAD_HEAT_PX_M
-#undef TOAD_HEAT_PX_S
-#undef TOAD_HEAT_PX
+#undef TOAD_HEAT
     return check_launch(what);
+}
+
+extern "C" int toad_region_heat_blend_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx, int cell,
+                                         const unsigned char *lut, int alpha, int down, unsigned char *out, int64_t out_pitch, void *stream) {
+    return launch_heat_blend("toad_region_heat_blend_u8", "the region and the canvas", region, pitch, Hr, Wr, cells, Gy, Gx, cell, lut, alpha, down, 0, nullptr, 0, 0,
+                             0, 0, 0, out, out_pitch, stream);
+}
+
+extern "C" int toad_region_heat_blend_px_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx, int cell,
+                                            const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch,
+                                            int Hm, int Wm, int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream) {
+    return launch_heat_blend("toad_region_heat_blend_px_u8", "the region, the mask and the canvas", region, pitch, Hr, Wr, cells, Gy, Gx, cell, lut, alpha, down,
+                             smooth, mask, mask_pitch, Hm, Wm, mask_down, mask_thresh, out, out_pitch, stream);
 }

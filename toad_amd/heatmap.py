@@ -136,7 +136,7 @@ def attention_canvas(region: torch.Tensor, origins, scores: torch.Tensor, tile=2
     0.4), ``lut`` uint8 [256,3] on the device (default ``jet_lut``), ``out`` as in ``ops.region_heat_blend``.
 
     ``smooth`` interpolates the colour index between cell centres and ``mask`` = (plane, t, mask_down) blends only tissue pixels (the module's per-pixel
-    definition; ``ops.region_heat_blend_px`` then takes the place of ``ops.region_heat_blend``). ``thresh`` makes a tile absent whose raw score is below
+    definition; without either ``ops.region_heat_blend_px`` is ``ops.region_heat_blend``, the same kernel). ``thresh`` makes a tile absent whose raw score is below
     it, ``binarize`` gives every present tile the top colour (``select_scores``).
 
     Two launches and a few small torch ops, no synchronisation. Empty ``origins`` give the box-filtered region."""
@@ -159,7 +159,5 @@ def attention_canvas(region: torch.Tensor, origins, scores: torch.Tensor, tile=2
     else:
         cells = torch.full((-(-hr // cell), -(-wr // cell)), -1, dtype=torch.int32, device=region.device)
     lut = jet_lut(region.device) if lut is None else lut
-    if not smooth and plane is None:
-        return ops.region_heat_blend(region, cells, cell, lut, a, down, out=out)
     return ops.region_heat_blend_px(region, cells, cell, lut, a, down, smooth=smooth, mask=plane, mask_down=mask_down if plane is not None else None,
                                     mask_thresh=t if plane is not None else 0, out=out)

@@ -1538,30 +1538,9 @@ def _heat_blend_args(name: str, region, cells, cell, lut, alpha, down, out):
     return pitch, hr, wr, ho, wo, out
 
 
-def region_heat_blend(region: torch.Tensor, cells: torch.Tensor, cell: int, lut: torch.Tensor, alpha: int, down: int, out=None) -> torch.Tensor:
-    """The heat-map canvas of one decoded uint8 region [Hr,Wr,3] (any row pitch, any alignment; read in place): uint8 [Hr // down, Wr // down, 3] on the
-    device. Per channel m = the down x down box mean rounded half up (partial boxes at the right and the bottom edge are dropped); the output is m where
-    the box's cell has cells = -1 and (alpha lut[cells][c] + (256 - alpha) m + 128) >> 8 elsewhere. cells int32 [ceil(Hr / cell), ceil(Wr / cell)] with
-    values -1 .. 255 (heat_cells), lut uint8 [256,3], alpha an int in [0, 256], down in HEAT_DOWNS. `out` may be a [Ho,Wo,3] uint8 view with strides
-    (pitch, 3, 1), a window of a larger canvas; it must not share storage with region. One launch, no synchronisation; an empty canvas launches nothing."""
-    pitch, hr, wr, ho, wo, out = _heat_blend_args("region_heat_blend", region, cells, cell, lut, alpha, down, out)
-    if ho == 0 or wo == 0:
-        return out
-    _lib.check(_lib.load().toad_region_heat_blend_u8(_p(region), pitch, hr, wr, _p(cells), cells.shape[0], cells.shape[1], cell, _p(lut), alpha, down,
-                                                     _p(out), _row_pitch(out, 3 * wo), _stream()), "toad_region_heat_blend_u8")
-    return out
-
-
-def region_heat_blend_px(region: torch.Tensor, cells: torch.Tensor, cell: int, lut: torch.Tensor, alpha: int, down: int, smooth: bool = False, mask=None,
-                         mask_down=None, mask_thresh: int = 0, out=None) -> torch.Tensor:
-    """region_heat_blend with the colour index and the alpha decided per canvas pixel (toad_region_heat_blend_px_u8; the definition is in
-    include/toad_hip.h and toad_amd.heatmap). ``smooth``: the index of a pixel is the bilinear tent between the centres of the four nearest cells, a
-    neighbour outside the table or without a value counting as the pixel's own cell; coverage edges stay sharp. ``mask``: a uint8 [Hr // mask_down,
-    Wr // mask_down] plane on the region's device (stride(1) == 1, any pitch, any alignment), ``mask_down`` in SEG_DOWNS and a multiple of ``down``,
-    ``mask_thresh`` an int in [0, 255]: only pixels whose mask pixel is > mask_thresh are blended, the others - the pixels of the partial boxes the plane
-    dropped among them - keep the box-filtered region. The (plane, t) pair of ``tissue.segment_tissue`` and its ``down`` are such a mask. With
-    smooth=False and mask=None the canvas is byte-equal to region_heat_blend's. One launch, no synchronisation; an empty canvas launches nothing."""
-    name = "region_heat_blend_px"
+def _heat_blend(name: str, region, cells, cell, lut, alpha, down, smooth, mask, mask_down, mask_thresh, out):
+    """The body of region_heat_blend and region_heat_blend_px: the px checks, then toad_<name>_u8 (both entries launch the same kernel; the flat one takes
+    no smooth and no mask arguments)."""
     pitch, hr, wr, ho, wo, out = _heat_blend_args(name, region, cells, cell, lut, alpha, down, out)
     if not isinstance(smooth, (bool, int)) or smooth not in (0, 1):
         raise ValueError(f"{name}: smooth must be False or True, got {smooth!r}")
@@ -1584,10 +1563,32 @@ def region_heat_blend_px(region: torch.Tensor, cells: torch.Tensor, cell: int, l
             mask, alpha, mp, hm, wm, md = None, 0, 0, 0, 0, 0
     if ho == 0 or wo == 0:
         return out
-    _lib.check(_lib.load().toad_region_heat_blend_px_u8(_p(region), pitch, hr, wr, _p(cells), cells.shape[0], cells.shape[1], cell, _p(lut), alpha, down,
-                                                        int(smooth), _p(mask), mp, hm, wm, md, mask_thresh if mask is not None else 0, _p(out),
-                                                        _row_pitch(out, 3 * wo), _stream()), "toad_region_heat_blend_px_u8")
+    px = () if name == "region_heat_blend" else (int(smooth), _p(mask), mp, hm, wm, md, mask_thresh if mask is not None else 0)
+    entry = f"toad_{name}_u8"
+    _lib.check(getattr(_lib.load(), entry)(_p(region), pitch, hr, wr, _p(cells), cells.shape[0], cells.shape[1], cell, _p(lut), alpha, down, *px, _p(out),
+                                           _row_pitch(out, 3 * wo), _stream()), entry)
     return out
+
+
+def region_heat_blend(region: torch.Tensor, cells: torch.Tensor, cell: int, lut: torch.Tensor, alpha: int, down: int, out=None) -> torch.Tensor:
+    """The heat-map canvas of one decoded uint8 region [Hr,Wr,3] (any row pitch, any alignment; read in place): uint8 [Hr // down, Wr // down, 3] on the
+    device. Per channel m = the down x down box mean rounded half up (partial boxes at the right and the bottom edge are dropped); the output is m where
+    the box's cell has cells = -1 and (alpha lut[cells][c] + (256 - alpha) m + 128) >> 8 elsewhere. cells int32 [ceil(Hr / cell), ceil(Wr / cell)] with
+    values -1 .. 255 (heat_cells), lut uint8 [256,3], alpha an int in [0, 256], down in HEAT_DOWNS. `out` may be a [Ho,Wo,3] uint8 view with strides
+    (pitch, 3, 1), a window of a larger canvas; it must not share storage with region. One launch, no synchronisation; an empty canvas launches nothing."""
+    return _heat_blend("region_heat_blend", region, cells, cell, lut, alpha, down, False, None, None, 0, out)
+
+
+def region_heat_blend_px(region: torch.Tensor, cells: torch.Tensor, cell: int, lut: torch.Tensor, alpha: int, down: int, smooth: bool = False, mask=None,
+                         mask_down=None, mask_thresh: int = 0, out=None) -> torch.Tensor:
+    """region_heat_blend with the colour index and the alpha decided per canvas pixel (toad_region_heat_blend_px_u8; the definition is in
+    include/toad_hip.h and toad_amd.heatmap). ``smooth``: the index of a pixel is the bilinear tent between the centres of the four nearest cells, a
+    neighbour outside the table or without a value counting as the pixel's own cell; coverage edges stay sharp. ``mask``: a uint8 [Hr // mask_down,
+    Wr // mask_down] plane on the region's device (stride(1) == 1, any pitch, any alignment), ``mask_down`` in SEG_DOWNS and a multiple of ``down``,
+    ``mask_thresh`` an int in [0, 255]: only pixels whose mask pixel is > mask_thresh are blended, the others - the pixels of the partial boxes the plane
+    dropped among them - keep the box-filtered region. The (plane, t) pair of ``tissue.segment_tissue`` and its ``down`` are such a mask. With
+    smooth=False and mask=None this is region_heat_blend: the same kernel. One launch, no synchronisation; an empty canvas launches nothing."""
+    return _heat_blend("region_heat_blend_px", region, cells, cell, lut, alpha, down, smooth, mask, mask_down, mask_thresh, out)
 
 
 def maxpool3x3s2_nhwc(x: torch.Tensor) -> torch.Tensor:

@@ -4,16 +4,18 @@ its alternation of the arms inside one process, warm-up of every arm, its four s
 
   resident: a synthetic slide of 4096 x 8192 pixels (100.7 MB) on the device, 256 x 256 tiles at stride 64 (61 x 125 tiles, cell 64, up to 16 tiles over
   a cell), about half of the tiles present with seeded scores, alpha 102, the jet colours; at down = 1 and at down = 4:
-      arm A   heat_cells_kernel + heat_blend_kernel<down> into a canvas allocated once;
-      arm B   the cell sums as 16 shifted adds on the small tables, repeat_interleave of the cell colours, the box sum as a reshape-sum, the blend in
-              int32 - several canvas-sized int32 intermediates are written and read again.
+      arm A   heat_cells_kernel + heat_blend_px_kernel<down,0,false> (ops.region_heat_blend) into a canvas allocated once;
+      arm B   the cell sums as 16 shifted adds on the small tables, a gather of the cell colours, the box sum as a reshape-sum, the blend in int32 -
+              several canvas-sized intermediates are written and read again. One torch definition serves this arm and --px's.
     Arm B's canvas is checked once to be bit-equal to arm A's. A region of 100.7 MB fits the 256 MB last-level cache, so each arm is timed twice: `_rot`
     calls walk round FOUR different slides (403 MB, every call finds its region evicted: the HBM figure, the one to quote) and `_same` calls repeat on
     one slide (the cache-resident figure). bytes/s = 3 Hr Wr read + 3 Ho Wo written over the call's time: the bytes the canvas NEEDS, for arm B too.
   launches: four calls of arm A (or B) on rotating slides, no warm-up, for a `rocprofv3 --kernel-trace --stats` run of its own.
-  px (--px): what the per-pixel pass (ops.region_heat_blend_px: heat_blend_px_kernel) costs over the flat one. Same slides, table and canvas; the mask of
-    each slide is the (plane, t) of tissue.segment_tissue at down 16, median 7, threshold 8. Arms, alternated in one process on the rotating slides:
-      flat      heat_cells_kernel + heat_blend_kernel<down> - arm A above, code this tool has always timed;
+  px (--px): what the per-pixel variants of the pass (ops.region_heat_blend_px) cost over the flat one, at down = 1, 2 and 4. Same slides, table and
+    canvas; the mask of each slide is the (plane, t) of tissue.segment_tissue at down 16, median 7, threshold 8. Arms, alternated in one process on the
+    rotating slides:
+      flat      arm A above, through ops.region_heat_blend;
+      px_plain  ops.region_heat_blend_px without keywords: the flat kernel through the other entry point;
       px_smooth / px_mask / px_both   heat_cells_kernel + heat_blend_px_kernel<down> with smooth, with the mask, with both;
       B_torch   px_both's definition in torch ops (gathers of the four neighbours, int64 canvas-sized intermediates), checked bit-equal to px_both on
                 every slide before anything is timed.
@@ -52,81 +54,32 @@ def make_table(seed, dev):
     return torch.where(torch.rand(NY, NX, generator=g) < 0.5, q, torch.full_like(q, -1)).to(dev)
 
 
-def hip_canvas(region, table, lut, down, out):
-    cells = ops.heat_cells(table, CELL, (0, 0), (TILE, TILE), (STRIDE, STRIDE), (NX, NY), (HR, WR))
-    return ops.region_heat_blend(region, cells, CELL, lut, ALPHA, down, out=out)
-
-
-def torch_canvas(region, table, lut, down):
-    """Arm B: the definition of include/toad_hip.h in torch ops, uint8 [HR // down, WR // down, 3]."""
-    ch, cs = TILE // CELL, STRIDE // CELL
-    present = (table >= 0).to(torch.int64)
-    q = table.clamp(min=0).to(torch.int64) * present
-    n = torch.zeros(GY, GX, dtype=torch.int64, device=region.device)
-    s = torch.zeros_like(n)
-    for a in range(ch):
-        for b in range(ch):
-            n[a:a + NY * cs:cs, b:b + NX * cs:cs] += present
-            s[a:a + NY * cs:cs, b:b + NX * cs:cs] += q
-    idx = torch.where(n > 0, (2 * s + 257 * n) // (514 * n.clamp(min=1)), torch.full_like(n, -1))
-    ho, wo, r = HR // down, WR // down, CELL // down
-    col = lut.to(torch.int32)[idx.clamp(min=0)].repeat_interleave(r, dim=0).repeat_interleave(r, dim=1)[:ho, :wo]
-    covered = (idx >= 0).repeat_interleave(r, dim=0).repeat_interleave(r, dim=1)[:ho, :wo].unsqueeze(2)
-    if down == 1:
-        m = region.to(torch.int32)
-    else:
-        m = (region[:ho * down, :wo * down].view(ho, down, wo, down, 3).sum(dim=(1, 3), dtype=torch.int32) + down * down // 2) // (down * down)
-    return torch.where(covered, (ALPHA * col + (256 - ALPHA) * m + 128) >> 8, m).to(torch.uint8)
-
-
-def setup(dev):
-    slides = [make_slide(s, dev) for s in range(4)]
-    return slides, make_table(11, dev), jet_lut(dev)
-
-
-def resident(seconds):
-    dev = torch.device("cuda:0")
-    slides, table, lut = setup(dev)
-    res = []
-    for down in (1, 4):
-        out = torch.empty((HR // down, WR // down, 3), dtype=torch.uint8, device=dev)
-        hip = lambda r: hip_canvas(r, table, lut, down, out)                   # noqa: E731
-        tor = lambda r: torch_canvas(r, table, lut, down)                      # noqa: E731
-        same = all(bool(torch.equal(hip(s), tor(s))) for s in slides)
-        if not same:                                                           # a wrong arm must not produce a quoted ratio
-            raise SystemExit(f"heatmap_bench: arm B's canvas differs from arm A's at down = {down}: nothing is timed")
-        covered = float((ops.heat_cells(table, CELL, (0, 0), (TILE, TILE), (STRIDE, STRIDE), (NX, NY), (HR, WR)) >= 0).float().mean())
-        arms = {"A_hip_rot": Rotating(hip, slides), "B_torch_rot": Rotating(tor, slides),
-                "A_hip_same": lambda: hip(slides[0]), "B_torch_same": lambda: tor(slides[0])}
-        t, iters = alternate(arms, seconds)
-        nbytes = 3 * HR * WR + 3 * (HR // down) * (WR // down)
-        a = t["A_hip_rot"]
-        a1, a2 = median(a[0::2]), median(a[1::2])
-        res.append(dict(kind="resident_heatmap", region=[HR, WR], tile=TILE, stride=STRIDE, cell=CELL, tiles=NX * NY, down=down, alpha=ALPHA,
-                        moved_bytes=nbytes, slides_rotated=len(slides), covered_cells=round(covered, 4), rounds=len(a), iters_per_round=iters,
-                        ms={k: round(median(v), 5) for k, v in t.items()}, ms_min={k: round(min(v), 5) for k, v in t.items()},
-                        ms_max={k: round(max(v), 5) for k, v in t.items()}, moved_tbps={k: round(nbytes / median(v) / 1e9, 3) for k, v in t.items()},
-                        arm_a_halves_ms=[round(a1, 5), round(a2, 5)], arm_a_spread=round(abs(a1 - a2) / median(a), 4),
-                        b_over_a_rot=round(median(t["B_torch_rot"]) / median(a), 2),
-                        b_over_a_same=round(median(t["B_torch_same"]) / median(t["A_hip_same"]), 2), hip_equals_torch=same))
-        del out
-    return res
-
-
 MASK_DOWN = 16
 
 
-def hip_canvas_px(region, table, lut, down, out, smooth, mask):
+def hip_canvas(region, table, lut, down, out, smooth=False, mask=None, px=True):
+    """The two launches. px=False goes through ops.region_heat_blend, the entry point without the keywords."""
     cells = ops.heat_cells(table, CELL, (0, 0), (TILE, TILE), (STRIDE, STRIDE), (NX, NY), (HR, WR))
+    if not px:
+        return ops.region_heat_blend(region, cells, CELL, lut, ALPHA, down, out=out)
     plane, t = mask if mask is not None else (None, 0)
     return ops.region_heat_blend_px(region, cells, CELL, lut, ALPHA, down, smooth=smooth, mask=plane, mask_down=MASK_DOWN if mask is not None else None,
                                     mask_thresh=t, out=out)
 
 
-def torch_canvas_px(region, table, lut, down, smooth, mask):
-    """The per-pixel definition of include/toad_hip.h in torch ops, uint8 [HR // down, WR // down, 3]."""
+def torch_canvas(region, table, lut, down, smooth=False, mask=None):
+    """The definition of include/toad_hip.h in torch ops, uint8 [HR // down, WR // down, 3]: the flat canvas without the keywords, the per-pixel one with."""
     dev = region.device
-    c = ops.heat_cells(table, CELL, (0, 0), (TILE, TILE), (STRIDE, STRIDE), (NX, NY), (HR, WR)).to(torch.int64).clamp(max=255)
+    ch, cs = TILE // CELL, STRIDE // CELL
+    present = (table >= 0).to(torch.int64)
+    q = table.clamp(min=0).to(torch.int64) * present
+    n = torch.zeros(GY, GX, dtype=torch.int64, device=dev)
+    s = torch.zeros_like(n)
+    for a in range(ch):
+        for b in range(ch):
+            n[a:a + NY * cs:cs, b:b + NX * cs:cs] += present
+            s[a:a + NY * cs:cs, b:b + NX * cs:cs] += q
+    c = torch.where(n > 0, (2 * s + 257 * n) // (514 * n.clamp(min=1)), torch.full_like(n, -1))
     ho, wo = HR // down, WR // down
     oy, ox = torch.arange(ho, device=dev) * down, torch.arange(wo, device=dev) * down
     own = c[oy // CELL][:, ox // CELL]
@@ -159,35 +112,54 @@ def torch_canvas_px(region, table, lut, down, smooth, mask):
     return torch.where(blend.unsqueeze(2), (ALPHA * col + (256 - ALPHA) * m + 128) >> 8, m).to(torch.uint8)
 
 
-def resident_px(seconds):
+def setup(dev):
+    slides = [make_slide(s, dev) for s in range(4)]
+    return slides, make_table(11, dev), jet_lut(dev)
+
+
+def resident(seconds, px):
+    """The resident figures (px=False) or the --px ones: the arms differ, the loop does not."""
     dev = torch.device("cuda:0")
     slides, table, lut = setup(dev)
-    masks = {s.data_ptr(): segment_tissue(s, MASK_DOWN, 7, 8) for s in slides}
+    masks = {s.data_ptr(): segment_tissue(s, MASK_DOWN, 7, 8) for s in slides} if px else {}
     res = []
-    for down in (1, 4):
+    for down in (1, 2, 4) if px else (1, 4):
         out = torch.empty((HR // down, WR // down, 3), dtype=torch.uint8, device=dev)
-        flat = lambda r: hip_canvas(r, table, lut, down, out)                                           # noqa: E731
-        px = lambda smooth, masked: (lambda r: hip_canvas_px(r, table, lut, down, out, smooth, masks[r.data_ptr()] if masked else None))      # noqa: E731
-        tor = lambda r: torch_canvas_px(r, table, lut, down, True, masks[r.data_ptr()])                 # noqa: E731
-        same = all(bool(torch.equal(px(True, True)(s), tor(s))) for s in slides)
-        same_flat = all(bool(torch.equal(px(False, False)(s).clone(), flat(s))) for s in slides)
+        hip = lambda smooth=False, masked=False, px=True: (                                             # noqa: E731
+            lambda r: hip_canvas(r, table, lut, down, out, smooth, masks[r.data_ptr()] if masked else None, px))
+        flat, most = hip(px=False), hip(px, px, px)                                                     # most: px_both, or the flat arm again
+        tor = lambda r: torch_canvas(r, table, lut, down, px, masks[r.data_ptr()] if px else None)      # noqa: E731
+        same = all(bool(torch.equal(most(s), tor(s))) for s in slides)
+        same_flat = all(bool(torch.equal(hip()(s).clone(), flat(s))) for s in slides)
         if not (same and same_flat):                                           # a wrong arm must not produce a quoted ratio
-            raise SystemExit(f"heatmap_bench: px_both differs from its torch arm ({same}) or px without keywords from the flat pass ({same_flat}) at down = "
-                             f"{down}: nothing is timed")
-        changed = float((px(True, True)(slides[0]).clone() != flat(slides[0])).any(dim=2).float().mean())
-        arms = {"flat": Rotating(flat, slides), "px_smooth": Rotating(px(True, False), slides), "px_mask": Rotating(px(False, True), slides),
-                "px_both": Rotating(px(True, True), slides), "B_torch": Rotating(tor, slides)}
+            raise SystemExit(f"heatmap_bench: the HIP canvas differs from its torch arm ({same}) or px without keywords from the flat pass ({same_flat}) "
+                             f"at down = {down}, px = {px}: nothing is timed")
+        if px:
+            arms = {"flat": Rotating(flat, slides), "px_plain": Rotating(hip(), slides), "px_smooth": Rotating(hip(True), slides),
+                    "px_mask": Rotating(hip(False, True), slides), "px_both": Rotating(most, slides), "B_torch": Rotating(tor, slides)}
+        else:
+            arms = {"A_hip_rot": Rotating(flat, slides), "B_torch_rot": Rotating(tor, slides),
+                    "A_hip_same": lambda: flat(slides[0]), "B_torch_same": lambda: tor(slides[0])}
         t, iters = alternate(arms, seconds)
         nbytes = 3 * HR * WR + 3 * (HR // down) * (WR // down)
-        a = t["flat"]
+        a = t["flat" if px else "A_hip_rot"]
         a1, a2 = median(a[0::2]), median(a[1::2])
-        res.append(dict(kind="resident_heatmap_px", region=[HR, WR], tile=TILE, stride=STRIDE, cell=CELL, down=down, alpha=ALPHA, mask_down=MASK_DOWN,
-                        moved_bytes=nbytes, slides_rotated=len(slides), pixels_changed_vs_flat=round(changed, 4), rounds=len(a), iters_per_round=iters,
-                        ms={k: round(median(v), 5) for k, v in t.items()}, ms_min={k: round(min(v), 5) for k, v in t.items()},
-                        ms_max={k: round(max(v), 5) for k, v in t.items()}, moved_tbps={k: round(nbytes / median(v) / 1e9, 3) for k, v in t.items()},
-                        flat_halves_ms=[round(a1, 5), round(a2, 5)], flat_spread=round(abs(a1 - a2) / median(a), 4),
-                        px_over_flat={k: round(median(t[k]) / median(a), 4) for k in ("px_smooth", "px_mask", "px_both")},
-                        torch_over_px_both=round(median(t["B_torch"]) / median(t["px_both"]), 2), px_equals_torch=same, px_plain_equals_flat=same_flat))
+        halves, spread = [round(a1, 5), round(a2, 5)], round(abs(a1 - a2) / median(a), 4)
+        rec = dict(kind="resident_heatmap_px" if px else "resident_heatmap", region=[HR, WR], tile=TILE, stride=STRIDE, cell=CELL, down=down, alpha=ALPHA,
+                   moved_bytes=nbytes, slides_rotated=len(slides), rounds=len(a), iters_per_round=iters,
+                   ms={k: round(median(v), 5) for k, v in t.items()}, ms_min={k: round(min(v), 5) for k, v in t.items()},
+                   ms_max={k: round(max(v), 5) for k, v in t.items()}, moved_tbps={k: round(nbytes / median(v) / 1e9, 3) for k, v in t.items()})
+        if px:
+            changed = float((most(slides[0]).clone() != flat(slides[0])).any(dim=2).float().mean())
+            rec.update(mask_down=MASK_DOWN, pixels_changed_vs_flat=round(changed, 4), flat_halves_ms=halves, flat_spread=spread,
+                       px_over_flat={k: round(median(t[k]) / median(a), 4) for k in ("px_plain", "px_smooth", "px_mask", "px_both")},
+                       torch_over_px_both=round(median(t["B_torch"]) / median(t["px_both"]), 2), px_equals_torch=same, px_plain_equals_flat=same_flat)
+        else:
+            covered = float((ops.heat_cells(table, CELL, (0, 0), (TILE, TILE), (STRIDE, STRIDE), (NX, NY), (HR, WR)) >= 0).float().mean())
+            rec.update(tiles=NX * NY, covered_cells=round(covered, 4), arm_a_halves_ms=halves, arm_a_spread=spread,
+                       b_over_a_rot=round(median(t["B_torch_rot"]) / median(a), 2),
+                       b_over_a_same=round(median(t["B_torch_same"]) / median(t["A_hip_same"]), 2), hip_equals_torch=same)
+        res.append(rec)
         del out
     return res
 
@@ -199,7 +171,7 @@ def launches(arm, down, calls=4):
     out = torch.empty((HR // down, WR // down, 3), dtype=torch.uint8, device=dev)
     torch.cuda.synchronize()
     for i in range(calls):
-        hip_canvas(slides[i % 4], table, lut, down, out) if arm == "A" else torch_canvas(slides[i % 4], table, lut, down)
+        hip_canvas(slides[i % 4], table, lut, down, out, px=False) if arm == "A" else torch_canvas(slides[i % 4], table, lut, down)
     torch.cuda.synchronize()
     return [dict(kind="launches_heatmap", calls=calls, arm=arm, down=down)]
 
@@ -213,7 +185,7 @@ def main():
     ap.add_argument("--seconds", type=float, default=3.0)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    res = launches(a.arm, a.down) if a.launches else resident_px(a.seconds) if a.px else resident(a.seconds)
+    res = launches(a.arm, a.down) if a.launches else resident(a.seconds, a.px)
     lines = [json.dumps(r) for r in res]
     print("\n".join(lines), flush=True)
     if a.out:
