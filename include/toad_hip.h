@@ -453,6 +453,28 @@ int toad_region_heat_blend_px_u8(const unsigned char *region, int64_t pitch, int
                                  const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm,
                                  int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream);
 
+/* The per-pixel canvas at overview scale (additive to ABI 15 too): the same 21 arguments and the same definition with down in {8, 16, 32} - the slide
+ * overview CLAM renders at its vis_level - in one streaming pass over the region, without a full-size canvas in between. The two calls above keep
+ * refusing such a down. For canvas pixel (ox, oy):
+ *   canvas        Ho = Hr / down, Wo = Wr / down (partial boxes at the right and the bottom edge are dropped); per channel
+ *                     m = (sum of the down x down box + down * down / 2) / (down * down).
+ *   own           own = cells[(down * oy) / cell][(down * ox) / cell], values above 255 read as 255. down <= cell is required, so that a box lies in one
+ *                 cell: cell = 4 is never legal here.
+ *   colour index  smooth = 0: idx_px = own. smooth = 1: the tent above, taken at the box centre: p = 2 * down * ox + down - cell, g0 = floor(p / (2 * cell)),
+ *                 f = p - 2 * cell * g0, the same along y; a neighbour outside the table or without a value counts as `own`;
+ *                 idx_px = (sum wy * wx * v + 2 * cell * cell) >> (2 * log2(cell) + 2). Where down == cell the tent is exactly `own`.
+ *   tissue        mask == NULL: every pixel. Otherwise iff mx = (down * ox) / mask_down < Wm, my = (down * oy) / mask_down < Hm and
+ *                 mask[my][mx] > mask_thresh; mask_down in 1 .. 32 and a multiple of down, so it lies in {down, .., 32}: one mask byte per box.
+ *   output byte   (alpha * lut[idx_px][c] + (256 - alpha) * m + 128) >> 8 where own >= 0 and the pixel is tissue, m elsewhere.
+ * Refusals in the order of toad_region_heat_blend_px_u8, with: down not in {8, 16, 32}, and directly after it down > cell (TOAD_ESHAPE). cells 4-byte
+ * aligned (TOAD_EALIGN); the region, the mask, lut and the canvas may lie at any byte address and pitch. No byte outside region + y * pitch +
+ * [0, 3 * down * Wo), 0 <= y < down * Ho, is read; no byte outside out + y * out_pitch + [0, 3 * Wo), 0 <= y < Ho, is written, and each of those once.
+ * Ho == 0 or Wo == 0: returns TOAD_OK and launches nothing. One launch: 3 * Hr * Wr bytes read, 3 * Ho * Wo written. Several levels in one call are
+ * not done. */
+int toad_region_heat_thumb_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx, int cell,
+                              const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm,
+                              int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream);
+
 /* ---- Segmented tissue selection: CLAM's recipe - a median-filtered saturation channel of a low-resolution level, thresholded by a fixed value or by
  * Otsu's - defined in integers (additive to ABI 15 too). A second selector next to the per-pixel predicate above, which does not change; csrc/tissue_seg.hip.
  *   1 box filter  down in {1, 2, 4, 8, 16, 32} (TOAD_ESHAPE otherwise): Hp = Hr / down, Wp = Wr / down, partial boxes at the right and the bottom edge are

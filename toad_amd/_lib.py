@@ -101,6 +101,8 @@ SIGNATURES = {
     "toad_region_heat_blend_u8": (I, [P, I64, I, I, P, I, I, I, P, I, I, P, I64, P]),
     # ... and the same canvas with the colour index (bilinear tent) and the alpha (tissue mask) per pixel: additive to ABI 15
     "toad_region_heat_blend_px_u8": (I, [P, I64, I, I, P, I, I, I, P, I, I, I, P, I64, I, I, I, I, P, I64, P]),
+    # ... and that canvas at overview scale, down in 8, 16, 32, in one pass: additive to ABI 15
+    "toad_region_heat_thumb_u8": (I, [P, I64, I, I, P, I, I, I, P, I, I, I, P, I64, I, I, I, I, P, I64, P]),
     # ... and the second tissue selector, CLAM's recipe in integers (saturation plane, median, histogram, cells): additive to ABI 15
     "toad_region_saturation_u8": (I, [P, I64, I, I, I, I, P, I64, P]),
     "toad_plane_median_u8": (I, [P, I64, I, I, I, P, I64, P, P]),

@@ -15,8 +15,12 @@
 //               [Hm][Wm] of mask_down x mask_down boxes a pixel is blended only where mask[(down oy) / mask_down][(down ox) / mask_down] > mask_thresh;
 //               the pixels of the partial boxes the plane dropped are not. Coverage and mask edges stay sharp: only the colour inside is interpolated.
 //
-// Two kernels:
-//   heat_cells_kernel                       one thread per cell: the covering tiles' index ranges in closed form from the lattice in cell units, a loop over them.
+//   overview    (toad_region_heat_thumb_u8) the per-pixel canvas at down in {8, 16, 32} with down <= cell, so that a box still lies in one cell: the
+//               slide overview of an 80k x 80k region without a full-size canvas in between.
+//
+// Three kernels:
+//   heat_thumb_kernel<DOWN>                 the overview canvas: the same streaming pass with a box's lanes and waves reduced, one thread per canvas pixel blends.
+//   heat_cells_kernel                      one thread per cell: the covering tiles' index ranges in closed form from the lattice in cell units, a loop over them.
 //   heat_blend_px_kernel<DOWN,SMOOTH,MASK>  one streaming pass over the region: read uint8, write uint8. <DOWN,0,false> is the flat canvas (one colour and one
 //                                           alpha per cell: both entry points launch it); the others decide the index, the colour and the alpha per canvas pixel.
 #include "region_u8.h"
@@ -320,6 +324,94 @@ __global__ __launch_bounds__(256, 8) void heat_blend_px_kernel(const HeatPxArgs 
     heat_px_lane<DOWN, SMOOTH, MASK>(a, lut_s, blockIdx.x % a.nchunks, blockIdx.x / a.nchunks, wave, lane);
 }
 
+// ---- the overview canvas: toad_region_heat_thumb_u8, down in {8, 16, 32} ----
+// sat_plane_kernel's DOWN >= 8 arm (tissue_seg.hip) with the three channel means kept and the blend in the tail. The work split and its addresses are
+// region_u8.h's, on strips of RB = strip_rows(DOWN) rows (12 or 24 dwords a lane in flight): the DOWN / 4 lanes of a box are summed by DPP moves, the 2 or
+// 4 waves of a box row meet in 3 KB of LDS behind the one barrier all 256 threads reach, and NB CPR = 64, 16 or 8 threads each finish one canvas pixel.
+// Hi = DOWN Ho and Wi = DOWN Wo are the rows and columns some box consumes: nothing outside them is read. Wi is a multiple of DOWN >= 8, so a lane has
+// all 4 of its pixels or none; a wave off the plain path holds zeros for what is not consumed, which is harmless because a box lies wholly inside
+// Hi x Wi or wholly outside. A box lies in one cell (down <= cell) and in one mask pixel (mask_down a multiple of down), so the pixel's own cell, its
+// tent (the formula of heat_px_lane's SMOOTH 1 at the box's corner: g0 and f are the pixel's) and its mask byte are single loads; smooth and the mask
+// are run-time values because only these few threads look at them, and the colour comes straight from lut in global memory. Every canvas byte is
+// written once, by one lane, with byte stores at any address; nothing outside oy out_pitch + [0, 3 Wo), oy < Ho, is written.
+template <int DOWN>
+__global__ __launch_bounds__(256) void heat_thumb_kernel(const HeatPxArgs a, int smooth, const unsigned char *__restrict__ lut) {
+    constexpr int RB = strip_rows(DOWN), RW = RB / 4;              // rows per workgroup, per wave
+    constexpr int LANES = DOWN / 4, SH = DOWN == 8 ? 6 : DOWN == 16 ? 8 : 10;      // lanes per box, log2(DOWN^2)
+    constexpr int NB = RB / DOWN, WPB = 4 / NB, CPR = 64 / LANES;  // box rows per workgroup, waves per box row, boxes per chunk
+    __shared__ int part[3][4][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned chunk = blockIdx.x % a.nchunks, rb = blockIdx.x / a.nchunks;
+    const unsigned x = chunk * 256u + (unsigned)lane * 4u, off = 3u * x;
+    const int64_t y0 = (int64_t)rb * RB + wave * RW;               // first row of this wave (may lie below Hi: then it reads nothing)
+    const unsigned char *src = a.region + y0 * a.pitch + off;
+    unsigned w[RW][3];
+    if (chunk * 256u + 256u <= (unsigned)a.Wi && y0 + RW <= a.Hi) {  // wave-uniform: all 768 bytes of all RW rows are consumed
+#pragma unroll
+        for (int r = 0; r < RW; ++r)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) w[r][k] = *reinterpret_cast<const u32_a1 *>(src + r * a.pitch + 4 * k);
+    } else {
+        const int rows = (int)max((int64_t)0, min((int64_t)RW, (int64_t)a.Hi - y0));
+        const int npx = x < (unsigned)a.Wi ? 4 : 0;                // Wi is a multiple of 8
+#pragma unroll
+        for (int r = 0; r < RW; ++r) load_px4(src + r * a.pitch, r < rows ? npx : 0, w[r]);
+    }
+    unsigned b[12];                                                // the 12 column sums over the wave's rows, each at most 8 * 255
+    column_sums<RW>(w, b);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) part[c][wave][lane] = lanes_allreduce_sum<LANES>((int)(b[c] + b[c + 3] + b[c + 6] + b[c + 9]));
+    __syncthreads();
+    if (tid >= NB * CPR) return;
+    const int band = tid / CPR, bx = tid - band * CPR;
+    const int64_t oy = (int64_t)rb * NB + band;
+    const unsigned ox = chunk * CPR + bx;
+    if (oy * DOWN >= a.Hi || ox * DOWN >= (unsigned)a.Wi) return;
+    int m[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        int t = 0;
+#pragma unroll
+        for (int k = 0; k < WPB; ++k) t += part[c][band * WPB + k][bx * LANES];
+        m[c] = (t + (1 << (SH - 1))) >> SH;
+    }
+    const int64_t py0 = oy * DOWN;                                 // the box's corner in the region
+    const int px0 = (int)(ox * DOWN);
+    const int own = min(a.cells[(py0 >> a.shift) * a.Gx + (px0 >> a.shift)], 255);
+    int idx = max(own, 0);
+    if (smooth) {
+        const int cell = 1 << a.shift, c2 = 2 * cell;
+        const int px = 2 * px0 + DOWN - cell;                      // 3 Wr < 2^31, so 2 x fits
+        const int64_t py = 2 * py0 + DOWN - cell;
+        const int gx0 = px >> (a.shift + 1), fx = px & (c2 - 1);
+        const int gy0 = (int)(py >> (a.shift + 1)), fy = (int)(py & (c2 - 1));
+        int H[2];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            int v[2];
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int yy = gy0 + r, xx = gx0 + c;
+                const bool in = yy >= 0 && yy < a.Gy && xx >= 0 && xx < a.Gx;
+                const int t = in ? a.cells[(int64_t)yy * a.Gx + xx] : -1;
+                v[c] = t >= 0 ? min(t, 255) : idx;
+            }
+            H[r] = c2 * v[0] + fx * (v[1] - v[0]);
+        }
+        idx = (c2 * H[0] + fy * (H[1] - H[0]) + 2 * cell * cell) >> (2 * a.shift + 2);
+    }
+    bool tissue = true;
+    if (a.mask) {
+        const int64_t my = py0 >> a.mshift;
+        const int mx = px0 >> a.mshift;
+        tissue = my < a.Hm && mx < a.Wm && (int)a.mask[my * a.mask_pitch + mx] > a.mask_thresh;
+    }
+    const int al = own >= 0 && tissue ? a.alpha : 0;               // alpha' = 0 leaves m: (256 m + 128) >> 8
+    unsigned char *d = a.out + oy * a.out_pitch + 3u * ox;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) d[c] = (unsigned char)((al * (int)lut[3 * idx + c] + (256 - al) * m[c] + 128) >> 8);
+}
+
 }  // namespace toad
 
 using namespace toad;
@@ -343,16 +435,26 @@ extern "C" int toad_heat_cells(const int *tile_q, int nx, int ny, int cell, int 
     return check_launch(what);
 }
 
-// Both blend entry points: every check in the order in which the first failing one wins, the geometry, the choice of the kernel. The flat entry passes
-// smooth = 0 and mask = NULL, for which the smooth and mask checks are no-ops; `unaligned` names the planes its alignment message lets lie anywhere.
-static int launch_heat_blend(const char *what, const char *unaligned, const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx,
+// All three canvas entry points: every check in the order in which the first failing one wins, the geometry, the choice of the kernel. The flat entry passes
+// smooth = 0 and mask = NULL, for which the smooth and mask checks are no-ops; `unaligned` names the planes its alignment message lets lie anywhere. `thumb`
+// is the overview entry: down in {8, 16, 32} and at most the cell, strips of strip_rows(down) rows, heat_thumb_kernel<down>.
+static int launch_heat_blend(const char *what, const char *unaligned, bool thumb, const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx,
                              int cell, const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm,
                              int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream) {
     if (!region || !cells || !lut || !out) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
     if (int rc = check_cell(what, cell)) return rc;
     if (int rc = check_hw(what, "Hr", Hr, "Wr", Wr)) return rc;
     if (alpha < 0 || alpha > 256) { set_error("%s: alpha = %d must lie in [0, 256] (256 = the colour alone)", what, alpha); return TOAD_ESHAPE; }
-    if (down != 1 && down != 2 && down != 4) { set_error("%s: down = %d is not one of 1, 2, 4", what, down); return TOAD_ESHAPE; }
+    if (thumb) {
+        if (down != 8 && down != 16 && down != 32) { set_error("%s: down = %d is not one of 8, 16, 32", what, down); return TOAD_ESHAPE; }
+        if (down > cell) {
+            set_error("%s: down = %d exceeds cell = %d (a canvas box must lie in one cell)", what, down, cell);
+            return TOAD_ESHAPE;
+        }
+    } else if (down != 1 && down != 2 && down != 4) {
+        set_error("%s: down = %d is not one of 1, 2, 4", what, down);
+        return TOAD_ESHAPE;
+    }
     if (smooth != 0 && smooth != 1) { set_error("%s: smooth = %d must be 0 or 1", what, smooth); return TOAD_EINVAL; }
     if (int rc = check_region_pitch(what, pitch, Wr)) return rc;
     int mshift = 0;
@@ -384,7 +486,8 @@ static int launch_heat_blend(const char *what, const char *unaligned, const unsi
         return TOAD_ESHAPE;
     }
     const int Hi = Ho * down, Wi = Wo * down;
-    const int64_t nchunks = ((int64_t)Wi + 255) / 256, blocks = nchunks * (((int64_t)Hi + 15) / 16);
+    const int rb = thumb ? strip_rows(down) : 16;
+    const int64_t nchunks = ((int64_t)Wi + 255) / 256, blocks = nchunks * (((int64_t)Hi + rb - 1) / rb);
     if (int rc = check_blocks(what, "region", blocks)) return rc;
     if (!aligned4(cells)) { set_error("%s: cells (int32 [Gy][Gx]) must be 4-byte aligned (%s may have any alignment)", what, unaligned); return TOAD_EALIGN; }
     if (Ho == 0 || Wo == 0) return TOAD_OK;
@@ -393,6 +496,14 @@ static int launch_heat_blend(const char *what, const char *unaligned, const unsi
     // the tent's variant: none; one quadrant per lane (cell >= 8); cell == 4, where at down == 4 a canvas pixel is a whole cell and the tent is the own value
     const int sm = !smooth || cell == down ? 0 : cell == 4 ? 2 : 1;
     const HeatPxArgs a = {region, pitch, Hi, Wi, cells, Gy, Gx, shift, alpha, mask, mask_pitch, Hm, Wm, mshift, mask_thresh, out, out_pitch, (unsigned)nchunks};
+    if (thumb) {                                                     // cell == down: the tent is the own value, its four loads are not needed
+        const int tent = smooth && cell != down;
+#define TOAD_THUMB(D) \
+    case D: hipLaunchKernelGGL(heat_thumb_kernel<D>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, tent, lut); break;
+        switch (down) { TOAD_THUMB(8) TOAD_THUMB(16) TOAD_THUMB(32) }
+#undef TOAD_THUMB
+        return check_launch(what);
+    }
 #define TOAD_HEAT(D, S, M) \
     case 8 * D + 2 * S + M: hipLaunchKernelGGL((heat_blend_px_kernel<D, S, M != 0>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, lut); break;
     switch (8 * down + 2 * sm + (mask ? 1 : 0)) {                    // <D, 0, 0> is the flat canvas; variant 2 does not occur at down == 4 (cell == down)
@@ -406,13 +517,20 @@ static int launch_heat_blend(const char *what, const char *unaligned, const unsi
 
 extern "C" int toad_region_heat_blend_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx, int cell,
                                          const unsigned char *lut, int alpha, int down, unsigned char *out, int64_t out_pitch, void *stream) {
-    return launch_heat_blend("toad_region_heat_blend_u8", "the region and the canvas", region, pitch, Hr, Wr, cells, Gy, Gx, cell, lut, alpha, down, 0, nullptr, 0, 0,
+    return launch_heat_blend("toad_region_heat_blend_u8", "the region and the canvas", false, region, pitch, Hr, Wr, cells, Gy, Gx, cell, lut, alpha, down, 0, nullptr, 0, 0,
                              0, 0, 0, out, out_pitch, stream);
 }
 
 extern "C" int toad_region_heat_blend_px_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx, int cell,
                                             const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch,
                                             int Hm, int Wm, int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream) {
-    return launch_heat_blend("toad_region_heat_blend_px_u8", "the region, the mask and the canvas", region, pitch, Hr, Wr, cells, Gy, Gx, cell, lut, alpha, down,
+    return launch_heat_blend("toad_region_heat_blend_px_u8", "the region, the mask and the canvas", false, region, pitch, Hr, Wr, cells, Gy, Gx, cell, lut, alpha, down,
+                             smooth, mask, mask_pitch, Hm, Wm, mask_down, mask_thresh, out, out_pitch, stream);
+}
+
+extern "C" int toad_region_heat_thumb_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx, int cell,
+                                         const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch,
+                                         int Hm, int Wm, int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream) {
+    return launch_heat_blend("toad_region_heat_thumb_u8", "the region, the mask and the canvas", true, region, pitch, Hr, Wr, cells, Gy, Gx, cell, lut, alpha, down,
                              smooth, mask, mask_pitch, Hm, Wm, mask_down, mask_thresh, out, out_pitch, stream);
 }

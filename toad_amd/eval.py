@@ -275,12 +275,15 @@ def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region
     ``smooth``, ``thresh``, ``binarize``: ``heatmap.attention_canvas`` (the colour index interpolated between cell centres; tiles below a percentile
     score dropped; present tiles saturated). ``tissue_mask=True`` (CLAM's ``segment=True``) colours only the tissue pixels of a selected tile: it needs
     a ``segment`` dict, whose mask plane - the one the tiles were counted on, nothing is recomputed - goes to the renderer with its threshold and its
-    ``down``; that ``down`` must be a multiple of the canvas ``down`` (ValueError otherwise, before anything is launched). CLAM's Gaussian ``blur``, its
-    vis-level pyramid and saving the image are not done here."""
+    ``down``; the canvas ``down`` must be one of 1 .. 32 and that ``down`` a multiple of it (ValueError otherwise, before anything is launched).
+
+    ``down`` in 8, 16, 32 gives the slide overview in one pass (``ops.region_heat_thumb``; the lattice's cell must be at least ``down``). With the CLAM
+    default segment ``down = 16`` masked canvases at 8 and 16 work; one at 32 needs ``segment=dict(down=32)``. CLAM's Gaussian ``blur``, several levels
+    of its vis-level pyramid in one call (one level per call is done) and saving the image are not done here."""
     from .heatmap import attention_canvas
     if tissue_mask and isinstance(segment, dict):                   # (without a dict _select_origins refuses)
         seg_down = _segment_down(segment)
-        if down not in (1, 2, 4) or not isinstance(seg_down, int) or seg_down % down:
+        if down not in (1, 2, 4, 8, 16, 32) or not isinstance(seg_down, int) or seg_down % down:
             raise ValueError(f"tissue_mask=True: the segment down = {seg_down!r} must be a multiple of the canvas down = {down!r} (a canvas box must lie "
                              "in one mask pixel)")
     origins, scores, mask = _tissue_scores(extractor, model, region, tile, stride, min_fraction, sat_thresh, val_min, bag_dtype, True, segment,

@@ -23,12 +23,17 @@ pixel (ox, oy), ``own`` being the value of the cell that holds it:
 * the byte is ``(alpha lut[idx_px][c] + (256 - alpha) m + 128) >> 8`` where ``own >= 0`` and the pixel is tissue, ``m`` elsewhere: coverage edges and
   mask edges stay sharp, only the colour inside them is interpolated.
 
+At overview scale - CLAM renders at a ``vis_level`` whose downsample is typically 16 to 64 - the same per-pixel definition holds with ``down`` in 8, 16,
+32 (``ops.region_heat_thumb``): one pass over the region, no full-size canvas in between and no second rounding. There ``down`` must not exceed the
+lattice's cell, so that a canvas box still lies in one cell, and ``mask_down`` is a multiple of ``down`` as before.
+
 This is CLAM's ``segment=True`` and a one-cell-wide stand-in for its ``blur``; it is NOT CLAM's Gaussian and does not claim to be. ``thresh`` and
 ``binarize`` (CLAM's ``thresh``, ``binarize``) act on the tiles' scores before the table is built.
 
 Conventions as in ``toad_amd.tissue``: ``tile`` = int or (H, W), ``stride`` = int or (sy, sx), ``origin`` = (x, y) of the lattice's first tile.
 Seams between separately rendered regions (a neighbour outside the table counts as ``own``), smoothing kernels wider than one cell, cell-level
-pre-smoothing passes, CLAM's Gaussian, its vis-level pyramid and saving images are not done here."""
+pre-smoothing passes, CLAM's Gaussian, several levels of its vis-level pyramid in one call (one level per call is done) and saving images are not done
+here."""
 from __future__ import annotations
 
 import numpy as np
@@ -139,10 +144,17 @@ def attention_canvas(region: torch.Tensor, origins, scores: torch.Tensor, tile=2
     definition; without either ``ops.region_heat_blend_px`` is ``ops.region_heat_blend``, the same kernel). ``thresh`` makes a tile absent whose raw score is below
     it, ``binarize`` gives every present tile the top colour (``select_scores``).
 
+    ``down`` in 8, 16, 32 renders the overview canvas through ``ops.region_heat_thumb`` with the same keywords and the same meaning; the lattice's cell
+    (``tissue.lattice_cell``) must be at least ``down`` (ValueError otherwise, before anything is launched).
+
     Two launches and a few small torch ops, no synchronisation. Empty ``origins`` give the box-filtered region."""
     _, hr, wr = ops._region_pitch(region, "attention_canvas")
     h, w, sy, sx, x0, y0 = _lattice_args(tile, stride, origin)
     cell = lattice_cell((h, w), (sy, sx), (x0, y0))
+    thumb = down in ops.HEAT_THUMB_DOWNS
+    if thumb and cell < down:
+        raise ValueError(f"attention_canvas: down = {down} exceeds the lattice's cell = {cell} (tile {(h, w)}, stride {(sy, sx)}, origin {(x0, y0)}): a canvas "
+                         "box must lie in one cell")
     a = _alpha_arg(alpha)
     if not isinstance(scores, torch.Tensor) or scores.device != region.device:
         raise ValueError(f"attention_canvas: scores must be a tensor on the region's device ({region.device}), got "
@@ -159,5 +171,6 @@ def attention_canvas(region: torch.Tensor, origins, scores: torch.Tensor, tile=2
     else:
         cells = torch.full((-(-hr // cell), -(-wr // cell)), -1, dtype=torch.int32, device=region.device)
     lut = jet_lut(region.device) if lut is None else lut
-    return ops.region_heat_blend_px(region, cells, cell, lut, a, down, smooth=smooth, mask=plane, mask_down=mask_down if plane is not None else None,
-                                    mask_thresh=t if plane is not None else 0, out=out)
+    blend = ops.region_heat_thumb if thumb else ops.region_heat_blend_px
+    return blend(region, cells, cell, lut, a, down, smooth=smooth, mask=plane, mask_down=mask_down if plane is not None else None,
+                 mask_thresh=t if plane is not None else 0, out=out)

@@ -1492,6 +1492,7 @@ def plane_area_select(labels: torch.Tensor, area: torch.Tensor, mode: int, limit
 
 
 HEAT_DOWNS = (1, 2, 4)                 # the box filters of csrc/heatmap.hip
+HEAT_THUMB_DOWNS = (8, 16, 32)         # ... and those of its overview canvas (region_heat_thumb), which must not exceed the cell
 
 
 def heat_cells(tile_q: torch.Tensor, cell: int, origin, tile, stride, n, region_hw) -> torch.Tensor:
@@ -1513,11 +1514,14 @@ def heat_cells(tile_q: torch.Tensor, cell: int, origin, tile, stride, n, region_
 
 
 def _heat_blend_args(name: str, region, cells, cell, lut, alpha, down, out):
-    """The checks region_heat_blend and region_heat_blend_px share -> (pitch, Hr, Wr, Ho, Wo, out)."""
+    """The checks region_heat_blend, region_heat_blend_px and region_heat_thumb share -> (pitch, Hr, Wr, Ho, Wo, out)."""
     pitch, hr, wr = _region_pitch(region, name)
     _cell_arg(name, cell)
-    if down not in HEAT_DOWNS:
-        raise ValueError(f"{name}: down must be one of {HEAT_DOWNS}, got {down!r}")
+    downs = HEAT_THUMB_DOWNS if name == "region_heat_thumb" else HEAT_DOWNS
+    if down not in downs:
+        raise ValueError(f"{name}: down must be one of {downs}, got {down!r}")
+    if down > cell:                                                  # (the overview canvas only: HEAT_DOWNS divide every cell)
+        raise ValueError(f"{name}: down = {down} exceeds cell = {cell}: a canvas box must lie in one cell")
     if not isinstance(alpha, int) or isinstance(alpha, bool) or not 0 <= alpha <= 256:
         raise ValueError(f"{name}: alpha must be an int in [0, 256], got {alpha!r}")
     _chk(cells, "cells", dtype=torch.int32)
@@ -1539,8 +1543,8 @@ def _heat_blend_args(name: str, region, cells, cell, lut, alpha, down, out):
 
 
 def _heat_blend(name: str, region, cells, cell, lut, alpha, down, smooth, mask, mask_down, mask_thresh, out):
-    """The body of region_heat_blend and region_heat_blend_px: the px checks, then toad_<name>_u8 (both entries launch the same kernel; the flat one takes
-    no smooth and no mask arguments)."""
+    """The body of region_heat_blend, region_heat_blend_px and region_heat_thumb: the px checks, then toad_<name>_u8 (the first two launch the same
+    kernel; the flat one takes no smooth and no mask arguments)."""
     pitch, hr, wr, ho, wo, out = _heat_blend_args(name, region, cells, cell, lut, alpha, down, out)
     if not isinstance(smooth, (bool, int)) or smooth not in (0, 1):
         raise ValueError(f"{name}: smooth must be False or True, got {smooth!r}")
@@ -1589,6 +1593,15 @@ def region_heat_blend_px(region: torch.Tensor, cells: torch.Tensor, cell: int, l
     dropped among them - keep the box-filtered region. The (plane, t) pair of ``tissue.segment_tissue`` and its ``down`` are such a mask. With
     smooth=False and mask=None this is region_heat_blend: the same kernel. One launch, no synchronisation; an empty canvas launches nothing."""
     return _heat_blend("region_heat_blend_px", region, cells, cell, lut, alpha, down, smooth, mask, mask_down, mask_thresh, out)
+
+
+def region_heat_thumb(region: torch.Tensor, cells: torch.Tensor, cell: int, lut: torch.Tensor, alpha: int, down: int, smooth: bool = False, mask=None,
+                      mask_down=None, mask_thresh: int = 0, out=None) -> torch.Tensor:
+    """region_heat_blend_px at overview scale (toad_region_heat_thumb_u8): ``down`` in HEAT_THUMB_DOWNS = 8, 16, 32, the same definition and the same
+    arguments, uint8 [Hr // down, Wr // down, 3] in ONE pass over the region - no full-size canvas in between, no second rounding. ``down`` must not
+    exceed ``cell`` (a canvas box must lie in one cell: ValueError before any launch), and ``mask_down`` is a multiple of ``down``, so it lies in
+    down .. 32. One launch, no synchronisation; an empty canvas launches nothing."""
+    return _heat_blend("region_heat_thumb", region, cells, cell, lut, alpha, down, smooth, mask, mask_down, mask_thresh, out)
 
 
 def maxpool3x3s2_nhwc(x: torch.Tensor) -> torch.Tensor:

@@ -22,8 +22,20 @@ its alternation of the arms inside one process, warm-up of every arm, its four s
     All arms move the same 3 Hr Wr + 3 Ho Wo bytes (the mask plane is 1 / 768 of the region). px_over_flat = median over median; flat_spread = the flat
     arm's own interleaved-halves spread, the yardstick for "no cost".
 
+  thumb (--thumb): what the overview canvas (ops.region_heat_thumb, heat_thumb_kernel<down>) costs at down = 8, 16 and 32. Same slides, table and colours;
+    the cell table is built once per run (ops.heat_cells is not timed in any arm), the mask of each slide is the (plane, t) of tissue.segment_tissue at
+    down 32, median 7, threshold 8. Arms, alternated in one process on the rotating slides:
+      T_flat / T_both   ops.region_heat_thumb without keywords / with smooth and the mask, into a canvas allocated once;
+      S                 the yardstick: ops.region_saturation at the same down (sat_plane_kernel<down>) - the same loads and the same reduction skeleton, a
+                        third of the output bytes;
+      P                 what was there before: ops.region_heat_blend_px at down = 4 with smooth and the mask into a canvas allocated once, then
+                        avg_pool2d by down / 4 and a round in torch ops. TIMED ONLY: it rounds twice and samples the tent and the mask at down = 4, so it
+                        is not bit-equal to T and is not checked against it.
+    T_flat and T_both are checked bit-equal to the torch statement of the definition (torch_canvas) on every slide before anything is timed. t_over_s =
+    median over median next to s_spread, S's own interleaved-halves spread; moved bytes = 3 Hr Wr read + 3 Ho Wo written.
+
 Prints one JSON line per result; --out FILE keeps them.
-usage: heatmap_bench.py [--launches --arm A|B --down D] [--px] [--seconds S] [--out FILE]"""
+usage: heatmap_bench.py [--launches --arm A|B --down D] [--px | --thumb] [--seconds S] [--out FILE]"""
 import argparse
 import json
 import os
@@ -67,7 +79,7 @@ def hip_canvas(region, table, lut, down, out, smooth=False, mask=None, px=True):
                                     mask_thresh=t, out=out)
 
 
-def torch_canvas(region, table, lut, down, smooth=False, mask=None):
+def torch_canvas(region, table, lut, down, smooth=False, mask=None, mask_down=MASK_DOWN):
     """The definition of include/toad_hip.h in torch ops, uint8 [HR // down, WR // down, 3]: the flat canvas without the keywords, the per-pixel one with."""
     dev = region.device
     ch, cs = TILE // CELL, STRIDE // CELL
@@ -102,7 +114,7 @@ def torch_canvas(region, table, lut, down, smooth=False, mask=None):
     if mask is not None:
         plane, t = mask
         hm, wm = plane.shape
-        my, mx = oy // MASK_DOWN, ox // MASK_DOWN
+        my, mx = oy // mask_down, ox // mask_down
         blend = blend & ((my < hm)[:, None] & (mx < wm)[None, :]) & (plane[my.clamp(max=hm - 1)][:, mx.clamp(max=wm - 1)] > t)
     col = lut.to(torch.int32)[idx.clamp(min=0)]
     if down == 1:
@@ -164,6 +176,64 @@ def resident(seconds, px):
     return res
 
 
+THUMB_MASK_DOWN = 32
+
+
+def thumb(seconds):
+    """The --thumb figures: one record per down in ops.HEAT_THUMB_DOWNS."""
+    import torch.nn.functional as F
+    dev = torch.device("cuda:0")
+    slides, table, lut = setup(dev)
+    masks = {s.data_ptr(): segment_tissue(s, THUMB_MASK_DOWN, 7, 8) for s in slides}
+    cells = ops.heat_cells(table, CELL, (0, 0), (TILE, TILE), (STRIDE, STRIDE), (NX, NY), (HR, WR))
+    out4 = torch.empty((HR // 4, WR // 4, 3), dtype=torch.uint8, device=dev)
+    res = []
+    for down in ops.HEAT_THUMB_DOWNS:
+        out = torch.empty((HR // down, WR // down, 3), dtype=torch.uint8, device=dev)
+        plane = torch.empty((HR // down, WR // down), dtype=torch.uint8, device=dev)
+
+        def t_flat(r):
+            return ops.region_heat_thumb(r, cells, CELL, lut, ALPHA, down, out=out)
+
+        def t_both(r):
+            m, t = masks[r.data_ptr()]
+            return ops.region_heat_thumb(r, cells, CELL, lut, ALPHA, down, smooth=True, mask=m, mask_down=THUMB_MASK_DOWN, mask_thresh=t, out=out)
+
+        def sat(r):
+            return ops.region_saturation(r, down, out=plane)
+
+        def parent(r):
+            m, t = masks[r.data_ptr()]
+            c4 = ops.region_heat_blend_px(r, cells, CELL, lut, ALPHA, 4, smooth=True, mask=m, mask_down=THUMB_MASK_DOWN, mask_thresh=t, out=out4)
+            return F.avg_pool2d(c4.permute(2, 0, 1).unsqueeze(0).float(), down // 4).add_(0.5).floor_().to(torch.uint8).squeeze(0).permute(1, 2, 0)
+
+        same_flat = all(bool(torch.equal(t_flat(s), torch_canvas(s, table, lut, down))) for s in slides)
+        same_both = all(bool(torch.equal(t_both(s), torch_canvas(s, table, lut, down, True, masks[s.data_ptr()], THUMB_MASK_DOWN))) for s in slides)
+        if not (same_flat and same_both):                                      # a wrong arm must not produce a quoted ratio
+            raise SystemExit(f"heatmap_bench: region_heat_thumb differs from the torch statement of the definition at down = {down} (flat {same_flat}, "
+                             f"smooth + mask {same_both}): nothing is timed")
+        changed = float((t_both(slides[0]).clone() != t_flat(slides[0])).any(dim=2).float().mean())
+        p_differs = float((parent(slides[0]) != t_both(slides[0])).any(dim=2).float().mean())
+        arms = {"T_flat": Rotating(t_flat, slides), "T_both": Rotating(t_both, slides), "S": Rotating(sat, slides), "P": Rotating(parent, slides)}
+        t, iters = alternate(arms, seconds)
+        nbytes = 3 * HR * WR + 3 * (HR // down) * (WR // down)
+        sv = t["S"]
+        s1, s2 = median(sv[0::2]), median(sv[1::2])
+        spread = abs(s1 - s2) / median(sv)
+        t_over_s = {k: round(median(t[k]) / median(sv), 4) for k in ("T_flat", "T_both")}
+        res.append(dict(kind="resident_heatmap_thumb", region=[HR, WR], tile=TILE, stride=STRIDE, cell=CELL, down=down, alpha=ALPHA, mask_down=THUMB_MASK_DOWN,
+                        moved_bytes=nbytes, slides_rotated=len(slides), rounds=len(sv), iters_per_round=iters,
+                        ms={k: round(median(v), 5) for k, v in t.items()}, ms_min={k: round(min(v), 5) for k, v in t.items()},
+                        ms_max={k: round(max(v), 5) for k, v in t.items()},
+                        moved_tbps={k: round(nbytes / median(t[k]) / 1e9, 3) for k in ("T_flat", "T_both")},
+                        s_read_tbps=round(3 * HR * WR / median(sv) / 1e9, 3), s_halves_ms=[round(s1, 5), round(s2, 5)], s_spread=round(spread, 4),
+                        t_over_s=t_over_s, t_exceeds_s_beyond_spread={k: bool(v > 1.0 + spread) for k, v in t_over_s.items()},
+                        p_over_t_both=round(median(t["P"]) / median(t["T_both"]), 3), thumb_equals_torch=same_flat and same_both,
+                        pixels_changed_vs_flat=round(changed, 4), p_pixels_differing_from_t=round(p_differs, 4), p_is_bit_equal=False))
+        del out, plane
+    return res
+
+
 def launches(arm, down, calls=4):
     """`calls` calls of one arm on rotating slides, no warm-up (run under rocprofv3 --kernel-trace --stats: every count divides by `calls`)."""
     dev = torch.device("cuda:0")
@@ -182,10 +252,11 @@ def main():
     ap.add_argument("--arm", default="A", choices=("A", "B"))
     ap.add_argument("--down", type=int, default=1, choices=(1, 2, 4))
     ap.add_argument("--px", action="store_true")
+    ap.add_argument("--thumb", action="store_true")
     ap.add_argument("--seconds", type=float, default=3.0)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    res = launches(a.arm, a.down) if a.launches else resident(a.seconds, a.px)
+    res = launches(a.arm, a.down) if a.launches else thumb(a.seconds) if a.thumb else resident(a.seconds, a.px)
     lines = [json.dumps(r) for r in res]
     print("\n".join(lines), flush=True)
     if a.out:
