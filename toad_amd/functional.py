@@ -184,6 +184,23 @@ def mil_backward(w: Dict[str, torch.Tensor], s: Saved, dlogits: torch.Tensor, ds
     return ret(dx)
 
 
+def _backward_inputs(w, b: int, dlogits, dsite, da, dfeat, fused: bool = True):
+    """What autograd hands a bridge's backward, made ready for the one-call backward of ``b`` slides -> (dlogits, dsite, da, dfeat, g): a missing
+    head gradient is zeros, the optional ones are contiguous or None, and ``g`` (None unless ``fused``) maps ops.STEP_SLOTS to fresh gradient
+    tensors, with the reference's ``wa`` / ``wb`` / ``ba`` / ``bb`` as views of its stacked ``wab`` / ``bab``."""
+    c, dev = w["wcls"].shape[0], w["wcls"].device
+    dlogits = torch.zeros((b, c), device=dev) if dlogits is None else dlogits.contiguous()
+    dsite = torch.zeros((b, 2), device=dev) if dsite is None else dsite.contiguous()
+    da = None if da is None else da.contiguous()
+    dfeat = None if dfeat is None else dfeat.contiguous()
+    g = None
+    if fused:
+        g = {k: torch.empty_like(w[k]) for k in ops.STEP_SLOTS}
+        d = w["wa"].shape[0]
+        g["wa"], g["wb"], g["ba"], g["bb"] = g["wab"][:d], g["wab"][d:], g["bab"][:d], g["bab"][d:]
+    return dlogits, dsite, da, dfeat, g
+
+
 class ToadMIL(torch.autograd.Function):
     """autograd bridge: inputs (x, sex, 14 parameters in SLOTS order, wab, bab, drop_p, seed).
 
@@ -220,22 +237,14 @@ class ToadMIL(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dlogits, dsite, da, dfeat, *unused):
         w = ctx.w
-        c = w["wcls"].shape[0]
-        dev = w["wcls"].device
-        dlogits = torch.zeros((1, c), device=dev) if dlogits is None else dlogits.contiguous()
-        dsite = torch.zeros((1, 2), device=dev) if dsite is None else dsite.contiguous()
-        da = None if da is None else da.contiguous()
-        dfeat = None if dfeat is None else dfeat.contiguous()
+        dlogits, dsite, da, dfeat, g = _backward_inputs(w, 1, dlogits, dsite, da, dfeat, fused=ctx.arena is not None)
         # the saved activations stay alive with the graph, so backward(retain_graph=True) can be followed by another backward
         if ctx.arena is None:
             g, dx, dsex = mil_backward(w, ctx.s, dlogits, dsite, da, dfeat, need_dx=ctx.need_dx, need_dsex=True)
         else:
-            g = {k: torch.empty_like(w[k]) for k in ops.STEP_SLOTS}
             drop_p, seed = ctx.drop
             dx, dsex = ops.mil_bwd(w, g, 0.0, ctx.x, ctx.arena, dlogits, dsite, da, dfeat, drop_p, seed,
                                    need_dx=ctx.need_dx, need_dsex=True)
-            d = w["wa"].shape[0]
-            g["wa"], g["wb"], g["ba"], g["bb"] = g["wab"][:d], g["wab"][d:], g["bab"][:d], g["bab"][d:]
         if not ctx.need_dsex:
             dsex = None
         return (dx, dsex) + tuple(g[k] for k in SLOTS) + (None, None, None, None)
@@ -266,14 +275,7 @@ class ToadMILBatch(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dlogits, dsite, da, dfeat, *unused):
         w, arena = ctx.w, ctx.arena
-        dev = w["wcls"].device
-        dlogits = torch.zeros((arena.b, arena.c), device=dev) if dlogits is None else dlogits.contiguous()
-        dsite = torch.zeros((arena.b, 2), device=dev) if dsite is None else dsite.contiguous()
-        da = None if da is None else da.contiguous()
-        dfeat = None if dfeat is None else dfeat.contiguous()
-        g = {k: torch.empty_like(w[k]) for k in ops.STEP_SLOTS}
+        dlogits, dsite, da, dfeat, g = _backward_inputs(w, arena.b, dlogits, dsite, da, dfeat)
         drop_p, seed = ctx.drop
         ops.mil_multi_bwd(w, g, 0.0, None, None, arena, dlogits, dsite, da, dfeat, drop_p, seed)
-        d = w["wa"].shape[0]
-        g["wa"], g["wb"], g["ba"], g["bb"] = g["wab"][:d], g["wab"][d:], g["bab"][:d], g["bab"][d:]
         return (None, None, None) + tuple(g[k] for k in SLOTS) + (None, None, None, None)

@@ -6,6 +6,7 @@ reference), the C side validates again and reports through toad_last_error().
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional, Tuple
 
 import torch
@@ -570,10 +571,52 @@ STEP_SLOTS = ("w1", "b1", "w2", "b2", "wab", "bab", "wc", "bc", "wcls", "bcls", 
 _GEMM_EVENT_NAMES = ("gemm_fwd", "gemm_fwd", "gemm_fwd", "gemm_wgrad", "gemm_dgrad", "gemm_wgrad", "gemm_dgrad", "gemm_wgrad")
 
 
-def _ptr_array(tensors):
-    import ctypes
-    arr = (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-    return arr
+def _slot_ptrs(slots, label: str = "", check: bool = True):
+    """The STEP_SLOTS tensors of a weight or gradient dict as the pointer array the whole-slide entries take, each checked like any operand
+    (``label`` prefixes the slot name in the message). The backward calls pass check=False for the weights: the forward that filled their
+    arena has checked them."""
+    ts = [slots[k] for k in STEP_SLOTS]
+    if check:
+        for k, t in zip(STEP_SLOTS, ts):
+            _chk(t, label + k)
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+# The bag kinds of the whole-slide calls and the suffix of their entry points, toad_mil_<family><suffix>_f32. The multi-slide families take the
+# first two.
+KIND_F32, KIND_F16, KIND_PREPARED = 0, 1, 2
+_KIND_SUFFIX = ("", "_x16", "_xp")
+
+# The argument list of each family's fp32 entry. The kinds differ in two places only: "bag" is one pointer for an fp32 / fp16 tensor and
+# (planes, amax) for a PreparedBag, and the argument marked "*" exists in the fp32 list alone.
+_MIL_FIELDS = {
+    "step": "w g beta bag sex label site w_cls w_site n c d drop_p seed *x_amax loss logits slog ws ws_bytes events stream",
+    "fwd": "w bag sex n c d drop_p seed *x_amax attention_only arena arena_bytes scratch scratch_bytes stream",
+    "bwd": "w g beta bag n c d drop_p seed arena arena_bytes dlogits dsite da_ext dmcat_ext *dx dsex scratch scratch_bytes stream",
+    "multi_step": "w g beta bag offsets b sex label site w_cls w_site c d drop_p seed loss logits slog ws ws_bytes events stream",
+    "multi_fwd": "w bag offsets b sex c d drop_p seed arena arena_bytes scratch scratch_bytes stream",
+    "multi_bwd": "w g beta bag offsets b c d drop_p seed arena arena_bytes dlogits dsite da_ext dmcat_ext scratch scratch_bytes stream",
+}
+_MIL_FIELDS = {family: tuple(fields.split()) for family, fields in _MIL_FIELDS.items()}
+# family -> (position of the bag, position of the fp32-only argument | None)
+_MIL_SPLICE = {family: (f.index("bag"), next((i for i, name in enumerate(f) if name[0] == "*"), None)) for family, f in _MIL_FIELDS.items()}
+_NO_DX = "mil_bwd: no gradient with respect to an fp16 / prepared bag (pass the float32 bag if the bag itself is trained)"
+
+
+def _mil_args(family: str, kind: int, vals: tuple):
+    """(entry name, its argument tuple) from one value per _MIL_FIELDS[family] field, ``bag`` being the pointer tuple of _bag_kind. Pure: it
+    touches neither a tensor nor the library."""
+    ib, ix = _MIL_SPLICE[family]
+    if kind != KIND_F32 and ix is not None:
+        if family == "bwd" and vals[ix] is not None:
+            raise ValueError(_NO_DX)
+        vals = vals[:ix] + vals[ix + 1:]
+    return f"toad_mil_{family}{_KIND_SUFFIX[kind]}_f32", vals[:ib] + vals[ib] + vals[ib + 1:]
+
+
+def _mil_call(lib, family: str, kind: int, vals: tuple) -> None:
+    name, args = _mil_args(family, kind, vals)
+    _lib.check(getattr(lib, name)(*args), name)
 
 
 class PreparedBag:
@@ -637,17 +680,39 @@ def prepare_bag(x: torch.Tensor, out: Optional[PreparedBag] = None) -> PreparedB
     return out if out is not None else PreparedBag(planes, amax, n, k)
 
 
-def _chk_bag(bag) -> int:
-    """The bag of a whole-slide call: fp32 (-> 0), fp16 (features stored in half precision: toad_mil_*_x16_f32, -> 1) or a
-    PreparedBag (toad_mil_*_xp_f32, -> 2)."""
+def _bag_kind(bag, name: str = "bag"):
+    """The bag of a whole-slide call (or the concatenated ``bags`` of a multi-slide one), checked -> (kind, what stands in the bag position of
+    the argument list): fp32, fp16 (features stored in half precision: toad_mil_*_x16_f32) or a PreparedBag (toad_mil_*_xp_f32)."""
     if getattr(bag, "is_prepared_bag", False):
-        _chk(bag.planes, "bag planes", dtype=torch.uint8); _chk(bag.amax, "bag amax")
-        return 2
-    if bag.dtype == torch.float16:
-        _chk(bag, "bag", dtype=torch.float16)
-        return 1
-    _chk(bag, "bag")
-    return 0
+        _chk(bag.planes, name + " planes", dtype=torch.uint8); _chk(bag.amax, name + " amax")
+        return KIND_PREPARED, (bag.planes.data_ptr(), bag.amax.data_ptr())
+    kind = KIND_F16 if bag.dtype == torch.float16 else KIND_F32
+    _chk(bag, name, dtype=torch.float16 if kind else torch.float32)
+    return kind, (bag.data_ptr(),)
+
+
+def _step_events():
+    """The events of a bracketed whole-slide step -> (event objects, the 18-slot array the library records into), or (None, None) when timing
+    is off or this call is not due (stride). Level 1 fills the pool-forward pair only."""
+    if _TIMING is None or not _timing_due():
+        return None, None
+    nev = 18 if _TIMING_LEVEL >= 2 else 2
+    evs = [_take_event() for _ in range(nev)]
+    return evs, (ctypes.c_void_p * 18)(*([e.cuda_event for e in evs] + [None] * (18 - nev)))
+
+
+def _file_events(evs, whole: Optional[str] = None) -> None:
+    """File the pairs the library recorded: pool forward, then the eight GEMM calls; ``whole`` names a bucket for the whole call, from the first
+    GEMM's start to the deferred weight-gradient reduction's end (the weight split launch in front of the first GEMM, ~6 us, is outside it;
+    no extra event packets on the stream)."""
+    if evs is None:
+        return
+    _TIMING.setdefault("pool_fwd", []).append((evs[0], evs[1]))
+    if len(evs) == 18:
+        for i, name in enumerate(_GEMM_EVENT_NAMES):
+            _TIMING.setdefault(name, []).append((evs[2 + 2 * i], evs[3 + 2 * i]))
+        if whole is not None:
+            _TIMING.setdefault(whole, []).append((evs[2], evs[17]))
 
 
 def _step_dims(w, bag):
@@ -662,16 +727,10 @@ def mil_step(w, grads, beta: float, bag, sex, label, site, w_cls: float = 0.75, 
              drop_p: float = 0.0, seed: int = 0, want_logits: bool = False, x_amax: Optional[torch.Tensor] = None):
     """forward + weighted CE + backward for one slide in ONE library call. ``w`` / ``grads`` map the STEP_SLOTS
     to tensors (grads = beta*grads + gradient). Returns (loss[3], logits [1,C] | None, site_logits [1,2] | None)."""
-    import ctypes
-    half = _chk_bag(bag)
+    kind, bagp = _bag_kind(bag)
     _chk(sex, "sex"); _chk(label, "label", dtype=torch.int64); _chk(site, "site", dtype=torch.int64)
     _chk(x_amax, "x_amax", allow_none=True)
-    ws_t = [w[k] for k in STEP_SLOTS]
-    gs_t = [grads[k] for k in STEP_SLOTS]
-    for k, t in zip(STEP_SLOTS, ws_t):
-        _chk(t, k)
-    for k, t in zip(STEP_SLOTS, gs_t):
-        _chk(t, "grad " + k)
+    wp, gp = _slot_ptrs(w), _slot_ptrs(grads, "grad ")
     n, c, d = _step_dims(w, bag)
     lib = _lib.load()
     dev = bag.device
@@ -679,29 +738,10 @@ def mil_step(w, grads, beta: float, bag, sex, label, site, w_cls: float = 0.75, 
     loss = torch.empty((3,), dtype=torch.float32, device=dev)
     logits = torch.empty((1, c), dtype=torch.float32, device=dev) if want_logits else None
     slog = torch.empty((1, 2), dtype=torch.float32, device=dev) if want_logits else None
-    events = None
-    ev_objs = None
-    if _TIMING is not None and _timing_due():
-        nev = 18 if _TIMING_LEVEL >= 2 else 2
-        ev_objs = [_take_event() for _ in range(nev)]
-        events = (ctypes.c_void_p * 18)(*([e.cuda_event for e in ev_objs] + [None] * (18 - nev)))
-    if half == 2:
-        _lib.check(lib.toad_mil_step_xp_f32(_ptr_array(ws_t), _ptr_array(gs_t), float(beta), _p(bag.planes), _p(bag.amax), _p(sex), _p(label),
-                                            _p(site), float(w_cls), float(w_site), n, c, d, float(drop_p), int(seed), _p(loss), _p(logits),
-                                            _p(slog), _p(ws), ws.numel(), events, _stream()), "toad_mil_step_xp_f32")
-    elif half:
-        _lib.check(lib.toad_mil_step_x16_f32(_ptr_array(ws_t), _ptr_array(gs_t), float(beta), _p(bag), _p(sex), _p(label), _p(site),
-                                             float(w_cls), float(w_site), n, c, d, float(drop_p), int(seed), _p(loss), _p(logits),
-                                             _p(slog), _p(ws), ws.numel(), events, _stream()), "toad_mil_step_x16_f32")
-    else:
-        _lib.check(lib.toad_mil_step_f32(_ptr_array(ws_t), _ptr_array(gs_t), float(beta), _p(bag), _p(sex), _p(label), _p(site),
-                                         float(w_cls), float(w_site), n, c, d, float(drop_p), int(seed), _p(x_amax), _p(loss), _p(logits),
-                                         _p(slog), _p(ws), ws.numel(), events, _stream()), "toad_mil_step_f32")
-    if ev_objs is not None:
-        _TIMING.setdefault("pool_fwd", []).append((ev_objs[0], ev_objs[1]))
-        if len(ev_objs) == 18:
-            for i, name in enumerate(_GEMM_EVENT_NAMES):
-                _TIMING.setdefault(name, []).append((ev_objs[2 + 2 * i], ev_objs[3 + 2 * i]))
+    evs, events = _step_events()
+    _mil_call(lib, "step", kind, (wp, gp, float(beta), bagp, _p(sex), _p(label), _p(site), float(w_cls), float(w_site), n, c, d, float(drop_p),
+                                  int(seed), _p(x_amax), _p(loss), _p(logits), _p(slog), _p(ws), ws.numel(), events, _stream()))
+    _file_events(evs)
     return loss, logits, slog
 
 
@@ -732,19 +772,13 @@ def mil_multi_step(w, grads, beta: float, bags, sex, label, site, w_cls: float =
     copy); mixed lists and totals toad_mil_multi_x16_ok refuses are up-cast.
     ``sex`` [B] float32, ``label`` / ``site`` [B] int64 device tensors. grads = beta*grads + sum over the batch.
     Returns (loss [B,3], logits [B,C] | None, site_logits [B,2] | None)."""
-    import ctypes
     xcat, offsets = _concat_bags(bags, offsets)
     nb = len(offsets) - 1
-    half = _chk_xcat(xcat)
+    kind, bagp = _bag_kind(xcat, "bags")
     _chk(sex, "sex"); _chk(label, "label", dtype=torch.int64); _chk(site, "site", dtype=torch.int64)
     if xcat.dim() != 2 or xcat.shape[0] != offsets[-1] or sex.numel() != nb or label.numel() != nb or site.numel() != nb:
         raise ValueError("mil_multi_step: one sex / label / site entry per slide and offsets[-1] == rows of the concatenation")
-    ws_t = [w[k] for k in STEP_SLOTS]
-    gs_t = [grads[k] for k in STEP_SLOTS]
-    for k, t in zip(STEP_SLOTS, ws_t):
-        _chk(t, k)
-    for k, t in zip(STEP_SLOTS, gs_t):
-        _chk(t, "grad " + k)
+    wp, gp = _slot_ptrs(w), _slot_ptrs(grads, "grad ")
     n, c, d = _step_dims(w, xcat)
     lib = _lib.load()
     dev = xcat.device
@@ -756,24 +790,10 @@ def mil_multi_step(w, grads, beta: float, bags, sex, label, site, w_cls: float =
     logits = torch.empty((nb, c), dtype=torch.float32, device=dev) if want_logits else None
     slog = torch.empty((nb, 2), dtype=torch.float32, device=dev) if want_logits else None
     offs = (ctypes.c_int64 * (nb + 1))(*offsets)
-    events = None
-    ev_objs = None
-    if _TIMING is not None and _timing_due():                # same 18-event layout as mil_step: pool forward, then the eight GEMM calls
-        nev = 18 if _TIMING_LEVEL >= 2 else 2
-        ev_objs = [_take_event() for _ in range(nev)]
-        events = (ctypes.c_void_p * 18)(*([e.cuda_event for e in ev_objs] + [None] * (18 - nev)))
-    fn, name = (lib.toad_mil_multi_step_x16_f32, "toad_mil_multi_step_x16_f32") if half else (lib.toad_mil_multi_step_f32, "toad_mil_multi_step_f32")
-    _lib.check(fn(_ptr_array(ws_t), _ptr_array(gs_t), float(beta), _p(xcat), offs, nb, _p(sex), _p(label), _p(site),
-                  float(w_cls), float(w_site), c, d, float(drop_p), int(seed), _p(loss), _p(logits), _p(slog),
-                  _p(ws), ws.numel(), events, _stream()), name)
-    if ev_objs is not None:
-        _TIMING.setdefault("pool_fwd", []).append((ev_objs[0], ev_objs[1]))
-        if len(ev_objs) == 18:
-            for i, name in enumerate(_GEMM_EVENT_NAMES):
-                _TIMING.setdefault(name, []).append((ev_objs[2 + 2 * i], ev_objs[3 + 2 * i]))
-            # whole-call bucket from the events the library already records: first GEMM's start .. the deferred weight-gradient reduction's end
-            # (the weight split launch in front of the first GEMM, ~6 us, is outside it; no extra event packets on the stream)
-            _TIMING.setdefault("mil_multi_step_x16" if half else "mil_multi_step", []).append((ev_objs[2], ev_objs[17]))
+    evs, events = _step_events()                             # same 18-event layout as mil_step
+    _mil_call(lib, "multi_step", kind, (wp, gp, float(beta), bagp, offs, nb, _p(sex), _p(label), _p(site), float(w_cls), float(w_site), c, d,
+                                        float(drop_p), int(seed), _p(loss), _p(logits), _p(slog), _p(ws), ws.numel(), events, _stream()))
+    _file_events(evs, "mil_multi_step" + _KIND_SUFFIX[kind])
     return loss, logits, slog
 
 
@@ -790,10 +810,16 @@ class MilArena:
         whose activations nobody will read back (no_grad / eval): the caller must CLONE the outputs it keeps, since the next
         cached forward overwrites them (a view of a fresh arena would pin ~7 KB per patch for as long as any output lives)."""
         self.n, self.c, self.d = n, c, d
-        nbytes, align, offs = _arena_layout(n, c, d)          # (three library queries, cached per shape: this runs once per forward)
+        self._carve("toad_mil_arena", ARENA_SLOTS, (n, c, d), device, cached)
+
+    def _carve(self, query: str, slots, shape, device, cached: bool) -> None:
+        """Allocate the buffer the library lays out for ``shape`` ((N, C, D), or (sum N_b, B, C, D) for a batch) and note where its slots lie."""
+        lay = _ARENA_LAYOUTS.get(shape)                       # (three library queries, cached per shape: this runs once per forward)
+        if lay is None:
+            lay = _remember(_ARENA_LAYOUTS, shape, _arena_layout(query, slots, shape))
+        nbytes, align, self.off = lay
         self.buf = _ws(nbytes, device, "eval_arena")[:nbytes] if cached else torch.empty(nbytes, dtype=torch.uint8, device=device)
         self.base = (-self.buf.data_ptr()) % align
-        self.off = offs
 
     def view(self, name: str, shape, dtype=torch.float32) -> torch.Tensor:
         nbytes = _ELEM_BYTES[dtype]
@@ -808,30 +834,31 @@ _ARENA_LAYOUTS = {}
 _SCRATCH_BYTES = {}
 
 
-def _arena_layout(n: int, c: int, d: int):
-    """(arena bytes, base alignment, slot -> offset from the aligned base) of toad_mil_arena_layout, cached per (N, C, D)."""
-    key = (n, c, d)
-    lay = _ARENA_LAYOUTS.get(key)
-    if lay is None:
-        import ctypes
-        lib = _lib.load()
-        offs = (ctypes.c_int64 * len(ARENA_SLOTS))()
-        _lib.check(lib.toad_mil_arena_layout(n, c, d, offs), "toad_mil_arena_layout")
-        lay = (int(lib.toad_mil_arena_bytes(n, c, d)), int(lib.toad_mil_buffer_align(n)), {k: int(o) for k, o in zip(ARENA_SLOTS, offs)})
-        if len(_ARENA_LAYOUTS) > 4096:
-            _ARENA_LAYOUTS.clear()
-        _ARENA_LAYOUTS[key] = lay
-    return lay
+def _remember(cache: dict, key, value):
+    """File a library query's answer under its shape key. The caches are bounded: past 4096 shapes one is dropped whole."""
+    if len(cache) > 4096:
+        cache.clear()
+    cache[key] = value
+    return value
 
 
-def _scratch_bytes(n: int, c: int, d: int) -> int:
-    key = (n, c, d)
-    b = _SCRATCH_BYTES.get(key)
+def _arena_layout(query: str, slots, shape):
+    """(arena bytes, base alignment, slot -> offset from the aligned base) of <query>_bytes / <query>_layout for one shape."""
+    lib = _lib.load()
+    nbytes = int(getattr(lib, query + "_bytes")(*shape))
+    if nbytes == 0 and len(shape) == 4:                       # a batch the library does not take (one slide's shape: the layout call reports it)
+        raise ValueError("unsupported batch (rows {}, slides {}, C={}, D={})".format(*shape))
+    offs = (ctypes.c_int64 * len(slots))()
+    _lib.check(getattr(lib, query + "_layout")(*shape, offs), query + "_layout")
+    return nbytes, int(lib.toad_mil_buffer_align(shape[0])), {k: int(o) for k, o in zip(slots, offs)}
+
+
+def _scratch_bytes(*shape) -> int:
+    """toad_mil_scratch_bytes(N, C, D), or toad_mil_multi_scratch_bytes(sum N_b, B, C, D), cached per shape."""
+    b = _SCRATCH_BYTES.get(shape)
     if b is None:
-        b = int(_lib.load().toad_mil_scratch_bytes(n, c, d))
-        if len(_SCRATCH_BYTES) > 4096:
-            _SCRATCH_BYTES.clear()
-        _SCRATCH_BYTES[key] = b
+        lib = _lib.load()
+        b = _remember(_SCRATCH_BYTES, shape, int((lib.toad_mil_multi_scratch_bytes if len(shape) == 4 else lib.toad_mil_scratch_bytes)(*shape)))
     return b
 
 
@@ -839,43 +866,28 @@ def mil_fwd(w, bag, sex, drop_p: float = 0.0, seed: int = 0, attention_only: boo
             x_amax: Optional[torch.Tensor] = None, cached_arena: bool = False) -> MilArena:
     """models/model_toad.py:90-116 for one bag in ONE library call; returns the arena (outputs + what backward needs).
     ``cached_arena``: forward-only use (see MilArena): clone what you keep."""
-    half = _chk_bag(bag)
+    kind, bagp = _bag_kind(bag)
     _chk(sex, "sex", allow_none=attention_only); _chk(x_amax, "x_amax", allow_none=True)
-    ws_t = [w[k] for k in STEP_SLOTS]
-    for k, t in zip(STEP_SLOTS, ws_t):
-        _chk(t, k)
+    wp = _slot_ptrs(w)
     n, c, d = _step_dims(w, bag)
     lib = _lib.load()
     arena = MilArena(n, c, d, bag.device, cached=cached_arena)
     scratch = _ws(_scratch_bytes(n, c, d), bag.device, "mil")
     with _timed("mil_fwd"):
-        if half == 2:
-            _lib.check(lib.toad_mil_fwd_xp_f32(_ptr_array(ws_t), _p(bag.planes), _p(bag.amax), _p(sex), n, c, d, float(drop_p), int(seed),
-                                               1 if attention_only else 0, _p(arena.buf), arena.buf.numel(), _p(scratch), scratch.numel(),
-                                               _stream()), "toad_mil_fwd_xp_f32")
-        elif half:
-            _lib.check(lib.toad_mil_fwd_x16_f32(_ptr_array(ws_t), _p(bag), _p(sex), n, c, d, float(drop_p), int(seed),
-                                                1 if attention_only else 0, _p(arena.buf), arena.buf.numel(), _p(scratch), scratch.numel(),
-                                                _stream()), "toad_mil_fwd_x16_f32")
-        else:
-            _lib.check(lib.toad_mil_fwd_f32(_ptr_array(ws_t), _p(bag), _p(sex), n, c, d, float(drop_p), int(seed), _p(x_amax),
-                                            1 if attention_only else 0, _p(arena.buf), arena.buf.numel(), _p(scratch), scratch.numel(),
-                                            _stream()), "toad_mil_fwd_f32")
+        _mil_call(lib, "fwd", kind, (wp, bagp, _p(sex), n, c, d, float(drop_p), int(seed), _p(x_amax), 1 if attention_only else 0,
+                                     _p(arena.buf), arena.buf.numel(), _p(scratch), scratch.numel(), _stream()))
     return arena
 
 
 def mil_bwd(w, grads, beta: float, bag, arena: MilArena, dlogits, dsite, da_ext=None, dmcat_ext=None, drop_p: float = 0.0,
             seed: int = 0, need_dx: bool = False, need_dsex: bool = False):
     """Backward of mil_fwd in ONE library call: grads[slot] = beta*grads[slot] + gradient. Returns (dX | None, dsex | None)."""
-    half = _chk_bag(bag)
-    if half and need_dx:
-        raise ValueError("mil_bwd: no gradient with respect to an fp16 / prepared bag (pass the float32 bag if the bag itself is trained)")
+    kind, bagp = _bag_kind(bag)
+    if kind != KIND_F32 and need_dx:
+        raise ValueError(_NO_DX)
     _chk(dlogits, "dlogits"); _chk(dsite, "dsite")
     _chk(da_ext, "da_ext", allow_none=True); _chk(dmcat_ext, "dmcat_ext", allow_none=True)
-    ws_t = [w[k] for k in STEP_SLOTS]
-    gs_t = [grads[k] for k in STEP_SLOTS]
-    for k, t in zip(STEP_SLOTS, gs_t):
-        _chk(t, "grad " + k)
+    wp, gp = _slot_ptrs(w, check=False), _slot_ptrs(grads, "grad ")
     n, c, d = arena.n, arena.c, arena.d
     if dlogits.numel() != c or dsite.numel() != 2 or bag.shape[0] != n:
         raise ValueError("mil_bwd: shape mismatch")
@@ -890,18 +902,8 @@ def mil_bwd(w, grads, beta: float, bag, arena: MilArena, dlogits, dsite, da_ext=
     scratch = _ws(_scratch_bytes(n, c, d), dev, "mil")
     buf = arena.buf
     with _timed("mil_bwd"):
-        if half == 2:
-            _lib.check(lib.toad_mil_bwd_xp_f32(_ptr_array(ws_t), _ptr_array(gs_t), float(beta), _p(bag.planes), _p(bag.amax), n, c, d, float(drop_p),
-                                               int(seed), _p(buf), buf.numel(), _p(dlogits), _p(dsite), _p(da_ext), _p(dmcat_ext), _p(dsex),
-                                               _p(scratch), scratch.numel(), _stream()), "toad_mil_bwd_xp_f32")
-        elif half:
-            _lib.check(lib.toad_mil_bwd_x16_f32(_ptr_array(ws_t), _ptr_array(gs_t), float(beta), _p(bag), n, c, d, float(drop_p), int(seed),
-                                                _p(buf), buf.numel(), _p(dlogits), _p(dsite), _p(da_ext), _p(dmcat_ext), _p(dsex),
-                                                _p(scratch), scratch.numel(), _stream()), "toad_mil_bwd_x16_f32")
-        else:
-            _lib.check(lib.toad_mil_bwd_f32(_ptr_array(ws_t), _ptr_array(gs_t), float(beta), _p(bag), n, c, d, float(drop_p), int(seed),
-                                            _p(buf), buf.numel(), _p(dlogits), _p(dsite), _p(da_ext), _p(dmcat_ext), _p(dx), _p(dsex),
-                                            _p(scratch), scratch.numel(), _stream()), "toad_mil_bwd_f32")
+        _mil_call(lib, "bwd", kind, (wp, gp, float(beta), bagp, n, c, d, float(drop_p), int(seed), _p(buf), buf.numel(), _p(dlogits), _p(dsite),
+                                     _p(da_ext), _p(dmcat_ext), _p(dx), _p(dsex), _p(scratch), scratch.numel(), _stream()))
     return dx, dsex
 
 
@@ -917,19 +919,10 @@ class MilMultiArena(MilArena):
     (fp32, or fp16 as stored: half the bytes held between forward and backward) and the offsets the forward ran on (the backward needs both)."""
 
     def __init__(self, xcat: torch.Tensor, offsets, c: int, d: int, cached: bool = False):
-        import ctypes
         n, nb = int(xcat.shape[0]), len(offsets) - 1
         self.n, self.c, self.d, self.b = n, c, d, nb
         self.xcat, self.offsets = xcat, tuple(offsets)
-        lib = _lib.load()
-        nbytes = int(lib.toad_mil_multi_arena_bytes(n, nb, c, d))
-        if nbytes == 0:
-            raise ValueError(f"unsupported batch (rows {n}, slides {nb}, C={c}, D={d})")
-        offs = (ctypes.c_int64 * len(MULTI_ARENA_SLOTS))()
-        _lib.check(lib.toad_mil_multi_arena_layout(n, nb, c, d, offs), "toad_mil_multi_arena_layout")
-        self.buf = _ws(nbytes, xcat.device, "eval_arena")[:nbytes] if cached else torch.empty(nbytes, dtype=torch.uint8, device=xcat.device)
-        self.base = (-self.buf.data_ptr()) % int(lib.toad_mil_buffer_align(n))
-        self.off = {k: int(o) for k, o in zip(MULTI_ARENA_SLOTS, offs)}
+        self._carve("toad_mil_multi_arena", MULTI_ARENA_SLOTS, (n, nb, c, d), xcat.device, cached)
 
     def outputs(self):
         """Dense per-slide outputs (views of the arena): logits [B,C], site_logits [B,2], a_raw [sum N_b,2], features [B,2,513],
@@ -963,17 +956,8 @@ def multi_x16_ok(rows: int) -> bool:
     return bool(_lib.load().toad_mil_multi_x16_ok(int(rows)))
 
 
-def _chk_xcat(xcat) -> bool:
-    """The concatenated bags of a multi-slide call: fp32 (-> False) or fp16 as stored (toad_mil_multi_*_x16_f32, -> True)."""
-    if xcat.dtype == torch.float16:
-        _chk(xcat, "bags", dtype=torch.float16)
-        return True
-    _chk(xcat, "bags")
-    return False
-
-
 def _multi_scratch(n: int, nb: int, c: int, d: int, dev) -> torch.Tensor:
-    nbytes = int(_lib.load().toad_mil_multi_scratch_bytes(n, nb, c, d))
+    nbytes = _scratch_bytes(n, nb, c, d)
     if nbytes == 0:
         raise ValueError(f"unsupported batch (rows {n}, slides {nb}, C={c}, D={d})")
     return _ws(nbytes, dev, "mil")
@@ -986,25 +970,21 @@ def mil_multi_fwd(w, bags_or_xcat, sex, drop_p: float = 0.0, seed: int = 0, offs
     the fp16 concatenation for the backward); ``sex`` [B] float32 on the device. Returns (arena, outputs): the MilMultiArena the backward needs
     and MilMultiArena.outputs(). Dropout masks are those of mil_multi_step for the same (drop_p, seed). ``cached_arena``: forward-only use (see
     MilArena): clone what you keep."""
-    import ctypes
     xcat, offsets = _concat_bags(bags_or_xcat, offsets)
     nb = len(offsets) - 1
-    half = _chk_xcat(xcat)
+    kind, bagp = _bag_kind(xcat, "bags")
     _chk(sex, "sex")
     if xcat.dim() != 2 or nb < 1 or xcat.shape[0] != offsets[-1] or sex.numel() != nb:
         raise ValueError("mil_multi_fwd: one sex entry per slide and offsets[-1] == rows of the concatenation")
-    ws_t = [w[k] for k in STEP_SLOTS]
-    for k, t in zip(STEP_SLOTS, ws_t):
-        _chk(t, k)
+    wp = _slot_ptrs(w)
     n, c, d = _step_dims(w, xcat)
     lib = _lib.load()
     arena = MilMultiArena(xcat, offsets, c, d, cached=cached_arena)
     scratch = _multi_scratch(n, nb, c, d, xcat.device)
     offs = (ctypes.c_int64 * (nb + 1))(*offsets)
-    fn, name = (lib.toad_mil_multi_fwd_x16_f32, "toad_mil_multi_fwd_x16_f32") if half else (lib.toad_mil_multi_fwd_f32, "toad_mil_multi_fwd_f32")
-    with _timed("mil_multi_fwd_x16" if half else "mil_multi_fwd"):
-        _lib.check(fn(_ptr_array(ws_t), _p(xcat), offs, nb, _p(sex), c, d, float(drop_p), int(seed), _p(arena.buf), arena.buf.numel(),
-                      _p(scratch), scratch.numel(), _stream()), name)
+    with _timed("mil_multi_fwd" + _KIND_SUFFIX[kind]):
+        _mil_call(lib, "multi_fwd", kind, (wp, bagp, offs, nb, _p(sex), c, d, float(drop_p), int(seed), _p(arena.buf), arena.buf.numel(),
+                                           _p(scratch), scratch.numel(), _stream()))
     return arena, arena.outputs()
 
 
@@ -1013,7 +993,6 @@ def mil_multi_bwd(w, grads, beta: float, xcat, offsets, arena: MilMultiArena, dl
     """Backward of mil_multi_fwd in ONE library call (toad_mil_multi_bwd_f32): grads[slot] = beta*grads[slot] + the gradient summed over the batch,
     from dlogits [B,C], dsite [B,2] and optionally da_ext [sum N_b,2] (through the raw scores) and dmcat_ext [B,2,513] (through the features).
     ``xcat`` / ``offsets`` as for mil_multi_fwd (None: the ones the forward ran on, kept by the arena); the same (drop_p, seed) as the forward."""
-    import ctypes
     if xcat is None:
         xcat, offsets = arena.xcat, list(arena.offsets)
     else:
@@ -1021,13 +1000,10 @@ def mil_multi_bwd(w, grads, beta: float, xcat, offsets, arena: MilMultiArena, dl
     nb = len(offsets) - 1
     if tuple(offsets) != arena.offsets or xcat.shape[0] != arena.n:
         raise ValueError("mil_multi_bwd: the offsets / bags must be those of the forward that filled the arena")
-    half = _chk_xcat(xcat)
+    kind, bagp = _bag_kind(xcat, "bags")
     _chk(dlogits, "dlogits"); _chk(dsite, "dsite")
     _chk(da_ext, "da_ext", allow_none=True); _chk(dmcat_ext, "dmcat_ext", allow_none=True)
-    ws_t = [w[k] for k in STEP_SLOTS]
-    gs_t = [grads[k] for k in STEP_SLOTS]
-    for k, t in zip(STEP_SLOTS, gs_t):
-        _chk(t, "grad " + k)
+    wp, gp = _slot_ptrs(w, check=False), _slot_ptrs(grads, "grad ")
     n, c, d = arena.n, arena.c, arena.d
     if tuple(dlogits.shape) != (nb, c) or tuple(dsite.shape) != (nb, 2):
         raise ValueError(f"mil_multi_bwd: dlogits must be [{nb},{c}] and dsite [{nb},2]")
@@ -1038,11 +1014,9 @@ def mil_multi_bwd(w, grads, beta: float, xcat, offsets, arena: MilMultiArena, dl
     lib = _lib.load()
     scratch = _multi_scratch(n, nb, c, d, xcat.device)
     offs = (ctypes.c_int64 * (nb + 1))(*offsets)
-    fn, name = (lib.toad_mil_multi_bwd_x16_f32, "toad_mil_multi_bwd_x16_f32") if half else (lib.toad_mil_multi_bwd_f32, "toad_mil_multi_bwd_f32")
-    with _timed("mil_multi_bwd_x16" if half else "mil_multi_bwd"):
-        _lib.check(fn(_ptr_array(ws_t), _ptr_array(gs_t), float(beta), _p(xcat), offs, nb, c, d, float(drop_p), int(seed),
-                      _p(arena.buf), arena.buf.numel(), _p(dlogits), _p(dsite), _p(da_ext), _p(dmcat_ext), _p(scratch),
-                      scratch.numel(), _stream()), name)
+    with _timed("mil_multi_bwd" + _KIND_SUFFIX[kind]):
+        _mil_call(lib, "multi_bwd", kind, (wp, gp, float(beta), bagp, offs, nb, c, d, float(drop_p), int(seed), _p(arena.buf), arena.buf.numel(),
+                                           _p(dlogits), _p(dsite), _p(da_ext), _p(dmcat_ext), _p(scratch), scratch.numel(), _stream()))
 
 
 # ---- feature-extractor pieces (conv.hip) --------------------------------------------------------------------------

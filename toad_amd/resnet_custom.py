@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .ops import IMAGENET_MEAN, IMAGENET_STD, check_origins, norm_constants_u8, region_layout_ok, tile_shape
+from .ops import IMAGENET_MEAN, IMAGENET_STD, _row_pitch, check_origins, norm_constants_u8, region_layout_ok, tile_shape
 
 __all__ = ["Bottleneck_Baseline", "ResNet_Baseline", "resnet50_baseline", "IMAGENET_MEAN", "IMAGENET_STD"]
 
@@ -150,33 +150,50 @@ class ResNet_Baseline(nn.Module):
         return self.to(torch.device("cuda", torch.cuda.current_device()))
 
     # ---- forward ------------------------------------------------------------------------------------------------
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """[B,3,H,W] fp32 NCHW on the HIP device -> [B,1024] (ResNet_Baseline.forward, :95-108)."""
+    def _ready(self, x: torch.Tensor, problem: Optional[str]) -> None:
+        """The refusals every forward makes, in their order: training mode, the ``problem`` its own checks found with the input (or None), a model
+        on another device."""
         if self.training:
             raise RuntimeError("the HIP extractor is inference-only: call .eval() (the reference never trains it)")
-        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
-            raise RuntimeError("expected a float32 [B,3,H,W] tensor on the HIP device (no CPU fallback)")
+        if problem is not None:
+            raise RuntimeError(problem)
         if self.conv1.weight.device != x.device:
             raise RuntimeError("model and input are on different devices; call model.relocate()")
-        lib = _lib.load()
+
+    def _chunked(self, out: torch.Tensor, H: int, W: int, ws_bytes, call) -> torch.Tensor:
+        """Fill the [B,1024] ``out``, at most max_tiles_per_call(H, W) tiles per library call. Folds the weights if they are stale, then
+        ``call(b0, nb, wp, bp, o32, o16, tail)`` launches rows [b0, b0 + nb): ``wp`` / ``bp`` are the folded weight / bias pointers, the rows'
+        destination is ``o32`` for an fp32 ``out`` and ``o16`` for an fp16 one (the other is None), and ``tail`` is the end of every entry's
+        argument list (nb, H, W, workspace, its bytes, stream). ``ws_bytes(nb, H, W)`` sizes the workspace, which the model keeps and only grows."""
         if self._folded is None or self._folded_sig != self._param_signature():
             self._fold_all()
         _, _, wp, bp = self._folded
-        x = x.contiguous()
-        B, _, H, W = x.shape
-        out = torch.empty(B, 1024, device=x.device, dtype=torch.float32)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
+        B, dev = out.shape[0], out.device
+        half = out.dtype == torch.float16
+        stream = torch.cuda.current_stream(dev).cuda_stream
         cap = max_tiles_per_call(H, W)
         for b0 in range(0, B, cap):
             nb = min(cap, B - b0)
-            need = lib.toad_resnet50_trunc_ws_bytes(nb, H, W)
+            need = ws_bytes(nb, H, W)
             if need == 0:
                 raise RuntimeError(f"unsupported tile shape {H}x{W}")
-            if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-            _lib.check(lib.toad_resnet50_trunc_fwd_f32(x[b0:b0 + nb].data_ptr(), wp, bp, out[b0:b0 + nb].data_ptr(), nb, H, W,
-                                                       self._ws.data_ptr(), self._ws.numel(), stream), "toad_resnet50_trunc_fwd_f32")
+            if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            o = out[b0:b0 + nb].data_ptr()
+            call(b0, nb, wp, bp, None if half else o, o if half else None, (nb, H, W, self._ws.data_ptr(), self._ws.numel(), stream))
         return out
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """[B,3,H,W] fp32 NCHW on the HIP device -> [B,1024] (ResNet_Baseline.forward, :95-108)."""
+        self._ready(x, None if x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3 else
+                    "expected a float32 [B,3,H,W] tensor on the HIP device (no CPU fallback)")
+        lib = _lib.load()
+        x = x.contiguous()
+        B, _, H, W = x.shape
+
+        def call(b0, nb, wp, bp, o32, _, tail):
+            _lib.check(lib.toad_resnet50_trunc_fwd_f32(x[b0:b0 + nb].data_ptr(), wp, bp, o32, *tail), "toad_resnet50_trunc_fwd_f32")
+        return self._chunked(torch.empty(B, 1024, device=x.device, dtype=torch.float32), H, W, lib.toad_resnet50_trunc_ws_bytes, call)
 
     def forward_u8(self, tiles: torch.Tensor, mean=IMAGENET_MEAN, std=IMAGENET_STD, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
         """[B,H,W,3] uint8 RGB tiles on the HIP device, as an image decoder hands them over -> [B,1024] bag rows, fp32 or fp16.
@@ -184,42 +201,21 @@ class ResNet_Baseline(nn.Module):
         ToTensor + Normalize(mean, std) happen on the device in one rounding, x = fmaf(u, 1/(255 std_c), -mean_c/std_c); the result is bitwise
         ``forward`` of that fp32 NCHW tensor (``out_dtype=torch.float16``: bitwise ``forward(...).half()``, stored by the last kernel). 256-wide tiles with
         H % 4 == 0 never exist as an fp32 image: the stem kernel reads the bytes. Other shapes are converted into a staging image inside the workspace."""
-        if self.training:
-            raise RuntimeError("the HIP extractor is inference-only: call .eval() (the reference never trains it)")
-        if tiles.dtype != torch.uint8:
-            raise RuntimeError(f"forward_u8 expects uint8 tiles, got {tiles.dtype} (normalised float32 [B,3,H,W] tiles go to forward)")
-        if tiles.dim() != 4 or tiles.shape[3] != 3:
-            raise RuntimeError(f"forward_u8 expects channels-last [B,H,W,3] tiles, got {tuple(tiles.shape)}")
-        if out_dtype not in (torch.float32, torch.float16):
-            raise RuntimeError(f"out_dtype must be torch.float32 or torch.float16, got {out_dtype}")
-        if not tiles.is_cuda:
-            raise RuntimeError("expected a uint8 [B,H,W,3] tensor on the HIP device (no CPU fallback)")
-        if self.conv1.weight.device != tiles.device:
-            raise RuntimeError("model and input are on different devices; call model.relocate()")
+        self._ready(tiles, (
+            f"forward_u8 expects uint8 tiles, got {tiles.dtype} (normalised float32 [B,3,H,W] tiles go to forward)" if tiles.dtype != torch.uint8 else
+            f"forward_u8 expects channels-last [B,H,W,3] tiles, got {tuple(tiles.shape)}" if tiles.dim() != 4 or tiles.shape[3] != 3 else
+            f"out_dtype must be torch.float32 or torch.float16, got {out_dtype}" if out_dtype not in (torch.float32, torch.float16) else
+            "expected a uint8 [B,H,W,3] tensor on the HIP device (no CPU fallback)" if not tiles.is_cuda else None))
         norm = norm_constants_u8(mean, std)
         lib = _lib.load()
-        if self._folded is None or self._folded_sig != self._param_signature():
-            self._fold_all()
-        _, _, wp, bp = self._folded
         tiles = tiles.contiguous()
         B, H, W, _ = tiles.shape
         if W == 256 and H >= 4 and H % 4 == 0 and tiles.data_ptr() % 2:
             tiles = tiles.clone()                       # the stem reads 2-byte aligned words: one copy of a source at an odd address
-        out = torch.empty(B, 1024, device=tiles.device, dtype=out_dtype)
-        half = out_dtype == torch.float16
-        stream = torch.cuda.current_stream(tiles.device).cuda_stream
-        cap = max_tiles_per_call(H, W)
-        for b0 in range(0, B, cap):
-            nb = min(cap, B - b0)
-            need = lib.toad_resnet50_trunc_u8_ws_bytes(nb, H, W)
-            if need == 0:
-                raise RuntimeError(f"unsupported tile shape {H}x{W}")
-            if self._ws is None or self._ws.numel() < need or self._ws.device != tiles.device:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=tiles.device)
-            o = out[b0:b0 + nb].data_ptr()
-            _lib.check(lib.toad_resnet50_trunc_fwd_u8(tiles[b0:b0 + nb].data_ptr(), norm, wp, bp, None if half else o, o if half else None, nb, H, W,
-                                                      self._ws.data_ptr(), self._ws.numel(), stream), "toad_resnet50_trunc_fwd_u8")
-        return out
+
+        def call(b0, nb, wp, bp, o32, o16, tail):
+            _lib.check(lib.toad_resnet50_trunc_fwd_u8(tiles[b0:b0 + nb].data_ptr(), norm, wp, bp, o32, o16, *tail), "toad_resnet50_trunc_fwd_u8")
+        return self._chunked(torch.empty(B, 1024, device=tiles.device, dtype=out_dtype), H, W, lib.toad_resnet50_trunc_u8_ws_bytes, call)
 
     def forward_u8_region(self, region: torch.Tensor, origins, tile=256, mean=IMAGENET_MEAN, std=IMAGENET_STD, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
         """Tiles read by origin from one decoded region -> [B,1024] bag rows, fp32 or fp16; no tile copy exists at any point.
@@ -230,21 +226,13 @@ class ResNet_Baseline(nn.Module):
         (``ValueError`` naming the first offender); duplicates, overlaps and any order are fine. ``tile``: an int or (H, W). Padding is the tile's, not the
         region's: the result is bitwise ``forward_u8(torch.stack([region[y:y+H, x:x+W] for x, y in origins]), mean, std, out_dtype)``. More than
         ``max_tiles_per_call`` origins are run in chunks that write into the one [B,1024] result."""
-        if self.training:
-            raise RuntimeError("the HIP extractor is inference-only: call .eval() (the reference never trains it)")
-        if region.dtype != torch.uint8:
-            raise RuntimeError(f"forward_u8_region expects a uint8 region, got {region.dtype}")
-        if region.dim() != 3 or region.shape[2] != 3:
-            raise RuntimeError(f"forward_u8_region expects a channels-last [Hr,Wr,3] region, got {tuple(region.shape)}")
-        if out_dtype not in (torch.float32, torch.float16):
-            raise RuntimeError(f"out_dtype must be torch.float32 or torch.float16, got {out_dtype}")
-        if not region.is_cuda:
-            raise RuntimeError("expected a uint8 [Hr,Wr,3] tensor on the HIP device (no CPU fallback)")
-        if not region_layout_ok(region):
-            raise RuntimeError(f"forward_u8_region expects a region with stride(2) == 1, stride(1) == 3 and a row pitch stride(0) >= 3 Wr (rows are read in "
-                               f"place, there is no hidden copy), got strides {tuple(region.stride())} for shape {tuple(region.shape)}")
-        if self.conv1.weight.device != region.device:
-            raise RuntimeError("model and input are on different devices; call model.relocate()")
+        self._ready(region, (
+            f"forward_u8_region expects a uint8 region, got {region.dtype}" if region.dtype != torch.uint8 else
+            f"forward_u8_region expects a channels-last [Hr,Wr,3] region, got {tuple(region.shape)}" if region.dim() != 3 or region.shape[2] != 3 else
+            f"out_dtype must be torch.float32 or torch.float16, got {out_dtype}" if out_dtype not in (torch.float32, torch.float16) else
+            "expected a uint8 [Hr,Wr,3] tensor on the HIP device (no CPU fallback)" if not region.is_cuda else
+            f"forward_u8_region expects a region with stride(2) == 1, stride(1) == 3 and a row pitch stride(0) >= 3 Wr (rows are read in "
+            f"place, there is no hidden copy), got strides {tuple(region.stride())} for shape {tuple(region.shape)}" if not region_layout_ok(region) else None))
         H, W = tile_shape(tile)
         Hr, Wr = region.shape[0], region.shape[1]
         org = check_origins(origins, Hr, Wr, H, W)
@@ -254,27 +242,13 @@ class ResNet_Baseline(nn.Module):
         if B == 0:
             return out
         lib = _lib.load()
-        if self._folded is None or self._folded_sig != self._param_signature():
-            self._fold_all()
-        _, _, wp, bp = self._folded
-        pitch = region.stride(0) if Hr > 1 else max(region.stride(0), 3 * Wr)
+        pitch = _row_pitch(region, 3 * Wr)
         org = org.to(region.device)                         # int32 [B,2]: the one small copy of the call
-        half = out_dtype == torch.float16
-        stream = torch.cuda.current_stream(region.device).cuda_stream
-        cap = max_tiles_per_call(H, W)
-        for b0 in range(0, B, cap):                         # the origins are sliced, never the region
-            nb = min(cap, B - b0)
-            need = lib.toad_resnet50_trunc_u8_ws_bytes(nb, H, W)
-            if need == 0:
-                raise RuntimeError(f"unsupported tile shape {H}x{W}")
-            if self._ws is None or self._ws.numel() < need or self._ws.device != region.device:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=region.device)
-            o = out[b0:b0 + nb].data_ptr()
-            _lib.check(lib.toad_resnet50_trunc_fwd_u8_region(region.data_ptr(), pitch, Hr, Wr, org[b0:b0 + nb].data_ptr(), norm, wp, bp, None if half else o,
-                                                             o if half else None, nb, H, W, self._ws.data_ptr(), self._ws.numel(), stream),
-                       "toad_resnet50_trunc_fwd_u8_region")
-        return out
 
+        def call(b0, nb, wp, bp, o32, o16, tail):           # the origins are sliced, never the region
+            _lib.check(lib.toad_resnet50_trunc_fwd_u8_region(region.data_ptr(), pitch, Hr, Wr, org[b0:b0 + nb].data_ptr(), norm, wp, bp, o32, o16, *tail),
+                       "toad_resnet50_trunc_fwd_u8_region")
+        return self._chunked(out, H, W, lib.toad_resnet50_trunc_u8_ws_bytes, call)
 
 
 def resnet50_baseline(pretrained: bool = False) -> ResNet_Baseline:
