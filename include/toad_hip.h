@@ -418,6 +418,26 @@ int toad_tissue_tile_counts(const int *counts, int Gy, int Gx, int cell, int x0,
  * 2 * S + 257 * n < 2^31): TOAD_ESHAPE otherwise. tile_q and cells 4-byte aligned (TOAD_EALIGN). */
 int toad_heat_cells(const int *tile_q, int nx, int ny, int cell, int x0, int y0, int H, int W, int sx, int sy, int Gy, int Gx, int *cells, void *stream);
 
+/* The Gaussian blur of the cell table (additive to ABI 15 too): CLAM's `blur`, taken on the cells before they are rendered, so that the canvas calls
+ * below - tent, mask, every down - render the smoothed table unchanged. Integers, one right answer.
+ *   input     cells int32 [Gy][Gx] as toad_heat_cells leaves them: -1 = no value, values above 255 read as 255.
+ *   kernel    the half-kernel taps[0 .. radius] on the HOST, 1 <= radius <= 16, taps[0] >= 1, every tap >= 0, taps[0] + 2 * (taps[1] + .. + taps[radius])
+ *             <= 1024; the full kernel is symmetric and separable, w[|dy|] * w[|dx|]. The taps travel as kernel arguments: they are read before the
+ *             call returns and no device table exists. toad_amd.heatmap.gaussian_taps gives Gaussian ones.
+ *   output    out[gy][gx] = -1 if cells[gy][gx] < 0 (coverage edges stay sharp). Otherwise, over dy, dx in -radius .. radius such that (gy + dy, gx + dx)
+ *             lies inside the table and holds a value v >= 0 (the cell itself is one of them, so D >= 1):
+ *                 N = sum w[|dy|] * w[|dx|] * min(v, 255),   D = sum w[|dy|] * w[|dx|],   out = (2 * N + D) / (2 * D),
+ *             which is N / D rounded half up. A normalised convolution: absent cells and cells outside the table carry no weight, so the colour does
+ *             not fade towards the edge of the tissue (CLAM's zero-filled overlay does; this does not claim to be OpenCV bit for bit); a constant
+ *             field is reproduced exactly; taps = (k, 0, .., 0) is the identity. N <= 255 * 1024^2 and 2 * N + D fit in int32 - the reason for the
+ *             bound of 1024 - and N and D are exactly separable with no rounding before the one division: the result does not depend on summation order.
+ * EVERY element of out is written by the call, by one thread; nothing outside cells[0 .. Gy * Gx) is read. One launch, asynchronous on `stream`, nothing
+ * allocated, no synchronisation. Refusals, in this order, before anything is launched: Gy or Gx < 1 or Gy * Gx >= 2^31 (TOAD_ESHAPE); radius outside
+ * 1 .. 16 (TOAD_ESHAPE); taps NULL, a negative tap, taps[0] < 1 or a sum above 1024 (TOAD_EINVAL); out == cells (TOAD_EINVAL; a NULL cells or out is
+ * TOAD_EINVAL before everything else); cells or out not 4-byte aligned (TOAD_EALIGN). Not done: per-axis kernels, radii above 16 cells, CLAM's second
+ * blur of the coloured image, seams between separately rendered regions. */
+int toad_heat_cells_blur(const int *cells, int Gy, int Gx, const int *taps /* HOST, radius + 1 ints */, int radius, int *out, void *stream);
+
 /* out uint8 [Ho][Wo][3] with row pitch out_pitch >= 3 * Wo bytes = the canvas of `region` under `cells` [Gy][Gx] (Gy = ceil(Hr / cell), Gx = ceil(Wr /
  * cell) exactly; values -1 .. 255), `lut` [256][3], `alpha` in [0, 256] and `down` in {1, 2, 4}: TOAD_ESHAPE otherwise. region and pitch as for
  * toad_region_tissue_cells_u8: any base address, any pitch >= 3 * Wr, 64-bit row bases, 32-bit offsets inside a row (3 * Wr >= 2^31: TOAD_ESHAPE). out
@@ -444,8 +464,8 @@ int toad_region_heat_blend_u8(const unsigned char *region, int64_t pitch, int Hr
  *                 not tissue. This is the (plane, t) pair of the segmented tissue selection below, read as it lies.
  *   output byte   (alpha * lut[idx_px][c] + (256 - alpha) * m + 128) >> 8 where own >= 0 and the pixel is tissue, m elsewhere. Coverage edges and mask
  *                 edges stay sharp; only the colour inside them is interpolated.
- * This is not CLAM's Gaussian `blur` and does not claim to be: the smoothing width is one cell. Seams between separately rendered regions (a neighbour
- * outside the table counts as `own`), wider kernels and cell-level pre-smoothing passes are not done.
+ * This is not CLAM's Gaussian `blur` and does not claim to be: the smoothing width is one cell. The wider kernel is toad_heat_cells_blur above, a pass
+ * over the cells in front of this call. Seams between separately rendered regions (a neighbour outside the table counts as `own`) are not done.
  * Refusals as for toad_region_heat_blend_u8, and: smooth not 0 or 1, mask_thresh outside 0 .. 255 (TOAD_EINVAL); a mask_down not in the list or not a
  * multiple of down, Hm or Wm not the floor quotients, mask_pitch < Wm (TOAD_ESHAPE). No byte outside mask + y * mask_pitch + [0, Wm), 0 <= y < Hm, is read;
  * the mask may have any base address. Ho == 0 or Wo == 0: returns TOAD_OK and launches nothing. One streaming pass. */

@@ -18,8 +18,12 @@
 //   overview    (toad_region_heat_thumb_u8) the per-pixel canvas at down in {8, 16, 32} with down <= cell, so that a box still lies in one cell: the
 //               slide overview of an 80k x 80k region without a full-size canvas in between.
 //
-// Three kernels:
-//   heat_thumb_kernel<DOWN>                 the overview canvas: the same streaming pass with a box's lanes and waves reduced, one thread per canvas pixel blends.
+//   blur        (toad_heat_cells_blur) the cell table smoothed before it is rendered: a normalised convolution with a symmetric separable integer kernel
+//               of radius 1 .. 16 cells, absent cells and cells outside the table carrying no weight, absent cells staying absent.
+//
+// Four kernels:
+//   heat_cells_blur_kernel                 a 16 x 64 tile of the cell table and its halo in LDS, a row pass and a column pass inside the workgroup.
+//   heat_thumb_kernel<DOWN>               the overview canvas: the same streaming pass with a box's lanes and waves reduced, one thread per canvas pixel blends.
 //   heat_cells_kernel                      one thread per cell: the covering tiles' index ranges in closed form from the lattice in cell units, a loop over them.
 //   heat_blend_px_kernel<DOWN,SMOOTH,MASK>  one streaming pass over the region: read uint8, write uint8. <DOWN,0,false> is the flat canvas (one colour and one
 //                                           alpha per cell: both entry points launch it); the others decide the index, the colour and the alpha per canvas pixel.
@@ -49,6 +53,68 @@ __global__ __launch_bounds__(256) void heat_cells_kernel(const int *__restrict__
             if (n > 0) idx = (2 * s + 257 * n) / (514 * n);
         }
         cells[t] = idx;
+    }
+}
+
+// ---- the Gaussian blur of the cell table: toad_heat_cells_blur ----
+// A normalised convolution in integers (include/toad_hip.h): out = (2 N + D) / (2 D) with N = sum w[|dy|] w[|dx|] min(v, 255) and D = sum w[|dy|] w[|dx|]
+// over the cells of the (2 r + 1)^2 window that lie inside the table and hold a value, -1 where the cell itself holds none. A workgroup owns a tile of
+// BLUR_TH x BLUR_TW cells. Its window of (TH + 2 r) x (TW + 2 r) cells goes to LDS as  min(v, 255) | 1 << 20  for a value and 0 for a cell that is absent
+// or outside the table, so that one multiply-add per tap sums N1 and D1 of the row pass in ONE dword, N1 | D1 << 20: N1 <= 255 * 1024 < 2^20 and
+// D1 <= 1024. The row pass (a wave per window row, a lane per tile column) leaves (TH + 2 r) x TW such dwords in LDS, the column pass takes them apart
+// again: N <= 255 * 1024^2 and 2 N + D < 2^31. Lanes read consecutive dwords in both passes. The taps are kernel arguments, zero beyond r; the tap
+// loops are unrolled with a uniform exit at r so that every tap is read from a scalar register. Nothing outside [0, Gy) x [0, Gx) is read, every
+// element of out is written once by one thread, there is no atomic. 30 KB of LDS, sized for r = 16.
+constexpr int BLUR_R = 16, BLUR_TH = 16, BLUR_TW = 64, BLUR_IW = BLUR_TW + 2 * BLUR_R, BLUR_IH = BLUR_TH + 2 * BLUR_R;
+struct HeatBlurTaps { int w[BLUR_R + 1]; };
+
+__global__ __launch_bounds__(256) void heat_cells_blur_kernel(const int *__restrict__ cells, int Gy, int Gx, const HeatBlurTaps taps, int r, unsigned ntx,
+                                                              int *__restrict__ out) {
+    __shared__ unsigned in_s[BLUR_IH * BLUR_IW], mid_s[BLUR_IH * BLUR_TW];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t tx0 = (int64_t)(blockIdx.x % ntx) * BLUR_TW, ty0 = (int64_t)(blockIdx.x / ntx) * BLUR_TH;
+    const int rows = BLUR_TH + 2 * r, cols = BLUR_TW + 2 * r;
+    for (int row = wave; row < rows; row += 4) {
+        const int64_t gy = ty0 - r + row;
+        const bool iny = gy >= 0 && gy < Gy;
+        for (int c = lane; c < cols; c += 64) {
+            const int64_t gx = tx0 - r + c;
+            const int v = iny && gx >= 0 && gx < Gx ? cells[gy * Gx + gx] : -1;
+            in_s[row * BLUR_IW + c] = v >= 0 ? (unsigned)min(v, 255) | (1u << 20) : 0u;
+        }
+    }
+    __syncthreads();
+    for (int row = wave; row < rows; row += 4) {                     // the row pass: N1 | D1 << 20 of window row `row` at tile column `lane`
+        const unsigned *p = in_s + row * BLUR_IW + r + lane;
+        unsigned s = (unsigned)taps.w[0] * p[0];
+#pragma unroll
+        for (int d = 1; d <= BLUR_R; ++d) {
+            if (d > r) break;
+            s += (unsigned)taps.w[d] * (p[-d] + p[d]);
+        }
+        mid_s[row * BLUR_TW + lane] = s;
+    }
+    __syncthreads();
+    const int64_t gx = tx0 + lane;
+#pragma unroll
+    for (int k = 0; k < BLUR_TH / 4; ++k) {                          // the column pass: tile row y, tile column `lane`
+        const int y = wave * (BLUR_TH / 4) + k;
+        const int64_t gy = ty0 + y;
+        if (gy >= Gy || gx >= Gx) continue;
+        int res = -1;
+        if (in_s[(y + r) * BLUR_IW + r + lane] != 0u) {
+            const unsigned *q = mid_s + (y + r) * BLUR_TW + lane;
+            unsigned N = (unsigned)taps.w[0] * (q[0] & 0xFFFFFu), D = (unsigned)taps.w[0] * (q[0] >> 20);
+#pragma unroll
+            for (int d = 1; d <= BLUR_R; ++d) {
+                if (d > r) break;
+                const unsigned a = q[-d * BLUR_TW], b = q[d * BLUR_TW];
+                N += (unsigned)taps.w[d] * ((a & 0xFFFFFu) + (b & 0xFFFFFu));
+                D += (unsigned)taps.w[d] * ((a >> 20) + (b >> 20));
+            }
+            res = (int)((2u * N + D) / (2u * D));                  // the cell itself counts and w[0] >= 1: D >= 1
+        }
+        out[gy * Gx + gx] = res;
     }
 }
 
@@ -432,6 +498,36 @@ extern "C" int toad_heat_cells(const int *tile_q, int nx, int ny, int cell, int 
     const uint64_t g = ((uint64_t)Gy * Gx + 255) / 256;
     hipLaunchKernelGGL(heat_cells_kernel, dim3((unsigned)(g > 8192 ? 8192 : g)), dim3(256), 0, (hipStream_t)stream, tile_q, nx, ny, x0 / cell, y0 / cell,
                        H / cell, W / cell, sx / cell, sy / cell, Gy, Gx, cells);
+    return check_launch(what);
+}
+
+extern "C" int toad_heat_cells_blur(const int *cells, int Gy, int Gx, const int *taps, int radius, int *out, void *stream) {
+    const char *what = "toad_heat_cells_blur";
+    if (!cells || !out) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (Gy < 1 || Gx < 1 || (int64_t)Gy * Gx >= ((int64_t)1 << 31)) {
+        set_error("%s: bad shape Gy=%d Gx=%d (both >= 1, Gy * Gx < 2^31)", what, Gy, Gx);
+        return TOAD_ESHAPE;
+    }
+    if (radius < 1 || radius > BLUR_R) { set_error("%s: radius = %d must lie in 1 .. %d cells", what, radius, BLUR_R); return TOAD_ESHAPE; }
+    if (!taps) { set_error("%s: null taps (a HOST array of radius + 1 ints)", what); return TOAD_EINVAL; }
+    HeatBlurTaps t = {};
+    int64_t sum = 0;
+    for (int d = 0; d <= radius; ++d) {
+        if (taps[d] < (d == 0 ? 1 : 0) || taps[d] > 1024) {
+            set_error("%s: taps[%d] = %d (taps[0] >= 1, every tap >= 0, taps[0] + 2 * sum of the others <= 1024)", what, d, taps[d]);
+            return TOAD_EINVAL;
+        }
+        t.w[d] = taps[d];
+        sum += d == 0 ? taps[d] : 2 * (int64_t)taps[d];
+    }
+    if (sum > 1024) {
+        set_error("%s: the taps sum to %lld: taps[0] + 2 * sum of the others must not exceed 1024 (2 N + D in int32)", what, (long long)sum);
+        return TOAD_EINVAL;
+    }
+    if (out == cells) { set_error("%s: out must not be cells (a cell is read by its neighbours' threads)", what); return TOAD_EINVAL; }
+    if (!aligned4(cells) || !aligned4(out)) { set_error("%s: cells and out (int32) must be 4-byte aligned", what); return TOAD_EALIGN; }
+    const int64_t ntx = ((int64_t)Gx + BLUR_TW - 1) / BLUR_TW, blocks = ntx * (((int64_t)Gy + BLUR_TH - 1) / BLUR_TH);      // < 2^21 + 2^27 + 2^25
+    hipLaunchKernelGGL(heat_cells_blur_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, cells, Gy, Gx, t, radius, (unsigned)ntx, out);
     return check_launch(what);
 }
 

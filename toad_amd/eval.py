@@ -265,7 +265,7 @@ def _tissue_scores(extractor, model, region, tile, stride, min_fraction, sat_thr
 def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region: torch.Tensor, tile=256, stride=None, min_fraction: float = 0.25,
                                     sat_thresh: int = 8, val_min: int = 0, bag_dtype: torch.dtype = torch.float16, alpha=102, down: int = 1, lut=None,
                                     out=None, segment: Optional[dict] = None, smooth: bool = False, tissue_mask: bool = False, thresh=None,
-                                    binarize: bool = False):
+                                    binarize: bool = False, blur=False):
     """``(origins, scores, canvas)`` of one decoded uint8 region [Hr,Wr,3]: ``region_tissue_attention_scores(..., percentile=True)`` selects and scores the
     tissue tiles, ``heatmap.attention_canvas`` renders those percentile scores onto the region on the same lattice, on the device - uint8
     [Hr // down, Wr // down, 3]; the tiles that were not selected keep the (box-filtered) pixels of the region. ``alpha``, ``down``, ``lut`` and ``out``:
@@ -278,9 +278,19 @@ def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region
     ``down``; the canvas ``down`` must be one of 1 .. 32 and that ``down`` a multiple of it (ValueError otherwise, before anything is launched).
 
     ``down`` in 8, 16, 32 gives the slide overview in one pass (``ops.region_heat_thumb``; the lattice's cell must be at least ``down``). With the CLAM
-    default segment ``down = 16`` masked canvases at 8 and 16 work; one at 32 needs ``segment=dict(down=32)``. CLAM's Gaussian ``blur``, several levels
-    of its vis-level pyramid in one call (one level per call is done) and saving the image are not done here."""
-    from .heatmap import attention_canvas
+    default segment ``down = 16`` masked canvases at 8 and 16 work; one at 32 needs ``segment=dict(down=32)``.
+
+    ``blur`` (CLAM's ``blur``): ``heatmap.attention_canvas`` - False, True for CLAM's Gaussian width ``0.6 tile + 0.5`` pixels, a sigma in pixels, or the
+    integer taps; the cell table is smoothed by ``ops.heat_cells_blur`` before it is rendered, and a bad value raises ValueError before the selection runs.
+
+    Not done here: a sigma per axis for tiles that are not square, radii above 16 cells (``blur=True`` on lattices whose cell is 16 or less), CLAM's
+    second blur of the coloured image, seams between separately rendered regions, several levels of the vis-level pyramid in one call (one level per
+    call is done) and saving the image."""
+    from .heatmap import attention_canvas, blur_taps
+    from .tissue import _lattice_args, lattice_cell
+    if blur is not None and blur is not False:                      # refuse a bad blur before the extractor runs; attention_canvas parses it again
+        h, w, sy, sx, x0, y0 = _lattice_args(tile, stride, (0, 0))
+        blur_taps(blur, (h, w), lattice_cell((h, w), (sy, sx), (x0, y0)))
     if tissue_mask and isinstance(segment, dict):                   # (without a dict _select_origins refuses)
         seg_down = _segment_down(segment)
         if down not in (1, 2, 4, 8, 16, 32) or not isinstance(seg_down, int) or seg_down % down:
@@ -289,4 +299,4 @@ def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region
     origins, scores, mask = _tissue_scores(extractor, model, region, tile, stride, min_fraction, sat_thresh, val_min, bag_dtype, True, segment,
                                            return_mask=tissue_mask)
     return origins, scores, attention_canvas(region, origins, scores, tile=tile, stride=stride, alpha=alpha, down=down, lut=lut, out=out, smooth=smooth,
-                                             mask=mask, thresh=thresh, binarize=binarize)
+                                             mask=mask, thresh=thresh, binarize=binarize, blur=blur)

@@ -27,14 +27,27 @@ At overview scale - CLAM renders at a ``vis_level`` whose downsample is typicall
 32 (``ops.region_heat_thumb``): one pass over the region, no full-size canvas in between and no second rounding. There ``down`` must not exceed the
 lattice's cell, so that a canvas box still lies in one cell, and ``mask_down`` is a multiple of ``down`` as before.
 
-This is CLAM's ``segment=True`` and a one-cell-wide stand-in for its ``blur``; it is NOT CLAM's Gaussian and does not claim to be. ``thresh`` and
+This is CLAM's ``segment=True``; ``smooth`` alone is one cell wide and removes the staircase inside a cell, not tile-to-tile score noise. ``thresh`` and
 ``binarize`` (CLAM's ``thresh``, ``binarize``) act on the tiles' scores before the table is built.
 
+``blur`` (CLAM's ``blur``) smooths the cell table itself, before any of the above renders it (``ops.heat_cells_blur``, one launch over the small
+``[Gy,Gx]`` table). CLAM blurs the overlay with ``cv2.GaussianBlur(overlay, (4 tile + 1, 4 tile + 1), 0)``, sigma = ``0.6 tile + 0.5`` pixels - about 2.4
+cells on the usual 256 / 64 lattice, a field band-limited far below the cell pitch, which the tent then renders. In integers, with a half-kernel
+``w[0 .. r]`` of ints, ``1 <= r <= 16``, ``w[0] >= 1``, ``w[d] >= 0``, ``w[0] + 2 sum w[1:] <= 1024`` (``gaussian_taps``):
+
+* a cell without a value keeps none; otherwise, over ``dy, dx`` in ``-r .. r`` such that cell ``(gy + dy, gx + dx)`` lies inside the table and holds a
+  value ``v``: ``N = sum w[|dy|] w[|dx|] min(v, 255)``, ``D = sum w[|dy|] w[|dx|]``, and the cell becomes ``(2 N + D) // (2 D)``;
+* a normalised convolution: absent cells and cells outside the table carry no weight, so the colour does not fade towards the edge of the tissue
+  (CLAM's zero-filled overlay does; this does not claim to be OpenCV bit for bit), a constant field is reproduced exactly, ``(k, 0, ..)`` is the
+  identity, and nothing rounds before the one division: the result does not depend on summation order.
+
 Conventions as in ``toad_amd.tissue``: ``tile`` = int or (H, W), ``stride`` = int or (sy, sx), ``origin`` = (x, y) of the lattice's first tile.
-Seams between separately rendered regions (a neighbour outside the table counts as ``own``), smoothing kernels wider than one cell, cell-level
-pre-smoothing passes, CLAM's Gaussian, several levels of its vis-level pyramid in one call (one level per call is done) and saving images are not done
-here."""
+Not done here: a sigma per axis for tiles that are not square, radii above 16 cells (``blur=True`` on lattices whose cell is 16 or less), CLAM's second
+blur of the coloured image, seams between separately rendered regions (a neighbour outside the table counts as ``own`` for the tent and carries no weight
+for the blur), several levels of the vis-level pyramid in one call (one level per call is done) and saving images."""
 from __future__ import annotations
+
+import math
 
 import numpy as np
 import torch
@@ -133,8 +146,50 @@ def _mask_arg(mask):
     return mask
 
 
+def gaussian_taps(sigma_cells, radius=None) -> tuple:
+    """The half-kernel ``w[0 .. r]`` of ``ops.heat_cells_blur`` for a Gaussian of ``sigma_cells`` cells, a tuple of Python ints: ``g[d] = exp(-d^2 / (2
+    sigma^2))`` in float64, ``G = g[0] + 2 sum g[1:]``, ``w[d] = floor((1023 - 2 r) g[d] / G + 0.5)``. ``radius`` defaults to ``ceil(3 sigma)``. Each of
+    the ``2 r + 1`` taps of the full kernel rounds by at most a half, so the scale ``1023 - 2 r`` keeps the full sum in ``[1024 - 2 (2 r + 1), 1024]``
+    with no fix-up step; the taps are symmetric by construction, non-increasing, and ``w[0] >= 1``. ValueError for a sigma that is not a positive finite
+    number and for a radius outside 1 .. ``ops.HEAT_BLUR_RADIUS`` = 16 cells."""
+    if isinstance(sigma_cells, bool) or not isinstance(sigma_cells, (int, float, np.integer, np.floating)) or not 0 < float(sigma_cells) < math.inf:
+        raise ValueError(f"gaussian_taps: sigma must be a positive finite number of cells, got {sigma_cells!r}")
+    sigma = float(sigma_cells)
+    if radius is None:
+        radius = max(1, math.ceil(3 * sigma))
+        if radius > ops.HEAT_BLUR_RADIUS:
+            raise ValueError(f"gaussian_taps: sigma = {sigma:g} cells needs a radius of ceil(3 sigma) = {radius} cells, above the limit of "
+                             f"{ops.HEAT_BLUR_RADIUS} cells (a coarser lattice cell, a smaller sigma or an explicit radius)")
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= radius <= ops.HEAT_BLUR_RADIUS:
+        raise ValueError(f"gaussian_taps: radius must be an int in 1 .. {ops.HEAT_BLUR_RADIUS} cells (sigma = {sigma:g} cells), got {radius!r}")
+    r = int(radius)
+    g = [math.exp(-(d * d) / (2.0 * sigma * sigma)) for d in range(r + 1)]
+    total = g[0] + 2.0 * sum(g[1:])
+    return tuple(int(math.floor((1023 - 2 * r) * gd / total + 0.5)) for gd in g)
+
+
+def blur_taps(blur, tile, cell):
+    """The ``blur`` keyword of ``attention_canvas`` -> None (no blur) or the taps of ``ops.heat_cells_blur``; ``tile`` = (h, w) and ``cell`` are the
+    lattice's. False / None: None. True: CLAM's width, ``cv2.GaussianBlur(overlay, (4 tile + 1, 4 tile + 1), 0)``, whose sigma is ``0.3 ((k - 1) / 2
+    - 1) + 0.8 = 0.6 tile + 0.5`` pixels - a square tile only. A positive number: sigma in region pixels. A sequence of ints: the taps themselves.
+    ValueError otherwise, and where the Gaussian needs more than ``ops.HEAT_BLUR_RADIUS`` cells."""
+    if blur is None or blur is False:
+        return None
+    h, w = tile
+    if blur is True:
+        if h != w:
+            raise ValueError(f"attention_canvas: blur=True is CLAM's width 0.6 tile + 0.5 and needs a square tile, got (H, W) = {(h, w)}; give sigma in "
+                             "pixels or the taps (per-axis sigma is not done)")
+        return gaussian_taps((0.6 * h + 0.5) / cell)
+    if isinstance(blur, (int, float, np.integer, np.floating)):
+        if not 0 < float(blur) < math.inf:
+            raise ValueError(f"attention_canvas: blur as a number is sigma in region pixels and must be positive and finite, got {blur!r}")
+        return gaussian_taps(float(blur) / cell)
+    return ops.heat_blur_taps("attention_canvas: blur", blur)
+
+
 def attention_canvas(region: torch.Tensor, origins, scores: torch.Tensor, tile=256, stride=None, origin=(0, 0), alpha=102, down: int = 1, lut=None,
-                     score_range=(0, 1), out=None, smooth: bool = False, mask=None, thresh=None, binarize: bool = False) -> torch.Tensor:
+                     score_range=(0, 1), out=None, smooth: bool = False, mask=None, thresh=None, binarize: bool = False, blur=False) -> torch.Tensor:
     """The heat map of one decoded uint8 region [Hr,Wr,3]: uint8 [Hr // down, Wr // down, 3] ON THE DEVICE. ``origins`` [B,2] of (x, y) on the host are
     tiles of the lattice (tile, stride, origin) inside the region - ``tissue.tissue_origins`` with the same arguments gives such - and ``scores`` their B
     scores on the device, in that order. The definition is the module's. ``alpha`` an int in [0, 256] or a float in [0, 1] (the default 102 is CLAM's
@@ -147,7 +202,12 @@ def attention_canvas(region: torch.Tensor, origins, scores: torch.Tensor, tile=2
     ``down`` in 8, 16, 32 renders the overview canvas through ``ops.region_heat_thumb`` with the same keywords and the same meaning; the lattice's cell
     (``tissue.lattice_cell``) must be at least ``down`` (ValueError otherwise, before anything is launched).
 
-    Two launches and a few small torch ops, no synchronisation. Empty ``origins`` give the box-filtered region."""
+    ``blur`` smooths the cell table between ``ops.heat_cells`` and the blend (``ops.heat_cells_blur``, the module's normalised convolution; ``blur_taps``):
+    False / None - today's launches and today's bytes; True - CLAM's width, sigma = ``0.6 tile + 0.5`` pixels (a square tile); a positive number - sigma
+    in region pixels; a sequence of ints - the taps. ``thresh`` and ``binarize`` act before it, ``smooth``, ``mask`` and every ``down`` after it, unchanged.
+    ValueError before anything is launched for any other value and for a Gaussian wider than 16 cells (``blur=True`` on a lattice whose cell is 16 or less).
+
+    Two launches (three with ``blur``) and a few small torch ops, no synchronisation. Empty ``origins`` give the box-filtered region and launch no blur."""
     _, hr, wr = ops._region_pitch(region, "attention_canvas")
     h, w, sy, sx, x0, y0 = _lattice_args(tile, stride, origin)
     cell = lattice_cell((h, w), (sy, sx), (x0, y0))
@@ -165,9 +225,12 @@ def attention_canvas(region: torch.Tensor, origins, scores: torch.Tensor, tile=2
     if thresh is not None and (isinstance(thresh, bool) or not isinstance(thresh, (int, float)) or thresh != thresh):
         raise ValueError(f"attention_canvas: thresh must be None or a number (a raw score), got {thresh!r}")
     plane, t, mask_down = _mask_arg(mask)
+    taps = blur_taps(blur, (h, w), cell)
     table = tile_table(origins, select_scores(scores, quantise_scores(scores, score_range), thresh, binarize), (h, w), (sy, sx), (x0, y0), (nx, ny))
     if table.numel() and len(origins):
         cells = ops.heat_cells(table, cell, (x0, y0), (h, w), (sy, sx), (nx, ny), (hr, wr))
+        if taps is not None:
+            cells = ops.heat_cells_blur(cells, taps)
     else:
         cells = torch.full((-(-hr // cell), -(-wr // cell)), -1, dtype=torch.int32, device=region.device)
     lut = jet_lut(region.device) if lut is None else lut

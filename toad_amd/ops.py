@@ -7,6 +7,7 @@ reference), the C side validates again and reports through toad_last_error().
 from __future__ import annotations
 
 import ctypes
+import numbers
 from typing import Optional, Tuple
 
 import torch
@@ -1485,6 +1486,47 @@ def heat_cells(tile_q: torch.Tensor, cell: int, origin, tile, stride, n, region_
     _lib.check(_lib.load().toad_heat_cells(_p(tile_q), nx, ny, cell, x0, y0, h, w, sx, sy, cells.shape[0], cells.shape[1], _p(cells), _stream()),
                "toad_heat_cells")
     return cells
+
+
+HEAT_BLUR_RADIUS = 16                  # the widest half-kernel of heat_cells_blur, in cells
+HEAT_BLUR_SUM = 1024                   # ... and the largest sum of its full 1-D kernel: 2 N + D then fits in int32
+
+
+def heat_blur_taps(name: str, taps) -> tuple:
+    """The half-kernel of heat_cells_blur as a tuple of Python ints, or ValueError: r + 1 ints with 1 <= r <= HEAT_BLUR_RADIUS, taps[0] >= 1, every tap >= 0
+    and taps[0] + 2 sum(taps[1:]) <= HEAT_BLUR_SUM."""
+    if isinstance(taps, (str, bytes, torch.Tensor)) or not hasattr(taps, "__len__") or not hasattr(taps, "__iter__"):
+        raise ValueError(f"{name}: taps must be a sequence of ints w[0 .. r] on the host (the half of a symmetric kernel), got {type(taps).__name__}")
+    w = tuple(taps)
+    if any(isinstance(t, bool) or not isinstance(t, numbers.Integral) for t in w):
+        raise ValueError(f"{name}: taps must be ints, got {w!r}")
+    w = tuple(int(t) for t in w)
+    if not 1 <= len(w) - 1 <= HEAT_BLUR_RADIUS:
+        raise ValueError(f"{name}: the radius len(taps) - 1 = {len(w) - 1} must lie in 1 .. {HEAT_BLUR_RADIUS} cells")
+    if w[0] < 1 or min(w) < 0:
+        raise ValueError(f"{name}: taps[0] must be >= 1 and every tap >= 0, got {w!r}")
+    if w[0] + 2 * sum(w[1:]) > HEAT_BLUR_SUM:
+        raise ValueError(f"{name}: taps[0] + 2 sum(taps[1:]) = {w[0] + 2 * sum(w[1:])} exceeds {HEAT_BLUR_SUM} (2 N + D must fit in int32)")
+    return w
+
+
+def heat_cells_blur(cells: torch.Tensor, taps) -> torch.Tensor:
+    """The cell table of heat_cells smoothed by the symmetric separable integer kernel w[|dy|] w[|dx|], w = taps (heat_blur_taps; heatmap.gaussian_taps gives
+    Gaussian ones): a new int32 [Gy,Gx] on the device. A cell without a value (-1) keeps none; elsewhere, over the cells of the (2 r + 1)^2 window that lie
+    inside the table and hold a value v (above 255 reads as 255), N = sum w w min(v, 255), D = sum w w and the result is (2 N + D) // (2 D) - a
+    normalised convolution in integers (include/toad_hip.h): absent cells carry no weight, a constant field is reproduced, (k, 0, ..) is the identity.
+    The taps travel as kernel arguments. One launch, no synchronisation; an empty table launches nothing."""
+    name = "heat_cells_blur"
+    _chk(cells, "cells", dtype=torch.int32)
+    if cells.dim() != 2 or cells.numel() >= 1 << 31:
+        raise ValueError(f"{name}: expected an int32 [Gy,Gx] table of fewer than 2^31 cells, got {tuple(cells.shape)}")
+    w = heat_blur_taps(name, taps)
+    out = torch.empty_like(cells)
+    if cells.numel() == 0:
+        return out
+    _lib.check(_lib.load().toad_heat_cells_blur(_p(cells), cells.shape[0], cells.shape[1], (ctypes.c_int * len(w))(*w), len(w) - 1, _p(out), _stream()),
+               "toad_heat_cells_blur")
+    return out
 
 
 def _heat_blend_args(name: str, region, cells, cell, lut, alpha, down, out):

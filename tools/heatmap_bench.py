@@ -34,8 +34,19 @@ its alternation of the arms inside one process, warm-up of every arm, its four s
     T_flat and T_both are checked bit-equal to the torch statement of the definition (torch_canvas) on every slide before anything is timed. t_over_s =
     median over median next to s_spread, S's own interleaved-halves spread; moved bytes = 3 Hr Wr read + 3 Ho Wo written.
 
+  blur (--blur): what the Gaussian blur of the cell table (ops.heat_cells_blur, heat_cells_blur_kernel) costs. Tables of 64 x 128 cells (the 4096 x 8192
+    slide at cell 64) and 1563 x 1563 cells (a 100k x 100k slide), about a third of the cells absent, Gaussian taps of radius 8 and 15. Arms, alternated in
+    one process:
+      A_hip     ops.heat_cells_blur;
+      B_torch   the same definition in torch device ops: v p and p stacked, a float64 conv2d along x and one along y (sums below 2^53: exact), then
+                (2 N + D) // (2 D) in int64 - checked torch.equal to A_hip before anything is timed;
+      cells     the yardstick: the ops.heat_cells launch that builds a table of this size (256 x 256 tiles at stride 64).
+    Then, on the rotating 4096 x 8192 slides at down = 1 and 16: heatmap.attention_canvas with blur=False and blur=True into a canvas allocated once (the
+    whole call: host arithmetic, the index upload and the launches), and the launches alone (heat_cells [+ heat_cells_blur] + the blend) - canvas_blur
+    is checked to differ from canvas_plain and launches_blur to equal canvas_blur bit for bit. Default output profiles/heatmap_blur_bench.jsonl.
+
 Prints one JSON line per result; --out FILE keeps them.
-usage: heatmap_bench.py [--launches --arm A|B --down D] [--px | --thumb] [--seconds S] [--out FILE]"""
+usage: heatmap_bench.py [--launches --arm A|B --down D] [--px | --thumb | --blur] [--seconds S] [--out FILE]"""
 import argparse
 import json
 import os
@@ -234,6 +245,92 @@ def thumb(seconds):
     return res
 
 
+BLUR_TABLES = ((GY, GX), (1563, 1563))
+BLUR_RADII = (8, 15)
+
+
+def torch_blur(cells, taps):
+    """ops.heat_cells_blur in torch device ops: the definition of include/toad_hip.h, separably, in float64 (every sum is an integer below 2^53)."""
+    import torch.nn.functional as F
+    r = len(taps) - 1
+    w = torch.tensor(list(taps[:0:-1]) + list(taps), dtype=torch.float64, device=cells.device)
+    p = cells >= 0
+    x = torch.stack([cells.clamp(0, 255) * p, p.to(cells.dtype)]).unsqueeze(1).to(torch.float64)      # [2,1,Gy,Gx]: v p and p
+    x = F.conv2d(F.conv2d(x, w.view(1, 1, 1, -1), padding=(0, r)), w.view(1, 1, -1, 1), padding=(r, 0))
+    n, d = x[0, 0].to(torch.int64), x[1, 0].to(torch.int64)
+    return torch.where(p, (2 * n + d) // (2 * d).clamp(min=1), torch.full_like(n, -1)).to(torch.int32)
+
+
+def blur(seconds):
+    """The --blur figures: one record per (table, radius), then one per canvas down."""
+    import numpy as np
+    from toad_amd.heatmap import attention_canvas, gaussian_taps
+    dev = torch.device("cuda:0")
+    res = []
+    for gy, gx in BLUR_TABLES:
+        ny, nx = gy - TILE // CELL + 1, gx - TILE // CELL + 1
+        g = torch.Generator().manual_seed(gy + gx)
+        q = torch.randint(0, 65536, (ny, nx), generator=g, dtype=torch.int32)
+        table = torch.where(torch.rand(ny, nx, generator=g) < 0.5, q, torch.full_like(q, -1)).to(dev)
+        build = lambda: ops.heat_cells(table, CELL, (0, 0), (TILE, TILE), (STRIDE, STRIDE), (nx, ny), (gy * CELL, gx * CELL))      # noqa: E731
+        cells = build()
+        hole = torch.rand(gy, gx, generator=g).to(dev) < 0.3        # coverage 4 x 4 at this stride leaves few cells absent: take a third out
+        cells = torch.where(hole, torch.full_like(cells, -1), cells).contiguous()
+        for radius in BLUR_RADII:
+            taps = gaussian_taps(radius / 3.0, radius)
+            same = bool(torch.equal(ops.heat_cells_blur(cells, taps), torch_blur(cells, taps)))
+            if not same:                                                       # a wrong arm must not produce a quoted ratio
+                raise SystemExit(f"heatmap_bench: heat_cells_blur differs from its torch arm on {gy} x {gx} cells at radius {radius}: nothing is timed")
+            arms = {"A_hip": lambda: ops.heat_cells_blur(cells, taps), "B_torch": lambda: torch_blur(cells, taps), "cells": build}
+            t, iters = alternate(arms, seconds)
+            a = t["A_hip"]
+            a1, a2 = median(a[0::2]), median(a[1::2])
+            res.append(dict(kind="heat_cells_blur", table=[gy, gx], radius=radius, taps=list(taps), absent_cells=round(float((cells < 0).float().mean()), 4),
+                            rounds=len(a), iters_per_round=iters, ms={k: round(median(v), 5) for k, v in t.items()},
+                            ms_min={k: round(min(v), 5) for k, v in t.items()}, ms_max={k: round(max(v), 5) for k, v in t.items()},
+                            a_halves_ms=[round(a1, 5), round(a2, 5)], a_spread=round(abs(a1 - a2) / median(a), 4),
+                            a_over_cells=round(median(a) / median(t["cells"]), 3), b_over_a=round(median(t["B_torch"]) / median(a), 2),
+                            cells_per_us_a=round(gy * gx / median(a) / 1e3, 1), hip_equals_torch=same))
+    slides, table, lut = setup(dev)
+    present = (table >= 0).cpu().numpy()
+    jj, ii = np.nonzero(present)
+    origins = np.stack([ii * STRIDE, jj * STRIDE], axis=1).astype(np.int64)
+    scores = (table[table >= 0].float() / 65535).contiguous()
+    lat = dict(tile=TILE, stride=STRIDE)
+    taps = gaussian_taps((0.6 * TILE + 0.5) / CELL)
+    for down in (1, 16):
+        out = torch.empty((HR // down, WR // down, 3), dtype=torch.uint8, device=dev)
+        blend = ops.region_heat_thumb if down in ops.HEAT_THUMB_DOWNS else ops.region_heat_blend_px
+
+        def launches_only(r, blurred):
+            c = ops.heat_cells(table, CELL, (0, 0), (TILE, TILE), (STRIDE, STRIDE), (NX, NY), (HR, WR))
+            return blend(r, ops.heat_cells_blur(c, taps) if blurred else c, CELL, lut, ALPHA, down, out=out)
+
+        plain = lambda r: attention_canvas(r, origins, scores, down=down, out=out, **lat)                   # noqa: E731
+        blurred = lambda r: attention_canvas(r, origins, scores, down=down, out=out, blur=True, **lat)      # noqa: E731
+        differs = float((blurred(slides[0]).clone() != plain(slides[0])).any(dim=2).float().mean())
+        same = all(bool(torch.equal(blurred(s).clone(), launches_only(s, True))) and bool(torch.equal(plain(s).clone(), launches_only(s, False))) for s in slides)
+        if not (same and differs > 0):
+            raise SystemExit(f"heatmap_bench: attention_canvas and its launches disagree at down = {down} ({same}), or blur=True changed nothing: nothing is timed")
+        arms = {"canvas_plain": Rotating(plain, slides), "canvas_blur": Rotating(blurred, slides),
+                "launches_plain": Rotating(lambda r: launches_only(r, False), slides), "launches_blur": Rotating(lambda r: launches_only(r, True), slides)}
+        t, iters = alternate(arms, seconds)
+        a = t["launches_plain"]
+        a1, a2 = median(a[0::2]), median(a[1::2])
+        res.append(dict(kind="resident_heatmap_blur", region=[HR, WR], tile=TILE, stride=STRIDE, cell=CELL, down=down, alpha=ALPHA, taps=list(taps),
+                        tiles_present=int(len(origins)), slides_rotated=len(slides), rounds=len(a), iters_per_round=iters,
+                        ms={k: round(median(v), 5) for k, v in t.items()}, ms_min={k: round(min(v), 5) for k, v in t.items()},
+                        ms_max={k: round(max(v), 5) for k, v in t.items()}, launches_plain_halves_ms=[round(a1, 5), round(a2, 5)],
+                        launches_plain_spread=round(abs(a1 - a2) / median(a), 4),
+                        blur_extra_ms={"canvas": round(median(t["canvas_blur"]) - median(t["canvas_plain"]), 5),
+                                       "launches": round(median(t["launches_blur"]) - median(a), 5)},
+                        blur_over_plain={"canvas": round(median(t["canvas_blur"]) / median(t["canvas_plain"]), 4),
+                                         "launches": round(median(t["launches_blur"]) / median(a), 4)},
+                        pixels_changed_by_blur=round(differs, 4), canvas_equals_launches=same))
+        del out
+    return res
+
+
 def launches(arm, down, calls=4):
     """`calls` calls of one arm on rotating slides, no warm-up (run under rocprofv3 --kernel-trace --stats: every count divides by `calls`)."""
     dev = torch.device("cuda:0")
@@ -253,10 +350,13 @@ def main():
     ap.add_argument("--down", type=int, default=1, choices=(1, 2, 4))
     ap.add_argument("--px", action="store_true")
     ap.add_argument("--thumb", action="store_true")
+    ap.add_argument("--blur", action="store_true")
     ap.add_argument("--seconds", type=float, default=3.0)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    res = launches(a.arm, a.down) if a.launches else thumb(a.seconds) if a.thumb else resident(a.seconds, a.px)
+    if a.blur and not a.out:
+        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "heatmap_blur_bench.jsonl")
+    res = launches(a.arm, a.down) if a.launches else blur(a.seconds) if a.blur else thumb(a.seconds) if a.thumb else resident(a.seconds, a.px)
     lines = [json.dumps(r) for r in res]
     print("\n".join(lines), flush=True)
     if a.out:
