@@ -367,6 +367,24 @@ int toad_resnet50_trunc_fwd_u8_region(const unsigned char *region, int64_t pitch
                                       const float *const *weights, const float *const *biases, float *feat, void *feat_f16, int B, int H, int W,
                                       void *ws, size_t ws_bytes, void *stream);
 
+/* ---- Tiles by origin with a box filter in front: 40x scans read at the 20x-equivalent pitch (an additive extension of ABI 15) ----
+ * The three region calls above with one more argument, `shrink` in {1, 2} (anything else: TOAD_ESHAPE; factors above 2 and filters other than the box are
+ * not built). H, W stay the NETWORK tile's; tile b is the FOOTPRINT of (shrink H) x (shrink W) region pixels at origin (x, y), and
+ *     t[iy, ix, c] = (sum of region[y + s iy + dy, x + s ix + dx, c] over dy, dx in 0 .. s-1, + s*s/2) / (s*s)          (integer division)
+ * the mean rounded half up - CLAM's custom_downsample = 2 as the box filter every `down` of this library uses. Each call is BITWISE its uint8 tile twin on
+ * those tiles t; padding is the tile's, no byte outside the footprints is read, and on the 256-wide route neither a tile copy nor a float image exists (the
+ * window loader of the stem sums the four bytes while it loads). shrink == 1 runs the launches of the call without the argument.
+ * Refusals, all on the host before any device work: those of the twin, in its order, with the FOOTPRINT in the region's checks - every origin must keep
+ * x + shrink W <= Wr, y + shrink H <= Hr (the caller's duty, as above), shrink H > Hr or shrink W > Wr and shrink H * pitch >= 2^31 are TOAD_ESHAPE; a bad
+ * shrink is reported right after the null pointers. Workspaces are the network tile's: toad_linear_ws_bytes / toad_resnet50_trunc_u8_ws_bytes(B, H, W). */
+int toad_tiles_u8_region_box_to_nchw_f32(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm, float *out,
+                                         int B, int H, int W, int shrink, void *stream);
+int toad_stem_pool_region_box_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm, const float *Wf,
+                                 const float *bias, float *Yp, int B, int H, int W, int shrink, void *ws, size_t ws_bytes, void *stream);
+int toad_resnet50_trunc_fwd_u8_region_box(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm,
+                                          const float *const *weights, const float *const *biases, float *feat, void *feat_f16, int B, int H, int W,
+                                          int shrink, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- Tissue selection: which tiles of a decoded region to read (an additive extension of ABI 15; the version number does not change) ----
  * The reference tree has no patching script: its bags come from CLAM's, which thresholds HSV saturation and keeps the tiles that hold tissue. The two
  * calls below produce the per-tile tissue-pixel counts from which the caller forms the `origins` of the region calls above; csrc/tissue.hip.

@@ -93,6 +93,10 @@ SIGNATURES = {
     "toad_tiles_u8_region_to_nchw_f32": (I, [P, I64, I, I, P, P, P, I, I, I, P]),
     "toad_stem_pool_region_u8": (I, [P, I64, I, I, P, P, P, P, P, I, I, I, P, SZ, P]),
     "toad_resnet50_trunc_fwd_u8_region": (I, [P, I64, I, I, P, P, P, P, P, P, I, I, I, P, SZ, P]),
+    # ... with a 2 x 2 box filter in front of the tile (shrink, after H and W; 1 = the calls above): additive to ABI 15
+    "toad_tiles_u8_region_box_to_nchw_f32": (I, [P, I64, I, I, P, P, P, I, I, I, I, P]),
+    "toad_stem_pool_region_box_u8": (I, [P, I64, I, I, P, P, P, P, P, I, I, I, I, P, SZ, P]),
+    "toad_resnet50_trunc_fwd_u8_region_box": (I, [P, I64, I, I, P, P, P, P, P, P, I, I, I, I, P, SZ, P]),
     # ... and the stage in front of them, tissue-pixel counts per cell and per lattice tile of a region: additive to ABI 15
     "toad_region_tissue_cells_u8": (I, [P, I64, I, I, I, I, I, P, P]),
     "toad_tissue_tile_counts": (I, [P, I, I, I, I, I, I, I, I, I, I, I, P, P]),

@@ -163,9 +163,12 @@ __global__ __launch_bounds__(256) void avgpool_nhwc_kernel(const float *__restri
 // REGION: the tiles are read by origin from one decoded image (src = uint8 [Hr, Wr, 3] with a row pitch in bytes, origins = int32 [B][2] = (x, y) of tile b's
 // top-left pixel): pixel p of tile b is at src + (y_b + p / W) pitch + (x_b + p % W) 3. A group that lies in one tile row is 12 contiguous bytes as above;
 // one that wraps into the next row takes its pixels one by one. Only bytes of the tile are read; the values and the stores are those of the tile form.
+// SHRINK == 2 (REGION only): tile b is the (2 H, 2 W) footprint at its origin and pixel p of the H x W tile the integer mean of its 2 x 2 box,
+// (sum + 2) >> 2 - the tile toad::stem_halo_pool_kernel<SH_U8_REGION_BOX2> sees - read byte by byte (this is the staged route, not the hot one); the fma and
+// the stores are the tile form's.
 struct TilesNoRegion {};
 struct TilesRegionArg { int64_t pitch; const int *origins; uint32_t W; };
-template <bool REGION>
+template <bool REGION, int SHRINK = 1>
 __global__ __launch_bounds__(256) void tiles_u8_nhwc_to_nchw_kernel(const unsigned char *__restrict__ src, float *__restrict__ out, uint64_t B, uint32_t HW,
                                                                     StemNorm nrm, typename std::conditional<REGION, TilesRegionArg, TilesNoRegion>::type rg) {
     const uint32_t gpi = (HW + 3) >> 2;                                   // groups per image
@@ -185,7 +188,17 @@ __global__ __launch_bounds__(256) void tiles_u8_nhwc_to_nchw_kernel(const unsign
             s = src + (b * HW + p0) * 3;
         }
         unsigned u[12];
-        if (!one_run) {
+        if constexpr (SHRINK == 2) {
+            // pixel (ye, xe) of the tile = the mean, rounded half up, of the 2 x 2 box at rows 2 ye, 2 ye + 1, bytes [6 xe, 6 xe + 6) of the footprint
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const uint32_t pe = p0 + e, ye = pe / rg.W, xe = pe - ye * rg.W;
+                const unsigned char *q = tile + (uint64_t)(2 * ye) * (uint64_t)rg.pitch + xe * 6;
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    u[3 * e + c] = (uint32_t)e < np ? ((unsigned)q[c] + q[3 + c] + q[rg.pitch + c] + q[rg.pitch + 3 + c] + 2u) >> 2 : 0u;
+            }
+        } else if (!one_run) {
             if constexpr (REGION) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -346,18 +359,27 @@ extern "C" int toad_tiles_u8_nhwc_to_nchw_f32(const unsigned char *tiles, const 
     return check_launch(what);
 }
 
-static int region_to_nchw(const RegionSrc &rg, const float *norm, float *out, int B, int H, int W, hipStream_t st, const char *what) {
+// shrink == 2: H x W is the network tile, the (2 H, 2 W) footprint at each origin is box-filtered on the way (stem_u8.h: check_region_u8)
+static int region_to_nchw(const RegionSrc &rg, const float *norm, float *out, int B, int H, int W, hipStream_t st, const char *what, int shrink = 1) {
     if (!norm || !out) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
-    if (int rc = check_region_u8(rg, H, W, what)) return rc;
+    if (int rc = check_region_u8(rg, H, W, what, shrink)) return rc;
     if (B <= 0 || (uint64_t)H * W >= (1ull << 31)) { set_error("%s: bad shape", what); return TOAD_ESHAPE; }
     if (int rc = check_norm_u8(norm, what)) return rc;
     if (!aligned16(out)) { set_error("%s: out must be 16-byte aligned (the region may have any alignment)", what); return TOAD_EALIGN; }
     StemNorm nrm;
     for (int c = 0; c < 3; ++c) { nrm.a[c] = norm[c]; nrm.b[c] = norm[3 + c]; }
     const uint32_t HW = (uint32_t)H * (uint32_t)W;
+    if (shrink == 2)
+        hipLaunchKernelGGL((tiles_u8_nhwc_to_nchw_kernel<true, 2>), dim3(grid_for((uint64_t)B * ((HW + 3) / 4))), dim3(256), 0, st, rg.region, out, (uint64_t)B, HW, nrm,
+                           TilesRegionArg{rg.pitch, rg.origins, (uint32_t)W});
+    else
     hipLaunchKernelGGL(tiles_u8_nhwc_to_nchw_kernel<true>, dim3(grid_for((uint64_t)B * ((HW + 3) / 4))), dim3(256), 0, st, rg.region, out, (uint64_t)B, HW, nrm,
                        TilesRegionArg{rg.pitch, rg.origins, (uint32_t)W});
     return check_launch(what);
+}
+extern "C" int toad_tiles_u8_region_box_to_nchw_f32(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm, float *out, int B,
+                                                    int H, int W, int shrink, void *stream) {
+    return region_to_nchw(RegionSrc{region, pitch, Hr, Wr, origins}, norm, out, B, H, W, (hipStream_t)stream, "toad_tiles_u8_region_box_to_nchw_f32", shrink);
 }
 extern "C" int toad_tiles_u8_region_to_nchw_f32(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm, float *out, int B,
                                                 int H, int W, void *stream) {
@@ -383,10 +405,11 @@ extern "C" size_t toad_resnet50_trunc_u8_ws_bytes(int B, int H, int W) {
 // biases[i]  : folded BN shift [Cout]; i runs in execution order (conv1, then per block conv1, conv2, conv3[, downsample]).
 // The network behind the three entry points. tiles_u8 == NULL: fp32 NCHW tiles (toad_resnet50_trunc_fwd_f32, arguments checked there). Otherwise uint8 NHWC tiles with
 // norm[6]: 256-wide tiles go straight into the stem kernel, others are converted into the staging image and take the fp32 call's three-kernel stem from there.
-// rg != NULL: the uint8 tiles are read by origin from rg->region (tiles_u8 == rg->region), by the region forms of the same two kernels.
+// rg != NULL: the uint8 tiles are read by origin from rg->region (tiles_u8 == rg->region), by the region forms of the same two kernels; shrink == 2: by their
+// box forms, H x W being the network tile and (2 H, 2 W) the footprint at each origin.
 // feat / feat16: either may be NULL; each one given receives the bag rows.
 static int trunc_fwd(const float *tiles_nchw, const unsigned char *tiles_u8, const float *norm, const float *const *weights, const float *const *biases, float *feat,
-                     void *feat16, const NetPlan &p, int B, int H, int W, void *ws, void *stream, const char *what, const RegionSrc *rg = nullptr) {
+                     void *feat16, const NetPlan &p, int B, int H, int W, void *ws, void *stream, const char *what, const RegionSrc *rg = nullptr, int shrink = 1) {
     hipStream_t st = (hipStream_t)stream;
     char *base = reinterpret_cast<char *>(ws);
     size_t off = align2m(reinterpret_cast<uintptr_t>(ws)) - reinterpret_cast<uintptr_t>(ws);
@@ -411,13 +434,13 @@ static int trunc_fwd(const float *tiles_nchw, const unsigned char *tiles_u8, con
     float *gx = slot();
     if (tiles_u8 && !stem_nchw_pool_ok(H, W)) {
         float *stage = reinterpret_cast<float *>(take((size_t)B * 3 * H * W * 4));
-        if (rg) TOAD_TRY(region_to_nchw(*rg, norm, stage, B, H, W, st, what));
+        if (rg) TOAD_TRY(region_to_nchw(*rg, norm, stage, B, H, W, st, what, shrink));
         else TOAD_TRY(toad_tiles_u8_nhwc_to_nchw_f32(tiles_u8, norm, stage, B, H, W, st));
         tiles_nchw = stage;
         tiles_u8 = nullptr;
     }
     if (tiles_u8 && rg) {
-        TOAD_TRY(ext_stem_region_u8_pool(*rg, norm, weights[0], biases[0], act[1], gx, B, H, W, gws, gcap, st, what));
+        TOAD_TRY(ext_stem_region_u8_pool(*rg, norm, weights[0], biases[0], act[1], gx, B, H, W, gws, gcap, st, what, shrink));
     } else if (tiles_u8) {
         // uint8 tiles, 256 wide: the same kernel body reads them as stored and normalises while it converts its window (stem_halo.inc, uint8 form)
         TOAD_TRY(ext_stem_nhwc_u8_pool(tiles_u8, norm, weights[0], biases[0], act[1], gx, B, H, W, gws, gcap, st, what));
@@ -514,18 +537,28 @@ extern "C" int toad_resnet50_trunc_fwd_u8(const unsigned char *tiles, const floa
     return trunc_fwd(nullptr, tiles, norm, weights, biases, feat, feat_f16, p, B, H, W, ws, stream, what);
 }
 
-extern "C" int toad_resnet50_trunc_fwd_u8_region(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm,
-                                                  const float *const *weights, const float *const *biases, float *feat, void *feat_f16, int B, int H, int W, void *ws,
-                                                  size_t ws_bytes, void *stream) {
-    const char *what = "toad_resnet50_trunc_fwd_u8_region";
+static int trunc_fwd_region(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm, const float *const *weights,
+                            const float *const *biases, float *feat, void *feat_f16, int B, int H, int W, int shrink, void *ws, size_t ws_bytes, void *stream,
+                            const char *what) {
     if (!region || !origins || !norm || !weights || !biases || (!feat && !feat_f16) || !ws) { set_error("%s: null pointer (feat and feat_f16 may not both be NULL)", what); return TOAD_EINVAL; }
     NetPlan p;
     if (!make_plan(B, H, W, p)) { set_error("%s: bad shape B=%d H=%d W=%d", what, B, H, W); return TOAD_ESHAPE; }
     const RegionSrc rg{region, pitch, Hr, Wr, origins};
-    if (int rc = check_region_u8(rg, H, W, what)) return rc;
+    if (int rc = check_region_u8(rg, H, W, what, shrink)) return rc;
     if (int rc = check_norm_u8(norm, what)) return rc;
     if (ws_bytes < toad_resnet50_trunc_u8_ws_bytes(B, H, W)) { set_error("%s: workspace too small", what); return TOAD_EWORKSPACE; }
     if (!aligned16(ws) || (feat && !aligned16(feat)) || (feat_f16 && !aligned16(feat_f16))) { set_error("%s: workspace / outputs must be 16-byte aligned", what); return TOAD_EALIGN; }
     for (int i = 0; i < kNumConvs; ++i) if (!weights[i] || !biases[i]) { set_error("%s: null weight/bias slot %d", what, i); return TOAD_EINVAL; }
-    return trunc_fwd(nullptr, region, norm, weights, biases, feat, feat_f16, p, B, H, W, ws, stream, what, &rg);
+    return trunc_fwd(nullptr, region, norm, weights, biases, feat, feat_f16, p, B, H, W, ws, stream, what, &rg, shrink);
+}
+extern "C" int toad_resnet50_trunc_fwd_u8_region(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm,
+                                                  const float *const *weights, const float *const *biases, float *feat, void *feat_f16, int B, int H, int W, void *ws,
+                                                  size_t ws_bytes, void *stream) {
+    return trunc_fwd_region(region, pitch, Hr, Wr, origins, norm, weights, biases, feat, feat_f16, B, H, W, 1, ws, ws_bytes, stream, "toad_resnet50_trunc_fwd_u8_region");
+}
+extern "C" int toad_resnet50_trunc_fwd_u8_region_box(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm,
+                                                      const float *const *weights, const float *const *biases, float *feat, void *feat_f16, int B, int H, int W,
+                                                      int shrink, void *ws, size_t ws_bytes, void *stream) {
+    return trunc_fwd_region(region, pitch, Hr, Wr, origins, norm, weights, biases, feat, feat_f16, B, H, W, shrink, ws, ws_bytes, stream,
+                            "toad_resnet50_trunc_fwd_u8_region_box");
 }

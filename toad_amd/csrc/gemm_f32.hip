@@ -105,6 +105,7 @@ static void cfg() {
         TOAD_ATTR(stem_halo_pool_kernel<SH_F32>, SH_SMEM);
         TOAD_ATTR(stem_halo_pool_kernel<SH_U8>, SH_SMEM);
         TOAD_ATTR(stem_halo_pool_kernel<SH_U8_REGION>, SH_SMEM);
+        TOAD_ATTR(stem_halo_pool_kernel<SH_U8_REGION_BOX2>, SH_SMEM);
         TOAD_ATTR(conv3x3_h2_halo_kernel<2>, 160 * 1024);
         TOAD_ATTR(conv3x3_h2_halo_kernel<4>, 160 * 1024);
 #undef TOAD_ATTR
@@ -712,10 +713,11 @@ extern "C" int toad_stem_conv_pool_s2d_f32(const float *Xs, const float *Wf, con
 
 // The stem + ReLU + 3x3/2 max-pool straight from the tiles (stem_halo.inc): no space-to-depth image, no fragment loads from global memory. norm == NULL: fp32 NCHW
 // tiles; otherwise uint8 NHWC tiles [B, H, 256, 3] and the six normalisation constants (stem_u8.h), checked before any device work. rg != NULL: the uint8 tiles
-// are read by origin from rg->region (X is not used; no alignment requirement on the region).
+// are read by origin from rg->region (X is not used; no alignment requirement on the region); with shrink == 2 tile b is the (2 H, 512) footprint at its origin,
+// box-filtered by the window loader (H, W stay the network tile's).
 bool toad::stem_nchw_pool_ok(int H, int W) { return W == 256 && H >= 4 && H % 4 == 0; }
 static int stem_pool_from_tiles(const void *X, bool u8, const float *norm, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W, void *ws,
-                                size_t ws_bytes, hipStream_t st, const char *what, const RegionSrc *rg = nullptr) {
+                                size_t ws_bytes, hipStream_t st, const char *what, const RegionSrc *rg = nullptr, int shrink = 1) {
     if (rg) X = rg->region;
     if (!X || (u8 && !norm) || !Wf || !Yp || !ws || (rg && !rg->origins)) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
     if (B <= 0 || !stem_nchw_pool_ok(H, W)) {
@@ -723,7 +725,7 @@ static int stem_pool_from_tiles(const void *X, bool u8, const float *norm, const
                   rg ? "toad_tiles_u8_region_to_nchw_f32 + " : u8 ? "toad_tiles_u8_nhwc_to_nchw_f32 + " : "");
         return TOAD_ESHAPE;
     }
-    if (rg) { if (int rc = check_region_u8(*rg, H, W, what)) return rc; }
+    if (rg) { if (int rc = check_region_u8(*rg, H, W, what, shrink)) return rc; }
     const int64_t M = (int64_t)B * (H / 2) * 128;
     if (M >= (1ll << 31)) { set_error("%s: batch too large for 32-bit offsets (split it)", what); return TOAD_ESHAPE; }
     if (u8) { if (int rc = check_norm_u8(norm, what)) return rc; }
@@ -741,7 +743,10 @@ static int stem_pool_from_tiles(const void *X, bool u8, const float *norm, const
     if (u8) {
         StemNorm nrm;
         for (int c = 0; c < 3; ++c) { nrm.a[c] = norm[c]; nrm.b[c] = norm[3 + c]; }
-        if (rg)
+        if (rg && shrink == 2)
+            hipLaunchKernelGGL(stem_halo_pool_kernel<SH_U8_REGION_BOX2>, grid, dim3(256), SH_SMEM, st, rg->region, planes, binv, bias, Yp, B, H, y_gmax, tiles,
+                               StemRegionArg{nrm, (int)rg->pitch, rg->origins});
+        else if (rg)
             hipLaunchKernelGGL(stem_halo_pool_kernel<SH_U8_REGION>, grid, dim3(256), SH_SMEM, st, rg->region, planes, binv, bias, Yp, B, H, y_gmax, tiles,
                                StemRegionArg{nrm, (int)rg->pitch, rg->origins});
         else
@@ -760,8 +765,8 @@ int toad::ext_stem_nhwc_u8_pool(const unsigned char *X8, const float *norm, cons
     return stem_pool_from_tiles(X8, true, norm, Wf, bias, Yp, y_gmax, B, H, W, ws, ws_bytes, st, what);
 }
 int toad::ext_stem_region_u8_pool(const RegionSrc &rg, const float *norm, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W, void *ws,
-                                  size_t ws_bytes, hipStream_t st, const char *what) {
-    return stem_pool_from_tiles(nullptr, true, norm, Wf, bias, Yp, y_gmax, B, H, W, ws, ws_bytes, st, what, &rg);
+                                  size_t ws_bytes, hipStream_t st, const char *what, int shrink) {
+    return stem_pool_from_tiles(nullptr, true, norm, Wf, bias, Yp, y_gmax, B, H, W, ws, ws_bytes, st, what, &rg, shrink);
 }
 extern "C" int toad_stem_pool_nchw_f32(const float *X, const float *Wf, const float *bias, float *Yp, int B, int H, int W, void *ws, size_t ws_bytes, void *stream) {
     return ext_stem_nchw_pool(X, Wf, bias, Yp, nullptr, B, H, W, ws, ws_bytes, (hipStream_t)stream, "toad_stem_pool_nchw_f32");
@@ -774,6 +779,11 @@ extern "C" int toad_stem_pool_region_u8(const unsigned char *region, int64_t pit
                                         const float *bias, float *Yp, int B, int H, int W, void *ws, size_t ws_bytes, void *stream) {
     return ext_stem_region_u8_pool(RegionSrc{region, pitch, Hr, Wr, origins}, norm, Wf, bias, Yp, nullptr, B, H, W, ws, ws_bytes, (hipStream_t)stream,
                                    "toad_stem_pool_region_u8");
+}
+extern "C" int toad_stem_pool_region_box_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm, const float *Wf,
+                                            const float *bias, float *Yp, int B, int H, int W, int shrink, void *ws, size_t ws_bytes, void *stream) {
+    return ext_stem_region_u8_pool(RegionSrc{region, pitch, Hr, Wr, origins}, norm, Wf, bias, Yp, nullptr, B, H, W, ws, ws_bytes, (hipStream_t)stream,
+                                   "toad_stem_pool_region_box_u8", shrink);
 }
 
 extern "C" int toad_linear_dgrad_f32(const float *dY, const float *WT, const float *addend, const float *relu_src,

@@ -58,24 +58,36 @@ constexpr int SH_TASKS = (SH_ROWS * SH_WS + 255) / 256;      // space-to-depth p
 //     4 registers per task as the uint8 form, on global memory the hardware takes a dword at any byte address (six byte loads assembled in registers compile
 //     to the same two loads at -O3: there is no second form to choose from). The loads are plain, not nontemporal:
 //     overlapping tiles (heat-map strides) read the same bytes again. From the raw words on it is the uint8 form's code.
+//   uint8 region, 2 x 2 box (stem_halo_pool_kernel<SH_U8_REGION_BOX2>): a 40x scan read at the 20x-equivalent pitch. Tile b is the (2 H, 512) FOOTPRINT at its
+//     origin, and pixel (iy, ix) of the (H, 256) tile the kernel works on is t[iy, ix, c] = (sum of the footprint's [2 iy + dy, 2 ix + dx, c], dy, dx in 0 .. 1,
+//     + 2) >> 2: the mean rounded half up, the box filter of every `down` of this library. The pixel pair of tile row iy at columns ix, ix + 1 is footprint
+//     rows 2 iy, 2 iy + 1, bytes [6 ix, 6 ix + 12) - three u32_a1 dwords per row (one 12-byte load), any byte address, any pitch parity, plain loads as above.
+//     v_perm_b32 spreads each row's left and right pixels over two 16-bit fields per dword, the four contributions and the rounding 2 are added per field (at
+//     most 1022: exact, nothing carries), and the six means are packed into the SAME raw[k][2 ry] / raw[k][2 ry + 1] words the region form loads, the
+//     SH_U8_OUTSIDE mark included: store_window, the abs-max, the split, the matrix loop and the epilogue do not know of it, and the result is bitwise the
+//     uint8 form on those box-filtered tiles. The edge predicate stays the TILE's, in shrunk coordinates (padding is the tile's; no byte outside a footprint
+//     is read); the in-footprint offset 2 iy pitch + 6 ix stays 32-bit (the launcher refuses 2 H pitch >= 2^31). Not built: factors above 2, other filters,
+//     and a shrink on the tile forms.
 constexpr unsigned SH_U8_OUTSIDE = 0xFFFF0000u;              // upper half of a row's 2-byte word: the pixel pair lies outside the image
 typedef unsigned sh_u32_a2 __attribute__((aligned(2)));      // a 4-byte load from a 2-byte aligned address
-constexpr int SH_F32 = 0, SH_U8 = 1, SH_U8_REGION = 2;   // the FORM parameter of the kernel
+constexpr int SH_F32 = 0, SH_U8 = 1, SH_U8_REGION = 2, SH_U8_REGION_BOX2 = 3;   // the FORM parameter of the kernel
 
 // (the constants are the LAST kernel argument, an empty struct in the fp32 form: that form's argument layout, registers and code are the ones it had as a
 //  plain kernel - 64 SGPRs, 242 VGPRs, no scratch; the uint8 form: 68 SGPRs, 218 VGPRs, no scratch; the region form, whose last argument also carries the
-//  pitch and the origins: 70 SGPRs, 217 VGPRs, no scratch; all 81,728 B of LDS, two workgroups per CU)
+//  pitch and the origins: 70 SGPRs, 217 VGPRs, no scratch; the box form, same arguments: 88 SGPRs, 220 VGPRs, no scratch; all 81,728 B of LDS, two workgroups
+//  per CU)
 struct StemNoNorm {};
 struct StemRegionArg { StemNorm nrm; int pitch; const int *origins; };      // origins: int32 [B][2] = (x, y) of each tile's top-left pixel
 template <int FORM> struct StemLastArg { typedef StemNoNorm type; };
 template <> struct StemLastArg<SH_U8> { typedef StemNorm type; };
 template <> struct StemLastArg<SH_U8_REGION> { typedef StemRegionArg type; };
+template <> struct StemLastArg<SH_U8_REGION_BOX2> { typedef StemRegionArg type; };
 template <int FORM>
 __global__ __launch_bounds__(256, 2) void stem_halo_pool_kernel(const typename std::conditional<FORM != SH_F32, unsigned char, float>::type *__restrict__ Xv,
                                                                 const unsigned short *__restrict__ Bp, const float *__restrict__ binv,
                                                                 const float *__restrict__ bias, float *Yp, int B, int H, float *y_gmax, int tiles,
                                                                 typename StemLastArg<FORM>::type nrm_arg) {
-    constexpr bool U8 = FORM != SH_F32, REGION = FORM == SH_U8_REGION;
+    constexpr bool U8 = FORM != SH_F32, BOX2 = FORM == SH_U8_REGION_BOX2, REGION = FORM == SH_U8_REGION || BOX2;
     using Cfg = StreamCfg<2, 2>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     char *lds = reinterpret_cast<char *>(smem);
@@ -126,9 +138,31 @@ __global__ __launch_bounds__(256, 2) void stem_halo_pool_kernel(const typename s
                 for (int ry = 0; ry < 2; ++ry) {
                     const int iy = 4 * t - 4 + 2 * Yl + ry;
                     const bool ok = tc >= 0 && iy >= 0 && iy < H && ix >= 0 && ix < W;       // the TILE's edges: bytes [0, 6) of the pair end inside row iy of the tile
+                    if constexpr (BOX2) {
+                        // footprint rows 2 iy, 2 iy + 1, bytes [6 ix, 6 ix + 12): columns 2 ix .. 2 ix + 3, the last one 2 W - 1 at most
+                        const unsigned char *p = img8 + ((unsigned)(2 * iy) * (unsigned)pitch + (unsigned)(ix * 6));      // (32-bit, unsigned: 2 H pitch < 2^31; only read where ok)
+                        unsigned w[2][3] = {{0u, 0u, 0u}, {0u, 0u, 0u}};
+                        if (ok) {                                     // (one branch around the six loads: hipcc then merges a row's three into one 12-byte load)
+#pragma unroll
+                            for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+                                for (int j = 0; j < 3; ++j) w[dy][j] = *reinterpret_cast<const u32_a1 *>(p + (dy ? (unsigned)pitch : 0u) + 4 * j);
+                        }
+                        unsigned s[3] = {0x00020002u, 0x00020002u, 0x00020002u};
+#pragma unroll
+                        for (int dy = 0; dy < 2; ++dy) {
+                            s[0] += __builtin_amdgcn_perm(w[dy][1], w[dy][0], 0x0c010c00u) + __builtin_amdgcn_perm(w[dy][1], w[dy][0], 0x0c040c03u);     // (b0, b1) + (b3, b4)
+                            s[1] += __builtin_amdgcn_perm(w[dy][1], w[dy][0], 0x0c060c02u) + __builtin_amdgcn_perm(w[dy][2], w[dy][1], 0x0c050c01u);     // (b2, b6) + (b5, b9)
+                            s[2] += __builtin_amdgcn_perm(w[dy][2], w[dy][1], 0x0c040c03u) + __builtin_amdgcn_perm(w[dy][2], w[dy][1], 0x0c070c06u);     // (b7, b8) + (b10, b11)
+                        }
+                        // each half of s[i] is a box's sum + 2, at most 1022: bytes 0 and 2 of s[i] >> 2 are the two rounded means, whatever leaks into byte 1
+                        raw[k][2 * ry] = __builtin_amdgcn_perm(s[1] >> 2, s[0] >> 2, 0x06040200u);
+                        raw[k][2 * ry + 1] = ok ? __builtin_amdgcn_perm(0u, s[2] >> 2, 0x0c0c0200u) : SH_U8_OUTSIDE;
+                    } else {
                     const unsigned char *p = img8 + ((unsigned)iy * (unsigned)pitch + (unsigned)(ix * 3));      // (32-bit, unsigned: H pitch < 2^31; only read where ok)
                     raw[k][2 * ry] = ok ? *reinterpret_cast<const u32_a1 *>(p) : 0u;
                     raw[k][2 * ry + 1] = ok ? (unsigned)*reinterpret_cast<const u16_a1 *>(p + 4) : SH_U8_OUTSIDE;
+                    }
                 }
             }
         } else if constexpr (U8) {

@@ -25,18 +25,31 @@ int ext_stem_nhwc_u8_pool(const unsigned char *X8, const float *norm, const floa
 // origins = DEVICE int32 [B][2], (x, y) of each tile's top-left pixel. What the host can see of it is checked here, by every entry point, before any
 // device work; that every origin keeps its tile inside the region is the caller's duty (the Python layer checks it on the host).
 struct RegionSrc { const unsigned char *region; int64_t pitch; int Hr, Wr; const int *origins; };
-static inline int check_region_u8(const RegionSrc &rg, int H, int W, const char *what) {
+// shrink (the *_box entries; 1 or 2): tile b is the (shrink H, shrink W) FOOTPRINT at its origin, box-filtered to the H x W network tile. The footprint is what has
+// to fit the region and what the 32-bit offsets span.
+static inline int check_region_u8(const RegionSrc &rg, int H, int W, const char *what, int shrink = 1) {
     if (!rg.region || !rg.origins) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (shrink != 1 && shrink != 2) { set_error("%s: shrink must be 1 or 2 (the box filter in front of the tile; larger factors are not built), got %d", what, shrink); return TOAD_ESHAPE; }
     if (rg.Hr <= 0 || rg.Wr <= 0 || H <= 0 || W <= 0) { set_error("%s: bad shape", what); return TOAD_ESHAPE; }
     if (rg.pitch < 3 * (int64_t)rg.Wr) { set_error("%s: pitch %lld is less than a row of the region (3 Wr = %lld bytes)", what, (long long)rg.pitch, 3ll * rg.Wr); return TOAD_ESHAPE; }
-    if (H > rg.Hr || W > rg.Wr) { set_error("%s: a %d x %d tile does not fit a %d x %d region", what, H, W, rg.Hr, rg.Wr); return TOAD_ESHAPE; }
-    if ((int64_t)H * rg.pitch >= (1ll << 31)) { set_error("%s: pitch too large: H * pitch must stay below 2^31 (32-bit offsets inside a tile)", what); return TOAD_ESHAPE; }
+    const int64_t fh = (int64_t)shrink * H, fw = (int64_t)shrink * W;
+    if (fh > rg.Hr || fw > rg.Wr) {
+        if (shrink == 1) set_error("%s: a %d x %d tile does not fit a %d x %d region", what, H, W, rg.Hr, rg.Wr);
+        else set_error("%s: the %lld x %lld footprint of a %d x %d tile (shrink %d) does not fit a %d x %d region", what, (long long)fh, (long long)fw, H, W, shrink, rg.Hr, rg.Wr);
+        return TOAD_ESHAPE;
+    }
+    if (fh * rg.pitch >= (1ll << 31)) {
+        if (shrink == 1) set_error("%s: pitch too large: H * pitch must stay below 2^31 (32-bit offsets inside a tile)", what);
+        else set_error("%s: pitch too large: %d H * pitch must stay below 2^31 (32-bit offsets inside a footprint)", what, shrink);
+        return TOAD_ESHAPE;
+    }
     if ((reinterpret_cast<uintptr_t>(rg.origins) & 3u) != 0) { set_error("%s: origins (int32 [B][2]) must be 4-byte aligned", what); return TOAD_EALIGN; }
     return TOAD_OK;
 }
 
-// ext_stem_nhwc_u8_pool with the tiles read by origin (stem_halo.inc, region form): any base address, any pitch parity.
+// ext_stem_nhwc_u8_pool with the tiles read by origin (stem_halo.inc, region form): any base address, any pitch parity. shrink == 2: the box form, H x W the
+// network tile and (2 H, 2 W) the footprint read.
 int ext_stem_region_u8_pool(const RegionSrc &rg, const float *norm, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W,
-                            void *ws, size_t ws_bytes, hipStream_t st, const char *what);
+                            void *ws, size_t ws_bytes, hipStream_t st, const char *what, int shrink = 1);
 
 }  // namespace toad

@@ -200,13 +200,16 @@ def attention_heatmap_scores(model: TOAD_fc_mtl_concat, data: torch.Tensor, perc
 
 
 def region_attention_scores(extractor, model: TOAD_fc_mtl_concat, region: torch.Tensor, origins, tile=256, bag_dtype: torch.dtype = torch.float16,
-                            percentile: bool = False) -> torch.Tensor:
+                            percentile: bool = False, shrink=1) -> torch.Tensor:
     """Heat-map scores of the tiles at ``origins`` of one decoded uint8 region [Hr,Wr,3], in the order of ``origins``, with no tile tensor at any point:
     ``extractor.forward_u8_region`` reads the tiles where they lie (overlapping ones - a heat-map stride below the tile size - included) and writes its
     rows chunk by chunk into one [B,1024] bag of ``bag_dtype``; ``attention_heatmap_scores(model, bag, percentile)`` scores that bag. Equal to scoring
     ``extractor.forward_u8(stacked tiles, out_dtype=bag_dtype)``. Putting the B scores on a canvas: ``heatmap.attention_canvas``, or
-    ``region_tissue_attention_heatmap`` for selection, scores and canvas in one call."""
-    bag = extractor.forward_u8_region(region, origins, tile=tile, out_dtype=bag_dtype)
+    ``region_tissue_attention_heatmap`` for selection, scores and canvas in one call.
+
+    ``shrink`` = 2 (a 40x scan): ``tile`` is the footprint in region pixels and the extractor reads it box-filtered to ``tile / 2``
+    (``forward_u8_region(..., shrink=2)``); equal to scoring ``extractor.forward_u8(ops.box_tiles_u8(region, origins, tile, 2), out_dtype=bag_dtype)``."""
+    bag = extractor.forward_u8_region(region, origins, tile=tile, out_dtype=bag_dtype, shrink=shrink)
     return attention_heatmap_scores(model, bag, percentile)
 
 
@@ -240,7 +243,7 @@ def _select_origins(region, tile, stride, min_fraction, sat_thresh, val_min, seg
 
 def region_tissue_attention_scores(extractor, model: TOAD_fc_mtl_concat, region: torch.Tensor, tile=256, stride=None, min_fraction: float = 0.25,
                                    sat_thresh: int = 8, val_min: int = 0, bag_dtype: torch.dtype = torch.float16, percentile: bool = False,
-                                   segment: Optional[dict] = None):
+                                   segment: Optional[dict] = None, shrink=1):
     """``(origins, scores)`` of the tissue tiles of one decoded uint8 region [Hr,Wr,3]: ``tissue.tissue_origins`` picks the lattice tiles that hold tissue
     from the pixels (two launches and one small read-back, on the region where it lies), ``region_attention_scores`` scores exactly those. ``origins`` is
     the int64 [B,2] host array of (x, y), row-major over the lattice; ``scores`` its B scores on the device. A region without a tissue tile returns an
@@ -248,24 +251,26 @@ def region_tissue_attention_scores(extractor, model: TOAD_fc_mtl_concat, region:
 
     ``segment``: None selects with ``tissue_origins``; a dict of ``tissue.segmented_tissue_origins`` keywords - any of ``down``, ``median``,
     ``sat_thresh``, ``val_min``, ``close``, ``min_area``, ``min_hole`` - selects with that function instead (CLAM's median-filtered saturation of a box-filtered level, ``sat_thresh`` an int
-    or ``"otsu"``). Keys it does not give take this call's ``sat_thresh`` / ``val_min`` and that function's ``down`` / ``median`` defaults."""
-    return _tissue_scores(extractor, model, region, tile, stride, min_fraction, sat_thresh, val_min, bag_dtype, percentile, segment)[:2]
+    or ``"otsu"``). Keys it does not give take this call's ``sat_thresh`` / ``val_min`` and that function's ``down`` / ``median`` defaults.
+
+    ``shrink``: ``region_attention_scores`` - it goes to the extractor only; the selection works on ``tile``, the footprint, as it does without it."""
+    return _tissue_scores(extractor, model, region, tile, stride, min_fraction, sat_thresh, val_min, bag_dtype, percentile, segment, shrink=shrink)[:2]
 
 
-def _tissue_scores(extractor, model, region, tile, stride, min_fraction, sat_thresh, val_min, bag_dtype, percentile, segment, return_mask=False):
+def _tissue_scores(extractor, model, region, tile, stride, min_fraction, sat_thresh, val_min, bag_dtype, percentile, segment, return_mask=False, shrink=1):
     """``region_tissue_attention_scores`` -> (origins, scores, mask): mask = None, or with ``return_mask`` the (plane, t, mask_down) of the selection."""
     origins, mask = _select_origins(region, tile, stride, min_fraction, sat_thresh, val_min, segment, return_mask), None
     if return_mask:
         origins, mask = origins
     if origins.shape[0] == 0:
         return origins, torch.empty(0, dtype=torch.float32, device=region.device), mask
-    return origins, region_attention_scores(extractor, model, region, origins, tile=tile, bag_dtype=bag_dtype, percentile=percentile), mask
+    return origins, region_attention_scores(extractor, model, region, origins, tile=tile, bag_dtype=bag_dtype, percentile=percentile, shrink=shrink), mask
 
 
 def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region: torch.Tensor, tile=256, stride=None, min_fraction: float = 0.25,
                                     sat_thresh: int = 8, val_min: int = 0, bag_dtype: torch.dtype = torch.float16, alpha=102, down: int = 1, lut=None,
                                     out=None, segment: Optional[dict] = None, smooth: bool = False, tissue_mask: bool = False, thresh=None,
-                                    binarize: bool = False, blur=False):
+                                    binarize: bool = False, blur=False, shrink=1):
     """``(origins, scores, canvas)`` of one decoded uint8 region [Hr,Wr,3]: ``region_tissue_attention_scores(..., percentile=True)`` selects and scores the
     tissue tiles, ``heatmap.attention_canvas`` renders those percentile scores onto the region on the same lattice, on the device - uint8
     [Hr // down, Wr // down, 3]; the tiles that were not selected keep the (box-filtered) pixels of the region. ``alpha``, ``down``, ``lut`` and ``out``:
@@ -283,11 +288,17 @@ def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region
     ``blur`` (CLAM's ``blur``): ``heatmap.attention_canvas`` - False, True for CLAM's Gaussian width ``0.6 tile + 0.5`` pixels, a sigma in pixels, or the
     integer taps; the cell table is smoothed by ``ops.heat_cells_blur`` before it is rendered, and a bad value raises ValueError before the selection runs.
 
+    ``shrink``: ``region_attention_scores`` - the extractor reads each ``tile`` footprint box-filtered by it (2 for a 40x scan); selection and canvas keep
+    working on ``tile`` and ``stride`` in region pixels. A bad value, or a footprint it does not divide, raises ValueError before the selection runs.
+
     Not done here: a sigma per axis for tiles that are not square, radii above 16 cells (``blur=True`` on lattices whose cell is 16 or less), CLAM's
     second blur of the coloured image, seams between separately rendered regions, several levels of the vis-level pyramid in one call (one level per
     call is done) and saving the image."""
     from .heatmap import attention_canvas, blur_taps
     from .tissue import _lattice_args, lattice_cell
+    if shrink != 1:                                                 # refuse a bad shrink before the selection runs; the extractor checks it again
+        from .ops import shrunk_tile
+        shrunk_tile(tile, shrink)
     if blur is not None and blur is not False:                      # refuse a bad blur before the extractor runs; attention_canvas parses it again
         h, w, sy, sx, x0, y0 = _lattice_args(tile, stride, (0, 0))
         blur_taps(blur, (h, w), lattice_cell((h, w), (sy, sx), (x0, y0)))
@@ -297,6 +308,6 @@ def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region
             raise ValueError(f"tissue_mask=True: the segment down = {seg_down!r} must be a multiple of the canvas down = {down!r} (a canvas box must lie "
                              "in one mask pixel)")
     origins, scores, mask = _tissue_scores(extractor, model, region, tile, stride, min_fraction, sat_thresh, val_min, bag_dtype, True, segment,
-                                           return_mask=tissue_mask)
+                                           return_mask=tissue_mask, shrink=shrink)
     return origins, scores, attention_canvas(region, origins, scores, tile=tile, stride=stride, alpha=alpha, down=down, lut=lut, out=out, smooth=smooth,
                                              mask=mask, thresh=thresh, binarize=binarize, blur=blur)

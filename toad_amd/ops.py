@@ -1229,30 +1229,77 @@ def _region_pitch(region: torch.Tensor, name: str):
     return _row_pitch(region, 3 * wr), hr, wr
 
 
-def _region_args(region: torch.Tensor, origins, tile, name: str):
+SHRINKS = (1, 2)      # the box filters the region calls can put in front of the network: a tile is a (shrink H, shrink W) footprint of the region
+
+
+def check_shrink(shrink):
+    if not isinstance(shrink, int) or isinstance(shrink, bool) or shrink not in SHRINKS:
+        raise ValueError(f"shrink must be one of {SHRINKS} (the footprint is box-filtered by that factor; larger factors are not built), got {shrink!r}")
+
+
+def shrunk_tile(tile, shrink=1):
+    """`tile` (the FOOTPRINT in region pixels, an int or (H, W)) and `shrink` of the region calls -> (footprint, network tile), each (H, W). shrink is 1 or
+    2 and must divide both sides of the footprint: ValueError otherwise, before anything else is looked at."""
+    check_shrink(shrink)
+    fh, fw = tile_shape(tile)
+    if fh % shrink or fw % shrink:
+        raise ValueError(f"shrink = {shrink} does not divide the {fh} x {fw} (H x W) footprint: tile stays the footprint in region pixels, the network "
+                         f"sees tile / shrink")
+    return (fh, fw), (fh // shrink, fw // shrink)
+
+
+def box_tiles_u8(region: torch.Tensor, origins, tile, shrink=1) -> torch.Tensor:
+    """The box-filtered tiles of the region calls, MATERIALISED with torch integer ops - the stated reference of `shrink`, for tests and benchmarks, on no
+    product path. region uint8 [Hr,Wr,3] on any device, origins [B,2] = (x, y) on the host, tile = the footprint -> uint8 [B, H/shrink, W/shrink, 3] with
+
+        t[iy, ix, c] = (sum of region[y + s iy + dy, x + s ix + dx, c] over dy, dx in 0 .. s-1, + s*s/2) // (s*s)
+
+    the mean rounded half up (the box filter of every `down` in this package)."""
+    (fh, fw), (h, w) = shrunk_tile(tile, shrink)
+    if not isinstance(region, torch.Tensor) or region.dtype != torch.uint8 or region.dim() != 3 or region.shape[2] != 3:
+        raise ValueError("box_tiles_u8: expected a uint8 [Hr,Wr,3] region")
+    o = check_origins(origins, region.shape[0], region.shape[1], fh, fw)
+    if o.shape[0] == 0:
+        return torch.empty((0, h, w, 3), dtype=torch.uint8, device=region.device)
+    t = torch.stack([region[y:y + fh, x:x + fw] for x, y in o.tolist()])
+    if shrink == 1:
+        return t
+    s = t.view(-1, h, shrink, w, shrink, 3).to(torch.int32).sum(dim=(2, 4))
+    return ((s + shrink * shrink // 2) // (shrink * shrink)).to(torch.uint8)
+
+
+def _region_args(region: torch.Tensor, origins, tile, name: str, shrink=1):
+    """-> (pitch, Hr, Wr, H, W, origins on the device); H, W = the NETWORK tile, the origins are checked for the footprint (shrink H, shrink W)."""
+    check_shrink(shrink)
     pitch, hr, wr = _region_pitch(region, name)
-    h, w = tile_shape(tile)
-    o = check_origins(origins, hr, wr, h, w)
+    (fh, fw), (h, w) = shrunk_tile(tile, shrink)
+    o = check_origins(origins, hr, wr, fh, fw)
     if o.shape[0] == 0:
         raise ValueError(f"{name}: no origins")
     return pitch, hr, wr, h, w, o.to(region.device)
 
 
-def tiles_u8_region_to_f32(region: torch.Tensor, origins, tile=256, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> torch.Tensor:
+def tiles_u8_region_to_f32(region: torch.Tensor, origins, tile=256, mean=IMAGENET_MEAN, std=IMAGENET_STD, shrink=1) -> torch.Tensor:
     """tiles_u8_to_f32 with the tiles read by origin from one decoded uint8 region [Hr,Wr,3] (any row pitch, any alignment): bitwise
-    tiles_u8_to_f32(torch.stack([region[y:y+H, x:x+W] for x, y in origins]), mean, std), and no such stack exists. origins: check_origins."""
-    pitch, hr, wr, h, w, o = _region_args(region, origins, tile, "tiles_u8_region_to_f32")
+    tiles_u8_to_f32(torch.stack([region[y:y+H, x:x+W] for x, y in origins]), mean, std), and no such stack exists. origins: check_origins.
+    shrink = 2: `tile` is the footprint, the result [B,3,H/2,W/2] is bitwise tiles_u8_to_f32(box_tiles_u8(region, origins, tile, 2), mean, std)."""
+    pitch, hr, wr, h, w, o = _region_args(region, origins, tile, "tiles_u8_region_to_f32", shrink)
     norm = norm_constants_u8(mean, std)
     out = torch.empty((o.shape[0], 3, h, w), dtype=torch.float32, device=region.device)
-    _lib.check(_lib.load().toad_tiles_u8_region_to_nchw_f32(_p(region), pitch, hr, wr, _p(o), norm, _p(out), o.shape[0], h, w, _stream()),
-               "toad_tiles_u8_region_to_nchw_f32")
+    if shrink == 1:
+        _lib.check(_lib.load().toad_tiles_u8_region_to_nchw_f32(_p(region), pitch, hr, wr, _p(o), norm, _p(out), o.shape[0], h, w, _stream()),
+                   "toad_tiles_u8_region_to_nchw_f32")
+    else:
+        _lib.check(_lib.load().toad_tiles_u8_region_box_to_nchw_f32(_p(region), pitch, hr, wr, _p(o), norm, _p(out), o.shape[0], h, w, shrink, _stream()),
+                   "toad_tiles_u8_region_box_to_nchw_f32")
     return out
 
 
-def stem_pool_region_u8(region: torch.Tensor, origins, wf: torch.Tensor, b, tile=256, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> torch.Tensor:
+def stem_pool_region_u8(region: torch.Tensor, origins, wf: torch.Tensor, b, tile=256, mean=IMAGENET_MEAN, std=IMAGENET_STD, shrink=1) -> torch.Tensor:
     """stem_pool_nhwc_u8 with the tiles (H, 256), H % 4 == 0, read by origin from one decoded uint8 region: bitwise stem_pool_nhwc_u8 on the stacked
-    tiles. Padding is the tile's, not the region's; the region is read in place whatever its address and pitch."""
-    pitch, hr, wr, h, w, o = _region_args(region, origins, tile, "stem_pool_region_u8")
+    tiles. Padding is the tile's, not the region's; the region is read in place whatever its address and pitch.
+    shrink = 2: `tile` is the footprint (2 H, 512), box-filtered while the window is loaded: bitwise stem_pool_nhwc_u8(box_tiles_u8(region, origins, tile, 2))."""
+    pitch, hr, wr, h, w, o = _region_args(region, origins, tile, "stem_pool_region_u8", shrink)
     _chk(wf, "wf"); _chk(b, "b", allow_none=True)
     if tuple(wf.shape) != (64, 192):
         raise ValueError("stem_pool_region_u8: expected a [64,192] space-to-depth weight")
@@ -1261,8 +1308,12 @@ def stem_pool_region_u8(region: torch.Tensor, origins, wf: torch.Tensor, b, tile
     y = torch.empty((bb, h // 4, w // 4, 64), dtype=torch.float32, device=region.device)
     lib = _lib.load()
     ws = _ws(lib.toad_linear_ws_bytes(bb * (h // 2) * (w // 2), 64, 192), region.device)
-    _lib.check(lib.toad_stem_pool_region_u8(_p(region), pitch, hr, wr, _p(o), norm, _p(wf), _p(b), _p(y), bb, h, w, _p(ws), ws.numel(), _stream()),
-               "toad_stem_pool_region_u8")
+    if shrink == 1:
+        _lib.check(lib.toad_stem_pool_region_u8(_p(region), pitch, hr, wr, _p(o), norm, _p(wf), _p(b), _p(y), bb, h, w, _p(ws), ws.numel(), _stream()),
+                   "toad_stem_pool_region_u8")
+    else:
+        _lib.check(lib.toad_stem_pool_region_box_u8(_p(region), pitch, hr, wr, _p(o), norm, _p(wf), _p(b), _p(y), bb, h, w, shrink, _p(ws), ws.numel(),
+                                                    _stream()), "toad_stem_pool_region_box_u8")
     return y
 
 

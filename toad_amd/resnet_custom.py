@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .ops import IMAGENET_MEAN, IMAGENET_STD, _row_pitch, check_origins, norm_constants_u8, region_layout_ok, tile_shape
+from .ops import IMAGENET_MEAN, IMAGENET_STD, _row_pitch, check_origins, check_shrink, norm_constants_u8, region_layout_ok, shrunk_tile, tile_shape
 
 __all__ = ["Bottleneck_Baseline", "ResNet_Baseline", "resnet50_baseline", "IMAGENET_MEAN", "IMAGENET_STD"]
 
@@ -217,7 +217,8 @@ class ResNet_Baseline(nn.Module):
             _lib.check(lib.toad_resnet50_trunc_fwd_u8(tiles[b0:b0 + nb].data_ptr(), norm, wp, bp, o32, o16, *tail), "toad_resnet50_trunc_fwd_u8")
         return self._chunked(torch.empty(B, 1024, device=tiles.device, dtype=out_dtype), H, W, lib.toad_resnet50_trunc_u8_ws_bytes, call)
 
-    def forward_u8_region(self, region: torch.Tensor, origins, tile=256, mean=IMAGENET_MEAN, std=IMAGENET_STD, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    def forward_u8_region(self, region: torch.Tensor, origins, tile=256, mean=IMAGENET_MEAN, std=IMAGENET_STD, out_dtype: torch.dtype = torch.float32,
+                          shrink=1) -> torch.Tensor:
         """Tiles read by origin from one decoded region -> [B,1024] bag rows, fp32 or fp16; no tile copy exists at any point.
 
         ``region``: uint8 [Hr,Wr,3] RGB on the HIP device with stride(2) == 1, stride(1) == 3 and any row pitch stride(0) >= 3 Wr (a column crop of a
@@ -225,7 +226,16 @@ class ResNet_Baseline(nn.Module):
         on the HOST (CPU tensor, numpy array or list) - every tile must lie inside the region, which is checked here before anything is launched
         (``ValueError`` naming the first offender); duplicates, overlaps and any order are fine. ``tile``: an int or (H, W). Padding is the tile's, not the
         region's: the result is bitwise ``forward_u8(torch.stack([region[y:y+H, x:x+W] for x, y in origins]), mean, std, out_dtype)``. More than
-        ``max_tiles_per_call`` origins are run in chunks that write into the one [B,1024] result."""
+        ``max_tiles_per_call`` origins are run in chunks that write into the one [B,1024] result.
+
+        ``shrink`` = 2 reads a 40x scan at the 20x-equivalent pitch (CLAM's ``custom_downsample = 2``): ``tile`` stays the FOOTPRINT in region pixels - the
+        origins, the tissue lattice and the heat-map lattice need no translation - ``shrink`` must divide both of its sides, and the network sees
+        ``tile / shrink``, each pixel the mean, rounded half up, of its 2 x 2 box. Bitwise ``forward_u8(ops.box_tiles_u8(region, origins, tile, shrink), mean,
+        std, out_dtype)``; on the 256-wide route (a (2 H, 512) footprint) the stem sums the boxes while it loads its window and neither those tiles nor a
+        float image exist. A shrink other than 1 or 2, or one that does not divide the footprint, is a ``ValueError`` before anything else is looked at."""
+        check_shrink(shrink)
+        if shrink != 1:
+            shrunk_tile(tile, shrink)
         self._ready(region, (
             f"forward_u8_region expects a uint8 region, got {region.dtype}" if region.dtype != torch.uint8 else
             f"forward_u8_region expects a channels-last [Hr,Wr,3] region, got {tuple(region.shape)}" if region.dim() != 3 or region.shape[2] != 3 else
@@ -233,9 +243,9 @@ class ResNet_Baseline(nn.Module):
             "expected a uint8 [Hr,Wr,3] tensor on the HIP device (no CPU fallback)" if not region.is_cuda else
             f"forward_u8_region expects a region with stride(2) == 1, stride(1) == 3 and a row pitch stride(0) >= 3 Wr (rows are read in "
             f"place, there is no hidden copy), got strides {tuple(region.stride())} for shape {tuple(region.shape)}" if not region_layout_ok(region) else None))
-        H, W = tile_shape(tile)
+        (FH, FW), (H, W) = shrunk_tile(tile, shrink)        # the footprint the origins are checked for, the tile the network and the chunking see
         Hr, Wr = region.shape[0], region.shape[1]
-        org = check_origins(origins, Hr, Wr, H, W)
+        org = check_origins(origins, Hr, Wr, FH, FW)
         B = org.shape[0]
         norm = norm_constants_u8(mean, std)
         out = torch.empty(B, 1024, device=region.device, dtype=out_dtype)
@@ -246,8 +256,12 @@ class ResNet_Baseline(nn.Module):
         org = org.to(region.device)                         # int32 [B,2]: the one small copy of the call
 
         def call(b0, nb, wp, bp, o32, o16, tail):           # the origins are sliced, never the region
-            _lib.check(lib.toad_resnet50_trunc_fwd_u8_region(region.data_ptr(), pitch, Hr, Wr, org[b0:b0 + nb].data_ptr(), norm, wp, bp, o32, o16, *tail),
-                       "toad_resnet50_trunc_fwd_u8_region")
+            if shrink == 1:
+                _lib.check(lib.toad_resnet50_trunc_fwd_u8_region(region.data_ptr(), pitch, Hr, Wr, org[b0:b0 + nb].data_ptr(), norm, wp, bp, o32, o16, *tail),
+                           "toad_resnet50_trunc_fwd_u8_region")
+            else:
+                _lib.check(lib.toad_resnet50_trunc_fwd_u8_region_box(region.data_ptr(), pitch, Hr, Wr, org[b0:b0 + nb].data_ptr(), norm, wp, bp, o32, o16,
+                                                                     *tail[:3], shrink, *tail[3:]), "toad_resnet50_trunc_fwd_u8_region_box")
         return self._chunked(out, H, W, lib.toad_resnet50_trunc_u8_ws_bytes, call)
 
 

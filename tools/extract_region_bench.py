@@ -13,8 +13,11 @@ extract_u8_bench.py (its event timing, its alternation of the arms inside one pr
     --stride 64 runs the same pair on the overlapping grid, where the tiles are 12 times the region.
   launches: four calls of ONE resident arm (--arm A | B | C) for a `rocprofv3 --kernel-trace --stats` run of its own: the stem instantiations' times.
 
+  --shrink 2: 512 footprints of 512 x 512 read box-filtered to 256 x 256 (forward_u8_region(shrink=2)) against today's 256-pixel call and against torch
+    glue in front of forward_u8; see shrunk().
+
 Prints one JSON line per result; --out FILE keeps them.
-usage: extract_region_bench.py [--resident] [--host-fed] [--launches --arm A|B|C] [--stride S] [--seconds S] [--steps K] [--out FILE]"""
+usage: extract_region_bench.py [--resident] [--host-fed] [--launches --arm A|B|C] [--shrink 2] [--stride S] [--seconds S] [--steps K] [--out FILE]"""
 import argparse
 import json
 import os
@@ -66,6 +69,46 @@ def resident(seconds):
                  arm_a_halves_ms=[round(a1, 4), round(a2, 4)], arm_a_spread=round(abs(a1 - a2) / median(a), 4),
                  b_over_a=round(median(t["B_region_grid"]) / median(a), 4), c_over_a=round(median(t["C_region_stride64"]) / median(a), 4),
                  b_within_1p02_a=bool(median(t["B_region_grid"]) <= 1.02 * median(a)), region_bitwise_tiles=same, region_stride64_fp16_bitwise_tiles=same64)]
+
+
+def shrunk(seconds, shrink=2):
+    """--shrink 2: a 40x scan read at the 20x-equivalent pitch. 512 footprints of 512 x 512 on the 16 x 32 grid of a resident 8192 x 16384 region:
+      arm A  forward_u8_region on 512 tiles of 256 x 256 of a 4096 x 8192 region (arm B of --resident): the yardstick, two interleaved halves for its spread;
+      arm S  forward_u8_region(tile=512, shrink=2): the box filter inside the stem's window loader;
+      arm G  ops.box_tiles_u8 (torch integer ops) then forward_u8, the glue inside the clock.
+    S is checked bitwise against G before anything is timed. The stem launches alone (ops.stem_pool_region_u8, the plane split and the output allocation
+    included) are timed for A and S in the same alternation."""
+    from toad_amd import ops
+    dev = torch.device("cuda:0")
+    model = make_model()
+    foot = TILE * shrink
+    region_a, origins_a = grid_region(TILE, dev)
+    gy, gx = GRID
+    g = torch.Generator(device=dev).manual_seed(2)
+    region_s = torch.randint(0, 256, (gy * foot, gx * foot, 3), device=dev, dtype=torch.uint8, generator=g)
+    origins_s = torch.tensor([(x * foot, y * foot) for y in range(gy) for x in range(gx)], dtype=torch.int32)
+
+    def arm_g():
+        return model.forward_u8(ops.box_tiles_u8(region_s, origins_s, foot, shrink))
+    same = bool(torch.equal(model.forward_u8_region(region_s, origins_s, tile=foot, shrink=shrink), arm_g()))
+    wf, bias = model._folded[0][0], model._folded[1][0]
+    arms = {"A_region_256": lambda: model.forward_u8_region(region_a, origins_a),
+            "S_region_512_shrink2": lambda: model.forward_u8_region(region_s, origins_s, tile=foot, shrink=shrink), "G_torch_box_then_u8": arm_g,
+            "stem_A": lambda: ops.stem_pool_region_u8(region_a, origins_a, wf, bias, TILE),
+            "stem_S": lambda: ops.stem_pool_region_u8(region_s, origins_s, wf, bias, foot, shrink=shrink)}
+    t, iters = alternate(arms, seconds)
+    a = t["A_region_256"]
+    a1, a2 = median(a[0::2]), median(a[1::2])
+    spread = abs(a1 - a2) / median(a)
+    s, gl = median(t["S_region_512_shrink2"]), median(t["G_torch_box_then_u8"])
+    n = origins_s.shape[0]
+    return [dict(kind="resident_shrink", shrink=shrink, tiles=n, footprint=f"{foot}x{foot}", network_tile="256x256", region=list(region_s.shape[:2]),
+                 region_a=list(region_a.shape[:2]), rounds=len(a), iters_per_round=iters, ms={k: round(median(v), 4) for k, v in t.items()},
+                 ms_min={k: round(min(v), 4) for k, v in t.items()}, ms_max={k: round(max(v), 4) for k, v in t.items()},
+                 tiles_per_s={k: round(n / median(v) * 1e3, 1) for k, v in t.items()}, arm_a_halves_ms=[round(a1, 4), round(a2, 4)],
+                 arm_a_spread=round(spread, 4), s_over_a=round(s / median(a), 4), s_over_g=round(s / gl, 4),
+                 stem_s_over_stem_a=round(median(t["stem_S"]) / median(t["stem_A"]), 4), s_faster_than_g_beyond_spread=bool(s * (1.0 + spread) < gl),
+                 s_bitwise_g=same)]
 
 
 def host_fed(stride, steps):
@@ -139,10 +182,13 @@ def main():
     ap.add_argument("--stride", type=int, default=TILE)
     ap.add_argument("--seconds", type=float, default=3.0)
     ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--shrink", type=int, default=1, choices=(1, 2))
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    every = not (a.resident or a.host_fed or a.launches)
+    every = not (a.resident or a.host_fed or a.launches or a.shrink != 1)
     res = []
+    if a.shrink != 1:
+        res += shrunk(a.seconds, a.shrink)
     if a.launches:
         res += launches(a.arm)
     if a.resident or every:
