@@ -453,7 +453,7 @@ int toad_heat_cells(const int *tile_q, int nx, int ny, int cell, int x0, int y0,
  * allocated, no synchronisation. Refusals, in this order, before anything is launched: Gy or Gx < 1 or Gy * Gx >= 2^31 (TOAD_ESHAPE); radius outside
  * 1 .. 16 (TOAD_ESHAPE); taps NULL, a negative tap, taps[0] < 1 or a sum above 1024 (TOAD_EINVAL); out == cells (TOAD_EINVAL; a NULL cells or out is
  * TOAD_EINVAL before everything else); cells or out not 4-byte aligned (TOAD_EALIGN). Not done: per-axis kernels, radii above 16 cells, CLAM's second
- * blur of the coloured image, seams between separately rendered regions. */
+ * blur of the coloured image. Blur the table of the whole image and render it window by window (toad_region_heat_window_u8): no seams. */
 int toad_heat_cells_blur(const int *cells, int Gy, int Gx, const int *taps /* HOST, radius + 1 ints */, int radius, int *out, void *stream);
 
 /* out uint8 [Ho][Wo][3] with row pitch out_pitch >= 3 * Wo bytes = the canvas of `region` under `cells` [Gy][Gx] (Gy = ceil(Hr / cell), Gx = ceil(Wr /
@@ -483,7 +483,7 @@ int toad_region_heat_blend_u8(const unsigned char *region, int64_t pitch, int Hr
  *   output byte   (alpha * lut[idx_px][c] + (256 - alpha) * m + 128) >> 8 where own >= 0 and the pixel is tissue, m elsewhere. Coverage edges and mask
  *                 edges stay sharp; only the colour inside them is interpolated.
  * This is not CLAM's Gaussian `blur` and does not claim to be: the smoothing width is one cell. The wider kernel is toad_heat_cells_blur above, a pass
- * over the cells in front of this call. Seams between separately rendered regions (a neighbour outside the table counts as `own`) are not done.
+ * over the cells in front of this call. Seams between separately rendered regions (a neighbour outside the table counts as `own`): toad_region_heat_window_u8 below.
  * Refusals as for toad_region_heat_blend_u8, and: smooth not 0 or 1, mask_thresh outside 0 .. 255 (TOAD_EINVAL); a mask_down not in the list or not a
  * multiple of down, Hm or Wm not the floor quotients, mask_pitch < Wm (TOAD_ESHAPE). No byte outside mask + y * mask_pitch + [0, Wm), 0 <= y < Hm, is read;
  * the mask may have any base address. Ho == 0 or Wo == 0: returns TOAD_OK and launches nothing. One streaming pass. */
@@ -512,6 +512,32 @@ int toad_region_heat_blend_px_u8(const unsigned char *region, int64_t pitch, int
 int toad_region_heat_thumb_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx, int cell,
                               const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm,
                               int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream);
+
+/* A window of a larger image (additive to ABI 15 too): a slide arrives from the decoder in strips or blocks, and a canvas put together from them must
+ * show no seams. `region` [Hr][Wr][3] is the window whose pixel (0, 0) is pixel (wx, wy) of the image that the table cells [Gy][Gx] and the mask plane
+ * [Hm][Wm] describe. The canvas written, Ho = Hr / down rows of Wo = Wr / down pixels, is byte for byte rows wy / down .. wy / down + Ho and columns
+ * wx / down .. wx / down + Wo of the canvas the per-pixel definition above gives for that whole image. down is any of {1, 2, 4, 8, 16, 32}: 1, 2, 4
+ * run the kernels of toad_region_heat_blend_px_u8, 8, 16, 32 (down <= cell) the kernel of toad_region_heat_thumb_u8. For canvas pixel (ox, oy) of the
+ * window, with X = down * ox + wx and Y = down * oy + wy:
+ *   own           own = cells[Y / cell][X / cell], values above 255 read as 255.
+ *   colour index  smooth = 0: idx_px = own. smooth = 1: p = 2 * X + down - cell, g0 = floor(p / (2 * cell)), f = p - 2 * cell * g0, weights 2 * cell - f
+ *                 for cell g0 and f for g0 + 1, the same along y from Y. A neighbour inside the TABLE contributes its value, also where it lies outside
+ *                 the window - that is what removes the seam; only a neighbour outside the table or without a value counts as `own`.
+ *                 idx_px = (sum wy * wx * v + 2 * cell * cell) >> (2 * log2(cell) + 2).
+ *   tissue        mask == NULL: every pixel. Otherwise iff mx = X / mask_down < Wm, my = Y / mask_down < Hm and mask[my][mx] > mask_thresh. Hm and Wm are
+ *                 the image's, any non-negative numbers: a pixel outside the plane is not tissue.
+ *   output byte   (alpha * lut[idx_px][c] + (256 - alpha) * m + 128) >> 8 where own >= 0 and the pixel is tissue, m elsewhere; m is the box mean of the
+ *                 window's own pixels, as above. Region and canvas addresses and the partial boxes dropped at the right and the bottom are the window's.
+ * Refusals in the order of toad_region_heat_blend_px_u8 with: down not in {1, 2, 4, 8, 16, 32}, then down >= 8 and down > cell; directly after the down
+ * checks wx or wy negative or not a multiple of max(4, down) - a lane's 4 x 4 block of pixels must still lie in one cell and, for mask_down >= 4, in one
+ * mask pixel, and a canvas box in one cell and one mask pixel - and wx + Wr >= 2^30 (2 * X must fit in an int) (all TOAD_ESHAPE); no Hm / Wm equality
+ * check, only Hm, Wm >= 0; in the place of the Gy x Gx equality check, ceil((wy + Hr) / cell) > Gy or ceil((wx + Wr) / cell) > Gx (TOAD_ESHAPE). cells
+ * 4-byte aligned (TOAD_EALIGN). No byte outside region + y * pitch + [0, 3 * down * Wo), 0 <= y < down * Ho, is read, none outside cells[0 .. Gy * Gx)
+ * and mask + y * mask_pitch + [0, Wm), 0 <= y < Hm; no byte outside out + y * out_pitch + [0, 3 * Wo), 0 <= y < Ho, is written. Ho == 0 or Wo == 0:
+ * returns TOAD_OK and launches nothing. With wx = wy = 0 and a table and a plane of the region's own extent this is the three calls above. */
+int toad_region_heat_window_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, int wx, int wy, const int *cells, int Gy, int Gx, int cell,
+                               const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm,
+                               int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream);
 
 /* ---- Segmented tissue selection: CLAM's recipe - a median-filtered saturation channel of a low-resolution level, thresholded by a fixed value or by
  * Otsu's - defined in integers (additive to ABI 15 too). A second selector next to the per-pixel predicate above, which does not change; csrc/tissue_seg.hip.

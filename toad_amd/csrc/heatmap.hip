@@ -18,12 +18,17 @@
 //   overview    (toad_region_heat_thumb_u8) the per-pixel canvas at down in {8, 16, 32} with down <= cell, so that a box still lies in one cell: the
 //               slide overview of an 80k x 80k region without a full-size canvas in between.
 //
+//   window      (toad_region_heat_window_u8) any of the canvases above for a region that is the window at (wx, wy) of the image the table and the mask plane
+//               describe: own cell, tent and mask coordinates from x + wx, y + wy, everything else - addresses, box means, the work split - the window's own.
+//               A tent neighbour inside the table counts also where it lies outside the window: canvases put together from strips or blocks show no seams.
+//               wx, wy are multiples of max(4, down), so that a lane's 4 x 4 block and a canvas box lie in one cell and one mask pixel as before.
+//
 //   blur        (toad_heat_cells_blur) the cell table smoothed before it is rendered: a normalised convolution with a symmetric separable integer kernel
 //               of radius 1 .. 16 cells, absent cells and cells outside the table carrying no weight, absent cells staying absent.
 //
 // Four kernels:
 //   heat_cells_blur_kernel                 a 16 x 64 tile of the cell table and its halo in LDS, a row pass and a column pass inside the workgroup.
-//   heat_thumb_kernel<DOWN>               the overview canvas: the same streaming pass with a box's lanes and waves reduced, one thread per canvas pixel blends.
+//   heat_thumb_kernel<DOWN,WINDOW>        the overview canvas: the same streaming pass with a box's lanes and waves reduced, one thread per canvas pixel blends.
 //   heat_cells_kernel                      one thread per cell: the covering tiles' index ranges in closed form from the lattice in cell units, a loop over them.
 //   heat_blend_px_kernel<DOWN,SMOOTH,MASK>  one streaming pass over the region: read uint8, write uint8. <DOWN,0,false> is the flat canvas (one colour and one
 //                                           alpha per cell: both entry points launch it); the others decide the index, the colour and the alpha per canvas pixel.
@@ -166,6 +171,7 @@ struct HeatPxArgs {
     int alpha;
     const unsigned char *mask; int64_t mask_pitch; int Hm, Wm, mshift, mask_thresh;
     unsigned char *out; int64_t out_pitch; unsigned nchunks;
+    int wx, wy;                                                      // the region's pixel (0, 0) in the image that cells and mask describe
 };
 
 // heat_px4 with a colour col[p] (0x00bbggrr, as in the LDS table) and an alpha al[p] of its own for each of the row's NP = 4 / DOWN output pixels. At
@@ -249,7 +255,9 @@ __device__ __forceinline__ void heat_px_lane(const HeatPxArgs &a, const unsigned
     const int64_t y0 = (int64_t)rb * 16 + wave * RW;               // first row of this wave (may lie below Hi: then it writes nothing)
     if (y0 >= a.Hi) return;
     const bool live = x < (unsigned)a.Wi;
-    const int gy = (int)(y0 >> a.shift), gx = (int)(x >> a.shift);
+    const unsigned sx = x + (unsigned)a.wx;                        // the block's corner in the table's image: multiples of 4 like x and y0
+    const int64_t sy0 = y0 + a.wy;
+    const int gy = (int)(sy0 >> a.shift), gx = (int)(sx >> a.shift);
     const int own = live ? min(a.cells[(int64_t)gy * a.Gx + gx], 255) : -1;
 
     unsigned ua[3], ubeta;                                         // FLAT: heat_px4's a[] and beta, alpha' = 0 on a cell without a value
@@ -269,8 +277,8 @@ __device__ __forceinline__ void heat_px_lane(const HeatPxArgs &a, const unsigned
         const int cell = 1 << a.shift, c2 = 2 * cell;
         int bx, by, fx0 = 0, fy0 = 0;
         if constexpr (SMOOTH == 1) {
-            const int px = 2 * (int)x + DOWN - cell;                 // 3 Wr < 2^31, so 2 x fits
-            const int64_t py = 2 * y0 + DOWN - cell;
+            const int px = (int)(2u * sx) + DOWN - cell;             // wx + Wr < 2^30, so 2 sx fits on every live lane
+            const int64_t py = 2 * sy0 + DOWN - cell;
             bx = px >> (a.shift + 1); fx0 = px & (c2 - 1);
             by = (int)(py >> (a.shift + 1)); fy0 = (int)(py & (c2 - 1));
         } else {
@@ -307,8 +315,8 @@ __device__ __forceinline__ void heat_px_lane(const HeatPxArgs &a, const unsigned
     int thr = -1;                                                    // without a mask every byte is above it
     if constexpr (MASK) {
         thr = a.mask_thresh;
-        const unsigned mx = x >> a.mshift;
-        const int64_t my = y0 >> a.mshift;
+        const unsigned mx = sx >> a.mshift;
+        const int64_t my = sy0 >> a.mshift;
         const int have = live && mx < (unsigned)a.Wm ? a.Wm - (int)mx : 0;      // mask columns from mx on that exist
         const unsigned char *mp = a.mask + my * a.mask_pitch + mx;
         if (a.mshift >= 2) {
@@ -399,8 +407,11 @@ __global__ __launch_bounds__(256, 8) void heat_blend_px_kernel(const HeatPxArgs 
 // Hi x Wi or wholly outside. A box lies in one cell (down <= cell) and in one mask pixel (mask_down a multiple of down), so the pixel's own cell, its
 // tent (the formula of heat_px_lane's SMOOTH 1 at the box's corner: g0 and f are the pixel's) and its mask byte are single loads; smooth and the mask
 // are run-time values because only these few threads look at them, and the colour comes straight from lut in global memory. Every canvas byte is
-// written once, by one lane, with byte stores at any address; nothing outside oy out_pitch + [0, 3 Wo), oy < Ho, is written.
-template <int DOWN>
+// written once, by one lane, with byte stores at any address; nothing outside oy out_pitch + [0, 3 Wo), oy < Ho, is written. WINDOW: the box's corner in
+// the table's image is the region's plus (wx, wy) - a template parameter here and not in heat_blend_px_kernel, because here the two adds were measured:
+// they sit in the dependent chain behind the barrier, where the few finishing threads wait for one load after the other, and cost the three older
+// instantiations 1 to 3 % (tools/heatmap_bench.py --window --w0-only against the library as it was); the px kernels showed no difference.
+template <int DOWN, bool WINDOW>
 __global__ __launch_bounds__(256) void heat_thumb_kernel(const HeatPxArgs a, int smooth, const unsigned char *__restrict__ lut) {
     constexpr int RB = strip_rows(DOWN), RW = RB / 4;              // rows per workgroup, per wave
     constexpr int LANES = DOWN / 4, SH = DOWN == 8 ? 6 : DOWN == 16 ? 8 : 10;      // lanes per box, log2(DOWN^2)
@@ -441,13 +452,13 @@ __global__ __launch_bounds__(256) void heat_thumb_kernel(const HeatPxArgs a, int
         for (int k = 0; k < WPB; ++k) t += part[c][band * WPB + k][bx * LANES];
         m[c] = (t + (1 << (SH - 1))) >> SH;
     }
-    const int64_t py0 = oy * DOWN;                                 // the box's corner in the region
-    const int px0 = (int)(ox * DOWN);
+    const int64_t py0 = oy * DOWN + (WINDOW ? a.wy : 0);           // the box's corner in the table's image
+    const int px0 = (int)(ox * DOWN) + (WINDOW ? a.wx : 0);
     const int own = min(a.cells[(py0 >> a.shift) * a.Gx + (px0 >> a.shift)], 255);
     int idx = max(own, 0);
     if (smooth) {
         const int cell = 1 << a.shift, c2 = 2 * cell;
-        const int px = 2 * px0 + DOWN - cell;                      // 3 Wr < 2^31, so 2 x fits
+        const int px = 2 * px0 + DOWN - cell;                      // wx + Wr < 2^30, so 2 x fits
         const int64_t py = 2 * py0 + DOWN - cell;
         const int gx0 = px >> (a.shift + 1), fx = px & (c2 - 1);
         const int gy0 = (int)(py >> (a.shift + 1)), fy = (int)(py & (c2 - 1));
@@ -533,14 +544,23 @@ extern "C" int toad_heat_cells_blur(const int *cells, int Gy, int Gx, const int 
 
 // All three canvas entry points: every check in the order in which the first failing one wins, the geometry, the choice of the kernel. The flat entry passes
 // smooth = 0 and mask = NULL, for which the smooth and mask checks are no-ops; `unaligned` names the planes its alignment message lets lie anywhere. `thumb`
-// is the overview entry: down in {8, 16, 32} and at most the cell, strips of strip_rows(down) rows, heat_thumb_kernel<down>.
-static int launch_heat_blend(const char *what, const char *unaligned, bool thumb, const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx,
-                             int cell, const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm,
-                             int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream) {
+// is the overview entry: down in {8, 16, 32} and at most the cell, strips of strip_rows(down) rows, heat_thumb_kernel<down>. `window` is the window entry
+// (toad_region_heat_window_u8): the region is the window at (wx, wy) of the image that cells and mask describe, any of the six down values picks its
+// kernel, the table and the plane need only hold the window; the other three pass wx = wy = 0 and demand a table and a plane of exactly the region's extent.
+static int launch_heat_blend(const char *what, const char *unaligned, bool thumb, bool window, const unsigned char *region, int64_t pitch, int Hr, int Wr, int wx, int wy,
+                             const int *cells, int Gy, int Gx, int cell, const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask,
+                             int64_t mask_pitch, int Hm, int Wm, int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream) {
     if (!region || !cells || !lut || !out) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
     if (int rc = check_cell(what, cell)) return rc;
     if (int rc = check_hw(what, "Hr", Hr, "Wr", Wr)) return rc;
     if (alpha < 0 || alpha > 256) { set_error("%s: alpha = %d must lie in [0, 256] (256 = the colour alone)", what, alpha); return TOAD_ESHAPE; }
+    if (window) {
+        if (down != 1 && down != 2 && down != 4 && down != 8 && down != 16 && down != 32) {
+            set_error("%s: down = %d is not one of 1, 2, 4, 8, 16, 32", what, down);
+            return TOAD_ESHAPE;
+        }
+        thumb = down >= 8;
+    }
     if (thumb) {
         if (down != 8 && down != 16 && down != 32) { set_error("%s: down = %d is not one of 8, 16, 32", what, down); return TOAD_ESHAPE; }
         if (down > cell) {
@@ -549,6 +569,16 @@ static int launch_heat_blend(const char *what, const char *unaligned, bool thumb
         }
     } else if (down != 1 && down != 2 && down != 4) {
         set_error("%s: down = %d is not one of 1, 2, 4", what, down);
+        return TOAD_ESHAPE;
+    }
+    const int walign = down > 4 ? down : 4;                          // a lane's 4 x 4 block and a canvas box stay in one cell and in one mask pixel
+    if (wx < 0 || wy < 0 || wx % walign || wy % walign) {
+        set_error("%s: window (wx, wy) = (%d, %d) is negative or not a multiple of max(4, down) = %d (a lane's 4 x 4 block and a canvas box must lie in one "
+                  "cell and in one mask pixel)", what, wx, wy, walign);
+        return TOAD_ESHAPE;
+    }
+    if (window && (int64_t)wx + Wr >= (1ll << 30)) {
+        set_error("%s: window too far right: wx + Wr = %lld must stay below 2^30 (doubled tent coordinates in 32 bits)", what, (long long)wx + Wr);
         return TOAD_ESHAPE;
     }
     if (smooth != 0 && smooth != 1) { set_error("%s: smooth = %d must be 0 or 1", what, smooth); return TOAD_EINVAL; }
@@ -563,7 +593,9 @@ static int launch_heat_blend(const char *what, const char *unaligned, bool thumb
             set_error("%s: mask_down = %d is not a multiple of down = %d (a canvas box must lie in one mask pixel)", what, mask_down, down);
             return TOAD_ESHAPE;
         }
-        if (Hm != Hr / mask_down || Wm != Wr / mask_down) {
+        if (window) {                                                // the plane is the image's: any extent, what lies outside it is not tissue
+            if (Hm < 0 || Wm < 0) { set_error("%s: Hm x Wm = %d x %d must not be negative", what, Hm, Wm); return TOAD_ESHAPE; }
+        } else if (Hm != Hr / mask_down || Wm != Wr / mask_down) {
             set_error("%s: Hm x Wm = %d x %d is not (Hr / mask_down) x (Wr / mask_down) = %d x %d", what, Hm, Wm, Hr / mask_down, Wr / mask_down);
             return TOAD_ESHAPE;
         }
@@ -576,7 +608,14 @@ static int launch_heat_blend(const char *what, const char *unaligned, bool thumb
         set_error("%s: out_pitch %lld is less than a row of the canvas (3 Wo = %lld bytes)", what, (long long)out_pitch, 3ll * Wo);
         return TOAD_ESHAPE;
     }
-    if (Gy != (int)(((int64_t)Hr + cell - 1) / cell) || Gx != (int)(((int64_t)Wr + cell - 1) / cell)) {
+    if (window) {
+        const int64_t gy_end = ((int64_t)wy + Hr + cell - 1) / cell, gx_end = ((int64_t)wx + Wr + cell - 1) / cell;
+        if (gy_end > Gy || gx_end > Gx) {
+            set_error("%s: the window ends at cell row %lld and cell column %lld, beyond the table's Gy x Gx = %d x %d (ceil((wy + Hr) / cell) <= Gy and "
+                      "ceil((wx + Wr) / cell) <= Gx)", what, (long long)gy_end, (long long)gx_end, Gy, Gx);
+            return TOAD_ESHAPE;
+        }
+    } else if (Gy != (int)(((int64_t)Hr + cell - 1) / cell) || Gx != (int)(((int64_t)Wr + cell - 1) / cell)) {
         set_error("%s: Gy x Gx = %d x %d is not ceil(Hr / cell) x ceil(Wr / cell) = %lld x %lld", what, Gy, Gx, ((long long)Hr + cell - 1) / cell,
                   ((long long)Wr + cell - 1) / cell);
         return TOAD_ESHAPE;
@@ -591,12 +630,13 @@ static int launch_heat_blend(const char *what, const char *unaligned, bool thumb
     while ((1 << shift) < cell) ++shift;
     // the tent's variant: none; one quadrant per lane (cell >= 8); cell == 4, where at down == 4 a canvas pixel is a whole cell and the tent is the own value
     const int sm = !smooth || cell == down ? 0 : cell == 4 ? 2 : 1;
-    const HeatPxArgs a = {region, pitch, Hi, Wi, cells, Gy, Gx, shift, alpha, mask, mask_pitch, Hm, Wm, mshift, mask_thresh, out, out_pitch, (unsigned)nchunks};
+    const HeatPxArgs a = {region, pitch, Hi, Wi, cells, Gy, Gx, shift, alpha, mask, mask_pitch, Hm, Wm, mshift, mask_thresh, out, out_pitch, (unsigned)nchunks,
+                          wx, wy};
     if (thumb) {                                                     // cell == down: the tent is the own value, its four loads are not needed
         const int tent = smooth && cell != down;
-#define TOAD_THUMB(D) \
-    case D: hipLaunchKernelGGL(heat_thumb_kernel<D>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, tent, lut); break;
-        switch (down) { TOAD_THUMB(8) TOAD_THUMB(16) TOAD_THUMB(32) }
+#define TOAD_THUMB(D, W) \
+    case 2 * D + W: hipLaunchKernelGGL((heat_thumb_kernel<D, W != 0>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, tent, lut); break;
+        switch (2 * down + (window ? 1 : 0)) { TOAD_THUMB(8, 0) TOAD_THUMB(16, 0) TOAD_THUMB(32, 0) TOAD_THUMB(8, 1) TOAD_THUMB(16, 1) TOAD_THUMB(32, 1) }
 #undef TOAD_THUMB
         return check_launch(what);
     }
@@ -613,20 +653,27 @@ static int launch_heat_blend(const char *what, const char *unaligned, bool thumb
 
 extern "C" int toad_region_heat_blend_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx, int cell,
                                          const unsigned char *lut, int alpha, int down, unsigned char *out, int64_t out_pitch, void *stream) {
-    return launch_heat_blend("toad_region_heat_blend_u8", "the region and the canvas", false, region, pitch, Hr, Wr, cells, Gy, Gx, cell, lut, alpha, down, 0, nullptr, 0, 0,
+    return launch_heat_blend("toad_region_heat_blend_u8", "the region and the canvas", false, false, region, pitch, Hr, Wr, 0, 0, cells, Gy, Gx, cell, lut, alpha, down, 0, nullptr, 0, 0,
                              0, 0, 0, out, out_pitch, stream);
 }
 
 extern "C" int toad_region_heat_blend_px_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx, int cell,
                                             const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch,
                                             int Hm, int Wm, int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream) {
-    return launch_heat_blend("toad_region_heat_blend_px_u8", "the region, the mask and the canvas", false, region, pitch, Hr, Wr, cells, Gy, Gx, cell, lut, alpha, down,
+    return launch_heat_blend("toad_region_heat_blend_px_u8", "the region, the mask and the canvas", false, false, region, pitch, Hr, Wr, 0, 0, cells, Gy, Gx, cell, lut, alpha, down,
                              smooth, mask, mask_pitch, Hm, Wm, mask_down, mask_thresh, out, out_pitch, stream);
 }
 
 extern "C" int toad_region_heat_thumb_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *cells, int Gy, int Gx, int cell,
                                          const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch,
                                          int Hm, int Wm, int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream) {
-    return launch_heat_blend("toad_region_heat_thumb_u8", "the region, the mask and the canvas", true, region, pitch, Hr, Wr, cells, Gy, Gx, cell, lut, alpha, down,
+    return launch_heat_blend("toad_region_heat_thumb_u8", "the region, the mask and the canvas", true, false, region, pitch, Hr, Wr, 0, 0, cells, Gy, Gx, cell, lut, alpha, down,
                              smooth, mask, mask_pitch, Hm, Wm, mask_down, mask_thresh, out, out_pitch, stream);
+}
+
+extern "C" int toad_region_heat_window_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, int wx, int wy, const int *cells, int Gy, int Gx, int cell,
+                                          const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch,
+                                          int Hm, int Wm, int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream) {
+    return launch_heat_blend("toad_region_heat_window_u8", "the region, the mask and the canvas", false, true, region, pitch, Hr, Wr, wx, wy, cells, Gy, Gx, cell, lut,
+                             alpha, down, smooth, mask, mask_pitch, Hm, Wm, mask_down, mask_thresh, out, out_pitch, stream);
 }

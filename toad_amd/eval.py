@@ -292,8 +292,8 @@ def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region
     working on ``tile`` and ``stride`` in region pixels. A bad value, or a footprint it does not divide, raises ValueError before the selection runs.
 
     Not done here: a sigma per axis for tiles that are not square, radii above 16 cells (``blur=True`` on lattices whose cell is 16 or less), CLAM's
-    second blur of the coloured image, seams between separately rendered regions, several levels of the vis-level pyramid in one call (one level per
-    call is done) and saving the image."""
+    second blur of the coloured image, several levels of the vis-level pyramid in one call (one level per call is done) and saving the image. A slide
+    that arrives strip by strip: ``slide_attention_heatmap`` (no seams, one colour scale); the segmented selector there still works on one region."""
     from .heatmap import attention_canvas, blur_taps
     from .tissue import _lattice_args, lattice_cell
     if shrink != 1:                                                 # refuse a bad shrink before the selection runs; the extractor checks it again
@@ -311,3 +311,90 @@ def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region
                                            return_mask=tissue_mask, shrink=shrink)
     return origins, scores, attention_canvas(region, origins, scores, tile=tile, stride=stride, alpha=alpha, down=down, lut=lut, out=out, smooth=smooth,
                                              mask=mask, thresh=thresh, binarize=binarize, blur=blur)
+
+
+def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_hw, tile=256, stride=None, origin=(0, 0), origins=None,
+                            min_fraction: float = 0.25, sat_thresh: int = 8, val_min: int = 0, bag_dtype: torch.dtype = torch.float16, alpha=102,
+                            down: int = 1, lut=None, out=None, smooth: bool = False, mask=None, thresh=None, binarize: bool = False, blur=False, shrink=1):
+    """``(origins, scores, canvas)`` of a slide of ``slide_hw`` = (Hs, Ws) pixels that arrives from the decoder strip by strip: what
+    ``region_tissue_attention_heatmap`` gives for one region, with no seam where two strips meet. ``strips`` is a sequence of ``(region, y_k)`` - a
+    decoded uint8 [H_k,Ws,3] full-width strip on the device and the slide row of its first row - sorted, each abutting or overlapping the one before,
+    covering rows 0 .. Hs (``heatmap.strip_plan``; its ValueErrors come before anything is launched). Strips must overlap by at least tile - stride
+    rows, so that every lattice tile row lies whole in one strip. The sequence is read once for its shapes and then walked twice:
+
+    1. per strip, the tissue tiles the strip owns (``tissue.tissue_origins`` on the strip with the strip's local lattice origin; or, with ``origins``
+       [B,2] of (x, y) in SLIDE coordinates, the caller's tiles whose lattice row the strip owns, in the order given) go through
+       ``extractor.forward_u8_region`` on that strip; the rows are put into one bag, strips in order, row-major inside a strip - the slide's row-major
+       lattice order. ``attention_heatmap_scores(model, bag, percentile=True)`` runs ONCE over that bag, so the ranks - the colour scale - are the
+       slide's, and ``heatmap.slide_cells`` builds the slide's cell table from them (``thresh``, ``binarize``, ``blur`` as in ``attention_canvas``).
+    2. per strip, ``heatmap.window_canvas`` renders the strip's rows from max(y_k, the end of the previous strip) on into its rows of ONE uint8
+       [Hs // down, Ws // down, 3] canvas (or ``out``), against the slide's table: the tent and the blur see the neighbouring strip's cells.
+
+    ``origins`` returned are slide coordinates, int64 [B,2] on the host. ``mask`` is a SLIDE-wide ``(plane, t, mask_down)``, for example
+    ``tissue.segment_tissue`` of the slide's overview level; ``alpha``, ``down`` (1 .. 32), ``lut``, ``smooth``: ``attention_canvas``; ``shrink``:
+    ``region_attention_scores``. A slide without a tissue tile gives empty origins, empty scores and the box-filtered slide; neither the extractor nor
+    the model is called. With the same tiles the canvas is byte for byte ``attention_canvas`` of the whole slide.
+
+    Not done here: the segmented selector across strips - its median, closing and component steps reach across strip seams, so
+    ``tissue.segmented_tissue_origins`` still works on one region per call; make that selection on an overview level and pass it in through
+    ``origins=`` and ``mask=``. Blocks that are not full-width strips (``heatmap.window_canvas`` renders any window; this walk does not), and the
+    "not done" list of ``region_tissue_attention_heatmap`` except seams."""
+    from .heatmap import slide_cells, strip_plan, window_canvas
+    from .heatmap import blur_taps
+    from .tissue import _lattice_args, lattice_cell, tissue_origins
+    hs, ws = slide_hw
+    h, w, sy, sx, x0, y0 = _lattice_args(tile, stride, origin)
+    if shrink != 1:                                                 # refuse what the second pass would refuse before the extractor runs
+        from .ops import shrunk_tile
+        shrunk_tile(tile, shrink)
+    cell = lattice_cell((h, w), (sy, sx), (x0, y0))
+    if down in (8, 16, 32) and cell < down:
+        raise ValueError(f"slide_attention_heatmap: down = {down} exceeds the lattice's cell = {cell}: a canvas box must lie in one cell")
+    blur_taps(blur, (h, w), cell)
+    shapes = []
+    for k, (region, y) in enumerate(strips):
+        if region.dim() != 3 or region.shape[1] != ws or region.shape[2] != 3:
+            raise ValueError(f"slide_attention_heatmap: strip {k} must be a full-width uint8 [H_k,{ws},3] region, got {tuple(region.shape)}")
+        shapes.append((y, region.shape[0]))
+    plan = strip_plan((hs, ws), shapes, (h, w), (sy, sx), (x0, y0), down)
+    device = strips[0][0].device
+    if origins is not None:
+        given = np.asarray(origins)
+        if given.ndim != 2 or given.shape[1] != 2 or given.dtype.kind not in "iu":
+            raise ValueError(f"slide_attention_heatmap: origins must be [B,2] integers (x, y) in slide coordinates, got shape {given.shape} dtype {given.dtype}")
+        given = given.astype(np.int64)
+        rows = (given[:, 1] - y0) // sy
+        off = (rows < 0) | (rows >= plan[-1]["rows"][1]) | ((given[:, 1] - y0) % sy != 0) | ((given[:, 0] - x0) % sx != 0)
+        if off.any():                                                # (outside the lattice along x, or given twice: slide_cells, after the first pass)
+            bad = given[off][0]
+            raise ValueError(f"slide_attention_heatmap: origin (x={int(bad[0])}, y={int(bad[1])}) is off the lattice or in none of the slide's lattice rows")
+    kept, bags = [], []
+    for (region, y), p in zip(strips, plan):                        # pass 1: the tiles each strip owns -> bag rows
+        j0, j1 = p["rows"]
+        if j1 == j0:
+            continue
+        if origins is None:
+            local = tissue_origins(region, tile=(h, w), stride=(sy, sx), min_fraction=min_fraction, sat_thresh=sat_thresh, val_min=val_min, origin=p["origin"])
+        else:
+            local = given[(rows >= j0) & (rows < j1)] - np.array([0, y], dtype=np.int64)
+        if local.shape[0] == 0:
+            continue
+        kept.append(local + np.array([0, y], dtype=np.int64))
+        bags.append(extractor.forward_u8_region(region, local, tile=(h, w), out_dtype=bag_dtype, shrink=shrink))
+    if kept:
+        found = np.concatenate(kept, axis=0)
+        scores = attention_heatmap_scores(model, bags[0] if len(bags) == 1 else torch.cat(bags, dim=0), percentile=True)
+    else:
+        found, scores = np.zeros((0, 2), dtype=np.int64), torch.empty(0, dtype=torch.float32, device=device)
+    cells, cell = slide_cells((hs, ws), found, scores, (h, w), (sy, sx), (x0, y0), thresh=thresh, binarize=binarize, blur=blur,
+                              name="slide_attention_heatmap")
+    ho, wo = hs // down, ws // down
+    if out is None:
+        out = torch.empty((ho, wo, 3), dtype=torch.uint8, device=device)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (ho, wo, 3):
+        raise ValueError(f"slide_attention_heatmap: out must be a uint8 [{ho},{wo},3] tensor on the strips' device")
+    for (region, y), p in zip(strips, plan):                        # pass 2: each strip's own rows of the one canvas
+        r0, r1 = p["render"]
+        n = (r1 - r0) // down
+        window_canvas(region[r0 - y:r1 - y], (0, r0), cells, cell, alpha=alpha, down=down, lut=lut, out=out[r0 // down:r0 // down + n], smooth=smooth, mask=mask)
+    return found, scores, out

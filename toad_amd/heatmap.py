@@ -43,8 +43,13 @@ cells on the usual 256 / 64 lattice, a field band-limited far below the cell pit
 
 Conventions as in ``toad_amd.tissue``: ``tile`` = int or (H, W), ``stride`` = int or (sy, sx), ``origin`` = (x, y) of the lattice's first tile.
 Not done here: a sigma per axis for tiles that are not square, radii above 16 cells (``blur=True`` on lattices whose cell is 16 or less), CLAM's second
-blur of the coloured image, seams between separately rendered regions (a neighbour outside the table counts as ``own`` for the tent and carries no weight
-for the blur), several levels of the vis-level pyramid in one call (one level per call is done) and saving images."""
+blur of the coloured image, several levels of the vis-level pyramid in one call (one level per call is done) and saving images.
+
+A slide that arrives from the decoder in strips or blocks is rendered window by window with no seams: ``slide_cells`` builds the cell table of the whole
+slide - only the lattice and the extent matter to it -, ``window_canvas`` renders one decoded window against that table (``ops.region_heat_window``: a
+tent neighbour inside the table contributes its value also where it lies outside the window, and the mask is the slide's), and ``strip_plan`` says which
+full-width strip owns which lattice rows and renders which canvas rows. ``attention_canvas`` is ``slide_cells`` plus the blend of one region that is the
+whole image. ``eval.slide_attention_heatmap`` is the whole walk, with ONE percentile ranking over the slide."""
 from __future__ import annotations
 
 import math
@@ -188,6 +193,90 @@ def blur_taps(blur, tile, cell):
     return ops.heat_blur_taps("attention_canvas: blur", blur)
 
 
+def slide_cells(slide_hw, origins, scores: torch.Tensor, tile=256, stride=None, origin=(0, 0), score_range=(0, 1), thresh=None, binarize: bool = False,
+                blur=False, name: str = "slide_cells"):
+    """``(cells, cell)``: the cell table of a whole image of ``slide_hw`` = (Hs, Ws) pixels - int32 [ceil(Hs / cell), ceil(Ws / cell)] on the device of
+    ``scores`` - and the lattice's cell (``tissue.lattice_cell``). The first half of ``attention_canvas``: the scores are quantised
+    (``quantise_scores``), ``thresh`` and ``binarize`` applied (``select_scores``), the tile table built (``tile_table``), the cells summed
+    (``ops.heat_cells``) and, with ``blur``, smoothed (``ops.heat_cells_blur``; ``blur_taps``). Only the lattice and the extent matter: no pixel is
+    involved, so the table of a slide that arrives strip by strip is built once and rendered window by window (``window_canvas``). Empty ``origins``
+    give a table of -1 and launch nothing. ``name`` is the caller's, for messages."""
+    hs, ws = slide_hw
+    h, w, sy, sx, x0, y0 = _lattice_args(tile, stride, origin)
+    cell = lattice_cell((h, w), (sy, sx), (x0, y0))
+    if not isinstance(scores, torch.Tensor):
+        raise ValueError(f"{name}: scores must be a tensor on the device, got {type(scores).__name__}")
+    if not isinstance(binarize, bool):
+        raise ValueError(f"{name}: binarize must be a bool, got {binarize!r}")
+    if thresh is not None and (isinstance(thresh, bool) or not isinstance(thresh, (int, float)) or thresh != thresh):
+        raise ValueError(f"{name}: thresh must be None or a number (a raw score), got {thresh!r}")
+    taps = blur_taps(blur, (h, w), cell)
+    nx, ny = lattice(hs, ws, (h, w), (sy, sx), (x0, y0))
+    table = tile_table(origins, select_scores(scores, quantise_scores(scores, score_range), thresh, binarize), (h, w), (sy, sx), (x0, y0), (nx, ny))
+    if table.numel() and len(origins):
+        cells = ops.heat_cells(table, cell, (x0, y0), (h, w), (sy, sx), (nx, ny), (hs, ws))
+        if taps is not None:
+            cells = ops.heat_cells_blur(cells, taps)
+    else:
+        cells = torch.full((-(-hs // cell), -(-ws // cell)), -1, dtype=torch.int32, device=scores.device)
+    return cells, cell
+
+
+def window_canvas(region: torch.Tensor, window, cells: torch.Tensor, cell: int, alpha=102, down: int = 1, lut=None, out=None, smooth: bool = False,
+                  mask=None) -> torch.Tensor:
+    """The heat map of one window of a slide: uint8 [Hr // down, Wr // down, 3] on the device, byte for byte the rows from ``wy // down`` and the columns
+    from ``wx // down`` of the canvas ``attention_canvas`` gives for the whole slide. ``region`` [Hr,Wr,3] is the decoded window, ``window`` = (wx, wy)
+    its place in the slide - multiples of max(4, ``down``) - ``cells`` and ``cell`` the slide's table from ``slide_cells``, ``mask`` the SLIDE-wide
+    (plane, t, mask_down) triple. ``alpha``, ``down`` (any of 1 .. 32), ``lut``, ``smooth``: ``attention_canvas``; ``out`` may be the window's rows and
+    columns of the slide's canvas. The second half of ``attention_canvas``, through ``ops.region_heat_window``: one launch."""
+    a = _alpha_arg(alpha)
+    if not isinstance(smooth, bool):
+        raise ValueError(f"window_canvas: smooth must be a bool, got {smooth!r}")
+    plane, t, mask_down = _mask_arg(mask)
+    lut = jet_lut(region.device) if lut is None else lut
+    return ops.region_heat_window(region, window, cells, cell, lut, a, down, smooth=smooth, mask=plane, mask_down=mask_down if plane is not None else None,
+                                  mask_thresh=t if plane is not None else 0, out=out)
+
+
+def strip_plan(slide_hw, strips, tile=256, stride=None, origin=(0, 0), down: int = 1):
+    """How a slide of ``slide_hw`` = (Hs, Ws) pixels that arrives as full-width row strips is scored and rendered strip by strip. Host arithmetic only.
+    ``strips`` = [(y_k, H_k)]: strip k holds the slide's rows y_k .. y_k + H_k, sorted, each abutting or overlapping the one before. One dict per strip:
+
+    * ``rows`` = (j0, j1): the lattice rows j0 <= j < j1 the strip owns - a tile row (y0 + j sy .. + h) belongs to the FIRST strip that holds it whole;
+    * ``origin`` = (x, y): the lattice origin of row j0 inside the strip, for ``tissue.tissue_origins`` / ``forward_u8_region`` on the strip (every
+      lattice tile of the strip from there on is one it owns; add (0, y_k) for slide coordinates). None where the strip owns no row;
+    * ``render`` = (r0, r1): the slide rows it renders, from max(y_k, the end of the previous strip) to its own end.
+
+    ValueError for strips that are not sorted or leave a gap, that do not cover 0 .. Hs, for a lattice tile row that lies whole in no strip (the strips
+    must overlap by at least tile - stride rows), and for a render start that is not a multiple of max(4, ``down``) (``ops.region_heat_window``)."""
+    hs, ws = slide_hw
+    h, w, sy, sx, x0, y0 = _lattice_args(tile, stride, origin)
+    _, ny = lattice(hs, ws, (h, w), (sy, sx), (x0, y0))
+    if down not in ops.HEAT_DOWNS + ops.HEAT_THUMB_DOWNS:
+        raise ValueError(f"strip_plan: down must be one of {ops.HEAT_DOWNS + ops.HEAT_THUMB_DOWNS}, got {down!r}")
+    strips = [(int(y), int(n)) for y, n in strips]
+    if not strips or strips[0][0] != 0 or strips[-1][0] + strips[-1][1] != hs:
+        raise ValueError(f"strip_plan: the strips must cover rows 0 .. Hs = {hs}, got {strips!r}")
+    align, plan, end, j = max(4, down), [], 0, 0
+    for k, (y, n) in enumerate(strips):
+        if n < 1 or y + n <= end or (k and y <= strips[k - 1][0]):
+            raise ValueError(f"strip_plan: strip {k} = (y, H) = {(y, n)} is empty or not sorted after the strips before it (rows up to {end})")
+        if y > end:
+            raise ValueError(f"strip_plan: a gap between strip {k - 1}, which ends at row {end}, and strip {k}, which starts at row {y}")
+        r0 = max(y, end)
+        if r0 % align:
+            raise ValueError(f"strip_plan: strip {k} renders from row {r0}, not a multiple of max(4, down) = {align}")
+        if j < ny and y0 + j * sy < y:
+            raise ValueError(f"strip_plan: lattice tile row {j} (rows {y0 + j * sy} .. {y0 + j * sy + h}) lies whole in no strip: strips {k - 1} and {k} "
+                             f"overlap by {end - y} rows, less than tile - stride = {h - sy}")
+        j0 = j
+        while j < ny and y0 + j * sy + h <= y + n:
+            j += 1
+        plan.append(dict(rows=(j0, j), origin=(x0, y0 + j0 * sy - y) if j > j0 else None, render=(r0, y + n)))
+        end = y + n
+    return plan
+
+
 def attention_canvas(region: torch.Tensor, origins, scores: torch.Tensor, tile=256, stride=None, origin=(0, 0), alpha=102, down: int = 1, lut=None,
                      score_range=(0, 1), out=None, smooth: bool = False, mask=None, thresh=None, binarize: bool = False, blur=False) -> torch.Tensor:
     """The heat map of one decoded uint8 region [Hr,Wr,3]: uint8 [Hr // down, Wr // down, 3] ON THE DEVICE. ``origins`` [B,2] of (x, y) on the host are
@@ -219,20 +308,12 @@ def attention_canvas(region: torch.Tensor, origins, scores: torch.Tensor, tile=2
     if not isinstance(scores, torch.Tensor) or scores.device != region.device:
         raise ValueError(f"attention_canvas: scores must be a tensor on the region's device ({region.device}), got "
                          f"{scores.device if isinstance(scores, torch.Tensor) else type(scores).__name__}")
-    nx, ny = lattice(hr, wr, (h, w), (sy, sx), (x0, y0))
     if not isinstance(smooth, bool) or not isinstance(binarize, bool):
         raise ValueError(f"attention_canvas: smooth and binarize must be bools, got {smooth!r} and {binarize!r}")
     if thresh is not None and (isinstance(thresh, bool) or not isinstance(thresh, (int, float)) or thresh != thresh):
         raise ValueError(f"attention_canvas: thresh must be None or a number (a raw score), got {thresh!r}")
     plane, t, mask_down = _mask_arg(mask)
-    taps = blur_taps(blur, (h, w), cell)
-    table = tile_table(origins, select_scores(scores, quantise_scores(scores, score_range), thresh, binarize), (h, w), (sy, sx), (x0, y0), (nx, ny))
-    if table.numel() and len(origins):
-        cells = ops.heat_cells(table, cell, (x0, y0), (h, w), (sy, sx), (nx, ny), (hr, wr))
-        if taps is not None:
-            cells = ops.heat_cells_blur(cells, taps)
-    else:
-        cells = torch.full((-(-hr // cell), -(-wr // cell)), -1, dtype=torch.int32, device=region.device)
+    cells, cell = slide_cells((hr, wr), origins, scores, (h, w), (sy, sx), (x0, y0), score_range, thresh, binarize, blur, name="attention_canvas")
     lut = jet_lut(region.device) if lut is None else lut
     blend = ops.region_heat_thumb if thumb else ops.region_heat_blend_px
     return blend(region, cells, cell, lut, a, down, smooth=smooth, mask=plane, mask_down=mask_down if plane is not None else None,

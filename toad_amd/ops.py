@@ -1580,11 +1580,30 @@ def heat_cells_blur(cells: torch.Tensor, taps) -> torch.Tensor:
     return out
 
 
-def _heat_blend_args(name: str, region, cells, cell, lut, alpha, down, out):
-    """The checks region_heat_blend, region_heat_blend_px and region_heat_thumb share -> (pitch, Hr, Wr, Ho, Wo, out)."""
+def _heat_window_arg(name: str, window, down, cell, hr, wr, cells):
+    """The window rules of region_heat_window -> (wx, wy): two non-negative ints, multiples of max(4, down), wx + Wr < 2^30, the window inside the table."""
+    if (not isinstance(window, (tuple, list)) or len(window) != 2
+            or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in window)):
+        raise ValueError(f"{name}: window must be (wx, wy), two ints, got {window!r}")
+    wx, wy = int(window[0]), int(window[1])
+    align = max(4, down)
+    if wx < 0 or wy < 0 or wx % align or wy % align:
+        raise ValueError(f"{name}: window (wx, wy) = ({wx}, {wy}) must be non-negative multiples of max(4, down) = {align}: a lane's 4 x 4 block and a canvas "
+                         "box must lie in one cell and in one mask pixel")
+    if wx + wr >= 1 << 30:
+        raise ValueError(f"{name}: wx + Wr = {wx + wr} must stay below 2^30")
+    if cells.dim() != 2 or -(-(wy + hr) // cell) > cells.shape[0] or -(-(wx + wr) // cell) > cells.shape[1]:
+        raise ValueError(f"{name}: the window ends at cell row {-(-(wy + hr) // cell)} and cell column {-(-(wx + wr) // cell)}, beyond the int32 [Gy,Gx] = "
+                         f"{list(cells.shape)} cells")
+    return wx, wy
+
+
+def _heat_blend_args(name: str, region, cells, cell, lut, alpha, down, out, window=None):
+    """The checks region_heat_blend, region_heat_blend_px, region_heat_thumb and region_heat_window share -> (pitch, Hr, Wr, Ho, Wo, out, window)."""
     pitch, hr, wr = _region_pitch(region, name)
     _cell_arg(name, cell)
-    downs = HEAT_THUMB_DOWNS if name == "region_heat_thumb" else HEAT_DOWNS
+    windowed = name == "region_heat_window"
+    downs = HEAT_THUMB_DOWNS if name == "region_heat_thumb" else HEAT_DOWNS + HEAT_THUMB_DOWNS if windowed else HEAT_DOWNS
     if down not in downs:
         raise ValueError(f"{name}: down must be one of {downs}, got {down!r}")
     if down > cell:                                                  # (the overview canvas only: HEAT_DOWNS divide every cell)
@@ -1592,7 +1611,9 @@ def _heat_blend_args(name: str, region, cells, cell, lut, alpha, down, out):
     if not isinstance(alpha, int) or isinstance(alpha, bool) or not 0 <= alpha <= 256:
         raise ValueError(f"{name}: alpha must be an int in [0, 256], got {alpha!r}")
     _chk(cells, "cells", dtype=torch.int32)
-    if tuple(cells.shape) != (-(-hr // cell), -(-wr // cell)):
+    if windowed:
+        window = _heat_window_arg(name, window, down, cell, hr, wr, cells)
+    elif tuple(cells.shape) != (-(-hr // cell), -(-wr // cell)):
         raise ValueError(f"{name}: expected int32 [Gy,Gx] = [{-(-hr // cell)},{-(-wr // cell)}] cells, got {tuple(cells.shape)}")
     if not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3) or not lut.is_contiguous() or lut.device != region.device:
         raise ValueError(f"{name}: lut must be a contiguous uint8 [256,3] tensor on the region's device")
@@ -1606,13 +1627,13 @@ def _heat_blend_args(name: str, region, cells, cell, lut, alpha, down, out):
             raise ValueError(f"{name}: out must have strides (pitch, 3, 1) with pitch >= 3 Wo, got {tuple(out.stride())}")
         if out.untyped_storage().data_ptr() == region.untyped_storage().data_ptr():
             raise ValueError(f"{name}: out must not share storage with region (the canvas is written while the region is read)")
-    return pitch, hr, wr, ho, wo, out
+    return pitch, hr, wr, ho, wo, out, window
 
 
-def _heat_blend(name: str, region, cells, cell, lut, alpha, down, smooth, mask, mask_down, mask_thresh, out):
-    """The body of region_heat_blend, region_heat_blend_px and region_heat_thumb: the px checks, then toad_<name>_u8 (the first two launch the same
-    kernel; the flat one takes no smooth and no mask arguments)."""
-    pitch, hr, wr, ho, wo, out = _heat_blend_args(name, region, cells, cell, lut, alpha, down, out)
+def _heat_blend(name: str, region, cells, cell, lut, alpha, down, smooth, mask, mask_down, mask_thresh, out, window=None):
+    """The body of region_heat_blend, region_heat_blend_px, region_heat_thumb and region_heat_window: the px checks, then toad_<name>_u8 (the first two
+    launch the same kernel; the flat one takes no smooth and no mask arguments; the window one takes (wx, wy) and a mask plane of any extent)."""
+    pitch, hr, wr, ho, wo, out, window = _heat_blend_args(name, region, cells, cell, lut, alpha, down, out, window)
     if not isinstance(smooth, (bool, int)) or smooth not in (0, 1):
         raise ValueError(f"{name}: smooth must be False or True, got {smooth!r}")
     mp, hm, wm, md = 0, 0, 0, 0
@@ -1626,7 +1647,7 @@ def _heat_blend(name: str, region, cells, cell, lut, alpha, down, smooth, mask, 
         if mask_down not in SEG_DOWNS or isinstance(mask_down, bool) or mask_down % down:
             raise ValueError(f"{name}: mask_down must be one of {SEG_DOWNS} and a multiple of down = {down}, got {mask_down!r}")
         _u8_arg(name, "mask_thresh", mask_thresh)
-        if (hm, wm) != (hr // mask_down, wr // mask_down):
+        if window is None and (hm, wm) != (hr // mask_down, wr // mask_down):
             raise ValueError(f"{name}: expected a uint8 [Hr // mask_down, Wr // mask_down] = [{hr // mask_down},{wr // mask_down}] mask, got "
                              f"{tuple(mask.shape)}")
         md = mask_down
@@ -1636,7 +1657,7 @@ def _heat_blend(name: str, region, cells, cell, lut, alpha, down, smooth, mask, 
         return out
     px = () if name == "region_heat_blend" else (int(smooth), _p(mask), mp, hm, wm, md, mask_thresh if mask is not None else 0)
     entry = f"toad_{name}_u8"
-    _lib.check(getattr(_lib.load(), entry)(_p(region), pitch, hr, wr, _p(cells), cells.shape[0], cells.shape[1], cell, _p(lut), alpha, down, *px, _p(out),
+    _lib.check(getattr(_lib.load(), entry)(_p(region), pitch, hr, wr, *(window or ()), _p(cells), cells.shape[0], cells.shape[1], cell, _p(lut), alpha, down, *px, _p(out),
                                            _row_pitch(out, 3 * wo), _stream()), entry)
     return out
 
@@ -1669,6 +1690,20 @@ def region_heat_thumb(region: torch.Tensor, cells: torch.Tensor, cell: int, lut:
     exceed ``cell`` (a canvas box must lie in one cell: ValueError before any launch), and ``mask_down`` is a multiple of ``down``, so it lies in
     down .. 32. One launch, no synchronisation; an empty canvas launches nothing."""
     return _heat_blend("region_heat_thumb", region, cells, cell, lut, alpha, down, smooth, mask, mask_down, mask_thresh, out)
+
+
+def region_heat_window(region: torch.Tensor, window, cells: torch.Tensor, cell: int, lut: torch.Tensor, alpha: int, down: int, smooth: bool = False,
+                       mask=None, mask_down=None, mask_thresh: int = 0, out=None) -> torch.Tensor:
+    """The canvas of a WINDOW of a larger image (toad_region_heat_window_u8; the definition is in include/toad_hip.h): ``region`` [Hr,Wr,3] is the window
+    whose pixel (0, 0) is pixel ``window`` = (wx, wy) of the image - "the slide" - that ``cells`` int32 [Gy,Gx] and the ``mask`` plane describe. The uint8
+    [Hr // down, Wr // down, 3] written is byte for byte rows wy // down .. and columns wx // down .. of the slide's canvas under region_heat_blend_px
+    (``down`` in 1, 2, 4) or region_heat_thumb (``down`` in 8, 16, 32, not above ``cell``): a tent neighbour inside the table contributes its value also
+    where it lies outside the window, so canvases put together from strips or blocks show no seams. wx and wy are non-negative multiples of
+    max(4, down), wx + Wr < 2^30, and the table holds the window: ceil((wy + Hr) / cell) <= Gy, ceil((wx + Wr) / cell) <= Gx. ``mask`` is the slide's
+    plane, uint8 of any extent (a pixel outside it is not tissue), ``mask_down`` and ``mask_thresh`` as for region_heat_blend_px. ``out`` may be a view
+    into the slide's canvas at any pitch. ValueError for anything else, before the library is called. One launch, no synchronisation; a canvas with no
+    rows or no columns launches nothing."""
+    return _heat_blend("region_heat_window", region, cells, cell, lut, alpha, down, smooth, mask, mask_down, mask_thresh, out, window)
 
 
 def maxpool3x3s2_nhwc(x: torch.Tensor) -> torch.Tensor:

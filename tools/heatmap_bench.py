@@ -45,8 +45,22 @@ its alternation of the arms inside one process, warm-up of every arm, its four s
     whole call: host arithmetic, the index upload and the launches), and the launches alone (heat_cells [+ heat_cells_blur] + the blend) - canvas_blur
     is checked to differ from canvas_plain and launches_blur to equal canvas_blur bit for bit. Default output profiles/heatmap_blur_bench.jsonl.
 
+  window (--window): what rendering a slide window by window (ops.region_heat_window, toad_region_heat_window_u8) costs. Same slides, table and colours;
+    the cell table is built once per run, the mask of each slide is the (plane, t) of tissue.segment_tissue at down 16 (down = 1) or 32 (down = 16),
+    median 7, threshold 8. Flat and with smooth + mask, at down = 1 and 16. Arms, alternated in one process on the rotating slides, each into a canvas
+    allocated once:
+      W0    the entry that was there before (ops.region_heat_blend_px / ops.region_heat_thumb), the whole slide;
+      W1    ops.region_heat_window, the whole slide as window (0, 0): the same kernel with the two offsets zero;
+      W4    the slide as 4 full-width strips of 1024 rows, W16 as a 4 x 4 grid of 1024 x 2048 blocks, through ops.region_heat_window: 4 and 16 launches.
+    W1, W4 and W16 are checked torch.equal to W0 on every slide before anything is timed. w_over_w0 = median over median next to w0_spread, W0's own
+    interleaved-halves spread: the margin for W1 / W0. W4 and W16 add launches and are reported without a bar. With TOAD_HIP_LIB=<a library built from
+    the parent commit's sources> (tools/ab/select_lib.py), which does not export the window entry, only W0 is timed (kind ..._w0, lib = its tag): the
+    same arm on the kernels as they were. --w0-only times W0 alone on this tree's library as well, so that the two processes run the same arms in the
+    same order: those two are the lines to set side by side (W0 next to the window arms runs in another cache and clock state than W0 alone). Default
+    output profiles/heatmap_window_bench.jsonl.
+
 Prints one JSON line per result; --out FILE keeps them.
-usage: heatmap_bench.py [--launches --arm A|B --down D] [--px | --thumb | --blur] [--seconds S] [--out FILE]"""
+usage: heatmap_bench.py [--launches --arm A|B --down D] [--px | --thumb | --blur | --window [--w0-only]] [--seconds S] [--out FILE]"""
 import argparse
 import json
 import os
@@ -331,6 +345,75 @@ def blur(seconds):
     return res
 
 
+def window(seconds, w0_only=False):
+    """The --window figures: one record per (down, flat | smooth + mask)."""
+    import ctypes
+    from toad_amd import _lib
+    name = "toad_region_heat_window_u8"
+    parent = not hasattr(ctypes.CDLL(_lib.LIB_PATH), name)          # a library from before the entry: W0 alone
+    if parent:
+        if tools.ab.select_lib.TAG == "(shipped)":
+            raise SystemExit(f"heatmap_bench: the shipped library does not export {name}: rebuild (python -m toad_amd.build --force)")
+        del _lib.SIGNATURES[name]                                    # this process only: the loader binds every symbol it knows
+    dev = torch.device("cuda:0")
+    slides, table, lut = setup(dev)
+    cells = ops.heat_cells(table, CELL, (0, 0), (TILE, TILE), (STRIDE, STRIDE), (NX, NY), (HR, WR))
+    strips = [(0, y, WR, HR // 4) for y in range(0, HR, HR // 4)]
+    blocks = [(x, y, WR // 4, HR // 4) for y in range(0, HR, HR // 4) for x in range(0, WR, WR // 4)]
+    res = []
+    for down in (1, 16):
+        md = MASK_DOWN if down == 1 else THUMB_MASK_DOWN
+        masks = {s.data_ptr(): segment_tissue(s, md, 7, 8) for s in slides}
+        whole = ops.region_heat_thumb if down in ops.HEAT_THUMB_DOWNS else ops.region_heat_blend_px
+        out = torch.empty((HR // down, WR // down, 3), dtype=torch.uint8, device=dev)
+        for both in (False, True):
+            def kw(r):
+                if not both:
+                    return {}
+                m, t = masks[r.data_ptr()]
+                return dict(smooth=True, mask=m, mask_down=md, mask_thresh=t)
+
+            def w0(r):
+                return whole(r, cells, CELL, lut, ALPHA, down, out=out, **kw(r))
+
+            def pieces(parts):
+                def run(r):
+                    k = kw(r)
+                    for wx, wy, w, h in parts:
+                        ops.region_heat_window(r[wy:wy + h, wx:wx + w], (wx, wy), cells, CELL, lut, ALPHA, down,
+                                               out=out[wy // down:(wy + h) // down, wx // down:(wx + w) // down], **k)
+                    return out
+                return run
+
+            arms = {"W0": Rotating(w0, slides)}
+            if not parent and not w0_only:
+                cand = {"W1": pieces([(0, 0, WR, HR)]), "W4": pieces(strips), "W16": pieces(blocks)}
+                for s_ in slides:
+                    want = w0(s_).clone()
+                    for k, fn in cand.items():
+                        out.fill_(0x7F)
+                        if not torch.equal(fn(s_), want):                      # a wrong arm must not produce a quoted ratio
+                            raise SystemExit(f"heatmap_bench: {k} differs from W0 at down = {down}, smooth + mask = {both}: nothing is timed")
+                arms.update({k: Rotating(fn, slides) for k, fn in cand.items()})
+            t, iters = alternate(arms, seconds)
+            a = t["W0"]
+            a1, a2 = median(a[0::2]), median(a[1::2])
+            nbytes = 3 * HR * WR + 3 * (HR // down) * (WR // down)
+            rec = dict(kind="resident_heatmap_window" + ("_w0" if parent or w0_only else ""), lib=tools.ab.select_lib.TAG, region=[HR, WR], tile=TILE, stride=STRIDE,
+                       cell=CELL, down=down, alpha=ALPHA, smooth_and_mask=both, mask_down=md if both else None, moved_bytes=nbytes, slides_rotated=len(slides),
+                       rounds=len(a), iters_per_round=iters, ms={k: round(median(v), 5) for k, v in t.items()},
+                       ms_min={k: round(min(v), 5) for k, v in t.items()}, ms_max={k: round(max(v), 5) for k, v in t.items()},
+                       moved_tbps={k: round(nbytes / median(v) / 1e9, 3) for k, v in t.items()}, w0_halves_ms=[round(a1, 5), round(a2, 5)],
+                       w0_spread=round(abs(a1 - a2) / median(a), 4))
+            if not parent and not w0_only:
+                over = {k: round(median(t[k]) / median(a), 4) for k in ("W1", "W4", "W16")}
+                rec.update(w_over_w0=over, w1_exceeds_w0_beyond_spread=bool(over["W1"] > 1.0 + rec["w0_spread"]), launches={"W0": 1, "W1": 1, "W4": 4, "W16": 16},
+                           windows_equal_w0=True)
+            res.append(rec)
+        del out
+    return res
+
+
 def launches(arm, down, calls=4):
     """`calls` calls of one arm on rotating slides, no warm-up (run under rocprofv3 --kernel-trace --stats: every count divides by `calls`)."""
     dev = torch.device("cuda:0")
@@ -351,12 +434,16 @@ def main():
     ap.add_argument("--px", action="store_true")
     ap.add_argument("--thumb", action="store_true")
     ap.add_argument("--blur", action="store_true")
+    ap.add_argument("--window", action="store_true")
+    ap.add_argument("--w0-only", action="store_true")
     ap.add_argument("--seconds", type=float, default=3.0)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     if a.blur and not a.out:
         a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "heatmap_blur_bench.jsonl")
-    res = launches(a.arm, a.down) if a.launches else blur(a.seconds) if a.blur else thumb(a.seconds) if a.thumb else resident(a.seconds, a.px)
+    if a.window and not a.out:
+        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "heatmap_window_bench.jsonl")
+    res = launches(a.arm, a.down) if a.launches else window(a.seconds, a.w0_only) if a.window else blur(a.seconds) if a.blur else thumb(a.seconds) if a.thumb else resident(a.seconds, a.px)
     lines = [json.dumps(r) for r in res]
     print("\n".join(lines), flush=True)
     if a.out:
