@@ -193,7 +193,11 @@ int toad_gated_pool_bwd_f32(const float *Pa, const float *Pb, int64_t ldp, const
 /* models/model_toad.py:99-107:
  *   Mcat[t,:] = [M[t,:], sex];  logits = Mcat[0] Wcls^T + bcls;  site_logits = Mcat[1] Wsite^T + bsite
  *   Y_prob/site_prob = softmax;  Y_hat/site_hat = argmax (first maximal index, as torch.topk).
- * Wcls [C,L+1], Wsite [2,L+1]; sex points at ONE device float. C <= 1024. */
+ * Wcls [C,L+1], Wsite [2,L+1]; sex points at ONE device float. 1 <= L <= 8192 and 1 <= C <= 1024 for every heads entry
+ * point; toad_heads_bwd_f32 and toad_heads_ce_fused_f32 also want C <= L. Anything else is TOAD_ESHAPE. The forward and the
+ * fused entry are one workgroup with Mcat in LDS: at L = 8192 they ask for 65,544 and 65,584 bytes of dynamic LDS, which a
+ * gfx950 launch carries without a function attribute (sharedMemPerBlock is 163,840 there); both limits run in
+ * tests/test_gpu_step_tail.py. */
 int toad_heads_fwd_f32(const float *M, const float *sex,
                        const float *Wcls, const float *bcls, const float *Wsite, const float *bsite,
                        float *Mcat, float *logits, float *Y_prob, int64_t *Y_hat,
