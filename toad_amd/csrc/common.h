@@ -19,6 +19,9 @@ void set_error(const char *fmt, ...);
 int check_launch(const char *what);
 void note_fallback_launch();      // an exact-fp32 fallback GEMM kernel was launched (toad_fallback_launches, capi.hip)
 
+// a host-side sequence of calls that each return a TOAD_* code: the first failure ends the sequence with its code
+#define TOAD_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
+
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
@@ -114,7 +117,7 @@ enum { TOAD_X_F32 = 0,      // fp32 [N][1024]
        TOAD_X_F16 = 1,      // fp16 [N][1024] (feature stores kept in half precision)
        TOAD_X_PT = 2 };     // plane-tiled two-piece form written by toad_bag_prepare_f32 (csrc/gemm_pt.inc)
 
-// ---- host-side launchers of the fp16 two-piece GEMMs (defined in gemm_f32.hip next to their kernels; used by step.hip) ----
+// ---- host-side launchers of the fp16 two-piece GEMMs (defined in gemm_f32.hip next to their kernels; used by step.hip and conv.hip) ----
 struct H2Operand { const float *src; int64_t sn, sk; int64_t N, K; unsigned short *planes; float *binv; };   // B[n,k] = src[n*sn + k*sk]
 struct H2Pool { const float *a_raw, *stats, *dM; int T; };                                                   // recomputed pooling addend (T = 0: none)
 struct EpiScalars { int relu; float mask_scale; DropArgs drop; int stagger = 0; };                           // epilogue scalars of every NT kernel; stagger: gemm_h2.inc
@@ -145,19 +148,18 @@ int launch_pool_bwd(const float *Pa, const float *Pb, int64_t ldp, const float *
                     const float *M, const float *dM, const float *dA_ext, float *dPa, float *dPb, int64_t ldd, float *dH, float *dWc, float *dbc,
                     float beta, float *dp_amax, bool zero_amax, void *ws, size_t ws_bytes, int64_t N, int L, int D, int T, float drop_p,
                     uint64_t seed_a, uint64_t seed_b, hipStream_t st);
-// the extractor's GEMMs with tensor-wide abs-max scalars threaded from producer to consumer (gemm_f32.hip; used by conv.hip)
-int launch_gmax(const float *x, int64_t n, float *out, hipStream_t st, const char *what);                   // out[0] = max |x| (zeroed here)
-int ext_linear(const float *X, const float *x_gmax, const float *W, const float *bias, const float *residual, float *Y, float *y_gmax,
-               int64_t M, int64_t K, int64_t N, int act, void *ws, size_t ws_bytes, hipStream_t st, const char *what);
-int ext_conv_nhwc(const float *X, const float *x_gmax, const float *Wf, const float *bias, const float *residual, float *Y, float *y_gmax, int B,
-                  int H, int W, int Cin, int kh, int kw, int stride, int pad, int Cout, int act, void *ws, size_t ws_bytes, hipStream_t st,
-                  const char *what);
-int ext_stem_conv(const float *Xs, const float *x_gmax, const float *Wf, const float *bias, float *Y, float *y_gmax, int B, int Ho, int Wo, int act,
-                  void *ws, size_t ws_bytes, hipStream_t st, const char *what, bool pooled = false);
-bool stem_nchw_pool_ok(int H, int W);                 // the stem + pool may run straight from the NCHW tiles (stem_halo.inc)
-int ext_stem_nchw_pool(const float *X, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W, void *ws, size_t ws_bytes,
-                       hipStream_t st, const char *what);
-bool stem_pool_ok(int Ho, int Wo, int act);           // the stem may take the 3x3/2 max-pool into its epilogue (gemm_stream.inc)
+// ---- the seam between the MIL unit (gemm_f32.hip) and the extractor's (conv.hip): the extractor's wide GEMMs run on the MIL 256x256 kernel through
+// launch_split_h2 + launch_nt_h2 above; what its shapes leave over takes the exact-fp32 128x128 kernel. Each of the three sets its own unit's kernel
+// attributes. (Hidden: a library-internal call, not one of the library's dynamic symbols.)
+__attribute__((visibility("hidden")))
+int launch_nt(const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc, int64_t M, int64_t N, int64_t K, const float *bias,
+              EpiScalars es, const float *addend, const float *mask_src, void *ws, hipStream_t st, const char *what);
+// the workspace of a per-op GEMM entry (toad_linear_ws_bytes): NULL is allowed (exact-fp32 fallback), a given one must be large enough and aligned
+static inline int check_ws(void *ws, size_t ws_bytes, int64_t M, int64_t N, int64_t K, const char *what) {
+    if (ws && ws_bytes < toad_linear_ws_bytes(M, N, K)) { set_error("%s: workspace too small", what); return TOAD_EWORKSPACE; }
+    if (ws && !aligned16(ws)) { set_error("%s: workspace must be 16-byte aligned", what); return TOAD_EALIGN; }
+    return TOAD_OK;
+}
 // batched pooling launches of the ragged multi-slide step (gated_pool.hip): blockIdx.y = slide, row ranges from the DEVICE array seg_dev [B+1]
 size_t pool_batch_ws_bytes(int B, int L, int D, int T);
 int launch_pool_fwd_batch(const float *Pa, const float *Pb, int64_t ldp, const float *H, const float *Wc, const float *bc, float *A_raw, float *M,

@@ -3,17 +3,36 @@
 //
 // Design for gfx950: activations live in HBM as NHWC fp32, so every convolution is the NT product the MIL trunk
 // already runs — Y[M, Cout] = act(cols[M, K] . Wf[Cout, K]^T + bf (+ residual)) with M = B*Ho*Wo pixels — in the
-// same fp16 two-piece MFMA arithmetic (gemm_f32.hip; fp32-accurate, so the extractor keeps the 1e-4 parity bar):
+// same fp16 two-piece MFMA arithmetic (h2_arith.h; fp32-accurate, so the extractor keeps the 1e-4 parity bar):
 // Cout >= 256 on the persistent 256x256 kernel, narrower layers, short-K residual expansions, the stem and the 3x3
 // convolutions on the kernels of gemm_stream.inc (A streamed through registers; stride-1 3x3 with the activation halo
 // in LDS) - those never materialise cols. Batch-norm (eval form) is folded into Wf / bf on the host; ReLU and the
 // bottleneck's residual add ride in the GEMM epilogue. 1x1 stride-1 convolutions need no data movement at all (cols ==
 // the NHWC activation); the explicit gathers below (16-B lanes, coalesced on the channel dimension) remain for strided
 // 1x1 convolutions, for small batches of the 256-channel 3x3, and as API entry points.
+//
+// This is the extractor's translation unit (a launcher and its own kernels must share a TU without -fgpu-rdc), organised as:
+//   h2_arith.h         the two-piece operand arithmetic and the persistent-grid constants, shared with the MIL unit (gemm_f32.hip)
+//   gemm_narrow.inc    the narrow-N weight-plane format, convolution geometry and gather modes
+//   gemm_stream.inc    narrow-N kernels: A streamed through registers; 3x3 convolutions with the activation halo in LDS
+//   stem_halo.inc      stem + ReLU + max-pool as one kernel, straight from fp32 NCHW / uint8 NHWC tiles or a uint8 region
+//   this file          the gathers and pools, the launchers of the kernels above with their kernel attributes (ext_cfg), the GEMM layer ext_* with
+//                      the tensor-wide abs-max scalars, the 43-convolution sequencer trunc_fwd, the extern "C" entry points of include/toad_hip.h
+// The wide GEMMs (Cout >= 256) are the one thing it takes from the MIL unit: launch_split_h2 / launch_nt_h2 and, as the last resort, launch_nt
+// (common.h), each of which sets its own unit's kernel attributes.
 #include "common.h"
+#include "h2_arith.h"
 #include "stem_u8.h"
 
+#include <algorithm>
+#include <mutex>
+#include <type_traits>
+
 namespace toad {
+
+#include "gemm_narrow.inc"
+#include "gemm_stream.inc"
+#include "stem_halo.inc"
 
 // ---- gathers ---------------------------------------------------------------------------------------------------
 // cols[m, (ky*kw + kx)*C + c] = X[b, oy*s - p + ky, ox*s - p + kx, c]  (0 outside), m = (b*Ho + oy)*Wo + ox.
@@ -231,6 +250,267 @@ __global__ __launch_bounds__(256) void tiles_u8_nhwc_to_nchw_kernel(const unsign
     }
 }
 
+// ---- host side of the extractor's GEMMs ------------------------------------------------------------------------
+// Residual GEMMs with a reduction of at most this many elements run on the narrow (streamed) tiles whatever their width: measured
+// (tools/gemm_shape_bench.py, same box) M=262144 K=64 N=256 +residual 170 -> 133 us; K=128 equal, K=256 slower (A is re-split per
+// 128-column tile)
+constexpr int kNarrowResKmax = 64;
+// One-time initialisation of this translation unit: the attributes (dynamic LDS sizes) of the extractor's own kernels, completed before the first
+// launch of any of them from any thread (launch_narrow_t, stem_pool_from_tiles). The MIL kernels' attributes are gemm_f32.hip's (cfg()).
+static std::once_flag g_ext_cfg_once;
+static void ext_cfg() {
+    std::call_once(g_ext_cfg_once, [] {
+#define TOAD_ATTR(K, BYTES) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, BYTES)
+        TOAD_ATTR((gemm_nt_h2_stream_kernel<2, 2, GATHER_NONE>), (StreamCfg<2, 2>::SMEM));
+        TOAD_ATTR((gemm_nt_h2_stream_kernel<2, 4, GATHER_NONE>), (StreamCfg<2, 4>::SMEM));
+        TOAD_ATTR((gemm_nt_h2_stream_kernel<2, 2, GATHER_CONV>), (StreamCfg<2, 2>::SMEM));
+        TOAD_ATTR((gemm_nt_h2_stream_kernel<2, 4, GATHER_CONV>), (StreamCfg<2, 4>::SMEM));
+        TOAD_ATTR((gemm_nt_h2_stream_kernel<2, 2, GATHER_STEM>), (StreamCfg<2, 2>::SMEM));
+        TOAD_ATTR((gemm_nt_h2_stream_kernel<2, 2, GATHER_STEM_POOL>), (StreamCfg<2, 2>::SMEM + STEM_POOL_LDS));
+        TOAD_ATTR(stem_halo_pool_kernel<SH_F32>, SH_SMEM);
+        TOAD_ATTR(stem_halo_pool_kernel<SH_U8>, SH_SMEM);
+        TOAD_ATTR(stem_halo_pool_kernel<SH_U8_REGION>, SH_SMEM);
+        TOAD_ATTR(stem_halo_pool_kernel<SH_U8_REGION_BOX2>, SH_SMEM);
+        TOAD_ATTR(conv3x3_h2_halo_kernel<2>, 160 * 1024);
+        TOAD_ATTR(conv3x3_h2_halo_kernel<4>, 160 * 1024);
+#undef TOAD_ATTR
+    });
+}
+
+// max |x| over n floats -> out[0] (bit pattern of a non-negative float, zeroed here): the tensor-wide abs-max a narrow / extractor GEMM
+// scales its A operand with when no producer handed one over (the per-op entry points; inside toad_resnet50_trunc_fwd_f32 every
+// producer emits it)
+__global__ __launch_bounds__(256) void gmax_kernel(const float *__restrict__ x, int64_t n4, float *__restrict__ out) {
+    __shared__ float s[4];
+    float mx = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256)
+        mx = __builtin_fmaxf(mx, h2_absmax4(__builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(x) + i)));
+    mx = h2_wave_max(mx);
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) h2_atomic_amax(out, __builtin_fmaxf(__builtin_fmaxf(s[0], s[1]), __builtin_fmaxf(s[2], s[3])));
+}
+int launch_gmax(const float *x, int64_t n, float *out, hipStream_t st, const char *what) {
+    (void)hipMemsetAsync(out, 0, sizeof(float), st);
+    int64_t grid = (n / 4 + 255) / 256;
+    if (grid > 2048) grid = 2048;
+    if (grid < 1) grid = 1;
+    hipLaunchKernelGGL(gmax_kernel, dim3((unsigned)grid), dim3(256), 0, st, x, n / 4, out);
+    return check_launch(what);
+}
+
+// C[M,N] = act(A' W^T + bias + addend) with N <= 128 on the narrow kernels; A' = A[M,K] (MODE = GATHER_NONE) or the implicit
+// im2col of the NHWC activation A described by cg. `ws` as for launch_nt (planes and inverse scales live behind the slab area).
+// a_gmax: device scalar max |A| (of the whole activation); y_gmax (optional): receives max |C| by atomic max (zeroed by the caller).
+template <int RA, int NB, int MODE>
+static int launch_narrow_t(const float *A, int64_t lda, const float *a_gmax, const float *W, int64_t ldw, float *C, int64_t ldc, int64_t M, int64_t N,
+                           int64_t K, const float *bias, int relu, const float *addend, const ConvGeom &cg, float *y_gmax, void *ws,
+                           hipStream_t st, const char *what) {
+    ext_cfg();
+    char *w = reinterpret_cast<char *>(ws) + (size_t)PB_GRID * PB * PB * sizeof(float);
+    constexpr int TNW = NB * 32;         // tile width (RA only names the instantiation; the streamed kernels run 64-row wave tiles)
+    const int tiles_n = (int)((N + TNW - 1) / TNW);
+    unsigned short *planes = reinterpret_cast<unsigned short *>(w);
+    float *binv;
+    // the streamed kernel walks an implicit convolution's k-stages channel-chunk outer, tap inner (gemm_stream.inc): its planes are split in that order
+    const int taps = MODE == GATHER_CONV ? (int)(K / cg.C) : 1;
+    const int nk = (int)(K / BK), nkp = (nk + 1) & ~1;                  // the streamed kernel walks k-stages in pairs: an odd count gets a zero stage
+    binv = reinterpret_cast<float *>(w + (size_t)tiles_n * TNW * (size_t)nkp * BK * 4);
+    hipLaunchKernelGGL(split_planes_narrow_h2_kernel<NB>, dim3((tiles_n * TNW + 3) / 4), dim3(256), 0, st, W, ldw, planes, binv, (int)N, (int)K, tiles_n,
+                       taps, cg.C, nkp);
+    if (int rc = check_launch(what)) return rc;
+    if (MODE == GATHER_CONV) {       // 3x3 / 1 / 1 with whole 256-pixel row blocks: the activation halo lives in LDS (gemm_stream.inc)
+        const int W = cg.W, H = cg.H;
+        const bool shape = cg.kw == 3 && K == 9 * (int64_t)cg.C && cg.stride == 1 && cg.pad == 1 && cg.Ho == H && cg.Wo == W && W >= 8 && W <= 128 &&
+                           (W & (W - 1)) == 0 && H % (256 / W) == 0 && cg.C % BK == 0 && M % 256 == 0;
+        if (shape) {
+            using HCfg = HaloCfg<NB>;
+            const int hb = HCfg::halo_bytes(W);
+            hipLaunchKernelGGL(conv3x3_h2_halo_kernel<NB>, dim3(2 * PB_GRID), dim3(HCfg::THREADS), HCfg::smem(W), st, A, a_gmax, planes, binv, C, ldc, (int)M, (int)N,
+                               (int)K, bias, relu, addend, cg, y_gmax, (int)(M / 256), tiles_n, hb);
+            return check_launch(what);
+        }
+    }
+    // A streamed through registers (gemm_stream.inc): wave tile 64 x 64 / 64 x 128
+    constexpr int SRA = 2;
+    using SCfg = StreamCfg<SRA, NB>;
+    const int stiles_m = (int)((M + SCfg::TM - 1) / SCfg::TM);
+    if constexpr (MODE == GATHER_STEM_POOL) {        // C = the POOLED output; every workgroup a contiguous range of row-pair tiles (ext_stem_conv checked the geometry)
+        hipLaunchKernelGGL((gemm_nt_h2_stream_kernel<SRA, NB, MODE>), dim3(std::min(stiles_m, SCfg::WG_PER_CU * PB_GRID)), dim3(SCfg::THREADS), SCfg::SMEM + STEM_POOL_LDS, st,
+                           A, lda, a_gmax, planes, binv, C, ldc, (int)M, (int)N, (int)K, bias, relu, addend, cg, y_gmax, stiles_m, tiles_n);
+        return check_launch(what);
+    }
+    hipLaunchKernelGGL((gemm_nt_h2_stream_kernel<SRA, NB, MODE>), dim3(SCfg::WG_PER_CU * PB_GRID), dim3(SCfg::THREADS), SCfg::SMEM, st, A, lda, a_gmax, planes, binv,
+                       C, ldc, (int)M, (int)N, (int)K, bias, relu, addend, cg, y_gmax, stiles_m, tiles_n);
+    return check_launch(what);
+}
+
+static bool narrow_ok(int64_t M, int64_t N, int64_t K, int64_t ldc, const float *bias, const float *addend, void *ws) {
+    const bool wide_ok = addend && K <= kNarrowResKmax;       // residual GEMMs with a short reduction: epilogue-bound, see DESIGN 10
+    return ws && (N <= 128 || wide_ok) && N % 4 == 0 && K % BK == 0 && ldc % 4 == 0 && M < (1ll << 31) &&
+           (!bias || aligned16(bias)) && (!addend || aligned16(addend));
+}
+
+// ---- the extractor's GEMMs (models/resnet_custom.py:19-119 as NHWC GEMMs, conv.hip): Y = act(X' W^T + bias + residual) -------------
+// x_gmax: device scalar max |X| of the whole activation (NULL: measured here, one extra read); y_gmax: device scalar that receives
+// max |Y| by atomic max (the caller zeroed it; NULL: not wanted). One tensor-wide power-of-two scale per activation: gemm_narrow.inc.
+static float *ext_scratch_scalar(void *ws, int64_t M, int64_t N, int64_t K) {          // a float inside the workspace's abs-max area
+    const size_t tiles_n = (size_t)((N + PB - 1) / PB), kpad = (size_t)((K + 2 * BK - 1) / (2 * BK) * (2 * BK));        // as toad_linear_ws_bytes
+    return reinterpret_cast<float *>(reinterpret_cast<char *>(ws) + (size_t)PB_GRID * PB * PB * sizeof(float) + tiles_n * PB * kpad * 6 + tiles_n * PB * sizeof(float)) + 8;
+}
+int ext_linear(const float *X, const float *x_gmax, const float *W, const float *bias, const float *residual, float *Y, float *y_gmax,
+                     int64_t M, int64_t K, int64_t N, int act, void *ws, size_t ws_bytes, hipStream_t st, const char *what) {
+    if (!X || !W || !Y) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (act != TOAD_ACT_NONE && act != TOAD_ACT_RELU) { set_error("%s: bad act %d", what, act); return TOAD_EINVAL; }
+    if (M <= 0 || N <= 0 || K <= 0) { set_error("%s: non-positive dimension", what); return TOAD_EINVAL; }
+    if (residual && (N % 4 != 0 || !aligned16(residual))) { set_error("%s: residual needs N %% 4 == 0 and 16-byte alignment", what); return TOAD_ESHAPE; }
+    if (int rc = check_ws(ws, ws_bytes, M, N, K, what)) return rc;
+    EpiScalars es{act == TOAD_ACT_RELU, 1.f, make_drop(0.f, 0)};
+    const bool narrow = narrow_ok(M, N, K, N, bias, residual, ws) && (uint64_t)M * K * 4 < (1ull << 32);
+    const bool big = !narrow && ws && h2_nt_ok(M, N, K, K, N);
+    if ((narrow || big) && !x_gmax) {
+        float *g = ext_scratch_scalar(ws, M, N, K);
+        if (int rc = launch_gmax(X, M * K, g, st, what)) return rc;
+        x_gmax = g;
+    }
+    if (narrow) {
+        const ConvGeom none{0, 0, 0, 0, 0, 0, 0, 0};
+        if (N <= 64) return launch_narrow_t<2, 2, GATHER_NONE>(X, K, x_gmax, W, K, Y, N, M, N, K, bias, es.relu, residual, none, y_gmax, ws, st, what);
+        return launch_narrow_t<1, 4, GATHER_NONE>(X, K, x_gmax, W, K, Y, N, M, N, K, bias, es.relu, residual, none, y_gmax, ws, st, what);
+    }
+    if (big) {
+        // wide outputs (1x1 expansions / downsamples, the 256-channel 3x3 after im2col): the persistent 256x256 kernel of the MIL path
+        // with the tensor-wide scalars in place of its per-block abs-max arrays (stride 0)
+        if (!aligned16(X) || !aligned16(W) || !aligned16(Y) || (bias && !aligned16(bias))) { set_error("%s: pointers must be 16-byte aligned", what); return TOAD_EALIGN; }
+        char *w = reinterpret_cast<char *>(ws);
+        float *slabs = reinterpret_cast<float *>(w);
+        w += (size_t)PB_GRID * PB * PB * sizeof(float);
+        unsigned short *planes = reinterpret_cast<unsigned short *>(w);
+        w += h2_planes_bytes(N, K);
+        float *binv = reinterpret_cast<float *>(w);
+        const H2Operand op{W, K, 1, N, K, planes, binv};
+        if (int rc = launch_split_h2(&op, 1, nullptr, 0, st, what)) return rc;
+        // short reductions: a tile is a few k-steps of matrix work followed by 256-512 KB of epilogue traffic, and 256 workgroups in phase make
+        // the GEMM the SUM of the two. Spread the starts over one expected tile period (10 ns ticks: ~1.95 us per k-step, ~8 us per 256 KB of
+        // epilogue traffic; measured on the extractor's shapes, tools/ab/duo_ext_bench.py: -8..-10 % on the residual GEMMs, neutral from K = 1024)
+        if (K <= 512 && M >= 32 * 1024) es.stagger = (int)std::min<int64_t>((K / BK) * 195 + (residual ? 1600 : 800), 3000);
+        return launch_nt_h2(X, K, x_gmax, planes, binv, Y, N, M, N, K, bias, es, residual, nullptr, nullptr, H2Pool{nullptr, nullptr, nullptr, 0}, slabs,
+                            y_gmax, nullptr, st, what, TOAD_X_F32, 0, 0);
+    }
+    if (int rc = launch_nt(X, K, W, K, Y, N, M, N, K, bias, es, residual, nullptr, ws, st, what)) return rc;
+    return y_gmax ? launch_gmax(Y, M * N, y_gmax, st, what) : TOAD_OK;
+}
+
+int ext_conv_nhwc(const float *X, const float *x_gmax, const float *Wf, const float *bias, const float *residual, float *Y, float *y_gmax, int B,
+                        int H, int W, int Cin, int kh, int kw, int stride, int pad, int Cout, int act, void *ws, size_t ws_bytes, hipStream_t st,
+                        const char *what) {
+    if (!X || !Wf || !Y || !ws) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (act != TOAD_ACT_NONE && act != TOAD_ACT_RELU) { set_error("%s: bad act %d", what, act); return TOAD_EINVAL; }
+    if (B <= 0 || H <= 0 || W <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || pad > 8 || H + 8 >= 32768 || W + 8 >= 32768) { set_error("%s: bad geometry", what); return TOAD_ESHAPE; }
+    if (Cin <= 0 || Cin % BK != 0) { set_error("%s: Cin must be a multiple of %d (use toad_im2col_nhwc_f32 + toad_linear_act_res_fwd_f32 otherwise)", what, BK); return TOAD_ESHAPE; }
+    if (Cout <= 0 || Cout > 512 || Cout % 4 != 0) { set_error("%s: implicit path needs Cout <= 512, a multiple of 4 (use im2col + linear for wider layers)", what); return TOAD_ESHAPE; }
+    const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
+    if (Ho < 1 || Wo < 1) { set_error("%s: empty output", what); return TOAD_ESHAPE; }
+    const int64_t M = (int64_t)B * Ho * Wo, K = (int64_t)kh * kw * Cin;
+    if ((uint64_t)B * H * W * Cin * 4 >= (1ull << 31) || M >= (1ll << 31)) { set_error("%s: activation too large for 32-bit offsets (split the batch)", what); return TOAD_ESHAPE; }
+    if (!aligned16(X) || !aligned16(Wf) || !aligned16(Y)) { set_error("%s: pointers must be 16-byte aligned", what); return TOAD_EALIGN; }
+    if (int rc = check_ws(ws, ws_bytes, M, Cout, K, what)) return rc;
+    if (!narrow_ok(M, Cout <= 128 ? Cout : 128, K, Cout, bias, residual, ws)) { set_error("%s: bias / residual must be 16-byte aligned", what); return TOAD_EALIGN; }
+    if (!x_gmax) {
+        float *g = ext_scratch_scalar(ws, M, Cout, K);
+        if (int rc = launch_gmax(X, (int64_t)B * H * W * Cin, g, st, what)) return rc;
+        x_gmax = g;
+    }
+    const ConvGeom cg{H, W, Cin, Ho, Wo, kw, stride, pad};
+    if (Cout <= 64)
+        return launch_narrow_t<2, 2, GATHER_CONV>(X, 0, x_gmax, Wf, K, Y, Cout, M, Cout, K, bias, act == TOAD_ACT_RELU, residual, cg, y_gmax, ws, st, what);
+    return launch_narrow_t<1, 4, GATHER_CONV>(X, 0, x_gmax, Wf, K, Y, Cout, M, Cout, K, bias, act == TOAD_ACT_RELU, residual, cg, y_gmax, ws, st, what);
+}
+
+bool stem_pool_ok(int Ho, int Wo, int act) { return Wo == 128 && Ho > 0 && Ho % 2 == 0 && act == TOAD_ACT_RELU; }   // the stem may take the 3x3/2 max-pool into its epilogue (gemm_stream.inc)
+int ext_stem_conv(const float *Xs, const float *x_gmax, const float *Wf, const float *bias, float *Y, float *y_gmax, int B, int Ho, int Wo, int act,
+                  void *ws, size_t ws_bytes, hipStream_t st, const char *what, bool pooled = false) {
+    if (!Xs || !Wf || !Y || !ws) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (act != TOAD_ACT_NONE && act != TOAD_ACT_RELU) { set_error("%s: bad act %d", what, act); return TOAD_EINVAL; }
+    if (B <= 0 || Ho <= 0 || Wo <= 0) { set_error("%s: bad geometry", what); return TOAD_ESHAPE; }
+    const int Hs = Ho + 3, Ws = Wo + 3;
+    const int64_t M = (int64_t)B * Ho * Wo;
+    if ((uint64_t)B * Hs * Ws * 48 >= (1ull << 31) || M >= (1ll << 31)) { set_error("%s: batch too large for 32-bit offsets (split it)", what); return TOAD_ESHAPE; }
+    if (!aligned16(Xs) || !aligned16(Wf) || !aligned16(Y)) { set_error("%s: pointers must be 16-byte aligned", what); return TOAD_EALIGN; }
+    if (int rc = check_ws(ws, ws_bytes, M, 64, 192, what)) return rc;
+    if (!narrow_ok(M, 64, 192, 64, bias, nullptr, ws)) { set_error("%s: bias must be 16-byte aligned", what); return TOAD_EALIGN; }
+    if (!x_gmax) {
+        float *g = ext_scratch_scalar(ws, M, 64, 192);
+        if (int rc = launch_gmax(Xs, (int64_t)B * Hs * Ws * 12, g, st, what)) return rc;
+        x_gmax = g;
+    }
+    const ConvGeom cg{Hs, Ws, 12, Ho, Wo, 0, 0, 0};
+    if (pooled) {
+        // the 3x3/2 max-pool in the stem's epilogue (gemm_stream.inc): a tile = two whole image rows, ReLU outputs
+        if (!stem_pool_ok(Ho, Wo, act)) { set_error("%s: the pooled stem needs Wo = 128, an even Ho and ReLU", what); return TOAD_ESHAPE; }
+        return launch_narrow_t<2, 2, GATHER_STEM_POOL>(Xs, 0, x_gmax, Wf, 192, Y, 64, M, 64, 192, bias, 1, nullptr, cg, y_gmax, ws, st, what);
+    }
+    return launch_narrow_t<2, 2, GATHER_STEM>(Xs, 0, x_gmax, Wf, 192, Y, 64, M, 64, 192, bias, act == TOAD_ACT_RELU, nullptr, cg, y_gmax, ws, st, what);
+}
+
+// The stem + ReLU + 3x3/2 max-pool straight from the tiles (stem_halo.inc): no space-to-depth image, no fragment loads from global memory. norm == NULL: fp32 NCHW
+// tiles; otherwise uint8 NHWC tiles [B, H, 256, 3] and the six normalisation constants (stem_u8.h), checked before any device work. rg != NULL: the uint8 tiles
+// are read by origin from rg->region (X is not used; no alignment requirement on the region); with shrink == 2 tile b is the (2 H, 512) footprint at its origin,
+// box-filtered by the window loader (H, W stay the network tile's).
+bool stem_nchw_pool_ok(int H, int W) { return W == 256 && H >= 4 && H % 4 == 0; }     // the shapes it takes
+static int stem_pool_from_tiles(const void *X, bool u8, const float *norm, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W, void *ws,
+                                size_t ws_bytes, hipStream_t st, const char *what, const RegionSrc *rg = nullptr, int shrink = 1) {
+    if (rg) X = rg->region;
+    if (!X || (u8 && !norm) || !Wf || !Yp || !ws || (rg && !rg->origins)) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (B <= 0 || !stem_nchw_pool_ok(H, W)) {
+        set_error("%s: needs W = 256 and H %% 4 == 0 (other tiles: %stoad_stem_s2d_nchw_f32 + toad_stem_conv_s2d_f32 + toad_maxpool3x3s2_nhwc_f32)", what,
+                  rg ? "toad_tiles_u8_region_to_nchw_f32 + " : u8 ? "toad_tiles_u8_nhwc_to_nchw_f32 + " : "");
+        return TOAD_ESHAPE;
+    }
+    if (rg) { if (int rc = check_region_u8(*rg, H, W, what, shrink)) return rc; }
+    const int64_t M = (int64_t)B * (H / 2) * 128;
+    if (M >= (1ll << 31)) { set_error("%s: batch too large for 32-bit offsets (split it)", what); return TOAD_ESHAPE; }
+    if (u8) { if (int rc = check_norm_u8(norm, what)) return rc; }
+    if (u8 && !rg && (reinterpret_cast<uintptr_t>(X) & 1u) != 0) { set_error("%s: the uint8 tiles must be 2-byte aligned", what); return TOAD_EALIGN; }
+    if ((!u8 && !aligned16(X)) || !aligned16(Wf) || !aligned16(Yp) || (bias && !aligned16(bias))) { set_error("%s: pointers must be 16-byte aligned", what); return TOAD_EALIGN; }
+    if (int rc = check_ws(ws, ws_bytes, M, 64, 192, what)) return rc;
+    ext_cfg();
+    char *w = reinterpret_cast<char *>(ws) + (size_t)PB_GRID * PB * PB * sizeof(float);
+    unsigned short *planes = reinterpret_cast<unsigned short *>(w);
+    float *binv = reinterpret_cast<float *>(w + (size_t)64 * 6 * BK * 4);
+    hipLaunchKernelGGL(split_planes_narrow_h2_kernel<2>, dim3(16), dim3(256), 0, st, Wf, (int64_t)192, planes, binv, 64, 192, 1, 1, 12, 6);
+    if (int rc = check_launch(what)) return rc;
+    const int tiles = B * (H / 4);
+    const dim3 grid(std::min(tiles, 2 * PB_GRID));                  // two workgroups per CU
+    if (u8) {
+        StemNorm nrm;
+        for (int c = 0; c < 3; ++c) { nrm.a[c] = norm[c]; nrm.b[c] = norm[3 + c]; }
+        if (rg && shrink == 2)
+            hipLaunchKernelGGL(stem_halo_pool_kernel<SH_U8_REGION_BOX2>, grid, dim3(256), SH_SMEM, st, rg->region, planes, binv, bias, Yp, B, H, y_gmax, tiles,
+                               StemRegionArg{nrm, (int)rg->pitch, rg->origins});
+        else if (rg)
+            hipLaunchKernelGGL(stem_halo_pool_kernel<SH_U8_REGION>, grid, dim3(256), SH_SMEM, st, rg->region, planes, binv, bias, Yp, B, H, y_gmax, tiles,
+                               StemRegionArg{nrm, (int)rg->pitch, rg->origins});
+        else
+            hipLaunchKernelGGL(stem_halo_pool_kernel<SH_U8>, grid, dim3(256), SH_SMEM, st, reinterpret_cast<const unsigned char *>(X), planes, binv, bias, Yp, B, H, y_gmax, tiles, nrm);
+    } else {
+        hipLaunchKernelGGL(stem_halo_pool_kernel<SH_F32>, grid, dim3(256), SH_SMEM, st, reinterpret_cast<const float *>(X), planes, binv, bias, Yp, B, H, y_gmax, tiles, StemNoNorm{});
+    }
+    return check_launch(what);
+}
+int ext_stem_nchw_pool(const float *X, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W, void *ws, size_t ws_bytes,
+                       hipStream_t st, const char *what) {
+    return stem_pool_from_tiles(X, false, nullptr, Wf, bias, Yp, y_gmax, B, H, W, ws, ws_bytes, st, what);
+}
+int ext_stem_nhwc_u8_pool(const unsigned char *X8, const float *norm, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W,
+                          void *ws, size_t ws_bytes, hipStream_t st, const char *what) {
+    return stem_pool_from_tiles(X8, true, norm, Wf, bias, Yp, y_gmax, B, H, W, ws, ws_bytes, st, what);
+}
+int ext_stem_region_u8_pool(const RegionSrc &rg, const float *norm, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W, void *ws,
+                            size_t ws_bytes, hipStream_t st, const char *what, int shrink = 1) {
+    return stem_pool_from_tiles(nullptr, true, norm, Wf, bias, Yp, y_gmax, B, H, W, ws, ws_bytes, st, what, &rg, shrink);
+}
+
 static int grid_for(uint64_t threads) {
     uint64_t g = (threads + 255) / 256;
     const uint64_t cap = 256 * 32;                     // 32 blocks per CU is plenty for a streaming gather
@@ -278,16 +558,55 @@ static bool make_plan(int B, int H, int W, NetPlan &p) {
     return n == kNumConvs;
 }
 
-static int implicit_conv_enabled() {
-    return 1;
-}
-
 static inline size_t align2m(size_t x) { return (x + ((size_t)1 << 21) - 1) & ~(((size_t)1 << 21) - 1); }
 
 }  // namespace toad
 
 using namespace toad;
 
+// ---- the per-op entry points of the extractor's GEMM layer --------------------------------------------------------
+extern "C" int toad_linear_act_res_fwd_f32(const float *X, const float *W, const float *bias, const float *residual, float *Y,
+                                            int64_t M, int64_t K, int64_t N, int act, void *ws, size_t ws_bytes, void *stream) {
+    return ext_linear(X, nullptr, W, bias, residual, Y, nullptr, M, K, N, act, ws, ws_bytes, (hipStream_t)stream, "toad_linear_act_res_fwd_f32");
+}
+
+extern "C" int toad_conv_nhwc_f32(const float *X, const float *Wf, const float *bias, const float *residual, float *Y, int B, int H,
+                                  int W, int Cin, int kh, int kw, int stride, int pad, int Cout, int act, void *ws, size_t ws_bytes,
+                                  void *stream) {
+    return ext_conv_nhwc(X, nullptr, Wf, bias, residual, Y, nullptr, B, H, W, Cin, kh, kw, stride, pad, Cout, act, ws, ws_bytes, (hipStream_t)stream,
+                         "toad_conv_nhwc_f32");
+}
+
+extern "C" int toad_stem_conv_s2d_f32(const float *Xs, const float *Wf, const float *bias, float *Y, int B, int Ho, int Wo, int act,
+                                      void *ws, size_t ws_bytes, void *stream) {
+    return ext_stem_conv(Xs, nullptr, Wf, bias, Y, nullptr, B, Ho, Wo, act, ws, ws_bytes, (hipStream_t)stream, "toad_stem_conv_s2d_f32");
+}
+// The stem AND nn.MaxPool2d(3, 2, 1) as one kernel (models/resnet_custom.py:96-99): Yp [B, Ho/2, Wo/2, 64]. Shapes: Wo = 128, Ho a multiple of 32
+// (256 x 256 tiles); others take toad_stem_conv_s2d_f32 + toad_maxpool3x3s2_nhwc_f32.
+extern "C" int toad_stem_conv_pool_s2d_f32(const float *Xs, const float *Wf, const float *bias, float *Yp, int B, int Ho, int Wo, void *ws, size_t ws_bytes,
+                                           void *stream) {
+    return ext_stem_conv(Xs, nullptr, Wf, bias, Yp, nullptr, B, Ho, Wo, TOAD_ACT_RELU, ws, ws_bytes, (hipStream_t)stream, "toad_stem_conv_pool_s2d_f32", true);
+}
+
+extern "C" int toad_stem_pool_nchw_f32(const float *X, const float *Wf, const float *bias, float *Yp, int B, int H, int W, void *ws, size_t ws_bytes, void *stream) {
+    return ext_stem_nchw_pool(X, Wf, bias, Yp, nullptr, B, H, W, ws, ws_bytes, (hipStream_t)stream, "toad_stem_pool_nchw_f32");
+}
+extern "C" int toad_stem_pool_nhwc_u8(const unsigned char *tiles, const float *norm, const float *Wf, const float *bias, float *Yp, int B, int H, int W, void *ws,
+                                      size_t ws_bytes, void *stream) {
+    return ext_stem_nhwc_u8_pool(tiles, norm, Wf, bias, Yp, nullptr, B, H, W, ws, ws_bytes, (hipStream_t)stream, "toad_stem_pool_nhwc_u8");
+}
+extern "C" int toad_stem_pool_region_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm, const float *Wf,
+                                        const float *bias, float *Yp, int B, int H, int W, void *ws, size_t ws_bytes, void *stream) {
+    return ext_stem_region_u8_pool(RegionSrc{region, pitch, Hr, Wr, origins}, norm, Wf, bias, Yp, nullptr, B, H, W, ws, ws_bytes, (hipStream_t)stream,
+                                   "toad_stem_pool_region_u8");
+}
+extern "C" int toad_stem_pool_region_box_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm, const float *Wf,
+                                            const float *bias, float *Yp, int B, int H, int W, int shrink, void *ws, size_t ws_bytes, void *stream) {
+    return ext_stem_region_u8_pool(RegionSrc{region, pitch, Hr, Wr, origins}, norm, Wf, bias, Yp, nullptr, B, H, W, ws, ws_bytes, (hipStream_t)stream,
+                                   "toad_stem_pool_region_box_u8", shrink);
+}
+
+// ---- the gathers, pools and tile converters as entry points --------------------------------------------------------
 extern "C" int toad_im2col_nhwc_f32(const float *X, float *cols, int B, int H, int W, int C, int kh, int kw, int stride,
                                      int pad, void *stream) {
     const char *what = "toad_im2col_nhwc_f32";
@@ -345,18 +664,29 @@ extern "C" int toad_avgpool_nhwc_f32(const float *X, float *feat, int B, int HW,
     return launch_avgpool(X, feat, false, B, HW, C, (hipStream_t)stream, "toad_avgpool_nhwc_f32");
 }
 
+// the one launch behind the tile converters (arguments checked by the callers): contiguous tiles (rg == NULL), tiles by origin, or their box form (shrink == 2)
+static int launch_tiles_to_nchw(const unsigned char *src, const RegionSrc *rg, int shrink, const float *norm, float *out, int B, int H, int W, hipStream_t st,
+                                const char *what) {
+    StemNorm nrm;
+    for (int c = 0; c < 3; ++c) { nrm.a[c] = norm[c]; nrm.b[c] = norm[3 + c]; }
+    const uint32_t HW = (uint32_t)H * (uint32_t)W;
+    const dim3 grid(grid_for((uint64_t)B * ((HW + 3) / 4)));
+    if (!rg)
+        hipLaunchKernelGGL(tiles_u8_nhwc_to_nchw_kernel<false>, grid, dim3(256), 0, st, src, out, (uint64_t)B, HW, nrm, TilesNoRegion{});
+    else if (shrink == 2)
+        hipLaunchKernelGGL((tiles_u8_nhwc_to_nchw_kernel<true, 2>), grid, dim3(256), 0, st, src, out, (uint64_t)B, HW, nrm, TilesRegionArg{rg->pitch, rg->origins, (uint32_t)W});
+    else
+        hipLaunchKernelGGL(tiles_u8_nhwc_to_nchw_kernel<true>, grid, dim3(256), 0, st, src, out, (uint64_t)B, HW, nrm, TilesRegionArg{rg->pitch, rg->origins, (uint32_t)W});
+    return check_launch(what);
+}
+
 extern "C" int toad_tiles_u8_nhwc_to_nchw_f32(const unsigned char *tiles, const float *norm, float *out, int B, int H, int W, void *stream) {
     const char *what = "toad_tiles_u8_nhwc_to_nchw_f32";
     if (!tiles || !norm || !out) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
     if (B <= 0 || H <= 0 || W <= 0 || (uint64_t)H * W >= (1ull << 31)) { set_error("%s: bad shape", what); return TOAD_ESHAPE; }
     if (int rc = check_norm_u8(norm, what)) return rc;
     if (!aligned16(out)) { set_error("%s: out must be 16-byte aligned (the uint8 source may have any alignment)", what); return TOAD_EALIGN; }
-    StemNorm nrm;
-    for (int c = 0; c < 3; ++c) { nrm.a[c] = norm[c]; nrm.b[c] = norm[3 + c]; }
-    const uint32_t HW = (uint32_t)H * (uint32_t)W;
-    hipLaunchKernelGGL(tiles_u8_nhwc_to_nchw_kernel<false>, dim3(grid_for((uint64_t)B * ((HW + 3) / 4))), dim3(256), 0, (hipStream_t)stream, tiles, out, (uint64_t)B, HW, nrm,
-                       TilesNoRegion{});
-    return check_launch(what);
+    return launch_tiles_to_nchw(tiles, nullptr, 1, norm, out, B, H, W, (hipStream_t)stream, what);
 }
 
 // shrink == 2: H x W is the network tile, the (2 H, 2 W) footprint at each origin is box-filtered on the way (stem_u8.h: check_region_u8)
@@ -366,16 +696,7 @@ static int region_to_nchw(const RegionSrc &rg, const float *norm, float *out, in
     if (B <= 0 || (uint64_t)H * W >= (1ull << 31)) { set_error("%s: bad shape", what); return TOAD_ESHAPE; }
     if (int rc = check_norm_u8(norm, what)) return rc;
     if (!aligned16(out)) { set_error("%s: out must be 16-byte aligned (the region may have any alignment)", what); return TOAD_EALIGN; }
-    StemNorm nrm;
-    for (int c = 0; c < 3; ++c) { nrm.a[c] = norm[c]; nrm.b[c] = norm[3 + c]; }
-    const uint32_t HW = (uint32_t)H * (uint32_t)W;
-    if (shrink == 2)
-        hipLaunchKernelGGL((tiles_u8_nhwc_to_nchw_kernel<true, 2>), dim3(grid_for((uint64_t)B * ((HW + 3) / 4))), dim3(256), 0, st, rg.region, out, (uint64_t)B, HW, nrm,
-                           TilesRegionArg{rg.pitch, rg.origins, (uint32_t)W});
-    else
-    hipLaunchKernelGGL(tiles_u8_nhwc_to_nchw_kernel<true>, dim3(grid_for((uint64_t)B * ((HW + 3) / 4))), dim3(256), 0, st, rg.region, out, (uint64_t)B, HW, nrm,
-                       TilesRegionArg{rg.pitch, rg.origins, (uint32_t)W});
-    return check_launch(what);
+    return launch_tiles_to_nchw(rg.region, &rg, shrink, norm, out, B, H, W, st, what);
 }
 extern "C" int toad_tiles_u8_region_box_to_nchw_f32(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm, float *out, int B,
                                                     int H, int W, int shrink, void *stream) {
@@ -403,7 +724,7 @@ extern "C" size_t toad_resnet50_trunc_u8_ws_bytes(int B, int H, int W) {
 // weights[i] : folded conv i as [Cout, K] fp32 (K = kh*kw*Cin in (ky, kx, c) order; the stem is [64, 192] in the space-to-depth
 //              order of toad_stem_conv_s2d_f32),
 // biases[i]  : folded BN shift [Cout]; i runs in execution order (conv1, then per block conv1, conv2, conv3[, downsample]).
-// The network behind the three entry points. tiles_u8 == NULL: fp32 NCHW tiles (toad_resnet50_trunc_fwd_f32, arguments checked there). Otherwise uint8 NHWC tiles with
+// The network behind the three entry points. tiles_u8 == NULL: fp32 NCHW tiles (arguments checked by trunc_entry below, for every form). Otherwise uint8 NHWC tiles with
 // norm[6]: 256-wide tiles go straight into the stem kernel, others are converted into the staging image and take the fp32 call's three-kernel stem from there.
 // rg != NULL: the uint8 tiles are read by origin from rg->region (tiles_u8 == rg->region), by the region forms of the same two kernels; shrink == 2: by their
 // box forms, H x W being the network tile and (2 H, 2 W) the footprint at each origin.
@@ -427,8 +748,6 @@ static int trunc_fwd(const float *tiles_nchw, const unsigned char *tiles_u8, con
     (void)hipMemsetAsync(gm, 0, 4096, st);
     int gi = 0;
     auto slot = [&]() { return gm + (gi++); };
-    int rc;
-#define TOAD_TRY(call) do { rc = (call); if (rc) return rc; } while (0)
     // stem: 7x7/2 conv + BN + ReLU (resnet_custom.py:96-98), 3x3/2 max-pool (:99)
     float *g_in = slot();
     float *gx = slot();
@@ -439,7 +758,10 @@ static int trunc_fwd(const float *tiles_nchw, const unsigned char *tiles_u8, con
         tiles_nchw = stage;
         tiles_u8 = nullptr;
     }
+    // five stems, all leaving the pooled activation in act[1] and its abs-max in gx: three forms of the one-kernel stem (stem_halo.inc) for 256-wide
+    // tiles (uint8 ones of another width were staged as fp32 above), two of the space-to-depth stem (gemm_stream.inc) for every other fp32 tile
     if (tiles_u8 && rg) {
+        // uint8 tiles read by origin from the region (region form; shrink == 2: box form)
         TOAD_TRY(ext_stem_region_u8_pool(*rg, norm, weights[0], biases[0], act[1], gx, B, H, W, gws, gcap, st, what, shrink));
     } else if (tiles_u8) {
         // uint8 tiles, 256 wide: the same kernel body reads them as stored and normalises while it converts its window (stem_halo.inc, uint8 form)
@@ -449,16 +771,16 @@ static int trunc_fwd(const float *tiles_nchw, const unsigned char *tiles_u8, con
         // max |tiles| is measured
         TOAD_TRY(ext_stem_nchw_pool(tiles_nchw, weights[0], biases[0], act[1], gx, B, H, W, gws, gcap, st, what));
     } else {
-    // 12-channel space-to-depth image (53 MB per 64 tiles); the gather also emits max |tiles| - the only measured tensor - into its slot
-    if (!aligned16(cols)) { set_error("%s: internal: cols not aligned", what); return TOAD_EALIGN; }
-    hipLaunchKernelGGL(stem_s2d_kernel, dim3(grid_for((uint64_t)B * (p.Hs + 3) * (p.Ws + 3))), dim3(256), 0, st, tiles_nchw, cols, B, H, W, p.Hs + 3, p.Ws + 3, g_in);
-    TOAD_TRY(check_launch(what));
-    if (stem_pool_ok(p.Hs, p.Ws, TOAD_ACT_RELU)) {      // tiles 256 wide: the max-pool rides in the stem's epilogue, the stem's own output is never stored
-        TOAD_TRY(ext_stem_conv(cols, g_in, weights[0], biases[0], act[1], gx, B, p.Hs, p.Ws, TOAD_ACT_RELU, gws, gcap, st, what, true));
-    } else {
-        TOAD_TRY(ext_stem_conv(cols, g_in, weights[0], biases[0], act[0], gx, B, p.Hs, p.Ws, TOAD_ACT_RELU, gws, gcap, st, what));
-        TOAD_TRY(toad_maxpool3x3s2_nhwc_f32(act[0], act[1], B, p.Hs, p.Ws, 64, st));      // max-pooling keeps the maximum: same slot
-    }
+        // 12-channel space-to-depth image (53 MB per 64 tiles); the gather also emits max |tiles| - the only measured tensor - into its slot
+        if (!aligned16(cols)) { set_error("%s: internal: cols not aligned", what); return TOAD_EALIGN; }
+        hipLaunchKernelGGL(stem_s2d_kernel, dim3(grid_for((uint64_t)B * (p.Hs + 3) * (p.Ws + 3))), dim3(256), 0, st, tiles_nchw, cols, B, H, W, p.Hs + 3, p.Ws + 3, g_in);
+        TOAD_TRY(check_launch(what));
+        if (stem_pool_ok(p.Hs, p.Ws, TOAD_ACT_RELU)) {      // tiles 256 wide: the max-pool rides in the stem's epilogue, the stem's own output is never stored
+            TOAD_TRY(ext_stem_conv(cols, g_in, weights[0], biases[0], act[1], gx, B, p.Hs, p.Ws, TOAD_ACT_RELU, gws, gcap, st, what, true));
+        } else {
+            TOAD_TRY(ext_stem_conv(cols, g_in, weights[0], biases[0], act[0], gx, B, p.Hs, p.Ws, TOAD_ACT_RELU, gws, gcap, st, what));
+            TOAD_TRY(toad_maxpool3x3s2_nhwc_f32(act[0], act[1], B, p.Hs, p.Ws, 64, st));      // max-pooling keeps the maximum: same slot
+        }
     }
     float *x = act[1];                          // block input (abs-max scalar: gx)
     auto other = [&](float *a0, float *a1, float *a2) {          // a buffer different from the (up to) three in use
@@ -480,7 +802,7 @@ static int trunc_fwd(const float *tiles_nchw, const unsigned char *tiles_u8, con
             // implicit convolution (halo in LDS for stride 1, streamed taps for stride 2), no cols buffer: always for the narrow
             // layers; for 256 output channels (two 128-column tiles per 256 pixels) only when there are enough tiles to fill
             // the chip's 512 workgroup slots - otherwise im2col + the 256x256 kernel with its K-split is faster (measured at B = 64 vs 512)
-            const bool implicit = implicit_conv_enabled() && (pl <= 128 || (pl <= 256 && (Mo / 256) * ((pl + 127) / 128) >= 512));
+            const bool implicit = pl <= 128 || (pl <= 256 && (Mo / 256) * ((pl + 127) / 128) >= 512);
             float *g2 = slot();
             if (implicit) {
                 TOAD_TRY(ext_conv_nhwc(t1, g1, weights[ci + 1], biases[ci + 1], nullptr, t2, g2, B, h, w, pl, 3, 3, s, 1, pl, TOAD_ACT_RELU, gws, gcap, st, what));
@@ -507,49 +829,49 @@ static int trunc_fwd(const float *tiles_nchw, const unsigned char *tiles_u8, con
         }
     if (feat) TOAD_TRY(launch_avgpool(x, feat, false, B, h * w, inpl, st, what));
     if (feat16) TOAD_TRY(launch_avgpool(x, feat16, true, B, h * w, inpl, st, what));
-#undef TOAD_TRY
     return TOAD_OK;
+}
+
+// What every entry in front of trunc_fwd checks, in the order the callers rely on (tests/test_abi_and_host.py): null pointers, the plan, the region
+// (tiles by origin), the normalisation constants (uint8 forms), the workspace size, alignment, the 43 weight / bias slots. Then the network.
+// u8 == false: fp32 NCHW tiles into feat; u8: uint8 tiles (tiles_u8, or rg->region by origin) into feat and / or feat16.
+static int trunc_entry(bool u8, const float *tiles_nchw, const unsigned char *tiles_u8, const RegionSrc *rg, int shrink, const float *norm,
+                       const float *const *weights, const float *const *biases, float *feat, void *feat16, int B, int H, int W, void *ws, size_t ws_bytes,
+                       void *stream, const char *what) {
+    const bool no_src = u8 ? (!tiles_u8 || (rg && !rg->origins) || !norm) : !tiles_nchw;
+    if (no_src || !weights || !biases || (!feat && !feat16) || !ws) {
+        set_error(u8 ? "%s: null pointer (feat and feat_f16 may not both be NULL)" : "%s: null pointer", what);
+        return TOAD_EINVAL;
+    }
+    NetPlan p;
+    if (!make_plan(B, H, W, p)) { set_error("%s: bad shape B=%d H=%d W=%d", what, B, H, W); return TOAD_ESHAPE; }
+    if (rg) TOAD_TRY(check_region_u8(*rg, H, W, what, shrink));
+    if (u8) TOAD_TRY(check_norm_u8(norm, what));
+    if (ws_bytes < (u8 ? toad_resnet50_trunc_u8_ws_bytes(B, H, W) : toad_resnet50_trunc_ws_bytes(B, H, W))) { set_error("%s: workspace too small", what); return TOAD_EWORKSPACE; }
+    if (!aligned16(ws) || (feat && !aligned16(feat)) || (feat16 && !aligned16(feat16))) {
+        set_error(u8 ? "%s: workspace / outputs must be 16-byte aligned" : "%s: workspace / output must be 16-byte aligned", what);
+        return TOAD_EALIGN;
+    }
+    if (u8 && !rg && stem_nchw_pool_ok(H, W) && (reinterpret_cast<uintptr_t>(tiles_u8) & 1u) != 0) { set_error("%s: 256-wide uint8 tiles must be 2-byte aligned", what); return TOAD_EALIGN; }
+    for (int i = 0; i < kNumConvs; ++i) if (!weights[i] || !biases[i]) { set_error("%s: null weight/bias slot %d", what, i); return TOAD_EINVAL; }
+    return trunc_fwd(tiles_nchw, tiles_u8, norm, weights, biases, feat, feat16, p, B, H, W, ws, stream, what, rg, shrink);
 }
 
 extern "C" int toad_resnet50_trunc_fwd_f32(const float *tiles_nchw, const float *const *weights, const float *const *biases,
                                             float *feat, int B, int H, int W, void *ws, size_t ws_bytes, void *stream) {
-    const char *what = "toad_resnet50_trunc_fwd_f32";
-    if (!tiles_nchw || !weights || !biases || !feat || !ws) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
-    NetPlan p;
-    if (!make_plan(B, H, W, p)) { set_error("%s: bad shape B=%d H=%d W=%d", what, B, H, W); return TOAD_ESHAPE; }
-    if (ws_bytes < toad_resnet50_trunc_ws_bytes(B, H, W)) { set_error("%s: workspace too small", what); return TOAD_EWORKSPACE; }
-    if (!aligned16(ws) || !aligned16(feat)) { set_error("%s: workspace / output must be 16-byte aligned", what); return TOAD_EALIGN; }
-    for (int i = 0; i < kNumConvs; ++i) if (!weights[i] || !biases[i]) { set_error("%s: null weight/bias slot %d", what, i); return TOAD_EINVAL; }
-    return trunc_fwd(tiles_nchw, nullptr, nullptr, weights, biases, feat, nullptr, p, B, H, W, ws, stream, what);
+    return trunc_entry(false, tiles_nchw, nullptr, nullptr, 1, nullptr, weights, biases, feat, nullptr, B, H, W, ws, ws_bytes, stream, "toad_resnet50_trunc_fwd_f32");
 }
 
 extern "C" int toad_resnet50_trunc_fwd_u8(const unsigned char *tiles, const float *norm, const float *const *weights, const float *const *biases, float *feat,
                                            void *feat_f16, int B, int H, int W, void *ws, size_t ws_bytes, void *stream) {
-    const char *what = "toad_resnet50_trunc_fwd_u8";
-    if (!tiles || !norm || !weights || !biases || (!feat && !feat_f16) || !ws) { set_error("%s: null pointer (feat and feat_f16 may not both be NULL)", what); return TOAD_EINVAL; }
-    NetPlan p;
-    if (!make_plan(B, H, W, p)) { set_error("%s: bad shape B=%d H=%d W=%d", what, B, H, W); return TOAD_ESHAPE; }
-    if (int rc = check_norm_u8(norm, what)) return rc;
-    if (ws_bytes < toad_resnet50_trunc_u8_ws_bytes(B, H, W)) { set_error("%s: workspace too small", what); return TOAD_EWORKSPACE; }
-    if (!aligned16(ws) || (feat && !aligned16(feat)) || (feat_f16 && !aligned16(feat_f16))) { set_error("%s: workspace / outputs must be 16-byte aligned", what); return TOAD_EALIGN; }
-    if (stem_nchw_pool_ok(H, W) && (reinterpret_cast<uintptr_t>(tiles) & 1u) != 0) { set_error("%s: 256-wide uint8 tiles must be 2-byte aligned", what); return TOAD_EALIGN; }
-    for (int i = 0; i < kNumConvs; ++i) if (!weights[i] || !biases[i]) { set_error("%s: null weight/bias slot %d", what, i); return TOAD_EINVAL; }
-    return trunc_fwd(nullptr, tiles, norm, weights, biases, feat, feat_f16, p, B, H, W, ws, stream, what);
+    return trunc_entry(true, nullptr, tiles, nullptr, 1, norm, weights, biases, feat, feat_f16, B, H, W, ws, ws_bytes, stream, "toad_resnet50_trunc_fwd_u8");
 }
 
 static int trunc_fwd_region(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm, const float *const *weights,
                             const float *const *biases, float *feat, void *feat_f16, int B, int H, int W, int shrink, void *ws, size_t ws_bytes, void *stream,
                             const char *what) {
-    if (!region || !origins || !norm || !weights || !biases || (!feat && !feat_f16) || !ws) { set_error("%s: null pointer (feat and feat_f16 may not both be NULL)", what); return TOAD_EINVAL; }
-    NetPlan p;
-    if (!make_plan(B, H, W, p)) { set_error("%s: bad shape B=%d H=%d W=%d", what, B, H, W); return TOAD_ESHAPE; }
     const RegionSrc rg{region, pitch, Hr, Wr, origins};
-    if (int rc = check_region_u8(rg, H, W, what, shrink)) return rc;
-    if (int rc = check_norm_u8(norm, what)) return rc;
-    if (ws_bytes < toad_resnet50_trunc_u8_ws_bytes(B, H, W)) { set_error("%s: workspace too small", what); return TOAD_EWORKSPACE; }
-    if (!aligned16(ws) || (feat && !aligned16(feat)) || (feat_f16 && !aligned16(feat_f16))) { set_error("%s: workspace / outputs must be 16-byte aligned", what); return TOAD_EALIGN; }
-    for (int i = 0; i < kNumConvs; ++i) if (!weights[i] || !biases[i]) { set_error("%s: null weight/bias slot %d", what, i); return TOAD_EINVAL; }
-    return trunc_fwd(nullptr, region, norm, weights, biases, feat, feat_f16, p, B, H, W, ws, stream, what, &rg, shrink);
+    return trunc_entry(true, nullptr, region, &rg, shrink, norm, weights, biases, feat, feat_f16, B, H, W, ws, ws_bytes, stream, what);
 }
 extern "C" int toad_resnet50_trunc_fwd_u8_region(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm,
                                                   const float *const *weights, const float *const *biases, float *feat, void *feat_f16, int B, int H, int W, void *ws,

@@ -1,15 +1,15 @@
-// gemm_f32.hip — the fp32-accurate MFMA GEMMs of libtoad_hip.so (gfx950): the Linear layers of TOAD's MIL path and the
-// convolutions-as-GEMMs of the feature extractor. One translation unit (kernels and launchers must share a TU without
-// -fgpu-rdc), organised as:
+// gemm_f32.hip — the fp32-accurate MFMA GEMMs of libtoad_hip.so (gfx950): the Linear layers of TOAD's MIL path. One translation unit
+// (a launcher and its own kernels must share a TU without -fgpu-rdc), organised as:
+//   h2_arith.h         the two-piece operand arithmetic and the persistent-grid constants, shared with the extractor's unit (conv.hip)
 //   gemm_nt_f32.inc    generic exact-fp32 128x128 NT kernel (the fallback for shapes the persistent kernels do not take); the per-XCD tile
 //                      plan and the shared epilogue of the persistent kernels
 //   gemm_tn.inc        wgrad: the generic exact-fp32 TN kernel, the split-M plan, slab reduction, transpose
-//   gemm_h2.inc        the MIL GEMMs (forward / dgrad / wgrad) and the extractor's wide convolutions: persistent 256x256 kernels on the
-//                      fp16 pipe with two-piece operands (x*s = h + m, three MFMA terms, power-of-two scales from per-256-row abs-max arrays)
+//   gemm_h2.inc        the MIL GEMMs (forward / dgrad / wgrad): persistent 256x256 kernels on the fp16 pipe with two-piece operands
+//                      (x*s = h + m, three MFMA terms, power-of-two scales from per-256-row abs-max arrays)
 //   gemm_pt.inc        plane-tiled prepared bags: the splitter and the weight-gradient kernel that reads them by LDS-DMA + transposing LDS reads
-//   gemm_narrow.inc    the narrow-N weight-plane format, convolution geometry and gather modes of the extractor
-//   gemm_stream.inc    narrow-N kernels of the extractor: A streamed through registers; 3x3 convolutions with the activation halo in LDS
-//   this file          shared constants, launch selection, the extern "C" entry points declared in include/toad_hip.h
+//   this file          launch selection, the extern "C" entry points declared in include/toad_hip.h
+// The feature extractor (conv.hip) owns its kernels, launchers and kernel attributes. Its wide GEMMs run on this unit's 256x256 kernel through
+// launch_split_h2 / launch_nt_h2, its last resort is launch_nt; common.h declares that seam.
 // (Round 1's exact-fp32 / split-bf16 persistent kernels and the LDS-staged narrow kernels were A/B arms; they left the tree in round 4 -
 //  tools/ab/README.md names the commit that still holds them.)
 //
@@ -22,15 +22,14 @@
 // Why not plain bf16: parity with the reference's PyTorch-CPU path is 1e-4 on fp32 outputs and bf16 operands miss it
 // (1e-3..6e-3); gfx950 has no TF32/xf32. DESIGN.md 4 gives the arithmetic and the measurements.
 #include "common.h"
-#include "stem_u8.h"
+#include "h2_arith.h"
 
 #include <stdlib.h>
 #include <mutex>
-#include <type_traits>
 
 namespace toad {
 
-constexpr int BM = 128, BN = 128, BK = 32;
+constexpr int BM = 128, BN = 128;
 constexpr int NT_LD = 36;                                  // padded LDS row (floats), conflict-free b128
 constexpr int NT_TILE = BM * NT_LD;                        // floats per operand tile
 constexpr int NT_SMEM = 2 * 2 * NT_TILE * (int)sizeof(float);   // 73,728 B -> 2 blocks / CU
@@ -54,20 +53,14 @@ __device__ __forceinline__ bool map_tile(int tiles_m, int tiles_n, int &tm, int 
 #include "gemm_tn.inc"
 #include "gemm_h2.inc"
 #include "gemm_pt.inc"
-#include "gemm_narrow.inc"
-#include "gemm_stream.inc"
-#include "stem_halo.inc"
 
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-// One-time initialisation of this translation unit: kernel attributes (dynamic LDS sizes). The library has ONE arithmetic per
+// One-time initialisation of this translation unit: the attributes (dynamic LDS sizes) of ITS kernels; the extractor's
+// kernels have their own in conv.hip (ext_cfg). The library has ONE arithmetic per
 // product shape and reads no environment variable anywhere; std::call_once makes the first call from any thread complete the
 // attribute calls before any launch (PyTorch runs backward on its own thread; the ingest workers are threads too).
-// Residual GEMMs with a reduction of at most this many elements run on the narrow (streamed) tiles whatever their width: measured
-// (tools/gemm_shape_bench.py, same box) M=262144 K=64 N=256 +residual 170 -> 133 us; K=128 equal, K=256 slower (A is re-split per
-// 128-column tile)
-constexpr int kNarrowResKmax = 64;
 static std::once_flag g_cfg_once;
 static void cfg() {
     std::call_once(g_cfg_once, [] {
@@ -96,94 +89,8 @@ static void cfg() {
         TOAD_ATTR(gemm_tn_pt_kernel, TP_SMEM);
         TOAD_ATTR(gemm_nt_f32_kernel, NT_SMEM);
         TOAD_ATTR(gemm_tn_f32_kernel, TN_SMEM);
-        TOAD_ATTR((gemm_nt_h2_stream_kernel<2, 2, GATHER_NONE>), (StreamCfg<2, 2>::SMEM));
-        TOAD_ATTR((gemm_nt_h2_stream_kernel<2, 4, GATHER_NONE>), (StreamCfg<2, 4>::SMEM));
-        TOAD_ATTR((gemm_nt_h2_stream_kernel<2, 2, GATHER_CONV>), (StreamCfg<2, 2>::SMEM));
-        TOAD_ATTR((gemm_nt_h2_stream_kernel<2, 4, GATHER_CONV>), (StreamCfg<2, 4>::SMEM));
-        TOAD_ATTR((gemm_nt_h2_stream_kernel<2, 2, GATHER_STEM>), (StreamCfg<2, 2>::SMEM));
-        TOAD_ATTR((gemm_nt_h2_stream_kernel<2, 2, GATHER_STEM_POOL>), (StreamCfg<2, 2>::SMEM + STEM_POOL_LDS));
-        TOAD_ATTR(stem_halo_pool_kernel<SH_F32>, SH_SMEM);
-        TOAD_ATTR(stem_halo_pool_kernel<SH_U8>, SH_SMEM);
-        TOAD_ATTR(stem_halo_pool_kernel<SH_U8_REGION>, SH_SMEM);
-        TOAD_ATTR(stem_halo_pool_kernel<SH_U8_REGION_BOX2>, SH_SMEM);
-        TOAD_ATTR(conv3x3_h2_halo_kernel<2>, 160 * 1024);
-        TOAD_ATTR(conv3x3_h2_halo_kernel<4>, 160 * 1024);
 #undef TOAD_ATTR
     });
-}
-
-// max |x| over n floats -> out[0] (bit pattern of a non-negative float, zeroed here): the tensor-wide abs-max a narrow / extractor GEMM
-// scales its A operand with when no producer handed one over (the per-op entry points; inside toad_resnet50_trunc_fwd_f32 every
-// producer emits it)
-__global__ __launch_bounds__(256) void gmax_kernel(const float *__restrict__ x, int64_t n4, float *__restrict__ out) {
-    __shared__ float s[4];
-    float mx = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256)
-        mx = __builtin_fmaxf(mx, h2_absmax4(__builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(x) + i)));
-    mx = h2_wave_max(mx);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) h2_atomic_amax(out, __builtin_fmaxf(__builtin_fmaxf(s[0], s[1]), __builtin_fmaxf(s[2], s[3])));
-}
-int launch_gmax(const float *x, int64_t n, float *out, hipStream_t st, const char *what) {
-    (void)hipMemsetAsync(out, 0, sizeof(float), st);
-    int64_t grid = (n / 4 + 255) / 256;
-    if (grid > 2048) grid = 2048;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(gmax_kernel, dim3((unsigned)grid), dim3(256), 0, st, x, n / 4, out);
-    return check_launch(what);
-}
-
-// C[M,N] = act(A' W^T + bias + addend) with N <= 128 on the narrow kernels; A' = A[M,K] (MODE = GATHER_NONE) or the implicit
-// im2col of the NHWC activation A described by cg. `ws` as for launch_nt (planes and inverse scales live behind the slab area).
-// a_gmax: device scalar max |A| (of the whole activation); y_gmax (optional): receives max |C| by atomic max (zeroed by the caller).
-template <int RA, int NB, int MODE>
-static int launch_narrow_t(const float *A, int64_t lda, const float *a_gmax, const float *W, int64_t ldw, float *C, int64_t ldc, int64_t M, int64_t N,
-                           int64_t K, const float *bias, int relu, const float *addend, const ConvGeom &cg, float *y_gmax, void *ws,
-                           hipStream_t st, const char *what) {
-    (void)cfg();
-    char *w = reinterpret_cast<char *>(ws) + (size_t)PB_GRID * PB * PB * sizeof(float);
-    constexpr int TNW = NB * 32;         // tile width (RA only names the instantiation; the streamed kernels run 64-row wave tiles)
-    const int tiles_n = (int)((N + TNW - 1) / TNW);
-    unsigned short *planes = reinterpret_cast<unsigned short *>(w);
-    float *binv;
-    // the streamed kernel walks an implicit convolution's k-stages channel-chunk outer, tap inner (gemm_stream.inc): its planes are split in that order
-    const int taps = MODE == GATHER_CONV ? (int)(K / cg.C) : 1;
-    const int nk = (int)(K / BK), nkp = (nk + 1) & ~1;                  // the streamed kernel walks k-stages in pairs: an odd count gets a zero stage
-    binv = reinterpret_cast<float *>(w + (size_t)tiles_n * TNW * (size_t)nkp * BK * 4);
-    hipLaunchKernelGGL(split_planes_narrow_h2_kernel<NB>, dim3((tiles_n * TNW + 3) / 4), dim3(256), 0, st, W, ldw, planes, binv, (int)N, (int)K, tiles_n,
-                       taps, cg.C, nkp);
-    if (int rc = check_launch(what)) return rc;
-    if (MODE == GATHER_CONV) {       // 3x3 / 1 / 1 with whole 256-pixel row blocks: the activation halo lives in LDS (gemm_stream.inc)
-        const int W = cg.W, H = cg.H;
-        const bool shape = cg.kw == 3 && K == 9 * (int64_t)cg.C && cg.stride == 1 && cg.pad == 1 && cg.Ho == H && cg.Wo == W && W >= 8 && W <= 128 &&
-                           (W & (W - 1)) == 0 && H % (256 / W) == 0 && cg.C % BK == 0 && M % 256 == 0;
-        if (shape) {
-            using HCfg = HaloCfg<NB>;
-            const int hb = HCfg::halo_bytes(W);
-            hipLaunchKernelGGL(conv3x3_h2_halo_kernel<NB>, dim3(2 * PB_GRID), dim3(HCfg::THREADS), HCfg::smem(W), st, A, a_gmax, planes, binv, C, ldc, (int)M, (int)N,
-                               (int)K, bias, relu, addend, cg, y_gmax, (int)(M / 256), tiles_n, hb);
-            return check_launch(what);
-        }
-    }
-    // A streamed through registers (gemm_stream.inc): wave tile 64 x 64 / 64 x 128
-    constexpr int SRA = 2;
-    using SCfg = StreamCfg<SRA, NB>;
-    const int stiles_m = (int)((M + SCfg::TM - 1) / SCfg::TM);
-    if constexpr (MODE == GATHER_STEM_POOL) {        // C = the POOLED output; every workgroup a contiguous range of row-pair tiles (ext_stem_conv checked the geometry)
-        hipLaunchKernelGGL((gemm_nt_h2_stream_kernel<SRA, NB, MODE>), dim3(std::min(stiles_m, SCfg::WG_PER_CU * PB_GRID)), dim3(SCfg::THREADS), SCfg::SMEM + STEM_POOL_LDS, st,
-                           A, lda, a_gmax, planes, binv, C, ldc, (int)M, (int)N, (int)K, bias, relu, addend, cg, y_gmax, stiles_m, tiles_n);
-        return check_launch(what);
-    }
-    hipLaunchKernelGGL((gemm_nt_h2_stream_kernel<SRA, NB, MODE>), dim3(SCfg::WG_PER_CU * PB_GRID), dim3(SCfg::THREADS), SCfg::SMEM, st, A, lda, a_gmax, planes, binv,
-                       C, ldc, (int)M, (int)N, (int)K, bias, relu, addend, cg, y_gmax, stiles_m, tiles_n);
-    return check_launch(what);
-}
-
-static bool narrow_ok(int64_t M, int64_t N, int64_t K, int64_t ldc, const float *bias, const float *addend, void *ws) {
-    const bool wide_ok = addend && K <= kNarrowResKmax;       // residual GEMMs with a short reduction: epilogue-bound, see DESIGN 10
-    return ws && (N <= 128 || wide_ok) && N % 4 == 0 && K % BK == 0 && ldc % 4 == 0 && M < (1ll << 31) &&
-           (!bias || aligned16(bias)) && (!addend || aligned16(addend));
 }
 
 // ---- h2 (fp16 two-piece) path ---------------------------------------------------------------------------------
@@ -439,9 +346,6 @@ int launch_nt_h2(const float *A, int64_t lda, const float *a_amax, const unsigne
 // Self-contained NT product for the per-op entry points: B[n,k] = Bsrc[n*bsn + k*bsk]. Uses the h2 kernel when the shape allows
 // (splitting B and, when a_amax == NULL, measuring A inside `ws`), else the older paths (launch_nt). y_amax, when requested, is
 // always produced (by the epilogue, or by a pass over C on the fallback paths).
-static int launch_nt(const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc,
-                     int64_t M, int64_t N, int64_t K, const float *bias, EpiScalars es, const float *addend,
-                     const float *mask_src, void *ws, hipStream_t st, const char *what);
 static int launch_nt_auto(const float *A, int64_t lda, const float *a_amax, const float *B, int64_t ldb, float *C, int64_t ldc,
                           int64_t M, int64_t N, int64_t K, const float *bias, EpiScalars es, const float *addend, const float *mask_src,
                           const unsigned long long *mask_bits, H2Pool pool, float *y_amax, unsigned long long *bits_out, void *ws,
@@ -484,9 +388,9 @@ static int launch_nt_auto(const float *A, int64_t lda, const float *a_amax, cons
     return check_launch(what);
 }
 
-static int launch_nt(const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc,
-                     int64_t M, int64_t N, int64_t K, const float *bias, EpiScalars es, const float *addend,
-                     const float *mask_src, void *ws, hipStream_t st, const char *what) {
+int launch_nt(const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc,
+              int64_t M, int64_t N, int64_t K, const float *bias, EpiScalars es, const float *addend,
+              const float *mask_src, void *ws, hipStream_t st, const char *what) {
     if (M <= 0 || N <= 0 || K <= 0) { set_error("%s: non-positive dimension", what); return TOAD_EINVAL; }
     if (M > INT32_MAX - BM || N > INT32_MAX - BN || K > INT32_MAX - BK) { set_error("%s: dimension too large", what); return TOAD_ESHAPE; }
     if (K % 4 != 0 || lda % 4 != 0 || ldb % 4 != 0) { set_error("%s: reduction dim %lld must be a multiple of 4", what, (long long)K); return TOAD_ESHAPE; }
@@ -566,12 +470,6 @@ extern "C" int toad_absmax_rows256_f32(const float *X, int64_t M, int64_t K, flo
     return launch_absmax(X, K, M, K, amax, true, (hipStream_t)stream, what);
 }
 
-static int check_ws(void *ws, size_t ws_bytes, int64_t M, int64_t N, int64_t K, const char *what) {
-    if (ws && ws_bytes < toad_linear_ws_bytes(M, N, K)) { set_error("%s: workspace too small", what); return TOAD_EWORKSPACE; }
-    if (ws && !aligned16(ws)) { set_error("%s: workspace must be 16-byte aligned", what); return TOAD_EALIGN; }
-    return TOAD_OK;
-}
-
 extern "C" int toad_linear_act_fwd_f32(const float *X, const float *W, const float *bias, float *Y, int64_t M,
                                         int64_t K, int64_t N, int act, float drop_p, uint64_t drop_seed,
                                         const float *x_amax, float *y_amax, uint64_t *relu_bits_out, void *ws, size_t ws_bytes,
@@ -586,204 +484,6 @@ extern "C" int toad_linear_act_fwd_f32(const float *X, const float *W, const flo
     if (relu_bits_out && act != TOAD_ACT_RELU) { set_error("%s: relu_bits_out needs act = RELU", what); return TOAD_EINVAL; }
     return launch_nt_auto(X, K, x_amax, W, K, Y, N, M, N, K, bias, es, nullptr, nullptr, nullptr, H2Pool{nullptr, nullptr, nullptr, 0}, y_amax,
                           reinterpret_cast<unsigned long long *>(relu_bits_out), ws, (hipStream_t)stream, what);
-}
-
-// ---- the extractor's GEMMs (models/resnet_custom.py:19-119 as NHWC GEMMs, conv.hip): Y = act(X' W^T + bias + residual) -------------
-// x_gmax: device scalar max |X| of the whole activation (NULL: measured here, one extra read); y_gmax: device scalar that receives
-// max |Y| by atomic max (the caller zeroed it; NULL: not wanted). One tensor-wide power-of-two scale per activation: gemm_narrow.inc.
-static float *ext_scratch_scalar(void *ws, int64_t M, int64_t N, int64_t K) {          // a float inside the workspace's abs-max area
-    const size_t tiles_n = (size_t)((N + PB - 1) / PB), kpad = (size_t)((K + 2 * BK - 1) / (2 * BK) * (2 * BK));        // as toad_linear_ws_bytes
-    return reinterpret_cast<float *>(reinterpret_cast<char *>(ws) + (size_t)PB_GRID * PB * PB * sizeof(float) + tiles_n * PB * kpad * 6 + tiles_n * PB * sizeof(float)) + 8;
-}
-int toad::ext_linear(const float *X, const float *x_gmax, const float *W, const float *bias, const float *residual, float *Y, float *y_gmax,
-                     int64_t M, int64_t K, int64_t N, int act, void *ws, size_t ws_bytes, hipStream_t st, const char *what) {
-    if (!X || !W || !Y) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
-    if (act != TOAD_ACT_NONE && act != TOAD_ACT_RELU) { set_error("%s: bad act %d", what, act); return TOAD_EINVAL; }
-    if (M <= 0 || N <= 0 || K <= 0) { set_error("%s: non-positive dimension", what); return TOAD_EINVAL; }
-    if (residual && (N % 4 != 0 || !aligned16(residual))) { set_error("%s: residual needs N %% 4 == 0 and 16-byte alignment", what); return TOAD_ESHAPE; }
-    if (int rc = check_ws(ws, ws_bytes, M, N, K, what)) return rc;
-    EpiScalars es{act == TOAD_ACT_RELU, 1.f, make_drop(0.f, 0)};
-    const bool narrow = narrow_ok(M, N, K, N, bias, residual, ws) && (uint64_t)M * K * 4 < (1ull << 32);
-    const bool big = !narrow && ws && h2_nt_ok(M, N, K, K, N);
-    if ((narrow || big) && !x_gmax) {
-        float *g = ext_scratch_scalar(ws, M, N, K);
-        if (int rc = launch_gmax(X, M * K, g, st, what)) return rc;
-        x_gmax = g;
-    }
-    if (narrow) {
-        const ConvGeom none{0, 0, 0, 0, 0, 0, 0, 0};
-        if (N <= 64) return launch_narrow_t<2, 2, GATHER_NONE>(X, K, x_gmax, W, K, Y, N, M, N, K, bias, es.relu, residual, none, y_gmax, ws, st, what);
-        return launch_narrow_t<1, 4, GATHER_NONE>(X, K, x_gmax, W, K, Y, N, M, N, K, bias, es.relu, residual, none, y_gmax, ws, st, what);
-    }
-    if (big) {
-        // wide outputs (1x1 expansions / downsamples, the 256-channel 3x3 after im2col): the persistent 256x256 kernel of the MIL path
-        // with the tensor-wide scalars in place of its per-block abs-max arrays (stride 0)
-        if (!aligned16(X) || !aligned16(W) || !aligned16(Y) || (bias && !aligned16(bias))) { set_error("%s: pointers must be 16-byte aligned", what); return TOAD_EALIGN; }
-        char *w = reinterpret_cast<char *>(ws);
-        float *slabs = reinterpret_cast<float *>(w);
-        w += (size_t)PB_GRID * PB * PB * sizeof(float);
-        unsigned short *planes = reinterpret_cast<unsigned short *>(w);
-        w += h2_planes_bytes(N, K);
-        float *binv = reinterpret_cast<float *>(w);
-        const H2Operand op{W, K, 1, N, K, planes, binv};
-        if (int rc = launch_split_h2(&op, 1, nullptr, 0, st, what)) return rc;
-        // short reductions: a tile is a few k-steps of matrix work followed by 256-512 KB of epilogue traffic, and 256 workgroups in phase make
-        // the GEMM the SUM of the two. Spread the starts over one expected tile period (10 ns ticks: ~1.95 us per k-step, ~8 us per 256 KB of
-        // epilogue traffic; measured on the extractor's shapes, tools/ab/duo_ext_bench.py: -8..-10 % on the residual GEMMs, neutral from K = 1024)
-        if (K <= 512 && M >= 32 * 1024) es.stagger = (int)std::min<int64_t>((K / BK) * 195 + (residual ? 1600 : 800), 3000);
-        return launch_nt_h2(X, K, x_gmax, planes, binv, Y, N, M, N, K, bias, es, residual, nullptr, nullptr, H2Pool{nullptr, nullptr, nullptr, 0}, slabs,
-                            y_gmax, nullptr, st, what, TOAD_X_F32, 0, 0);
-    }
-    if (int rc = launch_nt(X, K, W, K, Y, N, M, N, K, bias, es, residual, nullptr, ws, st, what)) return rc;
-    return y_gmax ? launch_gmax(Y, M * N, y_gmax, st, what) : TOAD_OK;
-}
-
-extern "C" int toad_linear_act_res_fwd_f32(const float *X, const float *W, const float *bias, const float *residual, float *Y,
-                                            int64_t M, int64_t K, int64_t N, int act, void *ws, size_t ws_bytes, void *stream) {
-    return ext_linear(X, nullptr, W, bias, residual, Y, nullptr, M, K, N, act, ws, ws_bytes, (hipStream_t)stream, "toad_linear_act_res_fwd_f32");
-}
-
-int toad::ext_conv_nhwc(const float *X, const float *x_gmax, const float *Wf, const float *bias, const float *residual, float *Y, float *y_gmax, int B,
-                        int H, int W, int Cin, int kh, int kw, int stride, int pad, int Cout, int act, void *ws, size_t ws_bytes, hipStream_t st,
-                        const char *what) {
-    if (!X || !Wf || !Y || !ws) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
-    if (act != TOAD_ACT_NONE && act != TOAD_ACT_RELU) { set_error("%s: bad act %d", what, act); return TOAD_EINVAL; }
-    if (B <= 0 || H <= 0 || W <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || pad > 8 || H + 8 >= 32768 || W + 8 >= 32768) { set_error("%s: bad geometry", what); return TOAD_ESHAPE; }
-    if (Cin <= 0 || Cin % BK != 0) { set_error("%s: Cin must be a multiple of %d (use toad_im2col_nhwc_f32 + toad_linear_act_res_fwd_f32 otherwise)", what, BK); return TOAD_ESHAPE; }
-    if (Cout <= 0 || Cout > 512 || Cout % 4 != 0) { set_error("%s: implicit path needs Cout <= 512, a multiple of 4 (use im2col + linear for wider layers)", what); return TOAD_ESHAPE; }
-    const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
-    if (Ho < 1 || Wo < 1) { set_error("%s: empty output", what); return TOAD_ESHAPE; }
-    const int64_t M = (int64_t)B * Ho * Wo, K = (int64_t)kh * kw * Cin;
-    if ((uint64_t)B * H * W * Cin * 4 >= (1ull << 31) || M >= (1ll << 31)) { set_error("%s: activation too large for 32-bit offsets (split the batch)", what); return TOAD_ESHAPE; }
-    if (!aligned16(X) || !aligned16(Wf) || !aligned16(Y)) { set_error("%s: pointers must be 16-byte aligned", what); return TOAD_EALIGN; }
-    if (int rc = check_ws(ws, ws_bytes, M, Cout, K, what)) return rc;
-    if (!narrow_ok(M, Cout <= 128 ? Cout : 128, K, Cout, bias, residual, ws)) { set_error("%s: bias / residual must be 16-byte aligned", what); return TOAD_EALIGN; }
-    if (!x_gmax) {
-        float *g = ext_scratch_scalar(ws, M, Cout, K);
-        if (int rc = launch_gmax(X, (int64_t)B * H * W * Cin, g, st, what)) return rc;
-        x_gmax = g;
-    }
-    const ConvGeom cg{H, W, Cin, Ho, Wo, kw, stride, pad};
-    if (Cout <= 64)
-        return launch_narrow_t<2, 2, GATHER_CONV>(X, 0, x_gmax, Wf, K, Y, Cout, M, Cout, K, bias, act == TOAD_ACT_RELU, residual, cg, y_gmax, ws, st, what);
-    return launch_narrow_t<1, 4, GATHER_CONV>(X, 0, x_gmax, Wf, K, Y, Cout, M, Cout, K, bias, act == TOAD_ACT_RELU, residual, cg, y_gmax, ws, st, what);
-}
-extern "C" int toad_conv_nhwc_f32(const float *X, const float *Wf, const float *bias, const float *residual, float *Y, int B, int H,
-                                  int W, int Cin, int kh, int kw, int stride, int pad, int Cout, int act, void *ws, size_t ws_bytes,
-                                  void *stream) {
-    return ext_conv_nhwc(X, nullptr, Wf, bias, residual, Y, nullptr, B, H, W, Cin, kh, kw, stride, pad, Cout, act, ws, ws_bytes, (hipStream_t)stream,
-                         "toad_conv_nhwc_f32");
-}
-
-int toad::ext_stem_conv(const float *Xs, const float *x_gmax, const float *Wf, const float *bias, float *Y, float *y_gmax, int B, int Ho, int Wo, int act,
-                        void *ws, size_t ws_bytes, hipStream_t st, const char *what, bool pooled) {
-    if (!Xs || !Wf || !Y || !ws) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
-    if (act != TOAD_ACT_NONE && act != TOAD_ACT_RELU) { set_error("%s: bad act %d", what, act); return TOAD_EINVAL; }
-    if (B <= 0 || Ho <= 0 || Wo <= 0) { set_error("%s: bad geometry", what); return TOAD_ESHAPE; }
-    const int Hs = Ho + 3, Ws = Wo + 3;
-    const int64_t M = (int64_t)B * Ho * Wo;
-    if ((uint64_t)B * Hs * Ws * 48 >= (1ull << 31) || M >= (1ll << 31)) { set_error("%s: batch too large for 32-bit offsets (split it)", what); return TOAD_ESHAPE; }
-    if (!aligned16(Xs) || !aligned16(Wf) || !aligned16(Y)) { set_error("%s: pointers must be 16-byte aligned", what); return TOAD_EALIGN; }
-    if (int rc = check_ws(ws, ws_bytes, M, 64, 192, what)) return rc;
-    if (!narrow_ok(M, 64, 192, 64, bias, nullptr, ws)) { set_error("%s: bias must be 16-byte aligned", what); return TOAD_EALIGN; }
-    if (!x_gmax) {
-        float *g = ext_scratch_scalar(ws, M, 64, 192);
-        if (int rc = launch_gmax(Xs, (int64_t)B * Hs * Ws * 12, g, st, what)) return rc;
-        x_gmax = g;
-    }
-    const ConvGeom cg{Hs, Ws, 12, Ho, Wo, 0, 0, 0};
-    if (pooled) {
-        // the 3x3/2 max-pool in the stem's epilogue (gemm_stream.inc): a tile = two whole image rows, ReLU outputs
-        if (!stem_pool_ok(Ho, Wo, act)) { set_error("%s: the pooled stem needs Wo = 128, an even Ho and ReLU", what); return TOAD_ESHAPE; }
-        return launch_narrow_t<2, 2, GATHER_STEM_POOL>(Xs, 0, x_gmax, Wf, 192, Y, 64, M, 64, 192, bias, 1, nullptr, cg, y_gmax, ws, st, what);
-    }
-    return launch_narrow_t<2, 2, GATHER_STEM>(Xs, 0, x_gmax, Wf, 192, Y, 64, M, 64, 192, bias, act == TOAD_ACT_RELU, nullptr, cg, y_gmax, ws, st, what);
-}
-bool toad::stem_pool_ok(int Ho, int Wo, int act) { return Wo == 128 && Ho > 0 && Ho % 2 == 0 && act == TOAD_ACT_RELU; }
-extern "C" int toad_stem_conv_s2d_f32(const float *Xs, const float *Wf, const float *bias, float *Y, int B, int Ho, int Wo, int act,
-                                      void *ws, size_t ws_bytes, void *stream) {
-    return ext_stem_conv(Xs, nullptr, Wf, bias, Y, nullptr, B, Ho, Wo, act, ws, ws_bytes, (hipStream_t)stream, "toad_stem_conv_s2d_f32");
-}
-// The stem AND nn.MaxPool2d(3, 2, 1) as one kernel (models/resnet_custom.py:96-99): Yp [B, Ho/2, Wo/2, 64]. Shapes: Wo = 128, Ho a multiple of 32
-// (256 x 256 tiles); others take toad_stem_conv_s2d_f32 + toad_maxpool3x3s2_nhwc_f32.
-extern "C" int toad_stem_conv_pool_s2d_f32(const float *Xs, const float *Wf, const float *bias, float *Yp, int B, int Ho, int Wo, void *ws, size_t ws_bytes,
-                                           void *stream) {
-    return ext_stem_conv(Xs, nullptr, Wf, bias, Yp, nullptr, B, Ho, Wo, TOAD_ACT_RELU, ws, ws_bytes, (hipStream_t)stream, "toad_stem_conv_pool_s2d_f32", true);
-}
-
-// The stem + ReLU + 3x3/2 max-pool straight from the tiles (stem_halo.inc): no space-to-depth image, no fragment loads from global memory. norm == NULL: fp32 NCHW
-// tiles; otherwise uint8 NHWC tiles [B, H, 256, 3] and the six normalisation constants (stem_u8.h), checked before any device work. rg != NULL: the uint8 tiles
-// are read by origin from rg->region (X is not used; no alignment requirement on the region); with shrink == 2 tile b is the (2 H, 512) footprint at its origin,
-// box-filtered by the window loader (H, W stay the network tile's).
-bool toad::stem_nchw_pool_ok(int H, int W) { return W == 256 && H >= 4 && H % 4 == 0; }
-static int stem_pool_from_tiles(const void *X, bool u8, const float *norm, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W, void *ws,
-                                size_t ws_bytes, hipStream_t st, const char *what, const RegionSrc *rg = nullptr, int shrink = 1) {
-    if (rg) X = rg->region;
-    if (!X || (u8 && !norm) || !Wf || !Yp || !ws || (rg && !rg->origins)) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
-    if (B <= 0 || !stem_nchw_pool_ok(H, W)) {
-        set_error("%s: needs W = 256 and H %% 4 == 0 (other tiles: %stoad_stem_s2d_nchw_f32 + toad_stem_conv_s2d_f32 + toad_maxpool3x3s2_nhwc_f32)", what,
-                  rg ? "toad_tiles_u8_region_to_nchw_f32 + " : u8 ? "toad_tiles_u8_nhwc_to_nchw_f32 + " : "");
-        return TOAD_ESHAPE;
-    }
-    if (rg) { if (int rc = check_region_u8(*rg, H, W, what, shrink)) return rc; }
-    const int64_t M = (int64_t)B * (H / 2) * 128;
-    if (M >= (1ll << 31)) { set_error("%s: batch too large for 32-bit offsets (split it)", what); return TOAD_ESHAPE; }
-    if (u8) { if (int rc = check_norm_u8(norm, what)) return rc; }
-    if (u8 && !rg && (reinterpret_cast<uintptr_t>(X) & 1u) != 0) { set_error("%s: the uint8 tiles must be 2-byte aligned", what); return TOAD_EALIGN; }
-    if ((!u8 && !aligned16(X)) || !aligned16(Wf) || !aligned16(Yp) || (bias && !aligned16(bias))) { set_error("%s: pointers must be 16-byte aligned", what); return TOAD_EALIGN; }
-    if (int rc = check_ws(ws, ws_bytes, M, 64, 192, what)) return rc;
-    (void)cfg();
-    char *w = reinterpret_cast<char *>(ws) + (size_t)PB_GRID * PB * PB * sizeof(float);
-    unsigned short *planes = reinterpret_cast<unsigned short *>(w);
-    float *binv = reinterpret_cast<float *>(w + (size_t)64 * 6 * BK * 4);
-    hipLaunchKernelGGL(split_planes_narrow_h2_kernel<2>, dim3(16), dim3(256), 0, st, Wf, (int64_t)192, planes, binv, 64, 192, 1, 1, 12, 6);
-    if (int rc = check_launch(what)) return rc;
-    const int tiles = B * (H / 4);
-    const dim3 grid(std::min(tiles, 2 * PB_GRID));                  // two workgroups per CU
-    if (u8) {
-        StemNorm nrm;
-        for (int c = 0; c < 3; ++c) { nrm.a[c] = norm[c]; nrm.b[c] = norm[3 + c]; }
-        if (rg && shrink == 2)
-            hipLaunchKernelGGL(stem_halo_pool_kernel<SH_U8_REGION_BOX2>, grid, dim3(256), SH_SMEM, st, rg->region, planes, binv, bias, Yp, B, H, y_gmax, tiles,
-                               StemRegionArg{nrm, (int)rg->pitch, rg->origins});
-        else if (rg)
-            hipLaunchKernelGGL(stem_halo_pool_kernel<SH_U8_REGION>, grid, dim3(256), SH_SMEM, st, rg->region, planes, binv, bias, Yp, B, H, y_gmax, tiles,
-                               StemRegionArg{nrm, (int)rg->pitch, rg->origins});
-        else
-            hipLaunchKernelGGL(stem_halo_pool_kernel<SH_U8>, grid, dim3(256), SH_SMEM, st, reinterpret_cast<const unsigned char *>(X), planes, binv, bias, Yp, B, H, y_gmax, tiles, nrm);
-    } else {
-        hipLaunchKernelGGL(stem_halo_pool_kernel<SH_F32>, grid, dim3(256), SH_SMEM, st, reinterpret_cast<const float *>(X), planes, binv, bias, Yp, B, H, y_gmax, tiles, StemNoNorm{});
-    }
-    return check_launch(what);
-}
-int toad::ext_stem_nchw_pool(const float *X, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W, void *ws, size_t ws_bytes,
-                             hipStream_t st, const char *what) {
-    return stem_pool_from_tiles(X, false, nullptr, Wf, bias, Yp, y_gmax, B, H, W, ws, ws_bytes, st, what);
-}
-int toad::ext_stem_nhwc_u8_pool(const unsigned char *X8, const float *norm, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W,
-                                void *ws, size_t ws_bytes, hipStream_t st, const char *what) {
-    return stem_pool_from_tiles(X8, true, norm, Wf, bias, Yp, y_gmax, B, H, W, ws, ws_bytes, st, what);
-}
-int toad::ext_stem_region_u8_pool(const RegionSrc &rg, const float *norm, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W, void *ws,
-                                  size_t ws_bytes, hipStream_t st, const char *what, int shrink) {
-    return stem_pool_from_tiles(nullptr, true, norm, Wf, bias, Yp, y_gmax, B, H, W, ws, ws_bytes, st, what, &rg, shrink);
-}
-extern "C" int toad_stem_pool_nchw_f32(const float *X, const float *Wf, const float *bias, float *Yp, int B, int H, int W, void *ws, size_t ws_bytes, void *stream) {
-    return ext_stem_nchw_pool(X, Wf, bias, Yp, nullptr, B, H, W, ws, ws_bytes, (hipStream_t)stream, "toad_stem_pool_nchw_f32");
-}
-extern "C" int toad_stem_pool_nhwc_u8(const unsigned char *tiles, const float *norm, const float *Wf, const float *bias, float *Yp, int B, int H, int W, void *ws,
-                                      size_t ws_bytes, void *stream) {
-    return ext_stem_nhwc_u8_pool(tiles, norm, Wf, bias, Yp, nullptr, B, H, W, ws, ws_bytes, (hipStream_t)stream, "toad_stem_pool_nhwc_u8");
-}
-extern "C" int toad_stem_pool_region_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm, const float *Wf,
-                                        const float *bias, float *Yp, int B, int H, int W, void *ws, size_t ws_bytes, void *stream) {
-    return ext_stem_region_u8_pool(RegionSrc{region, pitch, Hr, Wr, origins}, norm, Wf, bias, Yp, nullptr, B, H, W, ws, ws_bytes, (hipStream_t)stream,
-                                   "toad_stem_pool_region_u8");
-}
-extern "C" int toad_stem_pool_region_box_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm, const float *Wf,
-                                            const float *bias, float *Yp, int B, int H, int W, int shrink, void *ws, size_t ws_bytes, void *stream) {
-    return ext_stem_region_u8_pool(RegionSrc{region, pitch, Hr, Wr, origins}, norm, Wf, bias, Yp, nullptr, B, H, W, ws, ws_bytes, (hipStream_t)stream,
-                                   "toad_stem_pool_region_box_u8", shrink);
 }
 
 extern "C" int toad_linear_dgrad_f32(const float *dY, const float *WT, const float *addend, const float *relu_src,

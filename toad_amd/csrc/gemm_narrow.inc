@@ -1,4 +1,4 @@
-// gemm_narrow.inc — part of the single translation unit gemm_f32.hip (included inside namespace toad): what the extractor's narrow-N GEMMs
+// gemm_narrow.inc — part of the extractor's translation unit conv.hip (included inside namespace toad): what the extractor's narrow-N GEMMs
 // (Cout <= 128: stem, layer1, layer2's 1x1-in / 3x3; models/resnet_custom.py:19-108) share - the convolution geometry, the gather modes
 // and the weight-plane format. The kernels that consume them are in gemm_stream.inc.
 // ------------------------------------------------------------------------------------------

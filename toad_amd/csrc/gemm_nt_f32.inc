@@ -179,18 +179,15 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f32_kernel(
 //    (deterministic) by nt_fixup_kernel, which also applies the epilogue. Small bags (fewer tiles
 //    than CUs) are parallelised by the same mechanism.
 // ------------------------------------------------------------------------------------------
-constexpr int PB = 256;                                         // tile edge
+// (PB = 256, the tile edge, PB_BLOCKS_PER_XCD = 32 and PB_GRID: h2_arith.h)
 constexpr int PB_TILE = PB * BK;                                // floats per operand stage
 constexpr int PB_SMEM = 2 * 2 * PB_TILE * (int)sizeof(float);   // 131,072 B: one block per CU
-constexpr int PB_BLOCKS_PER_XCD = 32;
-constexpr int PB_GRID = kNumXCD * PB_BLOCKS_PER_XCD;
 #ifndef TOAD_PB_GMAX
 #define TOAD_PB_GMAX 16
 #endif
 constexpr int PB_GMAX = TOAD_PB_GMAX;                           // max K-split of a remainder tile
 
-typedef __attribute__((address_space(1))) const void *gptr_t;
-typedef __attribute__((address_space(3))) void *lptr_t;
+typedef __attribute__((address_space(1))) const void *gptr_t;      // (lptr_t: h2_arith.h)
 
 struct NtPlan { int mt_x, tiles, rounds, rem, g; };
 // K-slices an XCD would cut its remainder tiles into on its own: as many as it has idle workgroups, at most nk / PB_GMAX, and - every slice costs a

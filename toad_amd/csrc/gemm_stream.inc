@@ -1,4 +1,4 @@
-// gemm_stream.inc — part of the single translation unit gemm_f32.hip (included inside namespace toad after gemm_narrow.inc, whose
+// gemm_stream.inc — part of the extractor's translation unit conv.hip (included inside namespace toad after gemm_narrow.inc, whose
 // weight-plane format, ConvGeom and GATHER_* modes it shares).
 // ------------------------------------------------------------------------------------------
 // Narrow-N NT kernel with a STREAMED A operand (round 3).   C = act(A' W^T + bias + addend), N tile = 64 or 128 columns.

@@ -1,4 +1,4 @@
-// stem_halo.inc — part of the single translation unit gemm_f32.hip (included inside namespace toad after gemm_stream.inc, whose weight-plane
+// stem_halo.inc — part of the extractor's translation unit conv.hip (included inside namespace toad after gemm_stream.inc, whose weight-plane
 // format, StreamCfg<2, 2> fragment addressing and pooled epilogue it shares).
 // ------------------------------------------------------------------------------------------
 // The extractor's stem straight from the caller's NCHW tiles: nn.Conv2d(3, 64, 7, stride 2, pad 3) + folded BN + ReLU + nn.MaxPool2d(3, 2, 1)

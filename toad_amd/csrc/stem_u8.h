@@ -1,5 +1,5 @@
-// stem_u8.h — the uint8 front end of the extractor: what conv.hip needs from gemm_f32.hip (where stem_halo.inc is compiled) and the
-// one check of the normalisation constants both translation units share. Included after common.h.
+// stem_u8.h — the uint8 front end of the extractor (conv.hip): the normalisation constants and the region descriptor as the stem kernels
+// (stem_halo.inc), the tile converters and the entry points take them, each with its one host-side check. Included after common.h.
 #pragma once
 #include <math.h>
 
@@ -15,11 +15,6 @@ static inline int check_norm_u8(const float *norm, const char *what) {
         if (!isfinite(norm[i])) { set_error("%s: norm[%d] is not finite (a_c = 1 / (255 std_c) with std_c != 0, b_c = -mean_c / std_c)", what, i); return TOAD_EINVAL; }
     return TOAD_OK;
 }
-
-// The stem + ReLU + 3x3/2 max-pool straight from uint8 NHWC tiles [B, H, 256, 3] (stem_halo.inc, uint8 form): ext_stem_nchw_pool's shapes,
-// workspace and output; X8 must be 2-byte aligned. norm as above, read at call time (the six floats travel as kernel arguments).
-int ext_stem_nhwc_u8_pool(const unsigned char *X8, const float *norm, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W,
-                          void *ws, size_t ws_bytes, hipStream_t st, const char *what);
 
 // Tiles read by origin from one decoded image (include/toad_hip.h, "tiles by origin"): region = uint8 [Hr, Wr, 3] on the device with a row pitch in bytes,
 // origins = DEVICE int32 [B][2], (x, y) of each tile's top-left pixel. What the host can see of it is checked here, by every entry point, before any
@@ -46,10 +41,5 @@ static inline int check_region_u8(const RegionSrc &rg, int H, int W, const char 
     if ((reinterpret_cast<uintptr_t>(rg.origins) & 3u) != 0) { set_error("%s: origins (int32 [B][2]) must be 4-byte aligned", what); return TOAD_EALIGN; }
     return TOAD_OK;
 }
-
-// ext_stem_nhwc_u8_pool with the tiles read by origin (stem_halo.inc, region form): any base address, any pitch parity. shrink == 2: the box form, H x W the
-// network tile and (2 H, 2 W) the footprint read.
-int ext_stem_region_u8_pool(const RegionSrc &rg, const float *norm, const float *Wf, const float *bias, float *Yp, float *y_gmax, int B, int H, int W,
-                            void *ws, size_t ws_bytes, hipStream_t st, const char *what, int shrink = 1);
 
 }  // namespace toad

@@ -146,8 +146,6 @@ static DropSeeds drop_seeds(float drop_p, uint64_t seed) {          // must matc
     return DropSeeds{seed + 1 * G, seed + 2 * G, seed + 3 * G, seed + 4 * G, drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f};
 }
 
-#define TOAD_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
-
 // ---- bags beyond the NT kernels' 32-bit row offsets (more than ~1.05 M patches): the same kernels over ROW CHUNKS -----------------------------
 // gemm_nt_h2_big_kernel addresses its A operand with 32-bit byte offsets (h2_nt_ok: M * lda * 4 < 2^32, i.e. 1,048,575 rows of the 1024-wide
 // bag). Rows of an NT product are independent, so a longer bag runs as consecutive launches over chunks of kChunkRows rows (a multiple of the

@@ -13,7 +13,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=f
 def build(extra=()):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objs = []
-    for src, out in ((os.path.join(HERE, "exp_duo.hip"), "exp_duo.o"), (os.path.join(CSRC, "capi.hip"), "capi_duo.o")):
+    # exp_duo.hip includes gemm_f32.hip whole; conv.hip is the extractor's unit (its ext_* layer and entries), which calls into the former
+    for src, out in ((os.path.join(HERE, "exp_duo.hip"), "exp_duo.o"), (os.path.join(CSRC, "conv.hip"), "conv_duo.o"), (os.path.join(CSRC, "capi.hip"), "capi_duo.o")):
         o = os.path.join(HERE, out)
         subprocess.check_call([hipcc] + FLAGS + list(extra) + ["-c", src, "-o", o])
         objs.append(o)

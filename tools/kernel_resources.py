@@ -1,5 +1,6 @@
 """Per-kernel register / spill report of one csrc/*.hip file (device pass only).
-    python tools/kernel_resources.py gemm_f32 [name regex]"""
+    python tools/kernel_resources.py gemm_f32 [name regex]      # the MIL GEMMs (gemm_h2.inc, gemm_pt.inc, gemm_tn.inc, gemm_nt_f32.inc)
+    python tools/kernel_resources.py conv [name regex]          # the extractor (gemm_stream.inc, stem_halo.inc, gathers and pools)"""
 import os, re, subprocess, sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
