@@ -543,6 +543,25 @@ int toad_region_heat_window_u8(const unsigned char *region, int64_t pitch, int H
                                const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm,
                                int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream);
 
+/* Several levels of the pyramid from ONE read of the window (additive to ABI 15 too): a viewer wants the full-resolution map next to one or two
+ * overviews, and every level is defined from the region's own box sums, never from the level above. `levels` is a bit set: bit k asks for down = 2^k,
+ * k = 0 .. 5. outs and out_pitches are HOST arrays of 6 entries, read before the call returns (as toad_heat_cells_blur reads its taps) and only at the
+ * set bits: outs[k] is a device pointer that receives uint8 [Hr / down][Wr / down][3] at out_pitches[k], byte for byte what toad_region_heat_window_u8
+ * writes for that down with the same other arguments. Each level keeps its own Ho = Hr / down and Wo = Wr / down: rows and columns a coarse level drops
+ * are still rendered at the finer ones, a level with Ho == 0 or Wo == 0 writes nothing and the others are still rendered, and per level the tent is
+ * off where cell == down. With D the largest level asked for, the refusals are toad_region_heat_window_u8's in its order with D for `down`, and where
+ * the down check sits: levels == 0 or a bit above 5 (TOAD_ESHAPE), D >= 8 and D > cell (TOAD_ESHAPE), outs[k] == NULL at a set bit (TOAD_EINVAL). So wx
+ * and wy are non-negative multiples of max(4, D), wx + Wr < 2^30, mask_down is a multiple of D, every out_pitches[k] asked for is at least 3 * Wo_k
+ * (TOAD_ESHAPE, where the out_pitch check sits), and the table holds the window. With two or more levels smooth = 1 at cell == 4 is refused
+ * (TOAD_ESHAPE, after the smooth check): the nine-neighbour tent is not done here. A set of one level IS toad_region_heat_window_u8 - the same kernel,
+ * the same bytes; two or more levels are one launch of heat_pyramid_kernel (csrc/heatmap.hip). No byte outside region + y * pitch + [0, 3 * Wr),
+ * 0 <= y < Hr, is read; no byte outside outs[k] + y * out_pitches[k] + [0, 3 * Wo_k), 0 <= y < Ho_k, is written. Region, mask and canvases may have
+ * any alignment and pitch; the canvases must not overlap each other or the region. */
+int toad_region_heat_pyramid_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, int wx, int wy, const int *cells, int Gy, int Gx, int cell,
+                                const unsigned char *lut, int alpha, unsigned levels, int smooth, const unsigned char *mask, int64_t mask_pitch, int Hm,
+                                int Wm, int mask_down, int mask_thresh, unsigned char *const *outs /* HOST, 6 device pointers */,
+                                const int64_t *out_pitches /* HOST, 6 */, void *stream);
+
 /* ---- Segmented tissue selection: CLAM's recipe - a median-filtered saturation channel of a low-resolution level, thresholded by a fixed value or by
  * Otsu's - defined in integers (additive to ABI 15 too). A second selector next to the per-pixel predicate above, which does not change; csrc/tissue_seg.hip.
  *   1 box filter  down in {1, 2, 4, 8, 16, 32} (TOAD_ESHAPE otherwise): Hp = Hr / down, Wp = Wr / down, partial boxes at the right and the bottom edge are

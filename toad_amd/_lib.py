@@ -109,6 +109,8 @@ SIGNATURES = {
     "toad_region_heat_thumb_u8": (I, [P, I64, I, I, P, I, I, I, P, I, I, I, P, I64, I, I, I, I, P, I64, P]),
     # ... and any of these canvases for a window (wx, wy after Hr, Wr) of the image that the cell table and the mask plane describe: additive to ABI 15
     "toad_region_heat_window_u8": (I, [P, I64, I, I, I, I, P, I, I, I, P, I, I, I, P, I64, I, I, I, I, P, I64, P]),
+    # ... and several levels of that pyramid from one read of the window (levels: a bit set; outs, out_pitches: HOST arrays of 6): additive to ABI 15
+    "toad_region_heat_pyramid_u8": (I, [P, I64, I, I, I, I, P, I, I, I, P, I, ctypes.c_uint, I, P, I64, I, I, I, I, P, P, P]),
     # ... and the Gaussian blur of the cell table in front of any of these canvases (the taps are a HOST array): additive to ABI 15
     "toad_heat_cells_blur": (I, [P, I, I, P, I, P, P]),
     # ... and the second tissue selector, CLAM's recipe in integers (saturation plane, median, histogram, cells): additive to ABI 15

@@ -26,7 +26,11 @@
 //   blur        (toad_heat_cells_blur) the cell table smoothed before it is rendered: a normalised convolution with a symmetric separable integer kernel
 //               of radius 1 .. 16 cells, absent cells and cells outside the table carrying no weight, absent cells staying absent.
 //
-// Four kernels:
+//   pyramid     (toad_region_heat_pyramid_u8) several of the six window canvases in one call, each byte for byte the window entry's: every level is defined
+//               from the region's own box sums, never from the level above, and box sums nest, so one read of the region serves them all.
+//
+// Five kernels:
+//   heat_pyramid_kernel<RB,MASK>           two or more levels from one read: 1, 2, 4 finished in the lane, 8, 16, 32 in heat_thumb_kernel's tail.
 //   heat_cells_blur_kernel                 a 16 x 64 tile of the cell table and its halo in LDS, a row pass and a column pass inside the workgroup.
 //   heat_thumb_kernel<DOWN,WINDOW>        the overview canvas: the same streaming pass with a box's lanes and waves reduced, one thread per canvas pixel blends.
 //   heat_cells_kernel                      one thread per cell: the covering tiles' index ranges in closed form from the lattice in cell units, a loop over them.
@@ -489,6 +493,237 @@ __global__ __launch_bounds__(256) void heat_thumb_kernel(const HeatPxArgs a, int
     for (int c = 0; c < 3; ++c) d[c] = (unsigned char)((al * (int)lut[3 * idx + c] + (256 - al) * m[c] + 128) >> 8);
 }
 
+// ---- the pyramid: toad_region_heat_pyramid_u8, several of the six canvases from ONE read of the region ----
+// Every level is defined from the region's own box sums, and box sums nest, so each canvas is byte for byte the one its own kernel above writes. The work
+// split is region_u8.h's over the window's Hr x Wr on strips of RB = max(16, D) rows, D the largest level asked for: a lane holds RW = RB / 4 = 4 or 8
+// rows of 4 pixels, 12 or 24 dwords in flight, loaded once; what does not exist reads as 0 and is never part of a box that is written.
+//   1, 2, 4   finished in the lane from each of its 4 x 4 blocks: heat_px_lane's arithmetic through heat_px4_each, with the own cell, the four tent
+//             neighbours and the mask bytes of a block loaded ONCE for its up to three levels. 2 x + 1 - cell .. 2 x + 4 - cell crosses no multiple of
+//             2 cell (cell >= 8 under the tent), so g0 is the block's for every level and only f moves with the level: f = f_block + down + 2 down j.
+//   8, 16, 32 heat_thumb_kernel's tail: the lane's column sums over its RW rows, 2, 4 and 8 lanes summed by three DPP moves, the waves of a box row
+//             meeting in 4.5 KB of LDS behind the one barrier all 256 threads reach; threads 0 .. 127, 128 .. 159 and 192 .. 199 - three different
+//             waves - each finish one canvas pixel of level 8, 16 and 32.
+// levels and smooth are run-time, wave-uniform values; the template is the strip height and MASK. Each level keeps its own Ho x Wo: Ho[k] = 0 marks a
+// level that was not asked for or is empty. Every canvas byte is written once by one lane, nothing outside oy pitch_k + [0, 3 Wo_k) is written, there is
+// no atomic. The tent at cell == 4 (heat_px_lane's SMOOTH 2) is not done here: the launcher refuses it.
+struct HeatPyrArgs {
+    HeatPxArgs a;                                                    // Hi x Wi = Hr x Wr; out, out_pitch unused
+    unsigned char *out[6]; int64_t pitch[6]; int Ho[6], Wo[6];
+    unsigned levels; int smooth;
+};
+
+// One 4 x 4 block of a lane -> its 4 / DOWN rows of 4 / DOWN pixels of canvas log2(DOWN), where they exist. own, v, fxb, fyb, tis, thr: the block's.
+template <int DOWN>
+__device__ __forceinline__ void heat_pyr_fine(const HeatPyrArgs &p, const unsigned *lut_s, const unsigned (&w)[4][3], unsigned x, int64_t yg, int own,
+                                              bool tent, const int (&v)[2][2], int fxb, int fyb, const unsigned (&tis)[4], int thr) {
+    constexpr int K = DOWN == 1 ? 0 : DOWN == 2 ? 1 : 2, NP = 4 / DOWN, OB = 12 / DOWN;
+    const int Ho = p.Ho[K];
+    const int64_t oy0 = yg / DOWN;
+    const int npx = min(4, p.Wo[K] * DOWN - (int)x);               // pixels of this lane the level consumes: <= 0, DOWN, .., 4
+    if (npx <= 0 || oy0 >= Ho) return;
+    int idx[NP][NP];
+    if (!tent) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+#pragma unroll
+            for (int j = 0; j < NP; ++j) idx[i][j] = max(own, 0);
+    } else {
+        const int cell = 1 << p.a.shift, c2 = 2 * cell;
+        int H[2][NP];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            const int fx = fxb + DOWN + 2 * DOWN * j;
+#pragma unroll
+            for (int r = 0; r < 2; ++r) H[r][j] = c2 * v[r][0] + fx * (v[r][1] - v[r][0]);
+        }
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int fy = fyb + DOWN + 2 * DOWN * i;
+#pragma unroll
+            for (int j = 0; j < NP; ++j) idx[i][j] = (c2 * H[0][j] + fy * (H[1][j] - H[0][j]) + 2 * cell * cell) >> (2 * p.a.shift + 2);
+        }
+    }
+    unsigned char *dst = p.out[K] + oy0 * p.pitch[K] + 3u * x / DOWN;
+    const int nout = 3 * npx / DOWN;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        if (oy0 + q >= Ho) break;
+        unsigned wq[DOWN][3], col[NP], al[NP], o[3];
+#pragma unroll
+        for (int r = 0; r < DOWN; ++r)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) wq[r][k] = w[q * DOWN + r][k];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            col[j] = lut_s[idx[q][j]];
+            al[j] = own >= 0 && (int)((tis[DOWN * q] >> (8 * DOWN * j)) & 0xFFu) > thr ? (unsigned)p.a.alpha : 0u;
+        }
+        heat_px4_each<DOWN>(wq, col, al, o);
+        unsigned char *d = dst + q * p.pitch[K];
+        if (npx == 4) {
+            heat_store4<DOWN>(d, o);
+        } else {
+#pragma unroll
+            for (int k = 0; k < OB; ++k)
+                if (k < nout) d[k] = (unsigned char)(o[k >> 2] >> (8 * (k & 3)));
+        }
+    }
+}
+
+template <int RB, bool MASK>
+__global__ __launch_bounds__(256) void heat_pyramid_kernel(const HeatPyrArgs p, const unsigned char *__restrict__ lut) {
+    constexpr int RW = RB / 4, NG = RW / 4;                          // rows per wave, 4-row blocks per lane
+    __shared__ unsigned lut_s[256];
+    __shared__ int part[3][3][4][32];                                // [level - 8, 16, 32][channel][wave][box of the chunk]
+    const HeatPxArgs &a = p.a;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    lut_s[tid] = (unsigned)lut[3 * tid] | ((unsigned)lut[3 * tid + 1] << 8) | ((unsigned)lut[3 * tid + 2] << 16);
+    __syncthreads();
+    const unsigned chunk = blockIdx.x % a.nchunks, rb = blockIdx.x / a.nchunks;
+    const unsigned x = chunk * 256u + (unsigned)lane * 4u, off = 3u * x;
+    const int64_t y0 = (int64_t)rb * RB + wave * RW;               // first row of this wave (may lie below Hr: then it reads nothing)
+    const unsigned char *src = a.region + y0 * a.pitch + off;
+    unsigned w[RW][3];
+    if (chunk * 256u + 256u <= (unsigned)a.Wi && y0 + RW <= a.Hi) {  // wave-uniform: all 768 bytes of all RW rows exist
+#pragma unroll
+        for (int r = 0; r < RW; ++r)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) w[r][k] = *reinterpret_cast<const u32_a1 *>(src + r * a.pitch + 4 * k);
+    } else {
+        const int rows = (int)max((int64_t)0, min((int64_t)RW, (int64_t)a.Hi - y0));
+        const int npx = x < (unsigned)a.Wi ? min(4, a.Wi - (int)x) : 0;
+#pragma unroll
+        for (int r = 0; r < RW; ++r) load_px4(src + r * a.pitch, r < rows ? npx : 0, w[r]);
+    }
+
+    if (p.levels & 7u) {                                             // levels 1, 2, 4: in the lane, block by block
+        const bool live = x < (unsigned)a.Wi;
+        const unsigned sx = x + (unsigned)a.wx;                    // the block's corner in the table's image: multiples of 4
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const int64_t yg = y0 + 4 * g, sy0 = yg + a.wy;
+            if (yg >= a.Hi) break;
+            const int gy = (int)(sy0 >> a.shift), gx = (int)(sx >> a.shift);
+            const int own = live ? min(a.cells[(int64_t)gy * a.Gx + gx], 255) : -1;
+            int v[2][2] = {{0, 0}, {0, 0}}, fxb = 0, fyb = 0;
+            if (p.smooth) {                                          // cell >= 8: 2 sx - cell and 2 sy0 - cell are multiples of 8
+                const int cell = 1 << a.shift, c2 = 2 * cell;
+                const int px = (int)(2u * sx) - cell;                // wx + Wr < 2^30, so 2 sx fits on every live lane
+                const int64_t py = 2 * sy0 - cell;
+                const int bx = px >> (a.shift + 1), by = (int)(py >> (a.shift + 1));
+                fxb = px & (c2 - 1); fyb = (int)(py & (c2 - 1));
+#pragma unroll
+                for (int r = 0; r < 2; ++r)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        const int yy = by + r, xx = bx + c;
+                        const bool in = live && yy >= 0 && yy < a.Gy && xx >= 0 && xx < a.Gx;
+                        const int t = in ? a.cells[(int64_t)yy * a.Gx + xx] : -1;
+                        v[r][c] = t >= 0 ? min(t, 255) : max(own, 0);
+                    }
+            }
+            unsigned tis[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+            int thr = -1;                                            // without a mask every byte is above it
+            if constexpr (MASK) {                                    // mask_down is a multiple of D >= 2: one byte a block, or (levels 1 and 2) two rows of two
+                thr = a.mask_thresh;
+                const unsigned mx = sx >> a.mshift;
+                const int64_t my = sy0 >> a.mshift;
+                const int have = live && mx < (unsigned)a.Wm ? a.Wm - (int)mx : 0;
+                const unsigned char *mp = a.mask + my * a.mask_pitch + mx;
+                if (a.mshift >= 2) {
+                    const unsigned t = load_mask<1>(mp, my < a.Hm ? min(have, 1) : 0) * 0x01010101u;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) tis[r] = t;
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) {
+                        const unsigned t = load_mask<2>(mp + r * a.mask_pitch, my + r < a.Hm ? min(have, 2) : 0);
+                        tis[2 * r] = tis[2 * r + 1] = (t & 0xFFu) * 0x0101u | (t >> 8) * 0x01010000u;
+                    }
+                }
+            }
+            unsigned w4[4][3];
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int k = 0; k < 3; ++k) w4[r][k] = w[4 * g + r][k];
+            const bool tent = p.smooth != 0;
+            if (p.levels & 1u) heat_pyr_fine<1>(p, lut_s, w4, x, yg, own, tent, v, fxb, fyb, tis, thr);
+            if (p.levels & 2u) heat_pyr_fine<2>(p, lut_s, w4, x, yg, own, tent, v, fxb, fyb, tis, thr);
+            if (p.levels & 4u) heat_pyr_fine<4>(p, lut_s, w4, x, yg, own, tent, v, fxb, fyb, tis, thr);
+        }
+    }
+
+    if (!(p.levels & 0x38u)) return;                                 // uniform over the workgroup: nobody waits at the barrier below
+    unsigned b[12];                                                // the 12 column sums over the wave's rows, each at most 8 * 255
+    column_sums<RW>(w, b);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int s2 = lanes_allreduce_sum<2>((int)(b[c] + b[c + 3] + b[c + 6] + b[c + 9]));
+        const int s4 = s2 + dpp_mov<0x4E>(s2), s8 = s4 + dpp_mov<0x141>(s4);
+        if ((lane & 1) == 0) part[0][c][wave][lane >> 1] = s2;
+        if ((lane & 3) == 0) part[1][c][wave][lane >> 2] = s4;
+        if ((lane & 7) == 0) part[2][c][wave][lane >> 3] = s8;
+    }
+    __syncthreads();
+    int k, t;
+    if (tid < 128) { k = 3; t = tid; }
+    else if (tid < 160) { k = 4; t = tid - 128; }
+    else if (tid >= 192 && tid < 200) { k = 5; t = tid - 192; }
+    else return;
+    if (p.Ho[k] == 0) return;
+    const int down = 1 << k, band = t >> (8 - k), bx = t & ((256 >> k) - 1), wpb = down / RW;      // 256 / down boxes a chunk, RB / down box rows
+    if (band >= (RB >> k)) return;
+    const int64_t oy = (int64_t)rb * (RB >> k) + band;
+    const unsigned ox = chunk * (256u >> k) + (unsigned)bx;
+    if (oy >= p.Ho[k] || ox >= (unsigned)p.Wo[k]) return;
+    int m[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        int s = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < wpb) s += part[k - 3][c][band * wpb + j][bx];
+        m[c] = (s + (1 << (2 * k - 1))) >> (2 * k);
+    }
+    const int64_t py0 = oy * down + a.wy;                          // the box's corner in the table's image
+    const int px0 = (int)(ox * down) + a.wx;
+    const int own = min(a.cells[(py0 >> a.shift) * a.Gx + (px0 >> a.shift)], 255);
+    int idx = max(own, 0);
+    if (p.smooth && a.shift != k) {                                  // cell == down: the tent is the own value
+        const int cell = 1 << a.shift, c2 = 2 * cell;
+        const int px = 2 * px0 + down - cell;                      // wx + Wr < 2^30, so 2 x fits
+        const int64_t py = 2 * py0 + down - cell;
+        const int gx0 = px >> (a.shift + 1), fx = px & (c2 - 1);
+        const int gy0 = (int)(py >> (a.shift + 1)), fy = (int)(py & (c2 - 1));
+        int H[2];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            int v[2];
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int yy = gy0 + r, xx = gx0 + c;
+                const bool in = yy >= 0 && yy < a.Gy && xx >= 0 && xx < a.Gx;
+                const int tv = in ? a.cells[(int64_t)yy * a.Gx + xx] : -1;
+                v[c] = tv >= 0 ? min(tv, 255) : idx;
+            }
+            H[r] = c2 * v[0] + fx * (v[1] - v[0]);
+        }
+        idx = (c2 * H[0] + fy * (H[1] - H[0]) + 2 * cell * cell) >> (2 * a.shift + 2);
+    }
+    bool tissue = true;
+    if (MASK) {
+        const int64_t my = py0 >> a.mshift;
+        const int mx = px0 >> a.mshift;
+        tissue = my < a.Hm && mx < a.Wm && (int)a.mask[my * a.mask_pitch + mx] > a.mask_thresh;
+    }
+    const int al = own >= 0 && tissue ? a.alpha : 0;               // alpha' = 0 leaves m: (256 m + 128) >> 8
+    const unsigned col = lut_s[idx];
+    unsigned char *d = p.out[k] + oy * p.pitch[k] + 3u * ox;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) d[c] = (unsigned char)((al * (int)((col >> (8 * c)) & 255u) + (256 - al) * m[c] + 128) >> 8);
+}
+
 }  // namespace toad
 
 using namespace toad;
@@ -676,4 +911,100 @@ extern "C" int toad_region_heat_window_u8(const unsigned char *region, int64_t p
                                           int Hm, int Wm, int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream) {
     return launch_heat_blend("toad_region_heat_window_u8", "the region, the mask and the canvas", false, true, region, pitch, Hr, Wr, wx, wy, cells, Gy, Gx, cell, lut,
                              alpha, down, smooth, mask, mask_pitch, Hm, Wm, mask_down, mask_thresh, out, out_pitch, stream);
+}
+
+// The pyramid entry: the window entry's checks in the window entry's order, taken over the set of levels - D, the largest, stands where `down` stood, and the
+// checks of the set and of its canvases where the down check sat. One level is the window entry itself; two or more are ONE launch of heat_pyramid_kernel.
+extern "C" int toad_region_heat_pyramid_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, int wx, int wy, const int *cells, int Gy, int Gx, int cell,
+                                           const unsigned char *lut, int alpha, unsigned levels, int smooth, const unsigned char *mask, int64_t mask_pitch,
+                                           int Hm, int Wm, int mask_down, int mask_thresh, unsigned char *const *outs, const int64_t *out_pitches, void *stream) {
+    const char *what = "toad_region_heat_pyramid_u8";
+    if (!region || !cells || !lut || !outs || !out_pitches) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (int rc = check_cell(what, cell)) return rc;
+    if (int rc = check_hw(what, "Hr", Hr, "Wr", Wr)) return rc;
+    if (alpha < 0 || alpha > 256) { set_error("%s: alpha = %d must lie in [0, 256] (256 = the colour alone)", what, alpha); return TOAD_ESHAPE; }
+    if (levels == 0 || levels > 63u) {
+        set_error("%s: levels = 0x%x is not a non-empty set of bits 0 .. 5 (bit k asks for down = 2^k, down in 1 .. 32)", what, levels);
+        return TOAD_ESHAPE;
+    }
+    int kmax = 0, nlev = 0;
+    for (int k = 0; k < 6; ++k)
+        if (levels >> k & 1u) { kmax = k; ++nlev; }
+    const int D = 1 << kmax;
+    if (D >= 8 && D > cell) {
+        set_error("%s: down = %d, the largest level, exceeds cell = %d (a canvas box must lie in one cell)", what, D, cell);
+        return TOAD_ESHAPE;
+    }
+    for (int k = 0; k < 6; ++k)
+        if ((levels >> k & 1u) && !outs[k]) { set_error("%s: null pointer (outs[%d], the canvas of down = %d)", what, k, 1 << k); return TOAD_EINVAL; }
+    if (nlev == 1)                                                   // the same kernel, the same bytes, the same time
+        return launch_heat_blend(what, "the region, the mask and the canvases", false, true, region, pitch, Hr, Wr, wx, wy, cells, Gy, Gx, cell, lut, alpha, D, smooth,
+                                 mask, mask_pitch, Hm, Wm, mask_down, mask_thresh, outs[kmax], out_pitches[kmax], stream);
+    const int walign = D > 4 ? D : 4;
+    if (wx < 0 || wy < 0 || wx % walign || wy % walign) {
+        set_error("%s: window (wx, wy) = (%d, %d) is negative or not a multiple of max(4, down) = %d, down the largest level (a lane's 4 x 4 block and a "
+                  "canvas box must lie in one cell and in one mask pixel)", what, wx, wy, walign);
+        return TOAD_ESHAPE;
+    }
+    if ((int64_t)wx + Wr >= (1ll << 30)) {
+        set_error("%s: window too far right: wx + Wr = %lld must stay below 2^30 (doubled tent coordinates in 32 bits)", what, (long long)wx + Wr);
+        return TOAD_ESHAPE;
+    }
+    if (smooth != 0 && smooth != 1) { set_error("%s: smooth = %d must be 0 or 1", what, smooth); return TOAD_EINVAL; }
+    if (smooth && cell == 4) {
+        set_error("%s: smooth at cell = 4 is not done for more than one level (the nine-neighbour tent: render those levels one by one)", what);
+        return TOAD_ESHAPE;
+    }
+    if (int rc = check_region_pitch(what, pitch, Wr)) return rc;
+    int mshift = 0;
+    if (mask) {
+        if (mask_down != 1 && mask_down != 2 && mask_down != 4 && mask_down != 8 && mask_down != 16 && mask_down != 32) {
+            set_error("%s: mask_down = %d is not one of 1, 2, 4, 8, 16, 32", what, mask_down);
+            return TOAD_ESHAPE;
+        }
+        if (mask_down % D) {
+            set_error("%s: mask_down = %d is not a multiple of down = %d, the largest level (a canvas box must lie in one mask pixel)", what, mask_down, D);
+            return TOAD_ESHAPE;
+        }
+        if (Hm < 0 || Wm < 0) { set_error("%s: Hm x Wm = %d x %d must not be negative", what, Hm, Wm); return TOAD_ESHAPE; }
+        if (int rc = check_plane_pitch(what, Wm, "mask_pitch", mask_pitch)) return rc;
+        if (int rc = check_u8(what, "mask_thresh", mask_thresh)) return rc;
+        while ((1 << mshift) < mask_down) ++mshift;
+    }
+    for (int k = 0; k < 6; ++k)
+        if ((levels >> k & 1u) && out_pitches[k] < 3 * (int64_t)(Wr >> k)) {
+            set_error("%s: out_pitches[%d] = %lld is less than a row of the canvas of down = %d (3 Wo = %lld bytes)", what, k, (long long)out_pitches[k], 1 << k,
+                      3ll * (Wr >> k));
+            return TOAD_ESHAPE;
+        }
+    const int64_t gy_end = ((int64_t)wy + Hr + cell - 1) / cell, gx_end = ((int64_t)wx + Wr + cell - 1) / cell;
+    if (gy_end > Gy || gx_end > Gx) {
+        set_error("%s: the window ends at cell row %lld and cell column %lld, beyond the table's Gy x Gx = %d x %d (ceil((wy + Hr) / cell) <= Gy and "
+                  "ceil((wx + Wr) / cell) <= Gx)", what, (long long)gy_end, (long long)gx_end, Gy, Gx);
+        return TOAD_ESHAPE;
+    }
+    const int rb = strip_rows(D);
+    const int64_t nchunks = ((int64_t)Wr + 255) / 256, blocks = nchunks * (((int64_t)Hr + rb - 1) / rb);
+    if (int rc = check_blocks(what, "region", blocks)) return rc;
+    if (!aligned4(cells)) {
+        set_error("%s: cells (int32 [Gy][Gx]) must be 4-byte aligned (the region, the mask and the canvases may have any alignment)", what);
+        return TOAD_EALIGN;
+    }
+    int shift = 2;
+    while ((1 << shift) < cell) ++shift;
+    HeatPyrArgs p = {};
+    p.a = {region, pitch, Hr, Wr, cells, Gy, Gx, shift, alpha, mask, mask_pitch, Hm, Wm, mshift, mask_thresh, nullptr, 0, (unsigned)nchunks, wx, wy};
+    p.smooth = smooth;
+    for (int k = 0; k < 6; ++k) {
+        const int Ho = Hr >> k, Wo = Wr >> k;
+        if (!(levels >> k & 1u) || Ho == 0 || Wo == 0) continue;     // an empty level writes nothing; the others are still rendered
+        p.levels |= 1u << k;
+        p.out[k] = outs[k]; p.pitch[k] = out_pitches[k]; p.Ho[k] = Ho; p.Wo[k] = Wo;
+    }
+    if (p.levels == 0) return TOAD_OK;
+#define TOAD_PYR(R, M) hipLaunchKernelGGL((heat_pyramid_kernel<R, M>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, lut)
+    if (rb == 32) { if (mask) TOAD_PYR(32, true); else TOAD_PYR(32, false); }
+    else { if (mask) TOAD_PYR(16, true); else TOAD_PYR(16, false); }
+#undef TOAD_PYR
+    return check_launch(what);
 }

@@ -292,10 +292,24 @@ def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region
     working on ``tile`` and ``stride`` in region pixels. A bad value, or a footprint it does not divide, raises ValueError before the selection runs.
 
     Not done here: a sigma per axis for tiles that are not square, radii above 16 cells (``blur=True`` on lattices whose cell is 16 or less), CLAM's
-    second blur of the coloured image, several levels of the vis-level pyramid in one call (one level per call is done) and saving the image. A slide
+    second blur of the coloured image and saving the image. ``down`` may be a sequence of distinct levels from 1 .. 32: ``canvas`` is then a dict
+    ``{down: tensor}`` and ``out`` a dict of that kind or None; one selection, one scoring, one cell table and one read of the region
+    (``heatmap.attention_pyramid``), each level byte for byte the call with that ``down``; the lattice's cell must be at least the largest level and,
+    with ``tissue_mask=True``, the segment ``down`` a multiple of it (ValueError otherwise, before anything is launched). A slide
     that arrives strip by strip: ``slide_attention_heatmap`` (no seams, one colour scale); the segmented selector there still works on one region."""
-    from .heatmap import attention_canvas, blur_taps
+    from .heatmap import attention_canvas, attention_pyramid, blur_taps
     from .tissue import _lattice_args, lattice_cell
+    levels = None                                                   # a sequence of levels: one scoring, one cell table, one read of the region
+    if isinstance(down, (tuple, list)):
+        from .ops import heat_downs_arg
+        levels = heat_downs_arg("region_tissue_attention_heatmap", down)
+        h, w, sy, sx, x0, y0 = _lattice_args(tile, stride, (0, 0))
+        cell = lattice_cell((h, w), (sy, sx), (x0, y0))
+        if max(levels) > cell:
+            raise ValueError(f"region_tissue_attention_heatmap: down = {max(levels)}, the largest level, exceeds the lattice's cell = {cell}: a canvas box "
+                             "must lie in one cell")
+        if out is not None and (not isinstance(out, dict) or set(out) != set(levels)):
+            raise ValueError(f"region_tissue_attention_heatmap: with down = {levels} out must be None or a dict with one canvas per level")
     if shrink != 1:                                                 # refuse a bad shrink before the selection runs; the extractor checks it again
         from .ops import shrunk_tile
         shrunk_tile(tile, shrink)
@@ -304,11 +318,19 @@ def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region
         blur_taps(blur, (h, w), lattice_cell((h, w), (sy, sx), (x0, y0)))
     if tissue_mask and isinstance(segment, dict):                   # (without a dict _select_origins refuses)
         seg_down = _segment_down(segment)
-        if down not in (1, 2, 4, 8, 16, 32) or not isinstance(seg_down, int) or seg_down % down:
+        if levels is not None:
+            if not isinstance(seg_down, int) or seg_down % max(levels):
+                raise ValueError(f"tissue_mask=True: the segment down = {seg_down!r} must be a multiple of the largest canvas down = {max(levels)} (a canvas "
+                                 "box must lie in one mask pixel)")
+        elif down not in (1, 2, 4, 8, 16, 32) or not isinstance(seg_down, int) or seg_down % down:
             raise ValueError(f"tissue_mask=True: the segment down = {seg_down!r} must be a multiple of the canvas down = {down!r} (a canvas box must lie "
                              "in one mask pixel)")
     origins, scores, mask = _tissue_scores(extractor, model, region, tile, stride, min_fraction, sat_thresh, val_min, bag_dtype, True, segment,
                                            return_mask=tissue_mask, shrink=shrink)
+    if levels is not None:
+        canvases = attention_pyramid(region, origins, scores, tile=tile, stride=stride, alpha=alpha, downs=levels, lut=lut,
+                                     outs=None if out is None else [out[d] for d in levels], smooth=smooth, mask=mask, thresh=thresh, binarize=binarize, blur=blur)
+        return origins, scores, dict(zip(levels, canvases))
     return origins, scores, attention_canvas(region, origins, scores, tile=tile, stride=stride, alpha=alpha, down=down, lut=lut, out=out, smooth=smooth,
                                              mask=mask, thresh=thresh, binarize=binarize, blur=blur)
 
@@ -335,11 +357,15 @@ def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_
     ``region_attention_scores``. A slide without a tissue tile gives empty origins, empty scores and the box-filtered slide; neither the extractor nor
     the model is called. With the same tiles the canvas is byte for byte ``attention_canvas`` of the whole slide.
 
+    ``down`` may be a sequence of distinct levels from 1 .. 32: ``canvas`` is then a dict ``{down: tensor}`` and ``out`` such a dict or None. Still one
+    scoring and one cell table, and pass 2 is ONE walk over the strips - ``heatmap.window_pyramid`` renders every level of a strip from one read of
+    it; render starts are multiples of max(4, the largest level), and each level is byte for byte the call with that ``down``.
+
     Not done here: the segmented selector across strips - its median, closing and component steps reach across strip seams, so
     ``tissue.segmented_tissue_origins`` still works on one region per call; make that selection on an overview level and pass it in through
     ``origins=`` and ``mask=``. Blocks that are not full-width strips (``heatmap.window_canvas`` renders any window; this walk does not), and the
     "not done" list of ``region_tissue_attention_heatmap`` except seams."""
-    from .heatmap import slide_cells, strip_plan, window_canvas
+    from .heatmap import slide_cells, strip_plan, window_canvas, window_pyramid
     from .heatmap import blur_taps
     from .tissue import _lattice_args, lattice_cell, tissue_origins
     hs, ws = slide_hw
@@ -348,7 +374,16 @@ def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_
         from .ops import shrunk_tile
         shrunk_tile(tile, shrink)
     cell = lattice_cell((h, w), (sy, sx), (x0, y0))
-    if down in (8, 16, 32) and cell < down:
+    levels = None                                                   # a sequence of levels: pass 2 renders them all in one walk over the strips
+    if isinstance(down, (tuple, list)):
+        from .ops import heat_downs_arg
+        levels = heat_downs_arg("slide_attention_heatmap", down)
+        if cell < max(levels):
+            raise ValueError(f"slide_attention_heatmap: down = {max(levels)}, the largest level, exceeds the lattice's cell = {cell}: a canvas box must "
+                             "lie in one cell")
+        if out is not None and (not isinstance(out, dict) or set(out) != set(levels)):
+            raise ValueError(f"slide_attention_heatmap: with down = {levels} out must be None or a dict with one canvas per level")
+    elif down in (8, 16, 32) and cell < down:
         raise ValueError(f"slide_attention_heatmap: down = {down} exceeds the lattice's cell = {cell}: a canvas box must lie in one cell")
     blur_taps(blur, (h, w), cell)
     shapes = []
@@ -388,6 +423,18 @@ def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_
         found, scores = np.zeros((0, 2), dtype=np.int64), torch.empty(0, dtype=torch.float32, device=device)
     cells, cell = slide_cells((hs, ws), found, scores, (h, w), (sy, sx), (x0, y0), thresh=thresh, binarize=binarize, blur=blur,
                               name="slide_attention_heatmap")
+    if levels is not None:
+        canvases = {}
+        for d in levels:
+            c = torch.empty((hs // d, ws // d, 3), dtype=torch.uint8, device=device) if out is None else out[d]
+            if not isinstance(c, torch.Tensor) or tuple(c.shape) != (hs // d, ws // d, 3):
+                raise ValueError(f"slide_attention_heatmap: out[{d}] must be a uint8 [{hs // d},{ws // d},3] tensor on the strips' device")
+            canvases[d] = c
+        for (region, y), p in zip(strips, plan):                    # pass 2: each strip's own rows of every level's canvas, one read of the strip
+            r0, r1 = p["render"]
+            window_pyramid(region[r0 - y:r1 - y], (0, r0), cells, cell, alpha=alpha, downs=levels, lut=lut,
+                           outs=[canvases[d][r0 // d:r0 // d + (r1 - r0) // d] for d in levels], smooth=smooth, mask=mask)
+        return found, scores, canvases
     ho, wo = hs // down, ws // down
     if out is None:
         out = torch.empty((ho, wo, 3), dtype=torch.uint8, device=device)

@@ -43,7 +43,8 @@ cells on the usual 256 / 64 lattice, a field band-limited far below the cell pit
 
 Conventions as in ``toad_amd.tissue``: ``tile`` = int or (H, W), ``stride`` = int or (sy, sx), ``origin`` = (x, y) of the lattice's first tile.
 Not done here: a sigma per axis for tiles that are not square, radii above 16 cells (``blur=True`` on lattices whose cell is 16 or less), CLAM's second
-blur of the coloured image, several levels of the vis-level pyramid in one call (one level per call is done) and saving images.
+blur of the coloured image and saving images. Several levels of the vis-level pyramid come from one read of the region: ``window_pyramid`` and
+``attention_pyramid`` (``ops.region_heat_pyramid``), and ``down`` as a sequence in the two ``eval`` heat-map calls.
 
 A slide that arrives from the decoder in strips or blocks is rendered window by window with no seams: ``slide_cells`` builds the cell table of the whole
 slide - only the lattice and the extent matter to it -, ``window_canvas`` renders one decoded window against that table (``ops.region_heat_window``: a
@@ -238,6 +239,21 @@ def window_canvas(region: torch.Tensor, window, cells: torch.Tensor, cell: int, 
                                   mask_thresh=t if plane is not None else 0, out=out)
 
 
+def window_pyramid(region: torch.Tensor, window, cells: torch.Tensor, cell: int, alpha=102, downs=(1, 4, 16), lut=None, outs=None, smooth: bool = False,
+                   mask=None) -> tuple:
+    """``window_canvas`` at several levels from ONE read of the window: a tuple of uint8 [Hr // down, Wr // down, 3] canvases in the order of ``downs``,
+    each byte for byte ``window_canvas`` at that ``down``. ``downs``: distinct values from 1 .. 32; ``window`` = (wx, wy) in multiples of
+    max(4, max(downs)), and the lattice's cell and the mask's ``mask_down`` must suit max(downs) as they must suit ``down`` there. ``outs``: None or one
+    view per level, for example the window's rows and columns of per-level slide canvases. Through ``ops.region_heat_pyramid``: one launch."""
+    a = _alpha_arg(alpha)
+    if not isinstance(smooth, bool):
+        raise ValueError(f"window_pyramid: smooth must be a bool, got {smooth!r}")
+    plane, t, mask_down = _mask_arg(mask)
+    lut = jet_lut(region.device) if lut is None else lut
+    return ops.region_heat_pyramid(region, window, cells, cell, lut, a, downs, smooth=smooth, mask=plane, mask_down=mask_down if plane is not None else None,
+                                   mask_thresh=t if plane is not None else 0, outs=outs)
+
+
 def strip_plan(slide_hw, strips, tile=256, stride=None, origin=(0, 0), down: int = 1):
     """How a slide of ``slide_hw`` = (Hs, Ws) pixels that arrives as full-width row strips is scored and rendered strip by strip. Host arithmetic only.
     ``strips`` = [(y_k, H_k)]: strip k holds the slide's rows y_k .. y_k + H_k, sorted, each abutting or overlapping the one before. One dict per strip:
@@ -248,10 +264,13 @@ def strip_plan(slide_hw, strips, tile=256, stride=None, origin=(0, 0), down: int
     * ``render`` = (r0, r1): the slide rows it renders, from max(y_k, the end of the previous strip) to its own end.
 
     ValueError for strips that are not sorted or leave a gap, that do not cover 0 .. Hs, for a lattice tile row that lies whole in no strip (the strips
-    must overlap by at least tile - stride rows), and for a render start that is not a multiple of max(4, ``down``) (``ops.region_heat_window``)."""
+    must overlap by at least tile - stride rows), and for a render start that is not a multiple of max(4, ``down``) (``ops.region_heat_window``).
+    ``down`` may be a sequence of levels (``window_pyramid``): the alignment is then that of its largest."""
     hs, ws = slide_hw
     h, w, sy, sx, x0, y0 = _lattice_args(tile, stride, origin)
     _, ny = lattice(hs, ws, (h, w), (sy, sx), (x0, y0))
+    if isinstance(down, (tuple, list)):
+        down = max(ops.heat_downs_arg("strip_plan", down))
     if down not in ops.HEAT_DOWNS + ops.HEAT_THUMB_DOWNS:
         raise ValueError(f"strip_plan: down must be one of {ops.HEAT_DOWNS + ops.HEAT_THUMB_DOWNS}, got {down!r}")
     strips = [(int(y), int(n)) for y, n in strips]
@@ -318,3 +337,26 @@ def attention_canvas(region: torch.Tensor, origins, scores: torch.Tensor, tile=2
     blend = ops.region_heat_thumb if thumb else ops.region_heat_blend_px
     return blend(region, cells, cell, lut, a, down, smooth=smooth, mask=plane, mask_down=mask_down if plane is not None else None,
                  mask_thresh=t if plane is not None else 0, out=out)
+
+
+def attention_pyramid(region: torch.Tensor, origins, scores: torch.Tensor, tile=256, stride=None, origin=(0, 0), alpha=102, downs=(1, 4, 16), lut=None,
+                      score_range=(0, 1), outs=None, smooth: bool = False, mask=None, thresh=None, binarize: bool = False, blur=False) -> tuple:
+    """``attention_canvas`` at several levels: a tuple of uint8 [Hr // down, Wr // down, 3] canvases in the order of ``downs``, each byte for byte
+    ``attention_canvas`` at that ``down``. ``slide_cells`` builds the cell table ONCE, ``window_pyramid`` at (0, 0) renders every level from one read of
+    the region. The lattice's cell must be at least max(downs) where that is 8 or more, a mask's ``mask_down`` a multiple of max(downs); ``smooth`` on a
+    lattice whose cell is 4 is not done for more than one level. The other keywords: ``attention_canvas``; ``outs``: ``window_pyramid``."""
+    _, hr, wr = ops._region_pitch(region, "attention_pyramid")
+    ds = ops.heat_downs_arg("attention_pyramid", downs)
+    h, w, sy, sx, x0, y0 = _lattice_args(tile, stride, origin)
+    cell = lattice_cell((h, w), (sy, sx), (x0, y0))
+    if max(ds) > cell:
+        raise ValueError(f"attention_pyramid: down = {max(ds)}, the largest level, exceeds the lattice's cell = {cell} (tile {(h, w)}, stride {(sy, sx)}, "
+                         f"origin {(x0, y0)}): a canvas box must lie in one cell")
+    _alpha_arg(alpha)
+    if not isinstance(scores, torch.Tensor) or scores.device != region.device:
+        raise ValueError(f"attention_pyramid: scores must be a tensor on the region's device ({region.device}), got "
+                         f"{scores.device if isinstance(scores, torch.Tensor) else type(scores).__name__}")
+    if not isinstance(smooth, bool):
+        raise ValueError(f"attention_pyramid: smooth must be a bool, got {smooth!r}")
+    cells, cell = slide_cells((hr, wr), origins, scores, (h, w), (sy, sx), (x0, y0), score_range, thresh, binarize, blur, name="attention_pyramid")
+    return window_pyramid(region, (0, 0), cells, cell, alpha=alpha, downs=ds, lut=lut, outs=outs, smooth=smooth, mask=mask)

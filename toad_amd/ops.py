@@ -1706,6 +1706,93 @@ def region_heat_window(region: torch.Tensor, window, cells: torch.Tensor, cell: 
     return _heat_blend("region_heat_window", region, cells, cell, lut, alpha, down, smooth, mask, mask_down, mask_thresh, out, window)
 
 
+def heat_downs_arg(name: str, downs) -> tuple:
+    """The ``downs`` of the pyramid calls as a tuple of Python ints, or ValueError: a non-empty sequence of distinct values from 1, 2, 4, 8, 16, 32."""
+    legal = HEAT_DOWNS + HEAT_THUMB_DOWNS
+    if isinstance(downs, (str, bytes, torch.Tensor)) or not hasattr(downs, "__len__") or not hasattr(downs, "__iter__"):
+        raise ValueError(f"{name}: downs must be a non-empty sequence of distinct values from {legal}, got {downs!r}")
+    ds = tuple(downs)
+    if not ds or any(isinstance(d, bool) or not isinstance(d, numbers.Integral) or d not in legal for d in ds) or len(set(ds)) != len(ds):
+        raise ValueError(f"{name}: downs must be a non-empty sequence of distinct values from {legal}, got {downs!r}")
+    return tuple(int(d) for d in ds)
+
+
+def region_heat_pyramid(region: torch.Tensor, window, cells: torch.Tensor, cell: int, lut: torch.Tensor, alpha: int, downs, smooth: bool = False,
+                        mask=None, mask_down=None, mask_thresh: int = 0, outs=None) -> tuple:
+    """Several levels of region_heat_window from ONE read of the window (toad_region_heat_pyramid_u8; include/toad_hip.h): a tuple of uint8
+    [Hr // down, Wr // down, 3] canvases in the order of ``downs``, each byte for byte what region_heat_window gives for that ``down`` with the same other
+    arguments. ``downs`` is a non-empty sequence of distinct values from 1, 2, 4, 8, 16, 32; with D = max(downs) the rules are region_heat_window's at
+    ``down`` = D: D <= ``cell``, ``window`` = (wx, wy) non-negative multiples of max(4, D), wx + Wr < 2^30, the table holds the window, ``mask_down`` a
+    multiple of D. Each level keeps its own extent: the rows and columns a coarse level drops are still rendered at the finer ones, and an empty level
+    is returned empty. ``outs`` is None or one view per level, each as ``out`` of region_heat_window; no two of them may share storage, and none may
+    share storage with the region. ``smooth`` at ``cell`` = 4 with more than one level is not done (ValueError). ValueError for anything else, before the
+    library is called. One launch for any number of levels (one level: region_heat_window's kernel), no synchronisation; a call in which every level is
+    empty launches nothing."""
+    name = "region_heat_pyramid"
+    ds = heat_downs_arg(name, downs)
+    top = max(ds)
+    pitch, hr, wr = _region_pitch(region, name)
+    _cell_arg(name, cell)
+    if top > cell:
+        raise ValueError(f"{name}: down = {top}, the largest level, exceeds cell = {cell}: a canvas box must lie in one cell")
+    if not isinstance(alpha, int) or isinstance(alpha, bool) or not 0 <= alpha <= 256:
+        raise ValueError(f"{name}: alpha must be an int in [0, 256], got {alpha!r}")
+    _chk(cells, "cells", dtype=torch.int32)
+    wx, wy = _heat_window_arg(name, window, top, cell, hr, wr, cells)
+    if not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3) or not lut.is_contiguous() or lut.device != region.device:
+        raise ValueError(f"{name}: lut must be a contiguous uint8 [256,3] tensor on the region's device")
+    if not isinstance(smooth, (bool, int)) or smooth not in (0, 1):
+        raise ValueError(f"{name}: smooth must be False or True, got {smooth!r}")
+    if smooth and cell == 4 and len(ds) > 1:
+        raise ValueError(f"{name}: smooth at cell = 4 is not done for more than one level (render those levels one by one with region_heat_window)")
+    mp, hm, wm, md = 0, 0, 0, 0
+    if mask is None:
+        if mask_down is not None:
+            raise ValueError(f"{name}: mask_down = {mask_down!r} without a mask")
+    else:
+        mp, hm, wm = _plane_pitch(mask, name)
+        if mask.device != region.device:
+            raise ValueError(f"{name}: mask must be on the region's device ({region.device}), got {mask.device}")
+        if mask_down not in SEG_DOWNS or isinstance(mask_down, bool) or mask_down % top:
+            raise ValueError(f"{name}: mask_down must be one of {SEG_DOWNS} and a multiple of down = {top}, the largest level, got {mask_down!r}")
+        _u8_arg(name, "mask_thresh", mask_thresh)
+        md = mask_down
+        if hm == 0 or wm == 0:                                       # an empty plane has no address and no tissue: the box-filtered region
+            mask, alpha, mp, hm, wm, md = None, 0, 0, 0, 0, 0
+    shapes = [(hr // d, wr // d) for d in ds]
+    if outs is None:
+        outs = tuple(torch.empty((ho, wo, 3), dtype=torch.uint8, device=region.device) for ho, wo in shapes)
+    else:
+        if isinstance(outs, torch.Tensor) or not hasattr(outs, "__len__") or len(outs) != len(ds):
+            raise ValueError(f"{name}: outs must be None or a sequence of {len(ds)} canvases, one per level of downs = {ds}")
+        outs = tuple(outs)
+        for k, (d, out, (ho, wo)) in enumerate(zip(ds, outs, shapes)):
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != region.device or tuple(out.shape) != (ho, wo, 3):
+                raise ValueError(f"{name}: outs[{k}] (down = {d}) must be a uint8 [{ho},{wo},3] tensor on the region's device")
+            if ho and wo and not region_layout_ok(out):
+                raise ValueError(f"{name}: outs[{k}] (down = {d}) must have strides (pitch, 3, 1) with pitch >= 3 Wo, got {tuple(out.stride())}")
+        for k, (d, out, (ho, wo)) in enumerate(zip(ds, outs, shapes)):
+            if out.untyped_storage().data_ptr() == region.untyped_storage().data_ptr():
+                raise ValueError(f"{name}: outs[{k}] (down = {d}) must not share storage with region (the canvas is written while the region is read)")
+            for j in range(k):
+                if out.untyped_storage().data_ptr() == outs[j].untyped_storage().data_ptr() and ho and wo and shapes[j][0] and shapes[j][1]:
+                    raise ValueError(f"{name}: outs[{j}] and outs[{k}] must not share storage (every canvas is written in the same launch)")
+    levels = 0
+    ptrs, pitches = (ctypes.c_void_p * 6)(), (ctypes.c_int64 * 6)()
+    for d, out, (ho, wo) in zip(ds, outs, shapes):
+        if ho == 0 or wo == 0:
+            continue
+        k = d.bit_length() - 1
+        levels |= 1 << k
+        ptrs[k], pitches[k] = out.data_ptr(), _row_pitch(out, 3 * wo)
+    if levels == 0:
+        return outs
+    _lib.check(_lib.load().toad_region_heat_pyramid_u8(_p(region), pitch, hr, wr, wx, wy, _p(cells), cells.shape[0], cells.shape[1], cell, _p(lut), alpha, levels,
+                                                       int(smooth), _p(mask), mp, hm, wm, md, mask_thresh if mask is not None else 0, ptrs, pitches, _stream()),
+               "toad_region_heat_pyramid_u8")
+    return outs
+
+
 def maxpool3x3s2_nhwc(x: torch.Tensor) -> torch.Tensor:
     _chk(x, "x")
     b, h, w, c = x.shape

@@ -59,8 +59,19 @@ its alternation of the arms inside one process, warm-up of every arm, its four s
     same order: those two are the lines to set side by side (W0 next to the window arms runs in another cache and clock state than W0 alone). Default
     output profiles/heatmap_window_bench.jsonl.
 
+  pyramid (--pyramid): what several levels in ONE pass (ops.region_heat_pyramid, toad_region_heat_pyramid_u8) cost against one pass per level. The
+    --window setup: same slides, table and colours, the cell table built once per run. Level sets (1, 4, 16), all six and (8, 16, 32), each flat and
+    with smooth + mask; the mask of each slide is the (plane, t) of tissue.segment_tissue at down 16 for the first set and 32 for the others, median 7,
+    threshold 8. Arms, alternated in one process on the rotating slides, each into canvases allocated once:
+      P     ops.region_heat_pyramid: every level of the set from one read of the slide, one launch;
+      S     ops.region_heat_window once per level, back to back in one bracket: one read and one launch per level;
+      L1    ops.region_heat_window at down = 1 alone: P cannot be faster than this, its ratio carries no bar.
+    P is checked torch.equal to S, level by level, on every slide before anything is timed. p_over_s = median over median next to s_spread, S's own
+    interleaved-halves spread; p_faster_beyond_spread says whether P beats S by more than that. moved bytes = 3 Hr Wr read ONCE + every level's 3 Ho Wo
+    written (S reads the region once per level: s_moved_bytes). Default output profiles/heatmap_pyramid_bench.jsonl.
+
 Prints one JSON line per result; --out FILE keeps them.
-usage: heatmap_bench.py [--launches --arm A|B --down D] [--px | --thumb | --blur | --window [--w0-only]] [--seconds S] [--out FILE]"""
+usage: heatmap_bench.py [--launches --arm A|B --down D] [--px | --thumb | --blur | --window [--w0-only] | --pyramid] [--seconds S] [--out FILE]"""
 import argparse
 import json
 import os
@@ -414,6 +425,64 @@ def window(seconds, w0_only=False):
     return res
 
 
+PYRAMID_SETS = ((1, 4, 16), (1, 2, 4, 8, 16, 32), (8, 16, 32))
+
+
+def pyramid(seconds):
+    """The --pyramid figures: one record per (level set, flat | smooth + mask)."""
+    dev = torch.device("cuda:0")
+    slides, table, lut = setup(dev)
+    cells = ops.heat_cells(table, CELL, (0, 0), (TILE, TILE), (STRIDE, STRIDE), (NX, NY), (HR, WR))
+    out1 = torch.empty((HR, WR, 3), dtype=torch.uint8, device=dev)
+    res = []
+    for ds in PYRAMID_SETS:
+        md = MASK_DOWN if max(ds) <= MASK_DOWN else THUMB_MASK_DOWN
+        masks = {s.data_ptr(): segment_tissue(s, md, 7, 8) for s in slides}
+        outs_p = [torch.empty((HR // d, WR // d, 3), dtype=torch.uint8, device=dev) for d in ds]
+        outs_s = [torch.empty_like(o) for o in outs_p]
+        for both in (False, True):
+            def kw(r):
+                if not both:
+                    return {}
+                m, t = masks[r.data_ptr()]
+                return dict(smooth=True, mask=m, mask_down=md, mask_thresh=t)
+
+            def arm_p(r):
+                return ops.region_heat_pyramid(r, (0, 0), cells, CELL, lut, ALPHA, ds, outs=outs_p, **kw(r))
+
+            def arm_s(r):
+                k = kw(r)
+                for d, o in zip(ds, outs_s):
+                    ops.region_heat_window(r, (0, 0), cells, CELL, lut, ALPHA, d, out=o, **k)
+                return outs_s
+
+            def arm_l1(r):
+                return ops.region_heat_window(r, (0, 0), cells, CELL, lut, ALPHA, 1, out=out1, **kw(r))
+
+            for s_ in slides:
+                for o in outs_p:
+                    o.fill_(0x7F)
+                got, want = arm_p(s_), arm_s(s_)
+                if not all(torch.equal(g, w) for g, w in zip(got, want)):          # a wrong arm must not produce a quoted ratio
+                    raise SystemExit(f"heatmap_bench: the pyramid differs from the per-level calls for levels {ds}, smooth + mask = {both}: nothing is timed")
+            t, iters = alternate({"P": Rotating(arm_p, slides), "S": Rotating(arm_s, slides), "L1": Rotating(arm_l1, slides)}, seconds)
+            sv = t["S"]
+            s1, s2 = median(sv[0::2]), median(sv[1::2])
+            spread = abs(s1 - s2) / median(sv)
+            written = sum(3 * (HR // d) * (WR // d) for d in ds)
+            nbytes, sbytes = 3 * HR * WR + written, len(ds) * 3 * HR * WR + written
+            p_over_s = median(t["P"]) / median(sv)
+            res.append(dict(kind="resident_heatmap_pyramid", region=[HR, WR], tile=TILE, stride=STRIDE, cell=CELL, levels=list(ds), alpha=ALPHA, smooth_and_mask=both,
+                            mask_down=md if both else None, moved_bytes=nbytes, s_moved_bytes=sbytes, slides_rotated=len(slides), rounds=len(sv), iters_per_round=iters,
+                            ms={k: round(median(v), 5) for k, v in t.items()}, ms_min={k: round(min(v), 5) for k, v in t.items()},
+                            ms_max={k: round(max(v), 5) for k, v in t.items()}, p_moved_tbps=round(nbytes / median(t["P"]) / 1e9, 3),
+                            s_moved_tbps=round(sbytes / median(sv) / 1e9, 3), s_halves_ms=[round(s1, 5), round(s2, 5)], s_spread=round(spread, 4),
+                            p_over_s=round(p_over_s, 4), p_faster_beyond_spread=bool(p_over_s < 1.0 - spread), p_over_l1=round(median(t["P"]) / median(t["L1"]), 4),
+                            launches={"P": 1, "S": len(ds), "L1": 1}, pyramid_equals_levels=True))
+        del outs_p, outs_s
+    return res
+
+
 def launches(arm, down, calls=4):
     """`calls` calls of one arm on rotating slides, no warm-up (run under rocprofv3 --kernel-trace --stats: every count divides by `calls`)."""
     dev = torch.device("cuda:0")
@@ -436,6 +505,7 @@ def main():
     ap.add_argument("--blur", action="store_true")
     ap.add_argument("--window", action="store_true")
     ap.add_argument("--w0-only", action="store_true")
+    ap.add_argument("--pyramid", action="store_true")
     ap.add_argument("--seconds", type=float, default=3.0)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -443,7 +513,9 @@ def main():
         a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "heatmap_blur_bench.jsonl")
     if a.window and not a.out:
         a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "heatmap_window_bench.jsonl")
-    res = launches(a.arm, a.down) if a.launches else window(a.seconds, a.w0_only) if a.window else blur(a.seconds) if a.blur else thumb(a.seconds) if a.thumb else resident(a.seconds, a.px)
+    if a.pyramid and not a.out:
+        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "heatmap_pyramid_bench.jsonl")
+    res = launches(a.arm, a.down) if a.launches else pyramid(a.seconds) if a.pyramid else window(a.seconds, a.w0_only) if a.window else blur(a.seconds) if a.blur else thumb(a.seconds) if a.thumb else resident(a.seconds, a.px)
     lines = [json.dumps(r) for r in res]
     print("\n".join(lines), flush=True)
     if a.out:
