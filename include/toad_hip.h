@@ -543,6 +543,30 @@ int toad_region_heat_window_u8(const unsigned char *region, int64_t pitch, int H
                                const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm,
                                int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream);
 
+/* A LIST of windows of one image in one call (additive to ABI 15 too): a viewer that redraws the visible blocks of a slide, or a slide rendered strip by
+ * strip, pays one launch per window above, and at a 4 x 4 block grid the launches cost more than the bytes. `windows` is a HOST array of n descriptors,
+ * read before the call returns (as toad_heat_cells_blur reads its taps); region and out in them are device pointers. Window k is rendered exactly as
+ * toad_region_heat_window_u8 renders it with the same shared arguments - cells, Gy, Gx, cell, lut, alpha, down, smooth and the mask plane are the
+ * image's, shared by all windows - so every canvas is byte for byte what n such calls write. down is any of {1, 2, 4, 8, 16, 32}; extents, pitches and
+ * places may differ from window to window; canvases may be views of one canvas of the whole image. Canvases that overlap each other, or a canvas that
+ * overlaps a region of the list, are the caller's business: every canvas byte of a window is written once, by that window, in no defined order among
+ * the windows.
+ * Refusals: n < 0 (TOAD_EINVAL); cells, lut or, with n > 0, windows NULL (TOAD_EINVAL); then the checks of toad_region_heat_window_u8 that concern the
+ * shared arguments, in its order - cell, alpha, down, down >= 8 and down > cell, smooth, the mask plane - under this entry's name; then, window by
+ * window, its checks of what a window has of its own, in its order - region or out NULL, Hr or Wr not positive, (wx, wy), wx + Wr, pitch, out_pitch, the
+ * table holding the window - the first failing window winning, with a message that begins "window k:" (k counted from 0); then the workgroups of the
+ * whole list reaching 2^31 (TOAD_ESHAPE) and cells not 4-byte aligned (TOAD_EALIGN), where the window entry has them. Nothing is launched unless every
+ * window has passed. n == 0 launches nothing, and neither does a list whose windows are all empty; a window with Hr < down or Wr < down is checked
+ * like any other, writes nothing and the others are still rendered. The descriptors travel to the device by value in the kernel argument, 32 a launch
+ * (heat_blend_px_list_kernel, heat_thumb_list_kernel in csrc/heatmap.hip): a list of n non-empty windows is ceil(n / 32) launches inside this one call,
+ * with no allocation, no host synchronisation, no copy, and no device memory dereferenced on the host. What is read and written per window is what
+ * toad_region_heat_window_u8 reads and writes. Not done: several levels for a list (toad_region_heat_pyramid_u8 takes one window), windows of several
+ * images in one call. */
+typedef struct { const unsigned char *region; int64_t pitch; int Hr, Wr, wx, wy; unsigned char *out; int64_t out_pitch; } ToadHeatWindow;
+int toad_region_heat_windows_u8(const ToadHeatWindow *windows /* HOST array */, int n,
+        const int *cells, int Gy, int Gx, int cell, const unsigned char *lut, int alpha, int down, int smooth,
+        const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm, int mask_down, int mask_thresh, void *stream);
+
 /* Several levels of the pyramid from ONE read of the window (additive to ABI 15 too): a viewer wants the full-resolution map next to one or two
  * overviews, and every level is defined from the region's own box sums, never from the level above. `levels` is a bit set: bit k asks for down = 2^k,
  * k = 0 .. 5. outs and out_pitches are HOST arrays of 6 entries, read before the call returns (as toad_heat_cells_blur reads its taps) and only at the

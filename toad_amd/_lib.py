@@ -15,6 +15,13 @@ ABI_VERSION = 15
 
 P, I64, I, F, SZ, U64 = c_void_p, c_int64, c_int, c_float, c_size_t, c_uint64
 
+
+class ToadHeatWindow(ctypes.Structure):
+    """One window of toad_region_heat_windows_u8's HOST array (include/toad_hip.h): region and out are device addresses."""
+    _fields_ = [("region", c_void_p), ("pitch", c_int64), ("Hr", c_int), ("Wr", c_int), ("wx", c_int), ("wy", c_int), ("out", c_void_p),
+                ("out_pitch", c_int64)]
+
+
 # name -> (restype, argtypes); mirrors include/toad_hip.h one to one
 SIGNATURES = {
     "toad_abi_version": (I, []),
@@ -109,6 +116,8 @@ SIGNATURES = {
     "toad_region_heat_thumb_u8": (I, [P, I64, I, I, P, I, I, I, P, I, I, I, P, I64, I, I, I, I, P, I64, P]),
     # ... and any of these canvases for a window (wx, wy after Hr, Wr) of the image that the cell table and the mask plane describe: additive to ABI 15
     "toad_region_heat_window_u8": (I, [P, I64, I, I, I, I, P, I, I, I, P, I, I, I, P, I64, I, I, I, I, P, I64, P]),
+    # ... and a list of such windows of one image in one call (windows: a HOST array of n ToadHeatWindow): additive to ABI 15
+    "toad_region_heat_windows_u8": (I, [ctypes.POINTER(ToadHeatWindow), I, P, I, I, I, P, I, I, I, P, I64, I, I, I, I, P]),
     # ... and several levels of that pyramid from one read of the window (levels: a bit set; outs, out_pitches: HOST arrays of 6): additive to ABI 15
     "toad_region_heat_pyramid_u8": (I, [P, I64, I, I, I, I, P, I, I, I, P, I, ctypes.c_uint, I, P, I64, I, I, I, I, P, P, P]),
     # ... and the Gaussian blur of the cell table in front of any of these canvases (the taps are a HOST array): additive to ABI 15

@@ -26,10 +26,15 @@
 //   blur        (toad_heat_cells_blur) the cell table smoothed before it is rendered: a normalised convolution with a symmetric separable integer kernel
 //               of radius 1 .. 16 cells, absent cells and cells outside the table carrying no weight, absent cells staying absent.
 //
+//   list        (toad_region_heat_windows_u8) N windows of one slide, each with its own region, place and canvas, in one launch per 32 windows: every
+//               canvas byte for byte the window entry's.
+//
 //   pyramid     (toad_region_heat_pyramid_u8) several of the six window canvases in one call, each byte for byte the window entry's: every level is defined
 //               from the region's own box sums, never from the level above, and box sums nest, so one read of the region serves them all.
 //
-// Five kernels:
+// Seven kernels:
+//   heat_blend_px_list_kernel<DOWN,SMOOTH,MASK>, heat_thumb_list_kernel<DOWN>   the two single-level kernels below over a LIST of windows of one slide:
+//                                          descriptors by value in the kernel argument, a workgroup finds its window and runs the same body.
 //   heat_pyramid_kernel<RB,MASK>           two or more levels from one read: 1, 2, 4 finished in the lane, 8, 16, 32 in heat_thumb_kernel's tail.
 //   heat_cells_blur_kernel                 a 16 x 64 tile of the cell table and its halo in LDS, a row pass and a column pass inside the workgroup.
 //   heat_thumb_kernel<DOWN,WINDOW>        the overview canvas: the same streaming pass with a box's lanes and waves reduced, one thread per canvas pixel blends.
@@ -415,82 +420,61 @@ __global__ __launch_bounds__(256, 8) void heat_blend_px_kernel(const HeatPxArgs 
 // the table's image is the region's plus (wx, wy) - a template parameter here and not in heat_blend_px_kernel, because here the two adds were measured:
 // they sit in the dependent chain behind the barrier, where the few finishing threads wait for one load after the other, and cost the three older
 // instantiations 1 to 3 % (tools/heatmap_bench.py --window --w0-only against the library as it was); the px kernels showed no difference.
+// The body lies in heat_thumb_body.inc, which heat_thumb_list_kernel includes too.
 template <int DOWN, bool WINDOW>
 __global__ __launch_bounds__(256) void heat_thumb_kernel(const HeatPxArgs a, int smooth, const unsigned char *__restrict__ lut) {
-    constexpr int RB = strip_rows(DOWN), RW = RB / 4;              // rows per workgroup, per wave
-    constexpr int LANES = DOWN / 4, SH = DOWN == 8 ? 6 : DOWN == 16 ? 8 : 10;      // lanes per box, log2(DOWN^2)
-    constexpr int NB = RB / DOWN, WPB = 4 / NB, CPR = 64 / LANES;  // box rows per workgroup, waves per box row, boxes per chunk
-    __shared__ int part[3][4][64];
+    const unsigned bid = blockIdx.x;
+#include "heat_thumb_body.inc"
+}
+
+// ---- a list of windows of one slide in one launch: toad_region_heat_windows_u8 ----
+// The list forms of the two single-level kernels. The windows share the table, the mask plane, the colours, alpha and down - `shared`, whose region, out,
+// extents and place are unused - and each has a descriptor of its own; the descriptors travel by value in the kernel argument, as HeatBlurTaps does: no
+// device table, no upload. The grid is the windows' workgroups one after the other, descriptor k owning workgroups first[k] .. first[k + 1]; descriptors
+// from n on carry first = 0xFFFFFFFF, above every workgroup index, so the search needs no n: five uniform steps of a binary search over the 32 prefixes,
+// scalar loads from the kernarg segment, once per workgroup. From there on a workgroup is one of its window's: HeatPxArgs from the shared part and the
+// descriptor, chunk and rb from its index inside the window, and the body the single-window kernel runs. The grid is exact: every workgroup has a window.
+// Windows without a workgroup (Hr < down or Wr < down) never reach a descriptor.
+constexpr int HEAT_LIST_MAX = 32;                                    // 32 descriptors of 56 bytes and the shared part: 1.9 KB of the 4 KB a kernel argument may have
+struct HeatListWin {
+    const unsigned char *region; int64_t pitch; unsigned char *out; int64_t out_pitch;
+    int Hi, Wi, wx, wy; unsigned nchunks, first;
+};
+struct HeatListArgs { HeatPxArgs shared; HeatListWin w[HEAT_LIST_MAX]; };
+
+// the window of workgroup `bid` -> its HeatPxArgs; local = the workgroup's index inside the window
+__device__ __forceinline__ HeatPxArgs heat_list_window(const HeatListArgs &l, unsigned bid, unsigned &local) {
+    static_assert(HEAT_LIST_MAX == 32, "five steps search 32 prefixes");
+    int k = 0;
+#pragma unroll
+    for (int step = HEAT_LIST_MAX / 2; step >= 1; step >>= 1)
+        if (l.w[k + step].first <= bid) k += step;
+    const HeatListWin &w = l.w[k];
+    HeatPxArgs a = l.shared;
+    a.region = w.region; a.pitch = w.pitch; a.Hi = w.Hi; a.Wi = w.Wi;
+    a.out = w.out; a.out_pitch = w.out_pitch; a.nchunks = w.nchunks;
+    a.wx = w.wx; a.wy = w.wy;
+    local = bid - w.first;
+    return a;
+}
+
+template <int DOWN, int SMOOTH, bool MASK>
+__global__ __launch_bounds__(256, 8) void heat_blend_px_list_kernel(const HeatListArgs l, const unsigned char *__restrict__ lut) {
+    __shared__ unsigned lut_s[256];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned chunk = blockIdx.x % a.nchunks, rb = blockIdx.x / a.nchunks;
-    const unsigned x = chunk * 256u + (unsigned)lane * 4u, off = 3u * x;
-    const int64_t y0 = (int64_t)rb * RB + wave * RW;               // first row of this wave (may lie below Hi: then it reads nothing)
-    const unsigned char *src = a.region + y0 * a.pitch + off;
-    unsigned w[RW][3];
-    if (chunk * 256u + 256u <= (unsigned)a.Wi && y0 + RW <= a.Hi) {  // wave-uniform: all 768 bytes of all RW rows are consumed
-#pragma unroll
-        for (int r = 0; r < RW; ++r)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) w[r][k] = *reinterpret_cast<const u32_a1 *>(src + r * a.pitch + 4 * k);
-    } else {
-        const int rows = (int)max((int64_t)0, min((int64_t)RW, (int64_t)a.Hi - y0));
-        const int npx = x < (unsigned)a.Wi ? 4 : 0;                // Wi is a multiple of 8
-#pragma unroll
-        for (int r = 0; r < RW; ++r) load_px4(src + r * a.pitch, r < rows ? npx : 0, w[r]);
-    }
-    unsigned b[12];                                                // the 12 column sums over the wave's rows, each at most 8 * 255
-    column_sums<RW>(w, b);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) part[c][wave][lane] = lanes_allreduce_sum<LANES>((int)(b[c] + b[c + 3] + b[c + 6] + b[c + 9]));
+    lut_s[tid] = (unsigned)lut[3 * tid] | ((unsigned)lut[3 * tid + 1] << 8) | ((unsigned)lut[3 * tid + 2] << 16);
     __syncthreads();
-    if (tid >= NB * CPR) return;
-    const int band = tid / CPR, bx = tid - band * CPR;
-    const int64_t oy = (int64_t)rb * NB + band;
-    const unsigned ox = chunk * CPR + bx;
-    if (oy * DOWN >= a.Hi || ox * DOWN >= (unsigned)a.Wi) return;
-    int m[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        int t = 0;
-#pragma unroll
-        for (int k = 0; k < WPB; ++k) t += part[c][band * WPB + k][bx * LANES];
-        m[c] = (t + (1 << (SH - 1))) >> SH;
-    }
-    const int64_t py0 = oy * DOWN + (WINDOW ? a.wy : 0);           // the box's corner in the table's image
-    const int px0 = (int)(ox * DOWN) + (WINDOW ? a.wx : 0);
-    const int own = min(a.cells[(py0 >> a.shift) * a.Gx + (px0 >> a.shift)], 255);
-    int idx = max(own, 0);
-    if (smooth) {
-        const int cell = 1 << a.shift, c2 = 2 * cell;
-        const int px = 2 * px0 + DOWN - cell;                      // wx + Wr < 2^30, so 2 x fits
-        const int64_t py = 2 * py0 + DOWN - cell;
-        const int gx0 = px >> (a.shift + 1), fx = px & (c2 - 1);
-        const int gy0 = (int)(py >> (a.shift + 1)), fy = (int)(py & (c2 - 1));
-        int H[2];
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            int v[2];
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const int yy = gy0 + r, xx = gx0 + c;
-                const bool in = yy >= 0 && yy < a.Gy && xx >= 0 && xx < a.Gx;
-                const int t = in ? a.cells[(int64_t)yy * a.Gx + xx] : -1;
-                v[c] = t >= 0 ? min(t, 255) : idx;
-            }
-            H[r] = c2 * v[0] + fx * (v[1] - v[0]);
-        }
-        idx = (c2 * H[0] + fy * (H[1] - H[0]) + 2 * cell * cell) >> (2 * a.shift + 2);
-    }
-    bool tissue = true;
-    if (a.mask) {
-        const int64_t my = py0 >> a.mshift;
-        const int mx = px0 >> a.mshift;
-        tissue = my < a.Hm && mx < a.Wm && (int)a.mask[my * a.mask_pitch + mx] > a.mask_thresh;
-    }
-    const int al = own >= 0 && tissue ? a.alpha : 0;               // alpha' = 0 leaves m: (256 m + 128) >> 8
-    unsigned char *d = a.out + oy * a.out_pitch + 3u * ox;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) d[c] = (unsigned char)((al * (int)lut[3 * idx + c] + (256 - al) * m[c] + 128) >> 8);
+    unsigned local;
+    const HeatPxArgs a = heat_list_window(l, blockIdx.x, local);
+    heat_px_lane<DOWN, SMOOTH, MASK>(a, lut_s, local % a.nchunks, local / a.nchunks, wave, lane);
+}
+
+template <int DOWN>
+__global__ __launch_bounds__(256) void heat_thumb_list_kernel(const HeatListArgs l, int smooth, const unsigned char *__restrict__ lut) {
+    constexpr bool WINDOW = true;
+    unsigned bid;
+    const HeatPxArgs a = heat_list_window(l, blockIdx.x, bid);
+#include "heat_thumb_body.inc"
 }
 
 // ---- the pyramid: toad_region_heat_pyramid_u8, several of the six canvases from ONE read of the region ----
@@ -777,6 +761,76 @@ extern "C" int toad_heat_cells_blur(const int *cells, int Gy, int Gx, const int 
     return check_launch(what);
 }
 
+// The canvas checks that the window entry and the list entry both make, each with the one message: the list entry makes the ones about the shared arguments
+// once and the others per window, under a `what` that names the window.
+static int check_heat_alpha(const char *what, int alpha) {
+    if (alpha >= 0 && alpha <= 256) return TOAD_OK;
+    set_error("%s: alpha = %d must lie in [0, 256] (256 = the colour alone)", what, alpha);
+    return TOAD_ESHAPE;
+}
+static int check_heat_window_down(const char *what, int down, int cell) {      // any of the six; from 8 on heat_thumb_kernel, whose box must lie in one cell
+    if (down != 1 && down != 2 && down != 4 && down != 8 && down != 16 && down != 32) {
+        set_error("%s: down = %d is not one of 1, 2, 4, 8, 16, 32", what, down);
+        return TOAD_ESHAPE;
+    }
+    if (down >= 8 && down > cell) { set_error("%s: down = %d exceeds cell = %d (a canvas box must lie in one cell)", what, down, cell); return TOAD_ESHAPE; }
+    return TOAD_OK;
+}
+static int check_heat_place(const char *what, bool window, int down, int wx, int wy, int Wr) {
+    const int walign = down > 4 ? down : 4;                          // a lane's 4 x 4 block and a canvas box stay in one cell and in one mask pixel
+    if (wx < 0 || wy < 0 || wx % walign || wy % walign) {
+        set_error("%s: window (wx, wy) = (%d, %d) is negative or not a multiple of max(4, down) = %d (a lane's 4 x 4 block and a canvas box must lie in one "
+                  "cell and in one mask pixel)", what, wx, wy, walign);
+        return TOAD_ESHAPE;
+    }
+    if (window && (int64_t)wx + Wr >= (1ll << 30)) {
+        set_error("%s: window too far right: wx + Wr = %lld must stay below 2^30 (doubled tent coordinates in 32 bits)", what, (long long)wx + Wr);
+        return TOAD_ESHAPE;
+    }
+    return TOAD_OK;
+}
+static int check_heat_smooth(const char *what, int smooth) {
+    if (smooth == 0 || smooth == 1) return TOAD_OK;
+    set_error("%s: smooth = %d must be 0 or 1", what, smooth);
+    return TOAD_EINVAL;
+}
+// mshift = log2(mask_down), 0 without a plane. window: the plane is the image's, of any extent; otherwise it is exactly the region's (Hr x Wr).
+static int check_heat_mask(const char *what, bool window, int down, int Hr, int Wr, const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm, int mask_down,
+                           int mask_thresh, int &mshift) {
+    mshift = 0;
+    if (!mask) return TOAD_OK;
+    if (mask_down != 1 && mask_down != 2 && mask_down != 4 && mask_down != 8 && mask_down != 16 && mask_down != 32) {
+        set_error("%s: mask_down = %d is not one of 1, 2, 4, 8, 16, 32", what, mask_down);
+        return TOAD_ESHAPE;
+    }
+    if (mask_down % down) {
+        set_error("%s: mask_down = %d is not a multiple of down = %d (a canvas box must lie in one mask pixel)", what, mask_down, down);
+        return TOAD_ESHAPE;
+    }
+    if (window) {                                                    // what lies outside the plane is not tissue
+        if (Hm < 0 || Wm < 0) { set_error("%s: Hm x Wm = %d x %d must not be negative", what, Hm, Wm); return TOAD_ESHAPE; }
+    } else if (Hm != Hr / mask_down || Wm != Wr / mask_down) {
+        set_error("%s: Hm x Wm = %d x %d is not (Hr / mask_down) x (Wr / mask_down) = %d x %d", what, Hm, Wm, Hr / mask_down, Wr / mask_down);
+        return TOAD_ESHAPE;
+    }
+    if (int rc = check_plane_pitch(what, Wm, "mask_pitch", mask_pitch)) return rc;
+    if (int rc = check_u8(what, "mask_thresh", mask_thresh)) return rc;
+    while ((1 << mshift) < mask_down) ++mshift;
+    return TOAD_OK;
+}
+static int check_heat_out_pitch(const char *what, int64_t out_pitch, int Wo) {
+    if (out_pitch >= 3 * (int64_t)Wo) return TOAD_OK;
+    set_error("%s: out_pitch %lld is less than a row of the canvas (3 Wo = %lld bytes)", what, (long long)out_pitch, 3ll * Wo);
+    return TOAD_ESHAPE;
+}
+static int check_heat_table_holds(const char *what, int wx, int wy, int Hr, int Wr, int cell, int Gy, int Gx) {
+    const int64_t gy_end = ((int64_t)wy + Hr + cell - 1) / cell, gx_end = ((int64_t)wx + Wr + cell - 1) / cell;
+    if (gy_end <= Gy && gx_end <= Gx) return TOAD_OK;
+    set_error("%s: the window ends at cell row %lld and cell column %lld, beyond the table's Gy x Gx = %d x %d (ceil((wy + Hr) / cell) <= Gy and "
+              "ceil((wx + Wr) / cell) <= Gx)", what, (long long)gy_end, (long long)gx_end, Gy, Gx);
+    return TOAD_ESHAPE;
+}
+
 // All three canvas entry points: every check in the order in which the first failing one wins, the geometry, the choice of the kernel. The flat entry passes
 // smooth = 0 and mask = NULL, for which the smooth and mask checks are no-ops; `unaligned` names the planes its alignment message lets lie anywhere. `thumb`
 // is the overview entry: down in {8, 16, 32} and at most the cell, strips of strip_rows(down) rows, heat_thumb_kernel<down>. `window` is the window entry
@@ -788,15 +842,11 @@ static int launch_heat_blend(const char *what, const char *unaligned, bool thumb
     if (!region || !cells || !lut || !out) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
     if (int rc = check_cell(what, cell)) return rc;
     if (int rc = check_hw(what, "Hr", Hr, "Wr", Wr)) return rc;
-    if (alpha < 0 || alpha > 256) { set_error("%s: alpha = %d must lie in [0, 256] (256 = the colour alone)", what, alpha); return TOAD_ESHAPE; }
+    if (int rc = check_heat_alpha(what, alpha)) return rc;
     if (window) {
-        if (down != 1 && down != 2 && down != 4 && down != 8 && down != 16 && down != 32) {
-            set_error("%s: down = %d is not one of 1, 2, 4, 8, 16, 32", what, down);
-            return TOAD_ESHAPE;
-        }
+        if (int rc = check_heat_window_down(what, down, cell)) return rc;
         thumb = down >= 8;
-    }
-    if (thumb) {
+    } else if (thumb) {
         if (down != 8 && down != 16 && down != 32) { set_error("%s: down = %d is not one of 8, 16, 32", what, down); return TOAD_ESHAPE; }
         if (down > cell) {
             set_error("%s: down = %d exceeds cell = %d (a canvas box must lie in one cell)", what, down, cell);
@@ -806,50 +856,15 @@ static int launch_heat_blend(const char *what, const char *unaligned, bool thumb
         set_error("%s: down = %d is not one of 1, 2, 4", what, down);
         return TOAD_ESHAPE;
     }
-    const int walign = down > 4 ? down : 4;                          // a lane's 4 x 4 block and a canvas box stay in one cell and in one mask pixel
-    if (wx < 0 || wy < 0 || wx % walign || wy % walign) {
-        set_error("%s: window (wx, wy) = (%d, %d) is negative or not a multiple of max(4, down) = %d (a lane's 4 x 4 block and a canvas box must lie in one "
-                  "cell and in one mask pixel)", what, wx, wy, walign);
-        return TOAD_ESHAPE;
-    }
-    if (window && (int64_t)wx + Wr >= (1ll << 30)) {
-        set_error("%s: window too far right: wx + Wr = %lld must stay below 2^30 (doubled tent coordinates in 32 bits)", what, (long long)wx + Wr);
-        return TOAD_ESHAPE;
-    }
-    if (smooth != 0 && smooth != 1) { set_error("%s: smooth = %d must be 0 or 1", what, smooth); return TOAD_EINVAL; }
+    if (int rc = check_heat_place(what, window, down, wx, wy, Wr)) return rc;
+    if (int rc = check_heat_smooth(what, smooth)) return rc;
     if (int rc = check_region_pitch(what, pitch, Wr)) return rc;
     int mshift = 0;
-    if (mask) {
-        if (mask_down != 1 && mask_down != 2 && mask_down != 4 && mask_down != 8 && mask_down != 16 && mask_down != 32) {
-            set_error("%s: mask_down = %d is not one of 1, 2, 4, 8, 16, 32", what, mask_down);
-            return TOAD_ESHAPE;
-        }
-        if (mask_down % down) {
-            set_error("%s: mask_down = %d is not a multiple of down = %d (a canvas box must lie in one mask pixel)", what, mask_down, down);
-            return TOAD_ESHAPE;
-        }
-        if (window) {                                                // the plane is the image's: any extent, what lies outside it is not tissue
-            if (Hm < 0 || Wm < 0) { set_error("%s: Hm x Wm = %d x %d must not be negative", what, Hm, Wm); return TOAD_ESHAPE; }
-        } else if (Hm != Hr / mask_down || Wm != Wr / mask_down) {
-            set_error("%s: Hm x Wm = %d x %d is not (Hr / mask_down) x (Wr / mask_down) = %d x %d", what, Hm, Wm, Hr / mask_down, Wr / mask_down);
-            return TOAD_ESHAPE;
-        }
-        if (int rc = check_plane_pitch(what, Wm, "mask_pitch", mask_pitch)) return rc;
-        if (int rc = check_u8(what, "mask_thresh", mask_thresh)) return rc;
-        while ((1 << mshift) < mask_down) ++mshift;
-    }
+    if (int rc = check_heat_mask(what, window, down, Hr, Wr, mask, mask_pitch, Hm, Wm, mask_down, mask_thresh, mshift)) return rc;
     const int Ho = Hr / down, Wo = Wr / down;
-    if (out_pitch < 3 * (int64_t)Wo) {
-        set_error("%s: out_pitch %lld is less than a row of the canvas (3 Wo = %lld bytes)", what, (long long)out_pitch, 3ll * Wo);
-        return TOAD_ESHAPE;
-    }
+    if (int rc = check_heat_out_pitch(what, out_pitch, Wo)) return rc;
     if (window) {
-        const int64_t gy_end = ((int64_t)wy + Hr + cell - 1) / cell, gx_end = ((int64_t)wx + Wr + cell - 1) / cell;
-        if (gy_end > Gy || gx_end > Gx) {
-            set_error("%s: the window ends at cell row %lld and cell column %lld, beyond the table's Gy x Gx = %d x %d (ceil((wy + Hr) / cell) <= Gy and "
-                      "ceil((wx + Wr) / cell) <= Gx)", what, (long long)gy_end, (long long)gx_end, Gy, Gx);
-            return TOAD_ESHAPE;
-        }
+        if (int rc = check_heat_table_holds(what, wx, wy, Hr, Wr, cell, Gy, Gx)) return rc;
     } else if (Gy != (int)(((int64_t)Hr + cell - 1) / cell) || Gx != (int)(((int64_t)Wr + cell - 1) / cell)) {
         set_error("%s: Gy x Gx = %d x %d is not ceil(Hr / cell) x ceil(Wr / cell) = %lld x %lld", what, Gy, Gx, ((long long)Hr + cell - 1) / cell,
                   ((long long)Wr + cell - 1) / cell);
@@ -911,6 +926,90 @@ extern "C" int toad_region_heat_window_u8(const unsigned char *region, int64_t p
                                           int Hm, int Wm, int mask_down, int mask_thresh, unsigned char *out, int64_t out_pitch, void *stream) {
     return launch_heat_blend("toad_region_heat_window_u8", "the region, the mask and the canvas", false, true, region, pitch, Hr, Wr, wx, wy, cells, Gy, Gx, cell, lut,
                              alpha, down, smooth, mask, mask_pitch, Hm, Wm, mask_down, mask_thresh, out, out_pitch, stream);
+}
+
+// The list entry: the window entry's checks of what the windows share, in its order; then window by window its checks of what each window has of its own,
+// in its order, the first failing window winning under "window k:"; then the workgroup count of the whole list and the alignment of cells, where the
+// window entry has them. Nothing is launched before all of that has passed. Two walks over the host array, no allocation: the first checks and counts,
+// the second fills HEAT_LIST_MAX descriptors at a time and launches them.
+extern "C" int toad_region_heat_windows_u8(const ToadHeatWindow *windows, int n, const int *cells, int Gy, int Gx, int cell, const unsigned char *lut, int alpha,
+                                           int down, int smooth, const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm, int mask_down, int mask_thresh,
+                                           void *stream) {
+    const char *what = "toad_region_heat_windows_u8";
+    if (n < 0) { set_error("%s: n = %d windows", what, n); return TOAD_EINVAL; }
+    if (!cells || !lut || (n > 0 && !windows)) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (int rc = check_cell(what, cell)) return rc;
+    if (int rc = check_heat_alpha(what, alpha)) return rc;
+    if (int rc = check_heat_window_down(what, down, cell)) return rc;
+    if (int rc = check_heat_smooth(what, smooth)) return rc;
+    int mshift = 0;
+    if (int rc = check_heat_mask(what, true, down, 0, 0, mask, mask_pitch, Hm, Wm, mask_down, mask_thresh, mshift)) return rc;
+    const bool thumb = down >= 8;
+    const int rb = thumb ? strip_rows(down) : 16;
+    // a window's workgroups: 0 where it has no canvas pixel
+    auto geometry = [&](const ToadHeatWindow &w, int &Hi, int &Wi, int64_t &nchunks) {
+        Hi = w.Hr / down * down; Wi = w.Wr / down * down;
+        nchunks = ((int64_t)Wi + 255) / 256;
+        return nchunks * (((int64_t)Hi + rb - 1) / rb);
+    };
+    int64_t blocks = 0;
+    for (int k = 0; k < n; ++k) {
+        const ToadHeatWindow &w = windows[k];
+        char who[64];
+        snprintf(who, sizeof who, "window %d: %s", k, what);
+        if (!w.region || !w.out) { set_error("%s: null pointer", who); return TOAD_EINVAL; }
+        if (int rc = check_hw(who, "Hr", w.Hr, "Wr", w.Wr)) return rc;
+        if (int rc = check_heat_place(who, true, down, w.wx, w.wy, w.Wr)) return rc;
+        if (int rc = check_region_pitch(who, w.pitch, w.Wr)) return rc;
+        if (int rc = check_heat_out_pitch(who, w.out_pitch, w.Wr / down)) return rc;
+        if (int rc = check_heat_table_holds(who, w.wx, w.wy, w.Hr, w.Wr, cell, Gy, Gx)) return rc;
+        int Hi, Wi;
+        int64_t nchunks;
+        blocks += geometry(w, Hi, Wi, nchunks);                      // one window: below 2^50; the sum is refused as soon as it reaches 2^31
+        if (int rc = check_blocks(what, "list of regions", blocks)) return rc;
+    }
+    if (!aligned4(cells)) {
+        set_error("%s: cells (int32 [Gy][Gx]) must be 4-byte aligned (the regions, the mask and the canvases may have any alignment)", what);
+        return TOAD_EALIGN;
+    }
+    if (blocks == 0) return TOAD_OK;
+    int shift = 2;
+    while ((1 << shift) < cell) ++shift;
+    const int sm = !smooth || cell == down ? 0 : cell == 4 ? 2 : 1;  // the tent's variant, as in launch_heat_blend
+    const int tent = smooth && cell != down;
+    HeatListArgs l = {};
+    l.shared = {nullptr, 0, 0, 0, cells, Gy, Gx, shift, alpha, mask, mask_pitch, Hm, Wm, mshift, mask_thresh, nullptr, 0, 0u, 0, 0};
+    for (int k = 0; k < n;) {
+        int m = 0;
+        unsigned grid = 0;
+        for (; k < n && m < HEAT_LIST_MAX; ++k) {
+            const ToadHeatWindow &w = windows[k];
+            int Hi, Wi;
+            int64_t nchunks;
+            const int64_t b = geometry(w, Hi, Wi, nchunks);
+            if (b == 0) continue;
+            l.w[m++] = {w.region, w.pitch, w.out, w.out_pitch, Hi, Wi, w.wx, w.wy, (unsigned)nchunks, grid};
+            grid += (unsigned)b;
+        }
+        if (m == 0) break;
+        for (int j = m; j < HEAT_LIST_MAX; ++j) { l.w[j] = {}; l.w[j].first = 0xFFFFFFFFu; }      // above every workgroup index: the search stops short of them
+        if (thumb) {
+#define TOAD_THUMB_LIST(D) case D: hipLaunchKernelGGL((heat_thumb_list_kernel<D>), dim3(grid), dim3(256), 0, (hipStream_t)stream, l, tent, lut); break;
+            switch (down) { TOAD_THUMB_LIST(8) TOAD_THUMB_LIST(16) TOAD_THUMB_LIST(32) }
+#undef TOAD_THUMB_LIST
+        } else {
+#define TOAD_HEAT_LIST(D, S, M) \
+    case 8 * D + 2 * S + M: hipLaunchKernelGGL((heat_blend_px_list_kernel<D, S, M != 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, l, lut); break;
+            switch (8 * down + 2 * sm + (mask ? 1 : 0)) {            // the 16 shapes of launch_heat_blend
+                TOAD_HEAT_LIST(1, 0, 0) TOAD_HEAT_LIST(1, 0, 1) TOAD_HEAT_LIST(1, 1, 0) TOAD_HEAT_LIST(1, 1, 1) TOAD_HEAT_LIST(1, 2, 0) TOAD_HEAT_LIST(1, 2, 1)
+                TOAD_HEAT_LIST(2, 0, 0) TOAD_HEAT_LIST(2, 0, 1) TOAD_HEAT_LIST(2, 1, 0) TOAD_HEAT_LIST(2, 1, 1) TOAD_HEAT_LIST(2, 2, 0) TOAD_HEAT_LIST(2, 2, 1)
+                TOAD_HEAT_LIST(4, 0, 0) TOAD_HEAT_LIST(4, 0, 1) TOAD_HEAT_LIST(4, 1, 0) TOAD_HEAT_LIST(4, 1, 1)
+            }
+#undef TOAD_HEAT_LIST
+        }
+        if (int rc = check_launch(what)) return rc;
+    }
+    return TOAD_OK;
 }
 
 // The pyramid entry: the window entry's checks in the window entry's order, taken over the set of levels - D, the largest, stands where `down` stood, and the

@@ -337,7 +337,8 @@ def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region
 
 def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_hw, tile=256, stride=None, origin=(0, 0), origins=None,
                             min_fraction: float = 0.25, sat_thresh: int = 8, val_min: int = 0, bag_dtype: torch.dtype = torch.float16, alpha=102,
-                            down: int = 1, lut=None, out=None, smooth: bool = False, mask=None, thresh=None, binarize: bool = False, blur=False, shrink=1):
+                            down: int = 1, lut=None, out=None, smooth: bool = False, mask=None, thresh=None, binarize: bool = False, blur=False, shrink=1,
+                            batch_render: bool = False):
     """``(origins, scores, canvas)`` of a slide of ``slide_hw`` = (Hs, Ws) pixels that arrives from the decoder strip by strip: what
     ``region_tissue_attention_heatmap`` gives for one region, with no seam where two strips meet. ``strips`` is a sequence of ``(region, y_k)`` - a
     decoded uint8 [H_k,Ws,3] full-width strip on the device and the slide row of its first row - sorted, each abutting or overlapping the one before,
@@ -361,11 +362,15 @@ def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_
     scoring and one cell table, and pass 2 is ONE walk over the strips - ``heatmap.window_pyramid`` renders every level of a strip from one read of
     it; render starts are multiples of max(4, the largest level), and each level is byte for byte the call with that ``down``.
 
+    ``batch_render=True`` (an int ``down`` only) makes pass 2 ONE ``heatmap.windows_canvas`` call over all strips - each strip's rendered rows as a view,
+    its rows of the one canvas as ``out`` - and so one launch instead of one per strip; the strips are resident by then, and the bytes are the same.
+    With ``False`` every call is what it was. With a sequence of levels it is a ValueError: pyramid levels for a list of windows are not done.
+
     Not done here: the segmented selector across strips - its median, closing and component steps reach across strip seams, so
     ``tissue.segmented_tissue_origins`` still works on one region per call; make that selection on an overview level and pass it in through
     ``origins=`` and ``mask=``. Blocks that are not full-width strips (``heatmap.window_canvas`` renders any window; this walk does not), and the
     "not done" list of ``region_tissue_attention_heatmap`` except seams."""
-    from .heatmap import slide_cells, strip_plan, window_canvas, window_pyramid
+    from .heatmap import slide_cells, strip_plan, window_canvas, window_pyramid, windows_canvas
     from .heatmap import blur_taps
     from .tissue import _lattice_args, lattice_cell, tissue_origins
     hs, ws = slide_hw
@@ -374,8 +379,13 @@ def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_
         from .ops import shrunk_tile
         shrunk_tile(tile, shrink)
     cell = lattice_cell((h, w), (sy, sx), (x0, y0))
+    if not isinstance(batch_render, bool):
+        raise ValueError(f"slide_attention_heatmap: batch_render must be a bool, got {batch_render!r}")
     levels = None                                                   # a sequence of levels: pass 2 renders them all in one walk over the strips
     if isinstance(down, (tuple, list)):
+        if batch_render:
+            raise ValueError("slide_attention_heatmap: batch_render=True takes one down, not a sequence of levels (pyramid levels for a list of windows are "
+                             "not done)")
         from .ops import heat_downs_arg
         levels = heat_downs_arg("slide_attention_heatmap", down)
         if cell < max(levels):
@@ -440,6 +450,11 @@ def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_
         out = torch.empty((ho, wo, 3), dtype=torch.uint8, device=device)
     elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (ho, wo, 3):
         raise ValueError(f"slide_attention_heatmap: out must be a uint8 [{ho},{wo},3] tensor on the strips' device")
+    if batch_render:                                                # pass 2 in one call: every strip's own rows of the one canvas
+        spans = [p["render"] for p in plan]
+        windows_canvas([region[r0 - y:r1 - y] for (region, y), (r0, r1) in zip(strips, spans)], [(0, r0) for r0, _ in spans], cells, cell, alpha=alpha,
+                       down=down, lut=lut, outs=[out[r0 // down:r0 // down + (r1 - r0) // down] for r0, r1 in spans], smooth=smooth, mask=mask)
+        return found, scores, out
     for (region, y), p in zip(strips, plan):                        # pass 2: each strip's own rows of the one canvas
         r0, r1 = p["render"]
         n = (r1 - r0) // down

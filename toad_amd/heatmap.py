@@ -239,6 +239,22 @@ def window_canvas(region: torch.Tensor, window, cells: torch.Tensor, cell: int, 
                                   mask_thresh=t if plane is not None else 0, out=out)
 
 
+def windows_canvas(regions, windows, cells: torch.Tensor, cell: int, alpha=102, down: int = 1, lut=None, outs=None, smooth: bool = False, mask=None) -> tuple:
+    """``window_canvas`` for a list of windows of one slide: a tuple of uint8 [Hr_k // down, Wr_k // down, 3] canvases, canvas k byte for byte
+    ``window_canvas(regions[k], windows[k], ...)``. ``regions`` are the decoded windows - blocks, strips, of any extents - ``windows`` their places
+    (wx, wy) in the slide, ``outs`` None or one view per window, for example each window's rows and columns of the slide's canvas; everything else is
+    the slide's and shared. Through ``ops.region_heat_windows``: one library call, one launch per ``ops.HEAT_LIST_MAX`` windows."""
+    a = _alpha_arg(alpha)
+    if not isinstance(smooth, bool):
+        raise ValueError(f"windows_canvas: smooth must be a bool, got {smooth!r}")
+    plane, t, mask_down = _mask_arg(mask)
+    if lut is None:
+        first = regions[0] if not isinstance(regions, torch.Tensor) and hasattr(regions, "__len__") and len(regions) else cells
+        lut = jet_lut(first.device if isinstance(first, torch.Tensor) else cells.device)
+    return ops.region_heat_windows(regions, windows, cells, cell, lut, a, down, smooth=smooth, mask=plane, mask_down=mask_down if plane is not None else None,
+                                   mask_thresh=t if plane is not None else 0, outs=outs)
+
+
 def window_pyramid(region: torch.Tensor, window, cells: torch.Tensor, cell: int, alpha=102, downs=(1, 4, 16), lut=None, outs=None, smooth: bool = False,
                    mask=None) -> tuple:
     """``window_canvas`` at several levels from ONE read of the window: a tuple of uint8 [Hr // down, Wr // down, 3] canvases in the order of ``downs``,

@@ -1598,12 +1598,9 @@ def _heat_window_arg(name: str, window, down, cell, hr, wr, cells):
     return wx, wy
 
 
-def _heat_blend_args(name: str, region, cells, cell, lut, alpha, down, out, window=None):
-    """The checks region_heat_blend, region_heat_blend_px, region_heat_thumb and region_heat_window share -> (pitch, Hr, Wr, Ho, Wo, out, window)."""
-    pitch, hr, wr = _region_pitch(region, name)
+def _heat_shared_args(name: str, cells, cell, alpha, down, downs):
+    """What the canvas calls check of the arguments that do not belong to one region: cell, down (one of ``downs``, not above the cell), alpha, cells."""
     _cell_arg(name, cell)
-    windowed = name == "region_heat_window"
-    downs = HEAT_THUMB_DOWNS if name == "region_heat_thumb" else HEAT_DOWNS + HEAT_THUMB_DOWNS if windowed else HEAT_DOWNS
     if down not in downs:
         raise ValueError(f"{name}: down must be one of {downs}, got {down!r}")
     if down > cell:                                                  # (the overview canvas only: HEAT_DOWNS divide every cell)
@@ -1611,29 +1608,44 @@ def _heat_blend_args(name: str, region, cells, cell, lut, alpha, down, out, wind
     if not isinstance(alpha, int) or isinstance(alpha, bool) or not 0 <= alpha <= 256:
         raise ValueError(f"{name}: alpha must be an int in [0, 256], got {alpha!r}")
     _chk(cells, "cells", dtype=torch.int32)
+
+
+def _heat_lut_arg(name: str, lut, device):
+    if not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3) or not lut.is_contiguous() or lut.device != device:
+        raise ValueError(f"{name}: lut must be a contiguous uint8 [256,3] tensor on the region's device")
+
+
+def _heat_out_arg(name: str, region, out, ho, wo, what: str = "out"):
+    """The canvas of one region: a new [ho,wo,3] tensor, or the caller's view after its checks."""
+    if out is None:
+        return torch.empty((ho, wo, 3), dtype=torch.uint8, device=region.device)
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != region.device or tuple(out.shape) != (ho, wo, 3):
+        raise ValueError(f"{name}: {what} must be a uint8 [{ho},{wo},3] tensor on the region's device")
+    if ho and wo and not region_layout_ok(out):
+        raise ValueError(f"{name}: {what} must have strides (pitch, 3, 1) with pitch >= 3 Wo, got {tuple(out.stride())}")
+    if out.untyped_storage().data_ptr() == region.untyped_storage().data_ptr():
+        raise ValueError(f"{name}: {what} must not share storage with region (the canvas is written while the region is read)")
+    return out
+
+
+def _heat_blend_args(name: str, region, cells, cell, lut, alpha, down, out, window=None):
+    """The checks region_heat_blend, region_heat_blend_px, region_heat_thumb and region_heat_window share -> (pitch, Hr, Wr, Ho, Wo, out, window)."""
+    pitch, hr, wr = _region_pitch(region, name)
+    windowed = name == "region_heat_window"
+    downs = HEAT_THUMB_DOWNS if name == "region_heat_thumb" else HEAT_DOWNS + HEAT_THUMB_DOWNS if windowed else HEAT_DOWNS
+    _heat_shared_args(name, cells, cell, alpha, down, downs)
     if windowed:
         window = _heat_window_arg(name, window, down, cell, hr, wr, cells)
     elif tuple(cells.shape) != (-(-hr // cell), -(-wr // cell)):
         raise ValueError(f"{name}: expected int32 [Gy,Gx] = [{-(-hr // cell)},{-(-wr // cell)}] cells, got {tuple(cells.shape)}")
-    if not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3) or not lut.is_contiguous() or lut.device != region.device:
-        raise ValueError(f"{name}: lut must be a contiguous uint8 [256,3] tensor on the region's device")
+    _heat_lut_arg(name, lut, region.device)
     ho, wo = hr // down, wr // down
-    if out is None:
-        out = torch.empty((ho, wo, 3), dtype=torch.uint8, device=region.device)
-    else:
-        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != region.device or tuple(out.shape) != (ho, wo, 3):
-            raise ValueError(f"{name}: out must be a uint8 [{ho},{wo},3] tensor on the region's device")
-        if ho and wo and not region_layout_ok(out):
-            raise ValueError(f"{name}: out must have strides (pitch, 3, 1) with pitch >= 3 Wo, got {tuple(out.stride())}")
-        if out.untyped_storage().data_ptr() == region.untyped_storage().data_ptr():
-            raise ValueError(f"{name}: out must not share storage with region (the canvas is written while the region is read)")
-    return pitch, hr, wr, ho, wo, out, window
+    return pitch, hr, wr, ho, wo, _heat_out_arg(name, region, out, ho, wo), window
 
 
-def _heat_blend(name: str, region, cells, cell, lut, alpha, down, smooth, mask, mask_down, mask_thresh, out, window=None):
-    """The body of region_heat_blend, region_heat_blend_px, region_heat_thumb and region_heat_window: the px checks, then toad_<name>_u8 (the first two
-    launch the same kernel; the flat one takes no smooth and no mask arguments; the window one takes (wx, wy) and a mask plane of any extent)."""
-    pitch, hr, wr, ho, wo, out, window = _heat_blend_args(name, region, cells, cell, lut, alpha, down, out, window)
+def _heat_px_args(name: str, device, alpha, down, smooth, mask, mask_down, mask_thresh, extent=None):
+    """The smooth and mask checks of the per-pixel calls -> (alpha, mask, the library's (mask_pitch, Hm, Wm, mask_down, mask_thresh)). ``extent`` =
+    (Hr, Wr) where the plane must be exactly the region's, None where it is the image's, of any extent (the window calls)."""
     if not isinstance(smooth, (bool, int)) or smooth not in (0, 1):
         raise ValueError(f"{name}: smooth must be False or True, got {smooth!r}")
     mp, hm, wm, md = 0, 0, 0, 0
@@ -1642,20 +1654,28 @@ def _heat_blend(name: str, region, cells, cell, lut, alpha, down, smooth, mask, 
             raise ValueError(f"{name}: mask_down = {mask_down!r} without a mask")
     else:
         mp, hm, wm = _plane_pitch(mask, name)
-        if mask.device != region.device:
-            raise ValueError(f"{name}: mask must be on the region's device ({region.device}), got {mask.device}")
+        if mask.device != device:
+            raise ValueError(f"{name}: mask must be on the region's device ({device}), got {mask.device}")
         if mask_down not in SEG_DOWNS or isinstance(mask_down, bool) or mask_down % down:
             raise ValueError(f"{name}: mask_down must be one of {SEG_DOWNS} and a multiple of down = {down}, got {mask_down!r}")
         _u8_arg(name, "mask_thresh", mask_thresh)
-        if window is None and (hm, wm) != (hr // mask_down, wr // mask_down):
-            raise ValueError(f"{name}: expected a uint8 [Hr // mask_down, Wr // mask_down] = [{hr // mask_down},{wr // mask_down}] mask, got "
+        if extent is not None and (hm, wm) != (extent[0] // mask_down, extent[1] // mask_down):
+            raise ValueError(f"{name}: expected a uint8 [Hr // mask_down, Wr // mask_down] = [{extent[0] // mask_down},{extent[1] // mask_down}] mask, got "
                              f"{tuple(mask.shape)}")
         md = mask_down
         if hm == 0 or wm == 0:                                       # an empty plane has no address and no tissue: the box-filtered region
             mask, alpha, mp, hm, wm, md = None, 0, 0, 0, 0, 0
+    return alpha, mask, (mp, hm, wm, md, mask_thresh if mask is not None else 0)
+
+
+def _heat_blend(name: str, region, cells, cell, lut, alpha, down, smooth, mask, mask_down, mask_thresh, out, window=None):
+    """The body of region_heat_blend, region_heat_blend_px, region_heat_thumb and region_heat_window: the px checks, then toad_<name>_u8 (the first two
+    launch the same kernel; the flat one takes no smooth and no mask arguments; the window one takes (wx, wy) and a mask plane of any extent)."""
+    pitch, hr, wr, ho, wo, out, window = _heat_blend_args(name, region, cells, cell, lut, alpha, down, out, window)
+    alpha, mask, plane = _heat_px_args(name, region.device, alpha, down, smooth, mask, mask_down, mask_thresh, None if window is not None else (hr, wr))
     if ho == 0 or wo == 0:
         return out
-    px = () if name == "region_heat_blend" else (int(smooth), _p(mask), mp, hm, wm, md, mask_thresh if mask is not None else 0)
+    px = () if name == "region_heat_blend" else (int(smooth), _p(mask), *plane)
     entry = f"toad_{name}_u8"
     _lib.check(getattr(_lib.load(), entry)(_p(region), pitch, hr, wr, *(window or ()), _p(cells), cells.shape[0], cells.shape[1], cell, _p(lut), alpha, down, *px, _p(out),
                                            _row_pitch(out, 3 * wo), _stream()), entry)
@@ -1704,6 +1724,56 @@ def region_heat_window(region: torch.Tensor, window, cells: torch.Tensor, cell: 
     into the slide's canvas at any pitch. ValueError for anything else, before the library is called. One launch, no synchronisation; a canvas with no
     rows or no columns launches nothing."""
     return _heat_blend("region_heat_window", region, cells, cell, lut, alpha, down, smooth, mask, mask_down, mask_thresh, out, window)
+
+
+HEAT_LIST_MAX = 32                     # the windows one launch of region_heat_windows takes (csrc/heatmap.hip): a longer list is more launches in the one call
+
+
+def region_heat_windows(regions, windows, cells: torch.Tensor, cell: int, lut: torch.Tensor, alpha: int, down: int, smooth: bool = False, mask=None,
+                        mask_down=None, mask_thresh: int = 0, outs=None) -> tuple:
+    """region_heat_window for a LIST of windows of one slide in ONE library call and one launch per HEAT_LIST_MAX windows
+    (toad_region_heat_windows_u8; include/toad_hip.h): a tuple of uint8 [Hr_k // down, Wr_k // down, 3] canvases, each byte for byte what
+    region_heat_window gives for ``regions[k]`` at ``windows[k]`` = (wx, wy) with the same other arguments. ``regions`` is a sequence of uint8 [Hr,Wr,3]
+    views on one device, of any extents, pitches and alignment - blocks or strips of one resident slide, or buffers of their own; ``cells``, ``cell``,
+    ``lut``, ``alpha``, ``down``, ``smooth`` and the ``mask`` plane are the slide's and shared. ``outs`` is None or one view per window, for example each
+    window's rows and columns of the slide's canvas; no canvas may share storage with its own region, and canvases that overlap each other are the
+    caller's business. The checks are region_heat_window's, per window, with ValueErrors that name the window's index, all before the library is
+    called. A window without a canvas row or column is returned empty and the others are still rendered. No synchronisation, no copy to the device:
+    the descriptors travel in the kernel argument. An empty list, or one whose canvases are all empty, launches nothing."""
+    name = "region_heat_windows"
+    for arg, what in ((regions, "regions"), (windows, "windows")):
+        if isinstance(arg, (str, bytes, torch.Tensor)) or not hasattr(arg, "__len__") or not hasattr(arg, "__iter__"):
+            raise ValueError(f"{name}: {what} must be a sequence with one entry per window, got {type(arg).__name__}")
+    regions, windows = tuple(regions), tuple(windows)
+    n = len(regions)
+    if len(windows) != n:
+        raise ValueError(f"{name}: {n} regions but {len(windows)} windows: one (wx, wy) per region")
+    if outs is not None:
+        if isinstance(outs, torch.Tensor) or not hasattr(outs, "__len__") or len(outs) != n:
+            raise ValueError(f"{name}: outs must be None or a sequence of {n} canvases, one per window")
+        outs = tuple(outs)
+    _heat_shared_args(name, cells, cell, alpha, down, HEAT_DOWNS + HEAT_THUMB_DOWNS)
+    device = regions[0].device if n and isinstance(regions[0], torch.Tensor) else cells.device
+    _heat_lut_arg(name, lut, device)
+    alpha, mask, plane = _heat_px_args(name, device, alpha, down, smooth, mask, mask_down, mask_thresh)
+    canvases, live = [], []
+    for k, (region, window) in enumerate(zip(regions, windows)):
+        who = f"{name}: window {k}"
+        pitch, hr, wr = _region_pitch(region, who)
+        if region.device != device:
+            raise ValueError(f"{who}: every region must be on one device ({device}), got {region.device}")
+        wx, wy = _heat_window_arg(who, window, down, cell, hr, wr, cells)
+        ho, wo = hr // down, wr // down
+        out = _heat_out_arg(who, region, None if outs is None else outs[k], ho, wo, what=f"outs[{k}]")
+        canvases.append(out)
+        if ho and wo:
+            live.append((region, pitch, hr, wr, wx, wy, out, _row_pitch(out, 3 * wo)))
+    if live:
+        lib = _lib.load()
+        host = (_lib.ToadHeatWindow * len(live))(*(_lib.ToadHeatWindow(r.data_ptr(), rp, hr, wr, wx, wy, o.data_ptr(), op) for r, rp, hr, wr, wx, wy, o, op in live))
+        _lib.check(lib.toad_region_heat_windows_u8(host, len(live), _p(cells), cells.shape[0], cells.shape[1], cell, _p(lut), alpha, down, int(smooth), _p(mask),
+                                                   *plane, _stream()), "toad_region_heat_windows_u8")
+    return tuple(canvases)
 
 
 def heat_downs_arg(name: str, downs) -> tuple:

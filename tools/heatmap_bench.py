@@ -70,8 +70,19 @@ its alternation of the arms inside one process, warm-up of every arm, its four s
     interleaved-halves spread; p_faster_beyond_spread says whether P beats S by more than that. moved bytes = 3 Hr Wr read ONCE + every level's 3 Ho Wo
     written (S reads the region once per level: s_moved_bytes). Default output profiles/heatmap_pyramid_bench.jsonl.
 
+  windows (--windows): what a LIST of windows in one call (ops.region_heat_windows, toad_region_heat_windows_u8) saves over one call per window. The
+    --window setup: same slides, table, colours, masks, the cell table built once per run, flat and with smooth + mask, at down = 1 and 16. Arms,
+    alternated in one process on the rotating slides, each into a canvas allocated once:
+      W0        the entry that was there before, the whole slide;
+      W4, W16   --window's: the 4 strips and the 4 x 4 block grid through ops.region_heat_window, 4 and 16 calls and launches;
+      L4, L16   the same strips and blocks through ONE ops.region_heat_windows call: one launch;
+      C4, C16   the library entry itself on a host array built once per slide: the launch without the Python wrapper's per-window checks and views.
+    L4, L16, C4 and C16 are checked torch.equal to W0 on every slide before anything is timed. l_over_w = L4 / W4 and L16 / W16, median over median, next to
+    w0_spread, W0's own interleaved-halves spread: l_faster_beyond_spread says whether the list beats the per-window calls by more than that. l_over_w0
+    = L4 / W0 and L16 / W0, and c_over_w0 likewise, are reported without a bar. Default output profiles/heatmap_windows_bench.jsonl.
+
 Prints one JSON line per result; --out FILE keeps them.
-usage: heatmap_bench.py [--launches --arm A|B --down D] [--px | --thumb | --blur | --window [--w0-only] | --pyramid] [--seconds S] [--out FILE]"""
+usage: heatmap_bench.py [--launches --arm A|B --down D] [--px | --thumb | --blur | --window [--w0-only] | --windows | --pyramid] [--seconds S] [--out FILE]"""
 import argparse
 import json
 import os
@@ -425,6 +436,90 @@ def window(seconds, w0_only=False):
     return res
 
 
+def windows(seconds):
+    """The --windows figures: one record per (down, flat | smooth + mask)."""
+    from toad_amd import _lib
+    dev = torch.device("cuda:0")
+    slides, table, lut = setup(dev)
+    cells = ops.heat_cells(table, CELL, (0, 0), (TILE, TILE), (STRIDE, STRIDE), (NX, NY), (HR, WR))
+    strips = [(0, y, WR, HR // 4) for y in range(0, HR, HR // 4)]
+    blocks = [(x, y, WR // 4, HR // 4) for y in range(0, HR, HR // 4) for x in range(0, WR, WR // 4)]
+    res = []
+    for down in (1, 16):
+        md = MASK_DOWN if down == 1 else THUMB_MASK_DOWN
+        masks = {s.data_ptr(): segment_tissue(s, md, 7, 8) for s in slides}
+        whole = ops.region_heat_thumb if down in ops.HEAT_THUMB_DOWNS else ops.region_heat_blend_px
+        out = torch.empty((HR // down, WR // down, 3), dtype=torch.uint8, device=dev)
+        for both in (False, True):
+            def kw(r):
+                if not both:
+                    return {}
+                m, t = masks[r.data_ptr()]
+                return dict(smooth=True, mask=m, mask_down=md, mask_thresh=t)
+
+            def w0(r):
+                return whole(r, cells, CELL, lut, ALPHA, down, out=out, **kw(r))
+
+            def pieces(parts):
+                def run(r):
+                    k = kw(r)
+                    for wx, wy, w, h in parts:
+                        ops.region_heat_window(r[wy:wy + h, wx:wx + w], (wx, wy), cells, CELL, lut, ALPHA, down,
+                                               out=out[wy // down:(wy + h) // down, wx // down:(wx + w) // down], **k)
+                    return out
+                return run
+
+            def listed(parts):
+                places = [(wx, wy) for wx, wy, _, _ in parts]
+                outs = [out[wy // down:(wy + h) // down, wx // down:(wx + w) // down] for wx, wy, w, h in parts]
+
+                def run(r):
+                    ops.region_heat_windows([r[wy:wy + h, wx:wx + w] for wx, wy, w, h in parts], places, cells, CELL, lut, ALPHA, down, outs=outs, **kw(r))
+                    return out
+                return run
+
+            def direct(parts):
+                lib, win = _lib.load(), _lib.ToadHeatWindow
+                hosts = {s_.data_ptr(): (win * len(parts))(*(win(s_[wy:wy + h, wx:wx + w].data_ptr(), s_.stride(0), h, w, wx, wy,
+                                                                   out[wy // down:, wx // down:].data_ptr(), out.stride(0)) for wx, wy, w, h in parts))
+                         for s_ in slides}
+
+                def run(r):
+                    m, t = masks[r.data_ptr()] if both else (None, 0)
+                    plane = (m.data_ptr(), m.stride(0), m.shape[0], m.shape[1], md, t) if both else (None, 0, 0, 0, 0, 0)
+                    _lib.check(lib.toad_region_heat_windows_u8(hosts[r.data_ptr()], len(parts), cells.data_ptr(), GY, GX, CELL, lut.data_ptr(), ALPHA, down, int(both),
+                                                               *plane, ops._stream()), "toad_region_heat_windows_u8")
+                    return out
+                return run
+
+            cand = {"W4": pieces(strips), "W16": pieces(blocks), "L4": listed(strips), "L16": listed(blocks), "C4": direct(strips), "C16": direct(blocks)}
+            for s_ in slides:
+                want = w0(s_).clone()
+                for k, fn in cand.items():
+                    out.fill_(0x7F)
+                    if not torch.equal(fn(s_), want):                          # a wrong arm must not produce a quoted ratio
+                        raise SystemExit(f"heatmap_bench: {k} differs from W0 at down = {down}, smooth + mask = {both}: nothing is timed")
+            arms = {"W0": Rotating(w0, slides)}
+            arms.update({k: Rotating(fn, slides) for k, fn in cand.items()})
+            t, iters = alternate(arms, seconds)
+            a = t["W0"]
+            a1, a2 = median(a[0::2]), median(a[1::2])
+            spread = abs(a1 - a2) / median(a)
+            nbytes = 3 * HR * WR + 3 * (HR // down) * (WR // down)
+            m = {k: median(v) for k, v in t.items()}
+            l_over_w = {"L4": m["L4"] / m["W4"], "L16": m["L16"] / m["W16"]}
+            res.append(dict(kind="resident_heatmap_windows", region=[HR, WR], tile=TILE, stride=STRIDE, cell=CELL, down=down, alpha=ALPHA, smooth_and_mask=both,
+                            mask_down=md if both else None, moved_bytes=nbytes, slides_rotated=len(slides), rounds=len(a), iters_per_round=iters,
+                            ms={k: round(v, 5) for k, v in m.items()}, ms_min={k: round(min(v), 5) for k, v in t.items()},
+                            ms_max={k: round(max(v), 5) for k, v in t.items()}, moved_tbps={k: round(nbytes / v / 1e9, 3) for k, v in m.items()},
+                            w0_halves_ms=[round(a1, 5), round(a2, 5)], w0_spread=round(spread, 4), l_over_w={k: round(v, 4) for k, v in l_over_w.items()},
+                            l_faster_beyond_spread={k: bool(v < 1.0 - spread) for k, v in l_over_w.items()},
+                            l_over_w0={k: round(m[k] / m["W0"], 4) for k in ("L4", "L16")}, c_over_w0={k: round(m[k] / m["W0"], 4) for k in ("C4", "C16")}, w_over_w0={k: round(m[k] / m["W0"], 4) for k in ("W4", "W16")},
+                            launches={"W0": 1, "W4": 4, "W16": 16, "L4": 1, "L16": 1, "C4": 1, "C16": 1}, lists_equal_w0=True))
+        del out
+    return res
+
+
 PYRAMID_SETS = ((1, 4, 16), (1, 2, 4, 8, 16, 32), (8, 16, 32))
 
 
@@ -505,6 +600,7 @@ def main():
     ap.add_argument("--blur", action="store_true")
     ap.add_argument("--window", action="store_true")
     ap.add_argument("--w0-only", action="store_true")
+    ap.add_argument("--windows", action="store_true")
     ap.add_argument("--pyramid", action="store_true")
     ap.add_argument("--seconds", type=float, default=3.0)
     ap.add_argument("--out", default="")
@@ -513,9 +609,11 @@ def main():
         a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "heatmap_blur_bench.jsonl")
     if a.window and not a.out:
         a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "heatmap_window_bench.jsonl")
+    if a.windows and not a.out:
+        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "heatmap_windows_bench.jsonl")
     if a.pyramid and not a.out:
         a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "heatmap_pyramid_bench.jsonl")
-    res = launches(a.arm, a.down) if a.launches else pyramid(a.seconds) if a.pyramid else window(a.seconds, a.w0_only) if a.window else blur(a.seconds) if a.blur else thumb(a.seconds) if a.thumb else resident(a.seconds, a.px)
+    res = launches(a.arm, a.down) if a.launches else windows(a.seconds) if a.windows else pyramid(a.seconds) if a.pyramid else window(a.seconds, a.w0_only) if a.window else blur(a.seconds) if a.blur else thumb(a.seconds) if a.thumb else resident(a.seconds, a.px)
     lines = [json.dumps(r) for r in res]
     print("\n".join(lines), flush=True)
     if a.out:
