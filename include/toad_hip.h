@@ -560,7 +560,7 @@ int toad_region_heat_window_u8(const unsigned char *region, int64_t pitch, int H
  * like any other, writes nothing and the others are still rendered. The descriptors travel to the device by value in the kernel argument, 32 a launch
  * (heat_blend_px_list_kernel, heat_thumb_list_kernel in csrc/heatmap.hip): a list of n non-empty windows is ceil(n / 32) launches inside this one call,
  * with no allocation, no host synchronisation, no copy, and no device memory dereferenced on the host. What is read and written per window is what
- * toad_region_heat_window_u8 reads and writes. Not done: several levels for a list (toad_region_heat_pyramid_u8 takes one window), windows of several
+ * toad_region_heat_window_u8 reads and writes. Several levels for a list: toad_region_heat_pyramid_windows_u8 below. Not done: windows of several
  * images in one call. */
 typedef struct { const unsigned char *region; int64_t pitch; int Hr, Wr, wx, wy; unsigned char *out; int64_t out_pitch; } ToadHeatWindow;
 int toad_region_heat_windows_u8(const ToadHeatWindow *windows /* HOST array */, int n,
@@ -585,6 +585,32 @@ int toad_region_heat_pyramid_u8(const unsigned char *region, int64_t pitch, int 
                                 const unsigned char *lut, int alpha, unsigned levels, int smooth, const unsigned char *mask, int64_t mask_pitch, int Hm,
                                 int Wm, int mask_down, int mask_thresh, unsigned char *const *outs /* HOST, 6 device pointers */,
                                 const int64_t *out_pitches /* HOST, 6 */, void *stream);
+
+/* Several levels for a LIST of windows of one image in one call (additive to ABI 15 too): the two calls above at once. A viewer redraws the visible
+ * blocks of a slide at full resolution plus one or two overviews, and a slide rendered strip by strip wants every level of every strip: with the calls
+ * above that is either one launch per window or one read of every window per level. `windows` is a HOST array of n descriptors, read before the call
+ * returns; region and outs[k] in them are device pointers, outs and out_pitches are indexed by k = log2(down) as in the pyramid call. cells, Gy, Gx,
+ * cell, lut, alpha, smooth, the mask plane and the SET of levels are the image's, shared by all windows. Canvas k of window w is byte for byte what the
+ * pyramid call writes for that window and that set; each window and each level keeps its own extent, Ho = Hr >> k and Wo = Wr >> k. A level that is
+ * empty for a window (Ho == 0 or Wo == 0) has no canvas there: outs[k] may be NULL, out_pitches[k] is not looked at, nothing is written, and the
+ * window's other levels are still rendered. Canvases of different windows may be views of one canvas per level of the whole image; canvases that overlap
+ * each other or a region of the list are the caller's business.
+ * Refusals: n < 0 (TOAD_EINVAL); cells, lut or, with n > 0, windows NULL (TOAD_EINVAL); then what the windows share, in the pyramid call's order and with
+ * its messages under this entry's name - cell, alpha, levels == 0 or a bit above 5, D >= 8 and D > cell (D the largest level), smooth, smooth = 1 at
+ * cell == 4 with two or more levels, the mask plane with mask_down a multiple of D; then, window by window, the first failing window winning with a
+ * message that begins "window k:" (k counted from 0) - region NULL, outs[j] NULL at a level asked for that is not empty for this window (TOAD_EINVAL), Hr
+ * or Wr not positive, (wx, wy) not non-negative multiples of max(4, D), wx + Wr >= 2^30, pitch, out_pitches[j] below 3 * Wo_j at such a level, the table
+ * not holding the window (TOAD_ESHAPE); then the workgroups of the whole list reaching 2^31 (TOAD_ESHAPE) and cells not 4-byte aligned (TOAD_EALIGN).
+ * Nothing is launched unless every window has passed. n == 0 launches nothing, and neither does a list whose canvases are all empty. With ONE level this
+ * is the list call above for that down - the same kernels, the same bytes. With two or more the descriptors travel to the device by value in the kernel
+ * argument, 16 a launch (heat_pyramid_list_kernel in csrc/heatmap.hip): a list of n windows that have a canvas pixel is ceil(n / 16) launches inside
+ * this one call, with no allocation, no host synchronisation, no copy, and no device memory dereferenced on the host. What is read and written per
+ * window is what the pyramid call reads and writes. Not done: smooth at cell == 4 with several levels, windows of several images in one call. */
+typedef struct { const unsigned char *region; int64_t pitch; int Hr, Wr, wx, wy;
+                 unsigned char *outs[6]; int64_t out_pitches[6]; } ToadHeatPyramidWindow;
+int toad_region_heat_pyramid_windows_u8(const ToadHeatPyramidWindow *windows /* HOST array */, int n,
+        const int *cells, int Gy, int Gx, int cell, const unsigned char *lut, int alpha, unsigned levels, int smooth,
+        const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm, int mask_down, int mask_thresh, void *stream);
 
 /* ---- Segmented tissue selection: CLAM's recipe - a median-filtered saturation channel of a low-resolution level, thresholded by a fixed value or by
  * Otsu's - defined in integers (additive to ABI 15 too). A second selector next to the per-pixel predicate above, which does not change; csrc/tissue_seg.hip.

@@ -22,6 +22,13 @@ class ToadHeatWindow(ctypes.Structure):
                 ("out_pitch", c_int64)]
 
 
+class ToadHeatPyramidWindow(ctypes.Structure):
+    """One window of toad_region_heat_pyramid_windows_u8's HOST array (include/toad_hip.h): region and outs[k] are device addresses, outs and out_pitches
+    indexed by k = log2(down); a level that is empty for the window keeps a null address."""
+    _fields_ = [("region", c_void_p), ("pitch", c_int64), ("Hr", c_int), ("Wr", c_int), ("wx", c_int), ("wy", c_int), ("outs", c_void_p * 6),
+                ("out_pitches", c_int64 * 6)]
+
+
 # name -> (restype, argtypes); mirrors include/toad_hip.h one to one
 SIGNATURES = {
     "toad_abi_version": (I, []),
@@ -120,6 +127,8 @@ SIGNATURES = {
     "toad_region_heat_windows_u8": (I, [ctypes.POINTER(ToadHeatWindow), I, P, I, I, I, P, I, I, I, P, I64, I, I, I, I, P]),
     # ... and several levels of that pyramid from one read of the window (levels: a bit set; outs, out_pitches: HOST arrays of 6): additive to ABI 15
     "toad_region_heat_pyramid_u8": (I, [P, I64, I, I, I, I, P, I, I, I, P, I, ctypes.c_uint, I, P, I64, I, I, I, I, P, P, P]),
+    # ... and those levels for a list of windows of one image in one call (windows: a HOST array of n ToadHeatPyramidWindow): additive to ABI 15
+    "toad_region_heat_pyramid_windows_u8": (I, [ctypes.POINTER(ToadHeatPyramidWindow), I, P, I, I, I, P, I, ctypes.c_uint, I, P, I64, I, I, I, I, P]),
     # ... and the Gaussian blur of the cell table in front of any of these canvases (the taps are a HOST array): additive to ABI 15
     "toad_heat_cells_blur": (I, [P, I, I, P, I, P, P]),
     # ... and the second tissue selector, CLAM's recipe in integers (saturation plane, median, histogram, cells): additive to ABI 15

@@ -32,7 +32,11 @@
 //   pyramid     (toad_region_heat_pyramid_u8) several of the six window canvases in one call, each byte for byte the window entry's: every level is defined
 //               from the region's own box sums, never from the level above, and box sums nest, so one read of the region serves them all.
 //
-// Seven kernels:
+//   pyramid list (toad_region_heat_pyramid_windows_u8) both at once: N windows of one slide, several levels each, in one launch per 16 windows; every canvas
+//               byte for byte the pyramid entry's.
+//
+// Eight kernels:
+//   heat_pyramid_list_kernel<RB,MASK>      heat_pyramid_kernel over a LIST of windows: descriptors by value, the same body (heat_pyramid_body.inc).
 //   heat_blend_px_list_kernel<DOWN,SMOOTH,MASK>, heat_thumb_list_kernel<DOWN>   the two single-level kernels below over a LIST of windows of one slide:
 //                                          descriptors by value in the kernel argument, a workgroup finds its window and runs the same body.
 //   heat_pyramid_kernel<RB,MASK>           two or more levels from one read: 1, 2, 4 finished in the lane, 8, 16, 32 in heat_thumb_kernel's tail.
@@ -490,6 +494,7 @@ __global__ __launch_bounds__(256) void heat_thumb_list_kernel(const HeatListArgs
 // levels and smooth are run-time, wave-uniform values; the template is the strip height and MASK. Each level keeps its own Ho x Wo: Ho[k] = 0 marks a
 // level that was not asked for or is empty. Every canvas byte is written once by one lane, nothing outside oy pitch_k + [0, 3 Wo_k) is written, there is
 // no atomic. The tent at cell == 4 (heat_px_lane's SMOOTH 2) is not done here: the launcher refuses it.
+// The body lies in heat_pyramid_body.inc, which heat_pyramid_list_kernel includes too.
 struct HeatPyrArgs {
     HeatPxArgs a;                                                    // Hi x Wi = Hr x Wr; out, out_pitch unused
     unsigned char *out[6]; int64_t pitch[6]; int Ho[6], Wo[6];
@@ -556,156 +561,60 @@ __device__ __forceinline__ void heat_pyr_fine(const HeatPyrArgs &p, const unsign
 
 template <int RB, bool MASK>
 __global__ __launch_bounds__(256) void heat_pyramid_kernel(const HeatPyrArgs p, const unsigned char *__restrict__ lut) {
-    constexpr int RW = RB / 4, NG = RW / 4;                          // rows per wave, 4-row blocks per lane
-    __shared__ unsigned lut_s[256];
-    __shared__ int part[3][3][4][32];                                // [level - 8, 16, 32][channel][wave][box of the chunk]
-    const HeatPxArgs &a = p.a;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    lut_s[tid] = (unsigned)lut[3 * tid] | ((unsigned)lut[3 * tid + 1] << 8) | ((unsigned)lut[3 * tid + 2] << 16);
-    __syncthreads();
-    const unsigned chunk = blockIdx.x % a.nchunks, rb = blockIdx.x / a.nchunks;
-    const unsigned x = chunk * 256u + (unsigned)lane * 4u, off = 3u * x;
-    const int64_t y0 = (int64_t)rb * RB + wave * RW;               // first row of this wave (may lie below Hr: then it reads nothing)
-    const unsigned char *src = a.region + y0 * a.pitch + off;
-    unsigned w[RW][3];
-    if (chunk * 256u + 256u <= (unsigned)a.Wi && y0 + RW <= a.Hi) {  // wave-uniform: all 768 bytes of all RW rows exist
-#pragma unroll
-        for (int r = 0; r < RW; ++r)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) w[r][k] = *reinterpret_cast<const u32_a1 *>(src + r * a.pitch + 4 * k);
-    } else {
-        const int rows = (int)max((int64_t)0, min((int64_t)RW, (int64_t)a.Hi - y0));
-        const int npx = x < (unsigned)a.Wi ? min(4, a.Wi - (int)x) : 0;
-#pragma unroll
-        for (int r = 0; r < RW; ++r) load_px4(src + r * a.pitch, r < rows ? npx : 0, w[r]);
-    }
+    const unsigned bid = blockIdx.x;
+    auto level_Ho = [&](int k) { return p.Ho[k]; };
+    auto level_Wo = [&](int k) { return p.Wo[k]; };
+    auto level_out = [&](int k) { return p.out[k]; };
+    auto level_pitch = [&](int k) { return p.pitch[k]; };
+#include "heat_pyramid_body.inc"
+}
 
-    if (p.levels & 7u) {                                             // levels 1, 2, 4: in the lane, block by block
-        const bool live = x < (unsigned)a.Wi;
-        const unsigned sx = x + (unsigned)a.wx;                    // the block's corner in the table's image: multiples of 4
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const int64_t yg = y0 + 4 * g, sy0 = yg + a.wy;
-            if (yg >= a.Hi) break;
-            const int gy = (int)(sy0 >> a.shift), gx = (int)(sx >> a.shift);
-            const int own = live ? min(a.cells[(int64_t)gy * a.Gx + gx], 255) : -1;
-            int v[2][2] = {{0, 0}, {0, 0}}, fxb = 0, fyb = 0;
-            if (p.smooth) {                                          // cell >= 8: 2 sx - cell and 2 sy0 - cell are multiples of 8
-                const int cell = 1 << a.shift, c2 = 2 * cell;
-                const int px = (int)(2u * sx) - cell;                // wx + Wr < 2^30, so 2 sx fits on every live lane
-                const int64_t py = 2 * sy0 - cell;
-                const int bx = px >> (a.shift + 1), by = (int)(py >> (a.shift + 1));
-                fxb = px & (c2 - 1); fyb = (int)(py & (c2 - 1));
-#pragma unroll
-                for (int r = 0; r < 2; ++r)
-#pragma unroll
-                    for (int c = 0; c < 2; ++c) {
-                        const int yy = by + r, xx = bx + c;
-                        const bool in = live && yy >= 0 && yy < a.Gy && xx >= 0 && xx < a.Gx;
-                        const int t = in ? a.cells[(int64_t)yy * a.Gx + xx] : -1;
-                        v[r][c] = t >= 0 ? min(t, 255) : max(own, 0);
-                    }
-            }
-            unsigned tis[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-            int thr = -1;                                            // without a mask every byte is above it
-            if constexpr (MASK) {                                    // mask_down is a multiple of D >= 2: one byte a block, or (levels 1 and 2) two rows of two
-                thr = a.mask_thresh;
-                const unsigned mx = sx >> a.mshift;
-                const int64_t my = sy0 >> a.mshift;
-                const int have = live && mx < (unsigned)a.Wm ? a.Wm - (int)mx : 0;
-                const unsigned char *mp = a.mask + my * a.mask_pitch + mx;
-                if (a.mshift >= 2) {
-                    const unsigned t = load_mask<1>(mp, my < a.Hm ? min(have, 1) : 0) * 0x01010101u;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) tis[r] = t;
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 2; ++r) {
-                        const unsigned t = load_mask<2>(mp + r * a.mask_pitch, my + r < a.Hm ? min(have, 2) : 0);
-                        tis[2 * r] = tis[2 * r + 1] = (t & 0xFFu) * 0x0101u | (t >> 8) * 0x01010000u;
-                    }
-                }
-            }
-            unsigned w4[4][3];
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int k = 0; k < 3; ++k) w4[r][k] = w[4 * g + r][k];
-            const bool tent = p.smooth != 0;
-            if (p.levels & 1u) heat_pyr_fine<1>(p, lut_s, w4, x, yg, own, tent, v, fxb, fyb, tis, thr);
-            if (p.levels & 2u) heat_pyr_fine<2>(p, lut_s, w4, x, yg, own, tent, v, fxb, fyb, tis, thr);
-            if (p.levels & 4u) heat_pyr_fine<4>(p, lut_s, w4, x, yg, own, tent, v, fxb, fyb, tis, thr);
-        }
-    }
+// ---- the pyramid of a list of windows of one slide in one launch: toad_region_heat_pyramid_windows_u8 ----
+// The list form of heat_pyramid_kernel, as heat_blend_px_list_kernel is the list form of heat_blend_px_kernel. The windows share the table, the mask plane,
+// the colours, alpha, smooth and the SET of levels - so D, the largest level, and RB are the list's - and each has a descriptor of its own: region, pitch,
+// extent, place, six canvases and their pitches, nchunks and its first workgroup, 136 bytes against HeatListWin's 56. The descriptors travel by value in the
+// kernel argument, 16 a launch; descriptors from n on carry first = 0xFFFFFFFF, so four uniform steps of a binary search over the 16 prefixes find a
+// workgroup's window. It then forms the window's HeatPyrArgs: Ho[k] = Hr >> k and Wo[k] = Wr >> k for the levels asked for, and a level that is empty for
+// THIS window gets extent 0 and leaves the window's set, exactly as the pyramid entry leaves it out on the host. From there on the body is
+// heat_pyramid_kernel's. A window's workgroups are counted from its full Hr x Wr on strips of RB rows: the finer levels need the rows a coarse level
+// drops. The grid is exact, and a window in which every level is empty never reaches a descriptor.
+constexpr int HEAT_PYR_LIST_MAX = 16;                                // 16 descriptors of 136 bytes and the shared part: 2.3 KB of the 4 KB a kernel argument may have
+struct HeatPyrListWin {
+    const unsigned char *region; int64_t pitch; int Hr, Wr, wx, wy;
+    unsigned char *out[6]; int64_t out_pitch[6]; unsigned nchunks, first;
+};
+struct HeatPyrListArgs { HeatPxArgs shared; unsigned levels; int smooth; HeatPyrListWin w[HEAT_PYR_LIST_MAX]; };
+static_assert(sizeof(HeatPyrListWin) == 136 && sizeof(HeatPyrListArgs) + sizeof(const unsigned char *) <= 4096, "the descriptors and lut must fit a kernel argument");
 
-    if (!(p.levels & 0x38u)) return;                                 // uniform over the workgroup: nobody waits at the barrier below
-    unsigned b[12];                                                // the 12 column sums over the wave's rows, each at most 8 * 255
-    column_sums<RW>(w, b);
+template <int RB, bool MASK>
+__global__ __launch_bounds__(256) void heat_pyramid_list_kernel(const HeatPyrListArgs l, const unsigned char *__restrict__ lut) {
+    static_assert(HEAT_PYR_LIST_MAX == 16, "four steps search 16 prefixes");
+    int win = 0;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int s2 = lanes_allreduce_sum<2>((int)(b[c] + b[c + 3] + b[c + 6] + b[c + 9]));
-        const int s4 = s2 + dpp_mov<0x4E>(s2), s8 = s4 + dpp_mov<0x141>(s4);
-        if ((lane & 1) == 0) part[0][c][wave][lane >> 1] = s2;
-        if ((lane & 3) == 0) part[1][c][wave][lane >> 2] = s4;
-        if ((lane & 7) == 0) part[2][c][wave][lane >> 3] = s8;
+    for (int step = HEAT_PYR_LIST_MAX / 2; step >= 1; step >>= 1)
+        if (l.w[win + step].first <= blockIdx.x) win += step;
+    const HeatPyrListWin &lw = l.w[win];
+    HeatPyrArgs p;
+    p.a = l.shared;
+    p.a.region = lw.region; p.a.pitch = lw.pitch; p.a.Hi = lw.Hr; p.a.Wi = lw.Wr;
+    p.a.nchunks = lw.nchunks; p.a.wx = lw.wx; p.a.wy = lw.wy;
+    p.levels = 0; p.smooth = l.smooth;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const int Ho = lw.Hr >> k, Wo = lw.Wr >> k;
+        const bool has = (l.levels >> k & 1u) && Ho != 0 && Wo != 0;
+        p.out[k] = lw.out[k]; p.pitch[k] = lw.out_pitch[k];
+        p.Ho[k] = has ? Ho : 0; p.Wo[k] = has ? Wo : 0;
+        if (has) p.levels |= 1u << k;
     }
-    __syncthreads();
-    int k, t;
-    if (tid < 128) { k = 3; t = tid; }
-    else if (tid < 160) { k = 4; t = tid - 128; }
-    else if (tid >= 192 && tid < 200) { k = 5; t = tid - 192; }
-    else return;
-    if (p.Ho[k] == 0) return;
-    const int down = 1 << k, band = t >> (8 - k), bx = t & ((256 >> k) - 1), wpb = down / RW;      // 256 / down boxes a chunk, RB / down box rows
-    if (band >= (RB >> k)) return;
-    const int64_t oy = (int64_t)rb * (RB >> k) + band;
-    const unsigned ox = chunk * (256u >> k) + (unsigned)bx;
-    if (oy >= p.Ho[k] || ox >= (unsigned)p.Wo[k]) return;
-    int m[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        int s = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (j < wpb) s += part[k - 3][c][band * wpb + j][bx];
-        m[c] = (s + (1 << (2 * k - 1))) >> (2 * k);
-    }
-    const int64_t py0 = oy * down + a.wy;                          // the box's corner in the table's image
-    const int px0 = (int)(ox * down) + a.wx;
-    const int own = min(a.cells[(py0 >> a.shift) * a.Gx + (px0 >> a.shift)], 255);
-    int idx = max(own, 0);
-    if (p.smooth && a.shift != k) {                                  // cell == down: the tent is the own value
-        const int cell = 1 << a.shift, c2 = 2 * cell;
-        const int px = 2 * px0 + down - cell;                      // wx + Wr < 2^30, so 2 x fits
-        const int64_t py = 2 * py0 + down - cell;
-        const int gx0 = px >> (a.shift + 1), fx = px & (c2 - 1);
-        const int gy0 = (int)(py >> (a.shift + 1)), fy = (int)(py & (c2 - 1));
-        int H[2];
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            int v[2];
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const int yy = gy0 + r, xx = gx0 + c;
-                const bool in = yy >= 0 && yy < a.Gy && xx >= 0 && xx < a.Gx;
-                const int tv = in ? a.cells[(int64_t)yy * a.Gx + xx] : -1;
-                v[c] = tv >= 0 ? min(tv, 255) : idx;
-            }
-            H[r] = c2 * v[0] + fx * (v[1] - v[0]);
-        }
-        idx = (c2 * H[0] + fy * (H[1] - H[0]) + 2 * cell * cell) >> (2 * a.shift + 2);
-    }
-    bool tissue = true;
-    if (MASK) {
-        const int64_t my = py0 >> a.mshift;
-        const int mx = px0 >> a.mshift;
-        tissue = my < a.Hm && mx < a.Wm && (int)a.mask[my * a.mask_pitch + mx] > a.mask_thresh;
-    }
-    const int al = own >= 0 && tissue ? a.alpha : 0;               // alpha' = 0 leaves m: (256 m + 128) >> 8
-    const unsigned col = lut_s[idx];
-    unsigned char *d = p.out[k] + oy * p.pitch[k] + 3u * ox;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) d[c] = (unsigned char)((al * (int)((col >> (8 * c)) & 255u) + (256 - al) * m[c] + 128) >> 8);
+    const unsigned bid = blockIdx.x - lw.first;
+    // the tail's level by a per-thread index: the extents again from the descriptor, the canvas from the kernel argument where it lies
+    const unsigned has = p.levels;
+    auto level_Ho = [&](int k) { return has >> k & 1u ? lw.Hr >> k : 0; };
+    auto level_Wo = [&](int k) { return has >> k & 1u ? lw.Wr >> k : 0; };
+    auto level_out = [&](int k) { return lw.out[k]; };
+    auto level_pitch = [&](int k) { return lw.out_pitch[k]; };
+#include "heat_pyramid_body.inc"
 }
 
 }  // namespace toad
@@ -931,13 +840,15 @@ extern "C" int toad_region_heat_window_u8(const unsigned char *region, int64_t p
 // The list entry: the window entry's checks of what the windows share, in its order; then window by window its checks of what each window has of its own,
 // in its order, the first failing window winning under "window k:"; then the workgroup count of the whole list and the alignment of cells, where the
 // window entry has them. Nothing is launched before all of that has passed. Two walks over the host array, no allocation: the first checks and counts,
-// the second fills HEAT_LIST_MAX descriptors at a time and launches them.
-extern "C" int toad_region_heat_windows_u8(const ToadHeatWindow *windows, int n, const int *cells, int Gy, int Gx, int cell, const unsigned char *lut, int alpha,
-                                           int down, int smooth, const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm, int mask_down, int mask_thresh,
-                                           void *stream) {
-    const char *what = "toad_region_heat_windows_u8";
+// the second fills HEAT_LIST_MAX descriptors at a time and launches them. window(k) gives descriptor k of the caller's host array as a ToadHeatWindow, so that
+// the pyramid list entry with ONE level is this very call; `vacant`: a window without a canvas pixel may come without a canvas address and pitch (that entry's
+// rule, since such a level has no canvas; the windows entry checks an empty window like any other).
+template <class Window>
+static int launch_heat_windows(const char *what, bool vacant, Window window, bool have_windows, int n, const int *cells, int Gy, int Gx, int cell,
+                               const unsigned char *lut, int alpha, int down, int smooth, const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm, int mask_down,
+                               int mask_thresh, void *stream) {
     if (n < 0) { set_error("%s: n = %d windows", what, n); return TOAD_EINVAL; }
-    if (!cells || !lut || (n > 0 && !windows)) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (!cells || !lut || (n > 0 && !have_windows)) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
     if (int rc = check_cell(what, cell)) return rc;
     if (int rc = check_heat_alpha(what, alpha)) return rc;
     if (int rc = check_heat_window_down(what, down, cell)) return rc;
@@ -953,15 +864,19 @@ extern "C" int toad_region_heat_windows_u8(const ToadHeatWindow *windows, int n,
         return nchunks * (((int64_t)Hi + rb - 1) / rb);
     };
     int64_t blocks = 0;
+    int dshift = 0;
+    while ((1 << dshift) < down) ++dshift;
     for (int k = 0; k < n; ++k) {
-        const ToadHeatWindow &w = windows[k];
-        char who[64];
+        const ToadHeatWindow w = window(k);
+        char who[80];
         snprintf(who, sizeof who, "window %d: %s", k, what);
-        if (!w.region || !w.out) { set_error("%s: null pointer", who); return TOAD_EINVAL; }
+        const bool canvas = !vacant || ((w.Hr >> dshift) != 0 && (w.Wr >> dshift) != 0);
+        if (!w.region || (canvas && !w.out)) { set_error("%s: null pointer", who); return TOAD_EINVAL; }
         if (int rc = check_hw(who, "Hr", w.Hr, "Wr", w.Wr)) return rc;
         if (int rc = check_heat_place(who, true, down, w.wx, w.wy, w.Wr)) return rc;
         if (int rc = check_region_pitch(who, w.pitch, w.Wr)) return rc;
-        if (int rc = check_heat_out_pitch(who, w.out_pitch, w.Wr / down)) return rc;
+        if (canvas)
+            if (int rc = check_heat_out_pitch(who, w.out_pitch, w.Wr / down)) return rc;
         if (int rc = check_heat_table_holds(who, w.wx, w.wy, w.Hr, w.Wr, cell, Gy, Gx)) return rc;
         int Hi, Wi;
         int64_t nchunks;
@@ -983,7 +898,7 @@ extern "C" int toad_region_heat_windows_u8(const ToadHeatWindow *windows, int n,
         int m = 0;
         unsigned grid = 0;
         for (; k < n && m < HEAT_LIST_MAX; ++k) {
-            const ToadHeatWindow &w = windows[k];
+            const ToadHeatWindow w = window(k);
             int Hi, Wi;
             int64_t nchunks;
             const int64_t b = geometry(w, Hi, Wi, nchunks);
@@ -1012,33 +927,29 @@ extern "C" int toad_region_heat_windows_u8(const ToadHeatWindow *windows, int n,
     return TOAD_OK;
 }
 
-// The pyramid entry: the window entry's checks in the window entry's order, taken over the set of levels - D, the largest, stands where `down` stood, and the
-// checks of the set and of its canvases where the down check sat. One level is the window entry itself; two or more are ONE launch of heat_pyramid_kernel.
-extern "C" int toad_region_heat_pyramid_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, int wx, int wy, const int *cells, int Gy, int Gx, int cell,
-                                           const unsigned char *lut, int alpha, unsigned levels, int smooth, const unsigned char *mask, int64_t mask_pitch,
-                                           int Hm, int Wm, int mask_down, int mask_thresh, unsigned char *const *outs, const int64_t *out_pitches, void *stream) {
-    const char *what = "toad_region_heat_pyramid_u8";
-    if (!region || !cells || !lut || !outs || !out_pitches) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
-    if (int rc = check_cell(what, cell)) return rc;
-    if (int rc = check_hw(what, "Hr", Hr, "Wr", Wr)) return rc;
-    if (alpha < 0 || alpha > 256) { set_error("%s: alpha = %d must lie in [0, 256] (256 = the colour alone)", what, alpha); return TOAD_ESHAPE; }
+extern "C" int toad_region_heat_windows_u8(const ToadHeatWindow *windows, int n, const int *cells, int Gy, int Gx, int cell, const unsigned char *lut, int alpha,
+                                           int down, int smooth, const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm, int mask_down, int mask_thresh,
+                                           void *stream) {
+    return launch_heat_windows("toad_region_heat_windows_u8", false, [&](int k) { return windows[k]; }, windows != nullptr, n, cells, Gy, Gx, cell, lut, alpha, down,
+                               smooth, mask, mask_pitch, Hm, Wm, mask_down, mask_thresh, stream);
+}
+
+// The checks of a set of levels that the pyramid entry and its list form both make, each with the one message. kmax = log2 of D, the largest level.
+static int check_heat_levels(const char *what, unsigned levels, int cell, int &kmax, int &nlev) {
     if (levels == 0 || levels > 63u) {
         set_error("%s: levels = 0x%x is not a non-empty set of bits 0 .. 5 (bit k asks for down = 2^k, down in 1 .. 32)", what, levels);
         return TOAD_ESHAPE;
     }
-    int kmax = 0, nlev = 0;
+    kmax = 0; nlev = 0;
     for (int k = 0; k < 6; ++k)
         if (levels >> k & 1u) { kmax = k; ++nlev; }
-    const int D = 1 << kmax;
-    if (D >= 8 && D > cell) {
-        set_error("%s: down = %d, the largest level, exceeds cell = %d (a canvas box must lie in one cell)", what, D, cell);
+    if ((1 << kmax) >= 8 && (1 << kmax) > cell) {
+        set_error("%s: down = %d, the largest level, exceeds cell = %d (a canvas box must lie in one cell)", what, 1 << kmax, cell);
         return TOAD_ESHAPE;
     }
-    for (int k = 0; k < 6; ++k)
-        if ((levels >> k & 1u) && !outs[k]) { set_error("%s: null pointer (outs[%d], the canvas of down = %d)", what, k, 1 << k); return TOAD_EINVAL; }
-    if (nlev == 1)                                                   // the same kernel, the same bytes, the same time
-        return launch_heat_blend(what, "the region, the mask and the canvases", false, true, region, pitch, Hr, Wr, wx, wy, cells, Gy, Gx, cell, lut, alpha, D, smooth,
-                                 mask, mask_pitch, Hm, Wm, mask_down, mask_thresh, outs[kmax], out_pitches[kmax], stream);
+    return TOAD_OK;
+}
+static int check_heat_pyr_place(const char *what, int D, int wx, int wy, int Wr) {
     const int walign = D > 4 ? D : 4;
     if (wx < 0 || wy < 0 || wx % walign || wy % walign) {
         set_error("%s: window (wx, wy) = (%d, %d) is negative or not a multiple of max(4, down) = %d, down the largest level (a lane's 4 x 4 block and a "
@@ -1049,39 +960,66 @@ extern "C" int toad_region_heat_pyramid_u8(const unsigned char *region, int64_t 
         set_error("%s: window too far right: wx + Wr = %lld must stay below 2^30 (doubled tent coordinates in 32 bits)", what, (long long)wx + Wr);
         return TOAD_ESHAPE;
     }
+    return TOAD_OK;
+}
+static int check_heat_pyr_smooth(const char *what, int smooth, int cell) {     // two or more levels
     if (smooth != 0 && smooth != 1) { set_error("%s: smooth = %d must be 0 or 1", what, smooth); return TOAD_EINVAL; }
     if (smooth && cell == 4) {
         set_error("%s: smooth at cell = 4 is not done for more than one level (the nine-neighbour tent: render those levels one by one)", what);
         return TOAD_ESHAPE;
     }
-    if (int rc = check_region_pitch(what, pitch, Wr)) return rc;
-    int mshift = 0;
-    if (mask) {
-        if (mask_down != 1 && mask_down != 2 && mask_down != 4 && mask_down != 8 && mask_down != 16 && mask_down != 32) {
-            set_error("%s: mask_down = %d is not one of 1, 2, 4, 8, 16, 32", what, mask_down);
-            return TOAD_ESHAPE;
-        }
-        if (mask_down % D) {
-            set_error("%s: mask_down = %d is not a multiple of down = %d, the largest level (a canvas box must lie in one mask pixel)", what, mask_down, D);
-            return TOAD_ESHAPE;
-        }
-        if (Hm < 0 || Wm < 0) { set_error("%s: Hm x Wm = %d x %d must not be negative", what, Hm, Wm); return TOAD_ESHAPE; }
-        if (int rc = check_plane_pitch(what, Wm, "mask_pitch", mask_pitch)) return rc;
-        if (int rc = check_u8(what, "mask_thresh", mask_thresh)) return rc;
-        while ((1 << mshift) < mask_down) ++mshift;
-    }
-    for (int k = 0; k < 6; ++k)
-        if ((levels >> k & 1u) && out_pitches[k] < 3 * (int64_t)(Wr >> k)) {
-            set_error("%s: out_pitches[%d] = %lld is less than a row of the canvas of down = %d (3 Wo = %lld bytes)", what, k, (long long)out_pitches[k], 1 << k,
-                      3ll * (Wr >> k));
-            return TOAD_ESHAPE;
-        }
-    const int64_t gy_end = ((int64_t)wy + Hr + cell - 1) / cell, gx_end = ((int64_t)wx + Wr + cell - 1) / cell;
-    if (gy_end > Gy || gx_end > Gx) {
-        set_error("%s: the window ends at cell row %lld and cell column %lld, beyond the table's Gy x Gx = %d x %d (ceil((wy + Hr) / cell) <= Gy and "
-                  "ceil((wx + Wr) / cell) <= Gx)", what, (long long)gy_end, (long long)gx_end, Gy, Gx);
+    return TOAD_OK;
+}
+static int check_heat_pyr_mask(const char *what, int D, const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm, int mask_down, int mask_thresh, int &mshift) {
+    mshift = 0;
+    if (!mask) return TOAD_OK;
+    if (mask_down != 1 && mask_down != 2 && mask_down != 4 && mask_down != 8 && mask_down != 16 && mask_down != 32) {
+        set_error("%s: mask_down = %d is not one of 1, 2, 4, 8, 16, 32", what, mask_down);
         return TOAD_ESHAPE;
     }
+    if (mask_down % D) {
+        set_error("%s: mask_down = %d is not a multiple of down = %d, the largest level (a canvas box must lie in one mask pixel)", what, mask_down, D);
+        return TOAD_ESHAPE;
+    }
+    if (Hm < 0 || Wm < 0) { set_error("%s: Hm x Wm = %d x %d must not be negative", what, Hm, Wm); return TOAD_ESHAPE; }
+    if (int rc = check_plane_pitch(what, Wm, "mask_pitch", mask_pitch)) return rc;
+    if (int rc = check_u8(what, "mask_thresh", mask_thresh)) return rc;
+    while ((1 << mshift) < mask_down) ++mshift;
+    return TOAD_OK;
+}
+static int check_heat_pyr_out_pitch(const char *what, int k, int64_t out_pitch, int Wr) {
+    if (out_pitch >= 3 * (int64_t)(Wr >> k)) return TOAD_OK;
+    set_error("%s: out_pitches[%d] = %lld is less than a row of the canvas of down = %d (3 Wo = %lld bytes)", what, k, (long long)out_pitch, 1 << k, 3ll * (Wr >> k));
+    return TOAD_ESHAPE;
+}
+
+// The pyramid entry: the window entry's checks in the window entry's order, taken over the set of levels - D, the largest, stands where `down` stood, and the
+// checks of the set and of its canvases where the down check sat. One level is the window entry itself; two or more are ONE launch of heat_pyramid_kernel.
+extern "C" int toad_region_heat_pyramid_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, int wx, int wy, const int *cells, int Gy, int Gx, int cell,
+                                           const unsigned char *lut, int alpha, unsigned levels, int smooth, const unsigned char *mask, int64_t mask_pitch,
+                                           int Hm, int Wm, int mask_down, int mask_thresh, unsigned char *const *outs, const int64_t *out_pitches, void *stream) {
+    const char *what = "toad_region_heat_pyramid_u8";
+    if (!region || !cells || !lut || !outs || !out_pitches) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (int rc = check_cell(what, cell)) return rc;
+    if (int rc = check_hw(what, "Hr", Hr, "Wr", Wr)) return rc;
+    if (alpha < 0 || alpha > 256) { set_error("%s: alpha = %d must lie in [0, 256] (256 = the colour alone)", what, alpha); return TOAD_ESHAPE; }
+    int kmax = 0, nlev = 0;
+    if (int rc = check_heat_levels(what, levels, cell, kmax, nlev)) return rc;
+    const int D = 1 << kmax;
+    for (int k = 0; k < 6; ++k)
+        if ((levels >> k & 1u) && !outs[k]) { set_error("%s: null pointer (outs[%d], the canvas of down = %d)", what, k, 1 << k); return TOAD_EINVAL; }
+    if (nlev == 1)                                                   // the same kernel, the same bytes, the same time
+        return launch_heat_blend(what, "the region, the mask and the canvases", false, true, region, pitch, Hr, Wr, wx, wy, cells, Gy, Gx, cell, lut, alpha, D, smooth,
+                                 mask, mask_pitch, Hm, Wm, mask_down, mask_thresh, outs[kmax], out_pitches[kmax], stream);
+    if (int rc = check_heat_pyr_place(what, D, wx, wy, Wr)) return rc;
+    if (int rc = check_heat_pyr_smooth(what, smooth, cell)) return rc;
+    if (int rc = check_region_pitch(what, pitch, Wr)) return rc;
+    int mshift = 0;
+    if (int rc = check_heat_pyr_mask(what, D, mask, mask_pitch, Hm, Wm, mask_down, mask_thresh, mshift)) return rc;
+    for (int k = 0; k < 6; ++k)
+        if (levels >> k & 1u)
+            if (int rc = check_heat_pyr_out_pitch(what, k, out_pitches[k], Wr)) return rc;
+    if (int rc = check_heat_table_holds(what, wx, wy, Hr, Wr, cell, Gy, Gx)) return rc;
     const int rb = strip_rows(D);
     const int64_t nchunks = ((int64_t)Wr + 255) / 256, blocks = nchunks * (((int64_t)Hr + rb - 1) / rb);
     if (int rc = check_blocks(what, "region", blocks)) return rc;
@@ -1106,4 +1044,97 @@ extern "C" int toad_region_heat_pyramid_u8(const unsigned char *region, int64_t 
     else { if (mask) TOAD_PYR(16, true); else TOAD_PYR(16, false); }
 #undef TOAD_PYR
     return check_launch(what);
+}
+
+// The pyramid list entry: the list entry's walk over the pyramid entry's checks. What the windows share first, in the pyramid entry's order and with its
+// messages; then window by window what each has of its own, the first failing window winning under "window k:"; then the workgroup count of the whole list
+// and the alignment of cells. A level that is empty for a window has no canvas there: neither its address nor its pitch is looked at. One level is the list
+// entry itself; two or more are one launch of heat_pyramid_list_kernel per HEAT_PYR_LIST_MAX windows that have a canvas pixel. Two walks, no allocation.
+extern "C" int toad_region_heat_pyramid_windows_u8(const ToadHeatPyramidWindow *windows, int n, const int *cells, int Gy, int Gx, int cell, const unsigned char *lut,
+                                                   int alpha, unsigned levels, int smooth, const unsigned char *mask, int64_t mask_pitch, int Hm, int Wm,
+                                                   int mask_down, int mask_thresh, void *stream) {
+    const char *what = "toad_region_heat_pyramid_windows_u8";
+    if (n < 0) { set_error("%s: n = %d windows", what, n); return TOAD_EINVAL; }
+    if (!cells || !lut || (n > 0 && !windows)) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (int rc = check_cell(what, cell)) return rc;
+    if (int rc = check_heat_alpha(what, alpha)) return rc;
+    int kmax = 0, nlev = 0;
+    if (int rc = check_heat_levels(what, levels, cell, kmax, nlev)) return rc;
+    const int D = 1 << kmax;
+    if (nlev == 1) {                                                 // the same kernels, the same bytes; its shared checks are the window entry's, as the pyramid entry's are
+        auto window = [&](int k) {
+            const ToadHeatPyramidWindow &w = windows[k];
+            return ToadHeatWindow{w.region, w.pitch, w.Hr, w.Wr, w.wx, w.wy, w.outs[kmax], w.out_pitches[kmax]};
+        };
+        return launch_heat_windows(what, true, window, windows != nullptr, n, cells, Gy, Gx, cell, lut, alpha, D, smooth, mask, mask_pitch, Hm, Wm, mask_down,
+                                   mask_thresh, stream);
+    }
+    if (int rc = check_heat_pyr_smooth(what, smooth, cell)) return rc;
+    int mshift = 0;
+    if (int rc = check_heat_pyr_mask(what, D, mask, mask_pitch, Hm, Wm, mask_down, mask_thresh, mshift)) return rc;
+    const int rb = strip_rows(D);
+    // the levels window w has a canvas pixel at, and its workgroups: 0 where it has none
+    auto geometry = [&](const ToadHeatPyramidWindow &w, unsigned &has, int64_t &nchunks) {
+        has = 0;
+        for (int j = 0; j < 6; ++j)
+            if ((levels >> j & 1u) && (w.Hr >> j) != 0 && (w.Wr >> j) != 0) has |= 1u << j;
+        nchunks = ((int64_t)w.Wr + 255) / 256;
+        return has ? nchunks * (((int64_t)w.Hr + rb - 1) / rb) : (int64_t)0;
+    };
+    int64_t blocks = 0;
+    for (int k = 0; k < n; ++k) {
+        const ToadHeatPyramidWindow &w = windows[k];
+        char who[80];
+        snprintf(who, sizeof who, "window %d: %s", k, what);
+        unsigned has;
+        int64_t nchunks;
+        if (!w.region) { set_error("%s: null pointer", who); return TOAD_EINVAL; }
+        geometry(w, has, nchunks);
+        for (int j = 0; j < 6; ++j)
+            if ((has >> j & 1u) && !w.outs[j]) { set_error("%s: null pointer (outs[%d], the canvas of down = %d)", who, j, 1 << j); return TOAD_EINVAL; }
+        if (int rc = check_hw(who, "Hr", w.Hr, "Wr", w.Wr)) return rc;
+        if (int rc = check_heat_pyr_place(who, D, w.wx, w.wy, w.Wr)) return rc;
+        if (int rc = check_region_pitch(who, w.pitch, w.Wr)) return rc;
+        for (int j = 0; j < 6; ++j)
+            if (has >> j & 1u)
+                if (int rc = check_heat_pyr_out_pitch(who, j, w.out_pitches[j], w.Wr)) return rc;
+        if (int rc = check_heat_table_holds(who, w.wx, w.wy, w.Hr, w.Wr, cell, Gy, Gx)) return rc;
+        blocks += geometry(w, has, nchunks);                         // one window: below 2^50; the sum is refused as soon as it reaches 2^31
+        if (int rc = check_blocks(what, "list of regions", blocks)) return rc;
+    }
+    if (!aligned4(cells)) {
+        set_error("%s: cells (int32 [Gy][Gx]) must be 4-byte aligned (the regions, the mask and the canvases may have any alignment)", what);
+        return TOAD_EALIGN;
+    }
+    if (blocks == 0) return TOAD_OK;
+    int shift = 2;
+    while ((1 << shift) < cell) ++shift;
+    HeatPyrListArgs l = {};
+    l.shared = {nullptr, 0, 0, 0, cells, Gy, Gx, shift, alpha, mask, mask_pitch, Hm, Wm, mshift, mask_thresh, nullptr, 0, 0u, 0, 0};
+    l.levels = levels; l.smooth = smooth;
+    for (int k = 0; k < n;) {
+        int m = 0;
+        unsigned grid = 0;
+        for (; k < n && m < HEAT_PYR_LIST_MAX; ++k) {
+            const ToadHeatPyramidWindow &w = windows[k];
+            unsigned has;
+            int64_t nchunks;
+            const int64_t b = geometry(w, has, nchunks);
+            if (b == 0) continue;
+            HeatPyrListWin &d = l.w[m++];
+            d = {};
+            d.region = w.region; d.pitch = w.pitch; d.Hr = w.Hr; d.Wr = w.Wr; d.wx = w.wx; d.wy = w.wy; d.nchunks = (unsigned)nchunks; d.first = grid;
+            for (int j = 0; j < 6; ++j)
+                if (has >> j & 1u) { d.out[j] = w.outs[j]; d.out_pitch[j] = w.out_pitches[j]; }
+            grid += (unsigned)b;
+        }
+        if (m == 0) break;
+        for (int j = m; j < HEAT_PYR_LIST_MAX; ++j) { l.w[j] = {}; l.w[j].first = 0xFFFFFFFFu; }      // above every workgroup index: the search stops short of them
+#define TOAD_PYR_LIST(R, M) hipLaunchKernelGGL((heat_pyramid_list_kernel<R, M>), dim3(grid), dim3(256), 0, (hipStream_t)stream, l, lut)
+        if (rb == 32) { if (mask) TOAD_PYR_LIST(32, true); else TOAD_PYR_LIST(32, false); }
+        else { if (mask) TOAD_PYR_LIST(16, true); else TOAD_PYR_LIST(16, false); }
+#undef TOAD_PYR_LIST
+        if (int rc = check_launch(what)) return rc;
+    }
+    return TOAD_OK;
 }

@@ -338,7 +338,7 @@ def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region
 def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_hw, tile=256, stride=None, origin=(0, 0), origins=None,
                             min_fraction: float = 0.25, sat_thresh: int = 8, val_min: int = 0, bag_dtype: torch.dtype = torch.float16, alpha=102,
                             down: int = 1, lut=None, out=None, smooth: bool = False, mask=None, thresh=None, binarize: bool = False, blur=False, shrink=1,
-                            batch_render: bool = False):
+                            batch_render: bool = False, batch_levels: bool = False):
     """``(origins, scores, canvas)`` of a slide of ``slide_hw`` = (Hs, Ws) pixels that arrives from the decoder strip by strip: what
     ``region_tissue_attention_heatmap`` gives for one region, with no seam where two strips meet. ``strips`` is a sequence of ``(region, y_k)`` - a
     decoded uint8 [H_k,Ws,3] full-width strip on the device and the slide row of its first row - sorted, each abutting or overlapping the one before,
@@ -364,13 +364,17 @@ def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_
 
     ``batch_render=True`` (an int ``down`` only) makes pass 2 ONE ``heatmap.windows_canvas`` call over all strips - each strip's rendered rows as a view,
     its rows of the one canvas as ``out`` - and so one launch instead of one per strip; the strips are resident by then, and the bytes are the same.
-    With ``False`` every call is what it was. With a sequence of levels it is a ValueError: pyramid levels for a list of windows are not done.
+    With ``False`` every call is what it was. With a sequence of levels it is a ValueError: that is ``batch_levels``.
+
+    ``batch_levels=True`` (a sequence ``down`` only) makes pass 2 ONE ``heatmap.windows_pyramid`` call over all strips - each strip's rendered rows as
+    the region, its rows of every level's slide canvas as its ``outs`` - and so one launch per ``ops.HEAT_PYR_LIST_MAX`` strips and one read of every
+    strip; the dict ``{down: canvas}`` is byte for byte what the walk gives. With an int ``down`` it is a ValueError: that is ``batch_render``.
 
     Not done here: the segmented selector across strips - its median, closing and component steps reach across strip seams, so
     ``tissue.segmented_tissue_origins`` still works on one region per call; make that selection on an overview level and pass it in through
     ``origins=`` and ``mask=``. Blocks that are not full-width strips (``heatmap.window_canvas`` renders any window; this walk does not), and the
     "not done" list of ``region_tissue_attention_heatmap`` except seams."""
-    from .heatmap import slide_cells, strip_plan, window_canvas, window_pyramid, windows_canvas
+    from .heatmap import slide_cells, strip_plan, window_canvas, window_pyramid, windows_canvas, windows_pyramid
     from .heatmap import blur_taps
     from .tissue import _lattice_args, lattice_cell, tissue_origins
     hs, ws = slide_hw
@@ -381,11 +385,16 @@ def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_
     cell = lattice_cell((h, w), (sy, sx), (x0, y0))
     if not isinstance(batch_render, bool):
         raise ValueError(f"slide_attention_heatmap: batch_render must be a bool, got {batch_render!r}")
+    if not isinstance(batch_levels, bool):
+        raise ValueError(f"slide_attention_heatmap: batch_levels must be a bool, got {batch_levels!r}")
     levels = None                                                   # a sequence of levels: pass 2 renders them all in one walk over the strips
+    if batch_levels and not isinstance(down, (tuple, list)):
+        raise ValueError("slide_attention_heatmap: batch_levels=True takes a sequence of levels, not one down (one canvas for a list of windows: "
+                         "batch_render=True)")
     if isinstance(down, (tuple, list)):
         if batch_render:
-            raise ValueError("slide_attention_heatmap: batch_render=True takes one down, not a sequence of levels (pyramid levels for a list of windows are "
-                             "not done)")
+            raise ValueError("slide_attention_heatmap: batch_render=True takes one down, not a sequence of levels (pyramid levels for a list of windows: "
+                             "batch_levels=True)")
         from .ops import heat_downs_arg
         levels = heat_downs_arg("slide_attention_heatmap", down)
         if cell < max(levels):
@@ -440,7 +449,13 @@ def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_
             if not isinstance(c, torch.Tensor) or tuple(c.shape) != (hs // d, ws // d, 3):
                 raise ValueError(f"slide_attention_heatmap: out[{d}] must be a uint8 [{hs // d},{ws // d},3] tensor on the strips' device")
             canvases[d] = c
-        for (region, y), p in zip(strips, plan):                    # pass 2: each strip's own rows of every level's canvas, one read of the strip
+        if batch_levels:                                            # pass 2 in one call: every strip's own rows of every level's canvas
+            spans = [p["render"] for p in plan]
+            windows_pyramid([region[r0 - y:r1 - y] for (region, y), (r0, r1) in zip(strips, spans)], [(0, r0) for r0, _ in spans], cells, cell, alpha=alpha,
+                            downs=levels, lut=lut, outs=[[canvases[d][r0 // d:r0 // d + (r1 - r0) // d] for d in levels] for r0, r1 in spans], smooth=smooth,
+                            mask=mask)
+            return found, scores, canvases
+        for (region, y), p in zip(strips, plan):                  # pass 2: each strip's own rows of every level's canvas, one read of the strip
             r0, r1 = p["render"]
             window_pyramid(region[r0 - y:r1 - y], (0, r0), cells, cell, alpha=alpha, downs=levels, lut=lut,
                            outs=[canvases[d][r0 // d:r0 // d + (r1 - r0) // d] for d in levels], smooth=smooth, mask=mask)

@@ -44,7 +44,8 @@ cells on the usual 256 / 64 lattice, a field band-limited far below the cell pit
 Conventions as in ``toad_amd.tissue``: ``tile`` = int or (H, W), ``stride`` = int or (sy, sx), ``origin`` = (x, y) of the lattice's first tile.
 Not done here: a sigma per axis for tiles that are not square, radii above 16 cells (``blur=True`` on lattices whose cell is 16 or less), CLAM's second
 blur of the coloured image and saving images. Several levels of the vis-level pyramid come from one read of the region: ``window_pyramid`` and
-``attention_pyramid`` (``ops.region_heat_pyramid``), and ``down`` as a sequence in the two ``eval`` heat-map calls.
+``attention_pyramid`` (``ops.region_heat_pyramid``), ``windows_pyramid`` for a list of windows in one call (``ops.region_heat_pyramid_windows``), and
+``down`` as a sequence in the two ``eval`` heat-map calls.
 
 A slide that arrives from the decoder in strips or blocks is rendered window by window with no seams: ``slide_cells`` builds the cell table of the whole
 slide - only the lattice and the extent matter to it -, ``window_canvas`` renders one decoded window against that table (``ops.region_heat_window``: a
@@ -268,6 +269,24 @@ def window_pyramid(region: torch.Tensor, window, cells: torch.Tensor, cell: int,
     lut = jet_lut(region.device) if lut is None else lut
     return ops.region_heat_pyramid(region, window, cells, cell, lut, a, downs, smooth=smooth, mask=plane, mask_down=mask_down if plane is not None else None,
                                    mask_thresh=t if plane is not None else 0, outs=outs)
+
+
+def windows_pyramid(regions, windows, cells: torch.Tensor, cell: int, alpha=102, downs=(1, 4, 16), lut=None, outs=None, smooth: bool = False,
+                    mask=None) -> tuple:
+    """``window_pyramid`` for a list of windows of one slide: a tuple with one tuple of canvases per window, in the order of ``downs``, window k's
+    byte for byte ``window_pyramid(regions[k], windows[k], ...)``. ``regions`` are the decoded windows - blocks, strips, of any extents -
+    ``windows`` their places (wx, wy) in the slide, multiples of max(4, max(downs)); ``outs`` None or per window one view per level, for example each
+    window's rows and columns of per-level slide canvases; everything else is the slide's and shared. Through ``ops.region_heat_pyramid_windows``: one
+    library call, one launch per ``ops.HEAT_PYR_LIST_MAX`` windows, one read of every window."""
+    a = _alpha_arg(alpha)
+    if not isinstance(smooth, bool):
+        raise ValueError(f"windows_pyramid: smooth must be a bool, got {smooth!r}")
+    plane, t, mask_down = _mask_arg(mask)
+    if lut is None:
+        first = regions[0] if not isinstance(regions, torch.Tensor) and hasattr(regions, "__len__") and len(regions) else cells
+        lut = jet_lut(first.device if isinstance(first, torch.Tensor) else cells.device)
+    return ops.region_heat_pyramid_windows(regions, windows, cells, cell, lut, a, downs, smooth=smooth, mask=plane,
+                                           mask_down=mask_down if plane is not None else None, mask_thresh=t if plane is not None else 0, outs=outs)
 
 
 def strip_plan(slide_hw, strips, tile=256, stride=None, origin=(0, 0), down: int = 1):

@@ -1863,6 +1863,86 @@ def region_heat_pyramid(region: torch.Tensor, window, cells: torch.Tensor, cell:
     return outs
 
 
+HEAT_PYR_LIST_MAX = 16                 # the windows one launch of region_heat_pyramid_windows takes (csrc/heatmap.hip): a longer list is more launches in the one call
+
+
+def region_heat_pyramid_windows(regions, windows, cells: torch.Tensor, cell: int, lut: torch.Tensor, alpha: int, downs, smooth: bool = False, mask=None,
+                                mask_down=None, mask_thresh: int = 0, outs=None) -> tuple:
+    """region_heat_pyramid for a LIST of windows of one slide in ONE library call and one launch per HEAT_PYR_LIST_MAX windows
+    (toad_region_heat_pyramid_windows_u8; include/toad_hip.h): a tuple with one tuple of canvases per window, in the order of ``downs``, canvas j of
+    window k being uint8 [Hr_k // downs[j], Wr_k // downs[j], 3] and byte for byte what region_heat_pyramid gives for ``regions[k]`` at ``windows[k]`` =
+    (wx, wy) with the same other arguments. ``regions`` and ``windows`` are region_heat_windows's - views of any extents, pitches and alignment on one
+    device and their places, here multiples of max(4, max(downs)); ``cells``, ``cell``, ``lut``, ``alpha``, ``downs``, ``smooth`` and the ``mask`` plane
+    are the slide's and shared, under region_heat_pyramid's rules. ``outs`` is None or one sequence per window of one view per level, for example each
+    window's rows and columns of per-level slide canvases: within one window no two levels may share storage and none may share storage with its
+    region; across windows the canvases may be views of one canvas, and overlap between windows is the caller's business. The checks are
+    region_heat_pyramid's, per window, with ValueErrors that name the window's index, all before the library is called. A level that is empty for a
+    window is returned empty there, and the window's other levels and the other windows are still rendered. No synchronisation, no copy to the
+    device: the descriptors travel in the kernel argument. An empty list, or one whose canvases are all empty, launches nothing."""
+    name = "region_heat_pyramid_windows"
+    ds = heat_downs_arg(name, downs)
+    top = max(ds)
+    for arg, what in ((regions, "regions"), (windows, "windows")):
+        if isinstance(arg, (str, bytes, torch.Tensor)) or not hasattr(arg, "__len__") or not hasattr(arg, "__iter__"):
+            raise ValueError(f"{name}: {what} must be a sequence with one entry per window, got {type(arg).__name__}")
+    regions, windows = tuple(regions), tuple(windows)
+    n = len(regions)
+    if len(windows) != n:
+        raise ValueError(f"{name}: {n} regions but {len(windows)} windows: one (wx, wy) per region")
+    if outs is not None:
+        if isinstance(outs, torch.Tensor) or not hasattr(outs, "__len__") or len(outs) != n:
+            raise ValueError(f"{name}: outs must be None or a sequence of {n} sequences of {len(ds)} canvases, one per window and level of downs = {ds}")
+        outs = tuple(outs)
+    _cell_arg(name, cell)
+    if top > cell:
+        raise ValueError(f"{name}: down = {top}, the largest level, exceeds cell = {cell}: a canvas box must lie in one cell")
+    if not isinstance(alpha, int) or isinstance(alpha, bool) or not 0 <= alpha <= 256:
+        raise ValueError(f"{name}: alpha must be an int in [0, 256], got {alpha!r}")
+    _chk(cells, "cells", dtype=torch.int32)
+    device = regions[0].device if n and isinstance(regions[0], torch.Tensor) else cells.device
+    _heat_lut_arg(name, lut, device)
+    alpha, mask, plane = _heat_px_args(name, device, alpha, top, smooth, mask, mask_down, mask_thresh)
+    if smooth and cell == 4 and len(ds) > 1:
+        raise ValueError(f"{name}: smooth at cell = 4 is not done for more than one level (render those levels one by one with region_heat_windows)")
+    result, live = [], []
+    for k, (region, window) in enumerate(zip(regions, windows)):
+        who = f"{name}: window {k}"
+        pitch, hr, wr = _region_pitch(region, who)
+        if region.device != device:
+            raise ValueError(f"{who}: every region must be on one device ({device}), got {region.device}")
+        wx, wy = _heat_window_arg(who, window, top, cell, hr, wr, cells)
+        given = None
+        if outs is not None:
+            given = outs[k]
+            if isinstance(given, torch.Tensor) or not hasattr(given, "__len__") or len(given) != len(ds):
+                raise ValueError(f"{who}: outs[{k}] must be a sequence of {len(ds)} canvases, one per level of downs = {ds}")
+            given = tuple(given)
+        shapes = [(hr // d, wr // d) for d in ds]
+        canvases = tuple(_heat_out_arg(who, region, None if given is None else given[j], ho, wo, what=f"outs[{k}][{j}] (down = {d})")
+                         for j, (d, (ho, wo)) in enumerate(zip(ds, shapes)))
+        if given is not None:
+            for j, (ho, wo) in enumerate(shapes):
+                for i in range(j):
+                    if ho and wo and shapes[i][0] and shapes[i][1] and canvases[j].untyped_storage().data_ptr() == canvases[i].untyped_storage().data_ptr():
+                        raise ValueError(f"{who}: outs[{k}][{i}] and outs[{k}][{j}] must not share storage (every canvas of a window is written in the same launch)")
+        result.append(canvases)
+        if any(ho and wo for ho, wo in shapes):
+            live.append((region, pitch, hr, wr, wx, wy, [(d.bit_length() - 1, c, wo) for d, c, (ho, wo) in zip(ds, canvases, shapes) if ho and wo]))
+    if live:
+        lib = _lib.load()
+        host = (_lib.ToadHeatPyramidWindow * len(live))()
+        for desc, (r, rp, hr, wr, wx, wy, levels) in zip(host, live):
+            desc.region, desc.pitch, desc.Hr, desc.Wr, desc.wx, desc.wy = r.data_ptr(), rp, hr, wr, wx, wy
+            for b, c, wo in levels:
+                desc.outs[b], desc.out_pitches[b] = c.data_ptr(), _row_pitch(c, 3 * wo)
+        bits = 0
+        for d in ds:
+            bits |= d
+        _lib.check(lib.toad_region_heat_pyramid_windows_u8(host, len(live), _p(cells), cells.shape[0], cells.shape[1], cell, _p(lut), alpha, bits, int(smooth), _p(mask),
+                                                           *plane, _stream()), "toad_region_heat_pyramid_windows_u8")
+    return tuple(result)
+
+
 def maxpool3x3s2_nhwc(x: torch.Tensor) -> torch.Tensor:
     _chk(x, "x")
     b, h, w, c = x.shape

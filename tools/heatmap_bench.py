@@ -81,8 +81,21 @@ its alternation of the arms inside one process, warm-up of every arm, its four s
     w0_spread, W0's own interleaved-halves spread: l_faster_beyond_spread says whether the list beats the per-window calls by more than that. l_over_w0
     = L4 / W0 and L16 / W0, and c_over_w0 likewise, are reported without a bar. Default output profiles/heatmap_windows_bench.jsonl.
 
+  pyramid windows (--pyramid-windows): what several levels for a LIST of windows in one call (ops.region_heat_pyramid_windows,
+    toad_region_heat_pyramid_windows_u8) save over one pyramid call per window. The --window / --pyramid setup: same slides, table, colours and masks, the
+    cell table built once per run; level sets (1, 4, 16) and all six, each flat and with smooth + mask. Arms, alternated in one process on the rotating
+    slides, each into per-level canvases allocated once:
+      P           ops.region_heat_pyramid on the whole slide: one launch;
+      PW4, PW16   the 4 strips and the 4 x 4 block grid through one ops.region_heat_pyramid call each: 4 and 16 calls and launches;
+      PL4, PL16   the same strips and blocks through ONE ops.region_heat_pyramid_windows call: one launch;
+      CL4, CL16   the library entry itself on a host array built once per slide: the launch without the Python wrapper's per-window checks and views.
+    PW, PL and CL are checked torch.equal to P, level by level, on every slide before anything is timed. pl_over_pw = PL4 / PW4 and PL16 / PW16, median
+    over median, next to p_spread, P's own interleaved-halves spread: pl_faster_beyond_spread says whether the list beats the per-window calls by more
+    than that. pl_over_p, cl_over_p and pw_over_p are reported without a bar. Default output profiles/heatmap_pyramid_windows_bench.jsonl.
+
 Prints one JSON line per result; --out FILE keeps them.
-usage: heatmap_bench.py [--launches --arm A|B --down D] [--px | --thumb | --blur | --window [--w0-only] | --windows | --pyramid] [--seconds S] [--out FILE]"""
+usage: heatmap_bench.py [--launches --arm A|B --down D] [--px | --thumb | --blur | --window [--w0-only] | --windows | --pyramid | --pyramid-windows]
+                        [--seconds S] [--out FILE]"""
 import argparse
 import json
 import os
@@ -578,6 +591,102 @@ def pyramid(seconds):
     return res
 
 
+PYRAMID_WINDOWS_SETS = ((1, 4, 16), (1, 2, 4, 8, 16, 32))
+
+
+def pyramid_windows(seconds):
+    """The --pyramid-windows figures: one record per (level set, flat | smooth + mask)."""
+    from toad_amd import _lib
+    dev = torch.device("cuda:0")
+    slides, table, lut = setup(dev)
+    cells = ops.heat_cells(table, CELL, (0, 0), (TILE, TILE), (STRIDE, STRIDE), (NX, NY), (HR, WR))
+    strips = [(0, y, WR, HR // 4) for y in range(0, HR, HR // 4)]
+    blocks = [(x, y, WR // 4, HR // 4) for y in range(0, HR, HR // 4) for x in range(0, WR, WR // 4)]
+    res = []
+    for ds in PYRAMID_WINDOWS_SETS:
+        md = MASK_DOWN if max(ds) <= MASK_DOWN else THUMB_MASK_DOWN
+        masks = {s.data_ptr(): segment_tissue(s, md, 7, 8) for s in slides}
+        outs = [torch.empty((HR // d, WR // d, 3), dtype=torch.uint8, device=dev) for d in ds]
+        bits = sum(ds)
+        for both in (False, True):
+            def kw(r):
+                if not both:
+                    return {}
+                m, t = masks[r.data_ptr()]
+                return dict(smooth=True, mask=m, mask_down=md, mask_thresh=t)
+
+            def views(wx, wy, w, h):
+                return [o[wy // d:(wy + h) // d, wx // d:(wx + w) // d] for d, o in zip(ds, outs)]
+
+            def arm_p(r):
+                return ops.region_heat_pyramid(r, (0, 0), cells, CELL, lut, ALPHA, ds, outs=outs, **kw(r))
+
+            def pieces(parts):
+                def run(r):
+                    k = kw(r)
+                    for wx, wy, w, h in parts:
+                        ops.region_heat_pyramid(r[wy:wy + h, wx:wx + w], (wx, wy), cells, CELL, lut, ALPHA, ds, outs=views(wx, wy, w, h), **k)
+                    return outs
+                return run
+
+            def listed(parts):
+                places = [(wx, wy) for wx, wy, _, _ in parts]
+                vs = [views(*p) for p in parts]
+
+                def run(r):
+                    ops.region_heat_pyramid_windows([r[wy:wy + h, wx:wx + w] for wx, wy, w, h in parts], places, cells, CELL, lut, ALPHA, ds, outs=vs, **kw(r))
+                    return outs
+                return run
+
+            def direct(parts):
+                lib, win = _lib.load(), _lib.ToadHeatPyramidWindow
+                hosts = {}
+                for s_ in slides:
+                    host = (win * len(parts))()
+                    for desc, (wx, wy, w, h) in zip(host, parts):
+                        desc.region, desc.pitch, desc.Hr, desc.Wr, desc.wx, desc.wy = s_[wy:wy + h, wx:wx + w].data_ptr(), s_.stride(0), h, w, wx, wy
+                        for d, o in zip(ds, outs):
+                            desc.outs[d.bit_length() - 1], desc.out_pitches[d.bit_length() - 1] = o[wy // d:, wx // d:].data_ptr(), o.stride(0)
+                    hosts[s_.data_ptr()] = host
+
+                def run(r):
+                    m, t = masks[r.data_ptr()] if both else (None, 0)
+                    plane = (m.data_ptr(), m.stride(0), m.shape[0], m.shape[1], md, t) if both else (None, 0, 0, 0, 0, 0)
+                    _lib.check(lib.toad_region_heat_pyramid_windows_u8(hosts[r.data_ptr()], len(parts), cells.data_ptr(), GY, GX, CELL, lut.data_ptr(), ALPHA, bits,
+                                                                       int(both), *plane, ops._stream()), "toad_region_heat_pyramid_windows_u8")
+                    return outs
+                return run
+
+            cand = {"PW4": pieces(strips), "PW16": pieces(blocks), "PL4": listed(strips), "PL16": listed(blocks), "CL4": direct(strips), "CL16": direct(blocks)}
+            for s_ in slides:
+                want = [o.clone() for o in arm_p(s_)]
+                for k, fn in cand.items():
+                    for o in outs:
+                        o.fill_(0x7F)
+                    if not all(torch.equal(g, w) for g, w in zip(fn(s_), want)):      # a wrong arm must not produce a quoted ratio
+                        raise SystemExit(f"heatmap_bench: {k} differs from P for levels {ds}, smooth + mask = {both}: nothing is timed")
+            arms = {"P": Rotating(arm_p, slides)}
+            arms.update({k: Rotating(fn, slides) for k, fn in cand.items()})
+            t, iters = alternate(arms, seconds)
+            a = t["P"]
+            a1, a2 = median(a[0::2]), median(a[1::2])
+            spread = abs(a1 - a2) / median(a)
+            nbytes = 3 * HR * WR + sum(3 * (HR // d) * (WR // d) for d in ds)
+            m = {k: median(v) for k, v in t.items()}
+            pl_over_pw = {"PL4": m["PL4"] / m["PW4"], "PL16": m["PL16"] / m["PW16"]}
+            res.append(dict(kind="resident_heatmap_pyramid_windows", region=[HR, WR], tile=TILE, stride=STRIDE, cell=CELL, levels=list(ds), alpha=ALPHA,
+                            smooth_and_mask=both, mask_down=md if both else None, moved_bytes=nbytes, slides_rotated=len(slides), rounds=len(a), iters_per_round=iters,
+                            ms={k: round(v, 5) for k, v in m.items()}, ms_min={k: round(min(v), 5) for k, v in t.items()},
+                            ms_max={k: round(max(v), 5) for k, v in t.items()}, moved_tbps={k: round(nbytes / v / 1e9, 3) for k, v in m.items()},
+                            p_halves_ms=[round(a1, 5), round(a2, 5)], p_spread=round(spread, 4), pl_over_pw={k: round(v, 4) for k, v in pl_over_pw.items()},
+                            pl_faster_beyond_spread={k: bool(v < 1.0 - spread) for k, v in pl_over_pw.items()},
+                            pl_over_p={k: round(m[k] / m["P"], 4) for k in ("PL4", "PL16")}, cl_over_p={k: round(m[k] / m["P"], 4) for k in ("CL4", "CL16")},
+                            pw_over_p={k: round(m[k] / m["P"], 4) for k in ("PW4", "PW16")},
+                            launches={"P": 1, "PW4": 4, "PW16": 16, "PL4": 1, "PL16": 1, "CL4": 1, "CL16": 1}, lists_equal_p=True))
+        del outs
+    return res
+
+
 def launches(arm, down, calls=4):
     """`calls` calls of one arm on rotating slides, no warm-up (run under rocprofv3 --kernel-trace --stats: every count divides by `calls`)."""
     dev = torch.device("cuda:0")
@@ -602,6 +711,7 @@ def main():
     ap.add_argument("--w0-only", action="store_true")
     ap.add_argument("--windows", action="store_true")
     ap.add_argument("--pyramid", action="store_true")
+    ap.add_argument("--pyramid-windows", action="store_true")
     ap.add_argument("--seconds", type=float, default=3.0)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -613,7 +723,9 @@ def main():
         a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "heatmap_windows_bench.jsonl")
     if a.pyramid and not a.out:
         a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "heatmap_pyramid_bench.jsonl")
-    res = launches(a.arm, a.down) if a.launches else windows(a.seconds) if a.windows else pyramid(a.seconds) if a.pyramid else window(a.seconds, a.w0_only) if a.window else blur(a.seconds) if a.blur else thumb(a.seconds) if a.thumb else resident(a.seconds, a.px)
+    if a.pyramid_windows and not a.out:
+        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "heatmap_pyramid_windows_bench.jsonl")
+    res = launches(a.arm, a.down) if a.launches else pyramid_windows(a.seconds) if a.pyramid_windows else windows(a.seconds) if a.windows else pyramid(a.seconds) if a.pyramid else window(a.seconds, a.w0_only) if a.window else blur(a.seconds) if a.blur else thumb(a.seconds) if a.thumb else resident(a.seconds, a.px)
     lines = [json.dumps(r) for r in res]
     print("\n".join(lines), flush=True)
     if a.out:
