@@ -885,6 +885,29 @@ int toad_mil_multi_bwd_x16_f32(const float *const *params, float *const *grads, 
                                const float *dlogits, const float *dsite, const float *dA_ext, const float *dMcat_ext,
                                void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- e4m3 bags: 8-bit feature bags on the wire (an ADDITIVE extension of ABI 15 as well; csrc/bag_e4m3.hip) ----
+ * A bag stored as OCP e4m3fn codes (gfx950's FP8, not MI300's fnuz) and ONE integer exp, -7 <= exp <= 15: byte c has s = c >> 7, e = (c >> 3) & 15,
+ * m = c & 7 and the value (-1)^s m 2^-9 for e == 0, (-1)^s (8 + m) 2^(e - 10) otherwise; c & 0x7F == 0x7F is NaN, there is no infinity, the largest
+ * finite value is 448. An element is value(code) 2^-exp. Inside that range of exp every finite element is exactly an fp16 number (subnormal ones
+ * included; at exp = 15 code 1 is 2^-24), so the decode gives exactly the fp16 bag the x16 calls above read as stored.
+ *
+ * toad_bag_dequant_e4m3: out[i] = value(codes[i]) 2^-exp, 0 <= i < n, as fp16 (out_f32 == 0) or fp32; exact, nothing is flushed, a NaN code gives NaN.
+ * It serves the reference's bag load and device copy (datasets/dataset_mtl_concat.py:369-373 -> utils/core_utils_mtl_concat.py:201-204): the codes cross
+ * the link, and this pass runs behind the copy, on its stream, into the landing buffer. codes may lie at any byte address and out at any address
+ * aligned to its element (TOAD_EALIGN otherwise) - a row view of a landing buffer starts at row K 2 bytes and K may be odd. Where both arrays reach
+ * 16-byte alignment at the same element a lane moves 16 codes by 16-byte accesses, everything else goes element by element; no byte outside [0, n) of
+ * either array is touched. Offsets are 64-bit. One launch on `stream`, no workspace, no synchronisation.
+ *
+ * toad_bag_quant_e4m3: codes[i] = the code of x[i] (fp32, or fp16 for x_f16 != 0, up-cast exactly: ONE rounding), for the side that writes the files
+ * the reference reads at datasets/dataset_mtl_concat.py:369-373 and copies at utils/core_utils_mtl_concat.py:201-204. With y = |x| 2^exp: the code whose
+ * value is nearest to y, a tie going to the even code; every y >= 448 (an infinite x included) gives 0x7E; the sign bit of x is kept, on a zero result
+ * too; NaN gives 0x7F with the sign. Addresses, alignment and accesses as above with the roles exchanged (x aligned to its element).
+ *
+ * Both: a NULL pointer, n < 0 and exp outside -7 .. 15 are TOAD_EINVAL, reported before the device is touched; n == 0 launches nothing and returns 0.
+ * Not done: GEMMs that read the codes themselves, exponents per row or column, e5m2. */
+int toad_bag_dequant_e4m3(const void *codes, void *out, int out_f32, int64_t n, int exp, void *stream);
+int toad_bag_quant_e4m3(const void *x, int x_f16, void *codes, int64_t n, int exp, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

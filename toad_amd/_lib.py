@@ -139,6 +139,9 @@ SIGNATURES = {
     "toad_plane_close_u8": (I, [P, I64, I, I, I, I, P, I64, P]),
     "toad_plane_components_u8": (I, [P, I64, I, I, I, I, P, P, P]),
     "toad_plane_area_select_u8": (I, [P, P, I, I, I, I, P, I64, P]),
+    # ... and bags as 8-bit e4m3 codes with one exponent, decoded behind their copy and quantised where they are made (csrc/bag_e4m3.hip): additive to ABI 15
+    "toad_bag_dequant_e4m3": (I, [P, P, I, I64, I, P]),
+    "toad_bag_quant_e4m3": (I, [P, I, P, I64, I, P]),
 }
 
 _lib = None

@@ -13,7 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtoad_hip.so")
-SOURCES = ["capi.hip", "gemm_f32.hip", "gated_pool.hip", "heads.hip", "step.hip", "conv.hip", "tissue.hip", "heatmap.hip", "tissue_seg.hip", "tissue_morph.hip"]
+SOURCES = ["capi.hip", "gemm_f32.hip", "gated_pool.hip", "heads.hip", "step.hip", "conv.hip", "tissue.hip", "heatmap.hip", "tissue_seg.hip", "tissue_morph.hip",
+           "bag_e4m3.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "h2_arith.h"), os.path.join(CSRC, "stem_u8.h"), os.path.join(CSRC, "region_u8.h"),
            os.path.join(REPO, "include", "toad_hip.h")] + \
     [os.path.join(CSRC, f) for f in ("gemm_nt_f32.inc", "gemm_tn.inc", "gemm_h2.inc", "gemm_h2_epilogue.inc", "gemm_pt.inc", "gemm_narrow.inc", "gemm_stream.inc", "stem_halo.inc", "heat_thumb_body.inc",

@@ -9,6 +9,24 @@ the train loop copies it to the device synchronously (utils/core_utils_mtl_conca
 dedicated HIP stream, and the consumer's stream only waits on the copy's event. Features stored as fp16/bf16 are copied
 at half the bytes and upcast on the device. The wire format stays the reference's: one ``torch.save``d ``[N, 1024]``
 tensor per slide.
+
+e4m3 bags: a second wire format, 8 bits per feature (csrc/bag_e4m3.hip; DESIGN.md "e4m3 bags")
+-----------------------------------------------------------------------------------------------
+* Code: OCP ``e4m3fn``, the FP8 form gfx950 has (not MI300's ``fnuz``). Byte ``c`` has sign ``c >> 7``, ``e = (c >> 3) & 15``, ``m = c & 7``; its value
+  is ``m * 2^-9`` for ``e == 0`` and ``(8 + m) * 2^(e - 10)`` otherwise. ``0x7F`` and ``0xFF`` are NaN, there is no infinity, the largest finite value
+  is 448 (``0x7E``). This is ``torch.uint8 -> view(torch.float8_e4m3fn) -> float`` for all 256 codes.
+* Bag: codes ``[N, K]`` (uint8, or the same bytes as ``torch.float8_e4m3fn``) and ONE integer ``exp`` per bag, ``-7 <= exp <= 15``. An element is
+  ``value(code) * 2^-exp``. Inside that range every finite element is exactly an fp16 number, subnormal fp16 results included (at ``exp = 15`` code 1
+  is ``2^-24``); at -8 and 16 that fails. A NaN code decodes to NaN. So the decode of an e4m3 bag IS an fp16 bag, and the x16 calls read it as stored.
+* Quantiser, on real numbers, with ``y = |x| * 2^exp``: the code is the e4m3 value nearest to ``y``, a tie going to the even code; every ``y >= 448``
+  (an infinite ``x`` included) gives ``0x7E``; the sign bit of ``x`` is kept, also on a zero result; NaN gives a code with ``c & 0x7F == 0x7F``. fp32
+  input is rounded ONCE (not through fp16), fp16 input is up-cast exactly.
+* ``exp`` is chosen by ``ops.e4m3_exponent(amax)``: the largest ``e`` in -7 .. 15 with ``amax * 2^e <= 448``; 0 for an all-zero bag; -7 for
+  ``amax > 57344``, where magnitudes up to fp16's 65504 saturate.
+* File: ``torch.save({"e4m3": codes as torch.float8_e4m3fn [N, K], "exp": int})`` - a plain dict, so it loads with ``weights_only=True``.
+* Error: ``|decode(quantise(x)) - x| <= 2^-4 |x|`` where ``|x| * 2^exp >= 2^-6`` (half an ulp of a 4-bit significand) and ``<= 2^-10 * 2^-exp`` below
+  (half the spacing of the e4m3 subnormals), for ``|x| * 2^exp <= 448``.
+The codes cross the link; the decode runs on the copy stream right behind each bag's copy, into the landing buffer that is there for fp16 / fp32 files.
 """
 from __future__ import annotations
 
@@ -22,20 +40,74 @@ import torch
 Record = Tuple[Union[str, Callable[[], torch.Tensor], torch.Tensor], int, int, float]   # (source, label, site, sex)
 
 
-def _load(source) -> torch.Tensor:
-    if isinstance(source, torch.Tensor):
+class E4M3Bag:
+    """A bag as e4m3 codes ``[N, K]`` (kept as uint8; a ``torch.float8_e4m3fn`` tensor is taken as its bytes) and one exponent: see the module docstring."""
+    __slots__ = ("codes", "exp")
+
+    def __init__(self, codes: torch.Tensor, exp: int):
+        if not isinstance(codes, torch.Tensor) or codes.dtype not in (torch.uint8, torch.float8_e4m3fn):
+            raise ValueError("E4M3Bag: codes must be a torch.uint8 or torch.float8_e4m3fn tensor")
+        if codes.dim() != 2:
+            raise ValueError(f"bag must be [N, features], got {tuple(codes.shape)}")
+        if not isinstance(exp, int) or isinstance(exp, bool) or not -7 <= exp <= 15:
+            raise ValueError(f"E4M3Bag: exp must be an int in -7 .. 15, got {exp!r}")
+        self.codes = codes.contiguous().view(torch.uint8)
+        self.exp = exp
+
+    @property
+    def shape(self):
+        return self.codes.shape
+
+
+def _e4m3_from_dict(d: dict) -> E4M3Bag:
+    if "e4m3" not in d or "exp" not in d:
+        raise ValueError(f"an e4m3 bag is a dict with the keys 'e4m3' and 'exp', got {sorted(map(str, d))}")
+    return E4M3Bag(d["e4m3"], d["exp"])
+
+
+def quantise_bag(t: torch.Tensor, exp: Optional[int] = None) -> E4M3Bag:
+    """The e4m3 form of an fp32 / fp16 ``[N, K]`` bag, on whatever device it lies (``ops.bag_quantise_e4m3``); ``exp=None`` picks the exponent from
+    the bag's largest magnitude."""
+    from . import ops
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise ValueError("quantise_bag: bag must be a [N, features] tensor")
+    if t.dtype not in (torch.float32, torch.float16):
+        t = t.to(torch.float32)
+    codes, exp = ops.bag_quantise_e4m3(t.contiguous(), exp)
+    return E4M3Bag(codes, exp)
+
+
+def save_bag_e4m3(path, bag, exp: Optional[int] = None) -> E4M3Bag:
+    """Write ``bag`` - an ``E4M3Bag``, or a tensor that is quantised first (``exp`` as for ``quantise_bag``) - in the file form of the module docstring."""
+    if not isinstance(bag, E4M3Bag):
+        bag = quantise_bag(bag, exp)
+    elif exp is not None and exp != bag.exp:
+        raise ValueError(f"save_bag_e4m3: the bag has exp = {bag.exp}, not {exp}")
+    torch.save({"e4m3": bag.codes.cpu().view(torch.float8_e4m3fn), "exp": int(bag.exp)}, path)
+    return bag
+
+
+def _load(source):
+    """-> a contiguous [N, features] host tensor, or an ``E4M3Bag``."""
+    if isinstance(source, (torch.Tensor, E4M3Bag, dict)):
         t = source
     elif callable(source):
         t = source()
     else:
-        t = torch.load(source, map_location="cpu")            # the reference's .pt bag
+        t = torch.load(source, map_location="cpu")            # the reference's .pt bag, or the e4m3 dict
+    if isinstance(t, dict):
+        t = _e4m3_from_dict(t)
+    if isinstance(t, E4M3Bag):
+        return t
     if t.dim() != 2:
         raise ValueError(f"bag must be [N, features], got {tuple(t.shape)}")
     return t.contiguous()
 
 
 class BagPrefetcher:
-    """Iterate ``(bag, label, site, sex)`` device tensors in record order with ``depth`` bags in flight."""
+    """Iterate ``(bag, label, site, sex)`` device tensors in record order with ``depth`` bags in flight. A record's source is a tensor, a path or a
+    callable; an e4m3 bag (an ``E4M3Bag``, its dict form, or a path / callable that yields one) may stand in any place of the list: its codes cross the
+    link and are decoded on the copy stream into the same fp16 / fp32 tensors and landing buffers, so the consumer cannot tell the kinds apart."""
 
     def __init__(self, records: Sequence[Record], device: Union[str, torch.device], depth: int = 2, workers: int = 2,
                  dtype: Optional[torch.dtype] = torch.float32, prepare: bool = False, arena_rows: int = 0,
@@ -80,16 +152,30 @@ class BagPrefetcher:
         self._arena: Optional[torch.Tensor] = None              # current landing buffer [arena_rows, features] and the rows already taken
         self._arena_used = 0
 
-    def _land(self, t: torch.Tensor) -> torch.Tensor:
+    def _decode(self, t: E4M3Bag, dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The fp16 / fp32 tensor of e4m3 bag ``t`` on the device: the CODES cross the link into a staging tensor and ops.bag_dequantise_e4m3 decodes them
+        into ``out`` (or a new tensor of ``dtype``). Called with the copy stream current; the staging tensor is allocated and dropped here, under that
+        stream, so the allocator's stream ordering covers its reuse."""
+        from . import ops
+        codes = t.codes.to(self.device, non_blocking=True) if self.on_gpu else t.codes
+        return ops.bag_dequantise_e4m3(codes, t.exp, out=out, out_dtype=dtype)
+
+    def _land(self, t) -> torch.Tensor:
         """Device copy (in ``arena_dtype``) of host bag ``t`` inside the current landing buffer (called on the copy stream, in record order)."""
         n, k = t.shape
+        e4m3 = isinstance(t, E4M3Bag)
         if n > self.arena_rows or n == 0:
+            if e4m3:
+                return self._decode(t, self.arena_dtype)
             return t.to(self.device, non_blocking=True).to(self.arena_dtype)
         if self._arena is None or self._arena.shape[1] != k or self._arena_used + n > self.arena_rows:
             self._arena = torch.empty((self.arena_rows, k), dtype=self.arena_dtype, device=self.device)
             self._arena_used = 0
         view = self._arena[self._arena_used:self._arena_used + n]
-        view.copy_(t, non_blocking=True)                        # H2D (+ the cast of a file of another dtype) straight into place
+        if e4m3:
+            self._decode(t, out=view)                           # H2D of the codes, decoded straight into place
+        else:
+            view.copy_(t, non_blocking=True)                    # H2D (+ the cast of a file of another dtype) straight into place
         self._arena_used += n
         return view
 
@@ -103,7 +189,10 @@ class BagPrefetcher:
         meta = torch.tensor([int(label), int(site)], dtype=torch.int64)
         sx = torch.tensor([float(sex)], dtype=torch.float32)
         if self.on_gpu:                                         # page-locked so every copy is truly asynchronous
-            if not t.is_pinned():
+            if isinstance(t, E4M3Bag):
+                if not t.codes.is_pinned():
+                    t = E4M3Bag(t.codes.pin_memory(), t.exp)    # (the codes are uint8 here: pinning does not depend on float8 support)
+            elif not t.is_pinned():
                 t = t.pin_memory()
             meta, sx = meta.pin_memory(), sx.pin_memory()       # (a pageable source would be a synchronous copy queued
         return t, meta, sx                                      #  behind the bag transfer and stall the host)
@@ -111,13 +200,19 @@ class BagPrefetcher:
     # -- stage 2 (consumer thread, copy stream): H2D + on-device upcast
     def _stage_device(self, host):
         t, meta, sx = host
+        # an e4m3 bag outside a landing buffer decodes into `dtype` (fp16 where every file keeps its own: that is what the codes hold exactly)
+        e4m3_dtype = self.dtype if self.dtype in (torch.float16, torch.float32) else torch.float16 if self.dtype is None else torch.float32
         if not self.on_gpu:
             if self.arena_rows:
                 return (self._land(t), meta[0:1], meta[1:2], sx), None
+            if isinstance(t, E4M3Bag):
+                t = self._decode(t, e4m3_dtype)
             return (t if self.dtype is None else t.to(self.dtype), meta[0:1], meta[1:2], sx), None
         with torch.cuda.stream(self.copy_stream):
             if self.arena_rows:
                 bag = self._land(t)
+            elif isinstance(t, E4M3Bag):
+                bag = self._decode(t, e4m3_dtype)
             else:
                 bag = t.to(self.device, non_blocking=True)
             if self.dtype is not None and bag.dtype != self.dtype:

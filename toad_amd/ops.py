@@ -1958,3 +1958,78 @@ def avgpool_nhwc(x: torch.Tensor) -> torch.Tensor:
     y = torch.empty((b, c), dtype=torch.float32, device=x.device)
     _lib.check(_lib.load().toad_avgpool_nhwc_f32(_p(x), _p(y), b, hw, c, _stream()), "toad_avgpool_nhwc_f32")
     return y
+
+
+# ---- e4m3 bags: 8-bit codes with one power-of-two exponent per bag (csrc/bag_e4m3.hip; the format: toad_amd/ingest.py) ----------------------
+E4M3_EXP_MIN, E4M3_EXP_MAX = -7, 15        # the exponents at which every finite code is exactly an fp16 number
+E4M3_MAX = 448.0                           # the largest finite e4m3fn value (code 0x7E)
+
+
+def e4m3_exponent(amax) -> int:
+    """The exponent of a bag whose largest magnitude is ``amax``: the largest e in -7 .. 15 with amax * 2^e <= 448, so the bag uses the top of the
+    code range without saturating. 0 for amax == 0. -7 for amax > 57344: magnitudes up to fp16's 65504 then SATURATE at 448 * 2^7 = 57344.
+    A NaN or infinite amax is a ValueError. Python numbers only: nothing here touches a device."""
+    import math
+    amax = float(amax)
+    if math.isnan(amax) or math.isinf(amax):
+        raise ValueError(f"e4m3_exponent: amax must be finite, got {amax!r} (a NaN or Inf in the bag?)")
+    amax = abs(amax)
+    if amax == 0.0:
+        return 0
+    for e in range(E4M3_EXP_MAX, E4M3_EXP_MIN, -1):
+        if math.ldexp(amax, e) <= E4M3_MAX:
+            return e
+    return E4M3_EXP_MIN
+
+
+def _e4m3_exp_arg(name: str, exp) -> int:
+    if not isinstance(exp, int) or isinstance(exp, bool) or not E4M3_EXP_MIN <= exp <= E4M3_EXP_MAX:
+        raise ValueError(f"{name}: exp must be an int in {E4M3_EXP_MIN} .. {E4M3_EXP_MAX}, got {exp!r}")
+    return exp
+
+
+def bag_dequantise_e4m3(codes: torch.Tensor, exp: int, out: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float16) -> torch.Tensor:
+    """The fp16 / fp32 bag of an e4m3 bag: out[i, j] = value(codes[i, j]) * 2^-exp, exact (toad_bag_dequant_e4m3). ``codes``: contiguous [N, K]
+    torch.uint8 or the same bytes as torch.float8_e4m3fn. ``out``: a contiguous [N, K] fp16 or fp32 tensor on the same device - it may be a row view of
+    a larger buffer, at any row - or None for a new one of ``out_dtype``. On a device tensor: one launch on the current stream, no synchronisation. A
+    CPU tensor takes the same call through torch ops (view as float8_e4m3fn, up-cast, scale), with identical bits. Anything else is a ValueError."""
+    name = "bag_dequantise_e4m3"
+    exp = _e4m3_exp_arg(name, exp)
+    if not isinstance(codes, torch.Tensor) or codes.dtype not in (torch.uint8, torch.float8_e4m3fn) or codes.dim() != 2 or not codes.is_contiguous():
+        raise ValueError(f"{name}: codes must be a contiguous [N, K] torch.uint8 or torch.float8_e4m3fn tensor")
+    if out is None:
+        if out_dtype not in (torch.float16, torch.float32):
+            raise ValueError(f"{name}: out_dtype must be torch.float16 or torch.float32, got {out_dtype}")
+        out = torch.empty(codes.shape, dtype=out_dtype, device=codes.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype not in (torch.float16, torch.float32) or out.shape != codes.shape or not out.is_contiguous() \
+            or out.device != codes.device:
+        raise ValueError(f"{name}: out must be a contiguous fp16 or fp32 tensor of the codes' shape {tuple(codes.shape)} on their device")
+    if codes.numel() == 0:
+        return out
+    if not codes.is_cuda:
+        out.copy_(codes.view(torch.float8_e4m3fn).to(torch.float32) * 2.0 ** -exp)       # exact in fp32, and exact again in the cast to fp16
+        return out
+    _lib.check(_lib.load().toad_bag_dequant_e4m3(_p(codes), _p(out), int(out.dtype == torch.float32), codes.numel(), exp, _stream()),
+               "toad_bag_dequant_e4m3")
+    return out
+
+
+def bag_quantise_e4m3(x: torch.Tensor, exp: Optional[int] = None) -> Tuple[torch.Tensor, int]:
+    """-> (codes uint8 [N, K], exp): the e4m3 bag of a contiguous fp32 or fp16 [N, K] bag (toad_bag_quant_e4m3). With y = |x| * 2^exp the code is the
+    e4m3 value nearest to y, a tie going to the even code; y >= 448 (an infinite x included) saturates at 0x7E; the sign bit is kept; fp32 is rounded
+    ONCE. ``exp=None``: e4m3_exponent of x.abs().amax() - one read-back, and a ValueError where x holds a NaN or an Inf; with ``exp`` given a NaN
+    becomes a NaN code and there is no synchronisation. On a device tensor: one launch on the current stream. A CPU tensor takes the same call
+    through torch ops (scale, clamp to +-448, convert), with identical bits."""
+    name = "bag_quantise_e4m3"
+    if not isinstance(x, torch.Tensor) or x.dtype not in (torch.float32, torch.float16) or x.dim() != 2 or not x.is_contiguous():
+        raise ValueError(f"{name}: x must be a contiguous [N, K] fp32 or fp16 tensor")
+    if exp is None:
+        exp = e4m3_exponent(x.abs().amax().item() if x.numel() else 0.0)
+    exp = _e4m3_exp_arg(name, exp)
+    if not x.is_cuda:
+        y = x.to(torch.float32) * 2.0 ** exp
+        return torch.clamp(y, -E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn).view(torch.uint8), exp     # (torch alone gives NaN above 448)
+    codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    if x.numel():
+        _lib.check(_lib.load().toad_bag_quant_e4m3(_p(x), int(x.dtype == torch.float16), _p(codes), x.numel(), exp, _stream()), "toad_bag_quant_e4m3")
+    return codes, exp

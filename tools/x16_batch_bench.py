@@ -9,13 +9,18 @@
     has to exceed to mean anything.
   one_slide: the one-slide x16 step (toad_mil_step_x16_f32) at 10,000 and 100,000 patches. Run the tool once on the shipped library and once with
       TOAD_HIP_LIB=<a library built from the parent's csrc/> (tools/ab/select_lib.py) for the before / after of the one-launch weight gradient.
-  host_fed: 52 x 10,000-patch bags from page-locked host memory through BagPrefetcher(depth=2, arena_rows=524288) into SlideShardedDP.step
-      (one optimiser step per 52 slides), fp32 files landing in fp32 buffers against fp16 files landing in fp16 buffers: slides/s, link GB/s.
+  host_fed: 52 x 10,000-patch bags (--slides / --patches: another shape, 5 x 100,000 for one) from page-locked host memory through
+      BagPrefetcher(depth=2, arena_rows=524288) into SlideShardedDP.step (one optimiser step per 52 slides). Three wires, alternated, three runs each:
+      fp32 files landing in fp32 buffers, fp16 files and e4m3 files (8-bit codes, decoded behind each copy) landing in fp16 buffers: slides/s, link
+      GB/s. Together with --resident the rows carry the ratio to the resident x16 call of the same shape.
+  dequant: the e4m3 decode and quantise kernels alone at 524,288 x 1024 and 10,000 x 1024 (device events, four buffer sets in rotation): us and moved
+      bytes/s; and the decode of one step's 520,000 rows as a share of that step's x16 multi-slide call.
   launches: four calls of ONE arm (--arm A | B | ONE = the one-slide x16 step) at one shape, for a `rocprofv3 --kernel-trace --stats` run of
       its own: kernel names and counts per call show which weight-gradient and NT kernels the arm ran.
 
 Prints one JSON line per result; --out FILE keeps them.
-usage: x16_batch_bench.py [--resident] [--one-slide] [--host-fed] [--launches B,N --arm A|B|ONE] [--seconds S] [--out FILE]"""
+usage: x16_batch_bench.py [--resident] [--one-slide] [--host-fed] [--slides B --patches N] [--dequant] [--launches B,N --arm A|B|ONE] [--seconds S]
+                          [--out FILE]"""
 import argparse
 import json
 import os
@@ -151,49 +156,123 @@ def one_slide(seconds):
     return res
 
 
-def host_fed(steps=6, B=52, n=10000, arena_rows=524288):
+HAVE_E4M3 = "toad_bag_dequant_e4m3" in _lib.SIGNATURES
+
+
+def host_fed(steps=6, B=52, n=10000, arena_rows=524288, rounds=3):
+    """Three wires - fp32 files into fp32 landing buffers, fp16 files and e4m3 files (ingest.E4M3Bag: the codes cross the link, the decode runs behind
+    each copy) into fp16 ones - ALTERNATED, `rounds` runs of `steps` optimiser steps each. One row per wire with every run's figures, the medians, and
+    for the e4m3 wire whether its median slides/s lies above the fp16 wire's maximum."""
     from toad_amd.dp import SlideShardedDP
-    from toad_amd.ingest import BagPrefetcher
+    from toad_amd.ingest import BagPrefetcher, E4M3Bag
     dev = torch.device("cuda:0")
-    res = []
-    for wire, dt in (("fp32", torch.float32), ("fp16", torch.float16)):
-        if dt is torch.float16 and not HAVE_X16_MULTI:
+    arena_rows = max(arena_rows, n)
+    g = torch.Generator().manual_seed(3)
+    seedbags = [torch.randn(n, 1024, generator=g) * 0.7 for _ in range(min(B, 4))]       # the values do not move the clock: four bags, copied round
+    legs = {}
+    for wire, dt in (("fp32", torch.float32), ("fp16", torch.float16), ("e4m3", torch.uint8)):
+        if (wire != "fp32" and not HAVE_X16_MULTI) or (wire == "e4m3" and not HAVE_E4M3):
             continue
-        model = make_model()
-        dp = SlideShardedDP(model, {"lr": 2e-4, "weight_decay": 1e-5}, batch_rows=arena_rows)
-        g = torch.Generator().manual_seed(3)
+        if wire == "e4m3":
+            src = [ops.bag_quantise_e4m3(b) for b in seedbags]
+        else:
+            src = [(b.to(dt), None) for b in seedbags]
         host = []
         for i in range(B):                                       # one step's bags in page-locked memory, cycled step after step
             hb = torch.empty((n, 1024), dtype=dt, pin_memory=True)
-            hb.copy_((torch.randn(n, 1024, generator=g) * 0.7).to(dt))
-            host.append(hb)
-        nbytes = B * host[0].numel() * host[0].element_size()
-        kw = dict(dtype=dt, arena_rows=arena_rows)
-        if dt is torch.float16:
-            kw["arena_dtype"] = torch.float16
+            hb.copy_(src[i % len(src)][0])
+            host.append(E4M3Bag(hb, src[i % len(src)][1]) if wire == "e4m3" else hb)
+        land = torch.float32 if wire == "fp32" else torch.float16
+        kw = dict(dtype=land, arena_rows=arena_rows, arena_dtype=land)
+        dp = SlideShardedDP(make_model(), {"lr": 2e-4, "weight_decay": 1e-5}, batch_rows=arena_rows)
+        legs[wire] = dict(host=host, kw=kw, dp=dp, nbytes=B * n * 1024 * torch.empty((), dtype=dt).element_size(), runs=[], timed={}, calls=0)
 
-        def run(k):
-            recs = [(host[i % B], i % C, i % 2, float((i // 2) % 2)) for i in range(k * B)]
-            batch = []
-            for bag, lb, st, sx in BagPrefetcher(recs, dev, depth=2, workers=2, **kw):
-                batch.append((bag, sx, lb, st))
-                if len(batch) == B:
-                    dp.step(batch, B)
-                    batch = []
-        run(2)
-        torch.cuda.synchronize(); t0 = time.perf_counter()
-        ops.enable_timing(True, level=1)
-        run(steps)
-        names = {k: v[0] for k, v in ops.collect_timing().items()}
-        calls = ops.timing_call_count()
-        ops.enable_timing(False)
-        dt_s = time.perf_counter() - t0
-        res.append(dict(kind="host_fed", lib=select_lib.TAG, wire=wire, landing=str(kw.get("arena_dtype", torch.float32)), slides_per_step=B, patches=n,
-                        steps=steps, slides_per_s=round(steps * B / dt_s, 1), ms_per_step=round(dt_s / steps * 1e3, 3),
-                        link_gbps=round(steps * nbytes / dt_s / 1e9, 2), library_calls=calls, timed_ops=names))
-        del host, dp, model
-        ops.release_workspaces()
+    def run(leg, k):
+        recs = [(leg["host"][i % B], i % C, i % 2, float((i // 2) % 2)) for i in range(k * B)]
+        batch = []
+        for bag, lb, st, sx in BagPrefetcher(recs, dev, depth=2, workers=2, **leg["kw"]):
+            batch.append((bag, sx, lb, st))
+            if len(batch) == B:
+                leg["dp"].step(batch, B)
+                batch = []
+
+    for leg in legs.values():
+        run(leg, 2)
+    for _ in range(rounds):
+        for leg in legs.values():
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            ops.enable_timing(True, level=1)
+            run(leg, steps)
+            leg["timed"] = {k: [v[0], round(v[1], 3)] for k, v in ops.collect_timing().items()}        # (collect_timing synchronises)
+            leg["calls"] = ops.timing_call_count()
+            ops.enable_timing(False)
+            leg["runs"].append(time.perf_counter() - t0)
+    res = []
+    for wire, leg in legs.items():
+        sps = [steps * B / s for s in leg["runs"]]
+        res.append(dict(kind="host_fed", lib=select_lib.TAG, wire=wire, landing=str(leg["kw"]["arena_dtype"]), slides_per_step=B, patches=n, steps=steps,
+                        runs=len(sps), slides_per_s=round(median(sps), 1), slides_per_s_runs=[round(v, 1) for v in sps],
+                        ms_per_step=round(median(leg["runs"]) / steps * 1e3, 3), link_gbps=round(steps * leg["nbytes"] / median(leg["runs"]) / 1e9, 2),
+                        wire_mb_per_step=round(leg["nbytes"] / 1e6, 1), library_calls=leg["calls"], timed_ops_calls_ms=leg["timed"]))
+    by = {r["wire"]: r for r in res}
+    if "e4m3" in by and "fp16" in by:
+        by["e4m3"]["fp16_max_slides_per_s"] = max(by["fp16"]["slides_per_s_runs"])
+        by["e4m3"]["median_above_fp16_max"] = bool(by["e4m3"]["slides_per_s"] > max(by["fp16"]["slides_per_s_runs"]))
+    del legs
+    ops.release_workspaces()
+    torch.cuda.empty_cache()
+    return res
+
+
+def dequant(seconds, step_shape=(52, 10000)):
+    """bag_dequantise_e4m3 (fp16 and fp32 output) and bag_quantise_e4m3 (fp32 and fp16 input) alone, device events, four buffer sets in rotation so no
+    call finds its operands in a cache the previous call filled; then the decode of one step's rows as a share of that step's x16 multi-slide call."""
+    dev = torch.device("cuda:0")
+    res = []
+    for n in (524288, 10000):
+        g = torch.Generator(device=dev).manual_seed(n)
+        x32 = [torch.randn(n, 1024, device=dev, generator=g) * 0.7 for _ in range(4)]
+        x16 = [x.half() for x in x32]
+        codes = [ops.bag_quantise_e4m3(x, 7)[0] for x in x32]
+        o16, o32 = [torch.empty_like(x) for x in x16], [torch.empty_like(x) for x in x32]
+        turn = [0]
+
+        def rot(fn):
+            def call():
+                turn[0] = (turn[0] + 1) % 4
+                fn(turn[0])
+            return call
+        arms = {"dequant_f16": (rot(lambda i: ops.bag_dequantise_e4m3(codes[i], 7, out=o16[i])), 3),
+                "dequant_f32": (rot(lambda i: ops.bag_dequantise_e4m3(codes[i], 7, out=o32[i])), 5),
+                "quant_f32": (rot(lambda i: ops.bag_quantise_e4m3(x32[i], 7)), 5),
+                "quant_f16": (rot(lambda i: ops.bag_quantise_e4m3(x16[i], 7)), 3)}
+        t, iters = alternate({k: v[0] for k, v in arms.items()}, seconds)
+        for k, (_, bytes_per_elem) in arms.items():
+            ms = median(t[k])
+            res.append(dict(kind="dequant", lib=select_lib.TAG, op=k, rows=n, cols=1024, rounds=len(t[k]), iters_per_round=iters[k], us=round(ms * 1e3, 2),
+                            us_min=round(min(t[k]) * 1e3, 2), us_max=round(max(t[k]) * 1e3, 2), bytes_moved=n * 1024 * bytes_per_elem,
+                            tb_per_s=round(n * 1024 * bytes_per_elem / (ms * 1e-3) / 1e12, 3)))
+        del x32, x16, codes, o16, o32
         torch.cuda.empty_cache()
+    if HAVE_X16_MULTI:
+        B, n = step_shape
+        model = make_model()
+        w, gr = grad_views(model)
+        pool16 = (torch.randn(B * n, 1024, device=dev) * 0.7).half()
+        bags16 = [pool16[i * n:(i + 1) * n] for i in range(B)]
+        codes = ops.bag_quantise_e4m3(pool16, 7)[0]
+        land = torch.empty_like(pool16)
+        sex = (torch.arange(B, device=dev) % 2).float()
+        label = torch.arange(B, device=dev) % C
+        site = (torch.arange(B, device=dev) // 2) % 2
+        t, iters = alternate({"x16_step": lambda: ops.mil_multi_step(w, gr, 0.0, bags16, sex, label, site, 0.75 / B, 0.25 / B),
+                              "decode_step_rows": lambda: ops.bag_dequantise_e4m3(codes, 7, out=land),
+                              "decode_per_bag": lambda: [ops.bag_dequantise_e4m3(codes[i * n:(i + 1) * n], 7, out=land[i * n:(i + 1) * n]) for i in range(B)]},
+                             seconds)
+        ms = {k: round(median(v), 4) for k, v in t.items()}
+        res.append(dict(kind="dequant_share", lib=select_lib.TAG, slides=B, patches=n, rows=B * n, ms=ms, iters_per_round=iters,
+                        decode_share_of_x16_step=round(ms["decode_step_rows"] / ms["x16_step"], 4),
+                        decode_per_bag_share_of_x16_step=round(ms["decode_per_bag"] / ms["x16_step"], 4)))
     return res
 
 
@@ -228,11 +307,21 @@ def main():
     ap.add_argument("--arm", default="B", choices=("A", "B", "ONE"))
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--out", default="")
+    ap.add_argument("--dequant", action="store_true", help="time the e4m3 decode and quantise kernels alone")
+    ap.add_argument("--slides", type=int, default=0, help="with --patches: the one shape of --resident and --host-fed (default: 52 x 10,000 host-fed)")
+    ap.add_argument("--patches", type=int, default=0)
     a = ap.parse_args()
+    if bool(a.slides) != bool(a.patches) or a.slides < 0 or a.patches < 0:
+        ap.error("--slides and --patches go together")
+    global SHAPES
+    if a.slides:
+        SHAPES = ((a.slides, a.patches),)
     res = []
     if a.launches:
         B, n = (int(v) for v in a.launches.split(","))
         res += launches(B, n, a.arm)
+    elif a.dequant:
+        res += dequant(a.seconds)
     else:
         every = not (a.resident or a.one_slide or a.host_fed)
         if a.resident or every:
@@ -240,7 +329,13 @@ def main():
         if a.one_slide or every:
             res += one_slide(a.seconds)
         if a.host_fed or every:
-            res += host_fed()
+            fed = host_fed(B=a.slides, n=a.patches) if a.slides else host_fed()
+            x16 = [r["slides_per_s"].get("B_x16") for r in res if r["kind"] == "resident" and (r["slides"], r["patches"]) == (fed[0]["slides_per_step"], fed[0]["patches"])]
+            for r in fed:                                        # the resident x16 call of the same shape in this process, where it was run
+                if x16 and x16[0]:
+                    r["resident_x16_slides_per_s"] = x16[0]
+                    r["share_of_resident_x16"] = round(r["slides_per_s"] / x16[0], 4)
+            res += fed
     lines = [json.dumps(r) for r in res]
     print("\n".join(lines), flush=True)
     if a.out:
