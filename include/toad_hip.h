@@ -141,6 +141,18 @@ int toad_linear_wgrad_f32(const float *dY, const float *X, float *dW, float *db,
                           const float *dy_amax, const float *x_amax,
                           void *ws, size_t ws_bytes, void *stream);
 
+/* Test/debug helper (additive to ABI 15): two or three weight gradients over the SAME M rows through the one batched launch the whole-slide
+ * calls use for a slide's three trunk / attention weight gradients, on operands the caller chooses. Job i: dW[N,K] = beta*dW + dY[M,N]^T X[M,K],
+ * db[N] = beta*db + column sums of dY (db may be NULL); dy_amax and x_amax (toad_absmax_rows256_f32) are REQUIRED, ws is the job's own workspace
+ * of ws_bytes_each bytes (toad_linear_wgrad_ws_bytes(M, N, K) covers every shape the library's own callers hand over). x_mode_last: 0 = every X
+ * is fp32; 1 = the X of the LAST of three jobs is fp16 [M][K] (K % 8 == 0, x_amax ignored).
+ * TOAD_ESHAPE, with nothing launched or written, for anything but 2 or 3 jobs, M outside 64 .. 262,144, more than 256 tiles of 256 x 256 in
+ * all, a missing operand or abs-max array, or a workspace too small for the launch's row splits; TOAD_ESHAPE / TOAD_EALIGN for N or K not a
+ * multiple of 4 and pointers not 16-byte aligned. */
+typedef struct { const float *dY, *dy_amax; const void *X; const float *x_amax; float *dW, *db; int64_t N, K; void *ws; } ToadWgradJob;
+int toad_linear_wgrad_batch_f32(const ToadWgradJob *jobs /* HOST array */, int n_jobs, int64_t M, float beta, int x_mode_last,
+                                size_t ws_bytes_each, void *stream);
+
 /* out[e] = the dropout multiplier (0 or 1/(1-p)) the kernels apply to flat element e under `drop_seed`
  * (all ones when drop_p == 0). Lets a caller or test reproduce the masks, which are never stored. */
 int toad_dropout_mask_f32(float *out, int64_t n, float drop_p, uint64_t drop_seed, void *stream);

@@ -60,6 +60,9 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert lib.toad_gated_pool_ws_bytes(1000, 512, 384, 2) > 0
     assert lib.toad_gated_pool_ws_bytes(1000, 500, 384, 2) == 0      # unsupported shape
     assert lib.toad_linear_wgrad_ws_bytes(100000, 512, 1024) >= 512 * 1024 * 4
+    # the batched weight-gradient entry (a test/debug helper, additive to ABI 15) refuses before it launches; tests/test_wgrad_plans_host.py has the rest
+    assert "toad_linear_wgrad_batch_f32" in _lib.SIGNATURES and "toad_linear_wgrad_batch_f32" in header_functions()
+    assert lib.toad_linear_wgrad_batch_f32(None, 3, 1000, 0.0, 0, 1 << 40, None) == -1 and "no jobs" in err()
 
 
 def test_extractor_entry_points_validate_arguments_without_a_gpu():

@@ -29,6 +29,12 @@ class ToadHeatPyramidWindow(ctypes.Structure):
                 ("out_pitches", c_int64 * 6)]
 
 
+class ToadWgradJob(ctypes.Structure):
+    """One job of toad_linear_wgrad_batch_f32's HOST array (include/toad_hip.h): every pointer is a device address."""
+    _fields_ = [("dY", c_void_p), ("dy_amax", c_void_p), ("X", c_void_p), ("x_amax", c_void_p), ("dW", c_void_p), ("db", c_void_p),
+                ("N", c_int64), ("K", c_int64), ("ws", c_void_p)]
+
+
 # name -> (restype, argtypes); mirrors include/toad_hip.h one to one
 SIGNATURES = {
     "toad_abi_version": (I, []),
@@ -142,6 +148,9 @@ SIGNATURES = {
     # ... and bags as 8-bit e4m3 codes with one exponent, decoded behind their copy and quantised where they are made (csrc/bag_e4m3.hip): additive to ABI 15
     "toad_bag_dequant_e4m3": (I, [P, P, I, I64, I, P]),
     "toad_bag_quant_e4m3": (I, [P, I, P, I64, I, P]),
+    # ... and the batched weight-gradient launch of the whole-slide calls on operands of the caller's choice (jobs: a HOST array of n ToadWgradJob;
+    # a test/debug helper like toad_dropout_mask_f32): additive to ABI 15
+    "toad_linear_wgrad_batch_f32": (I, [ctypes.POINTER(ToadWgradJob), I, I64, F, I, SZ, P]),
 }
 
 _lib = None

@@ -677,6 +677,33 @@ extern "C" int toad_linear_wgrad_xp_f32(const float *dY, const void *Xp, const f
     return launch_wgrad(dY, dy_amax, reinterpret_cast<const float *>(Xp), x_amax, dW, db, M, N, K, beta, ws, (hipStream_t)stream, what, TOAD_X_PT);
 }
 
+// Two or three weight gradients over the same M rows through the batched launch of the whole-slide calls, on operands the caller chooses:
+// test/debug helper (the whole-slide calls hand this launch operands that other kernels produced). wgrad_batch_ok, launch_wgrad_batch,
+// launch_wgrad_reduce and nothing else.
+extern "C" int toad_linear_wgrad_batch_f32(const ToadWgradJob *jobs, int n_jobs, int64_t M, float beta, int x_mode_last, size_t ws_bytes_each,
+                                            void *stream) {
+    const char *what = "toad_linear_wgrad_batch_f32";
+    if (!jobs || n_jobs < 1) { set_error("%s: no jobs", what); return TOAD_EINVAL; }
+    if (x_mode_last != TOAD_X_F32 && x_mode_last != TOAD_X_F16) { set_error("%s: x_mode_last must be 0 (fp32) or 1 (fp16)", what); return TOAD_EINVAL; }
+    WgradJob wj[3];
+    for (int i = 0; i < n_jobs && i < 3; ++i) {
+        const ToadWgradJob &j = jobs[i];
+        if (j.N % 4 != 0 || j.K % 4 != 0) { set_error("%s: job %d: N and K must be multiples of 4", what, i); return TOAD_ESHAPE; }
+        if (!aligned16(j.dY) || !aligned16(j.X) || !aligned16(j.dW) || !aligned16(j.ws)) { set_error("%s: job %d: pointers must be 16-byte aligned", what, i); return TOAD_EALIGN; }
+        wj[i] = WgradJob{j.dY, j.dy_amax, reinterpret_cast<const float *>(j.X), j.x_amax, j.dW, j.db, j.N, j.K, j.ws,
+                         i == n_jobs - 1 ? x_mode_last : TOAD_X_F32};
+    }
+    if (!wgrad_batch_ok(M, wj, n_jobs, ws_bytes_each)) {
+        set_error("%s: the batched launch takes 2 or 3 jobs over 64 .. %lld rows, at most %d tiles in all, fp32 operands with their abs-max arrays "
+                  "(fp16 X, K %% 8 == 0, only as the last of three) and a workspace of toad_linear_wgrad_ws_bytes each (M = %lld, %d jobs)",
+                  what, (long long)kTnBatchMaxRows, PB_GRID, (long long)M, n_jobs);
+        return TOAD_ESHAPE;
+    }
+    WgradDeferred dw[3];
+    if (int rc = launch_wgrad_batch(wj, n_jobs, M, beta, (hipStream_t)stream, what, dw)) return rc;
+    return launch_wgrad_reduce(dw, n_jobs, (hipStream_t)stream, what);
+}
+
 extern "C" int toad_transpose_f32(const float *in, float *out, int64_t rows, int64_t cols, void *stream) {
     if (!in || !out || rows <= 0 || cols <= 0) { set_error("toad_transpose_f32: bad argument"); return TOAD_EINVAL; }
     dim3 grid((unsigned)((cols + 31) / 32), (unsigned)((rows + 31) / 32));

@@ -390,6 +390,67 @@ def linear_wgrad(dy, x, dw: Optional[torch.Tensor] = None, db: Optional[torch.Te
     return dw, db
 
 
+def linear_wgrad_batch_ws_bytes(m: int, shapes) -> int:
+    """Bytes of ONE job's workspace for linear_wgrad_batch over m rows; shapes = [(N, K)] of all its jobs. The launch runs at most one item per
+    workgroup, so it cuts the rows into at most 256 // (tiles of all jobs) splits of whole 32-row stages; the per-op sizes alone can be too small
+    for that (a 300-row call of the model's three products: 10 splits against the per-op plans' 5)."""
+    lib = _lib.load()
+    tiles = sum(((n + 255) // 256) * ((k + 255) // 256) for n, k in shapes)
+    splits = max(min(256 // max(tiles, 1), (m + 31) // 32), 1)
+    return max(max(int(lib.toad_linear_wgrad_ws_bytes(m, n, k)) for n, k in shapes),
+               splits * max(n * k + n for n, k in shapes) * 4 + (2 * amax_floats(m) + 64) * 4)
+
+
+def linear_wgrad_batch(jobs, outs=None, beta: float = 0.0, want_db: bool = True, ws=None):
+    """Two or three weight gradients over the same M rows in the ONE batched launch the whole-slide calls use (toad_linear_wgrad_batch_f32; a
+    test/debug entry: those calls hand the launch operands that other kernels produced). jobs: [(dy [M,N], x [M,K], dy_amax, x_amax)]; the x of
+    the last of three may be float16 (its x_amax is ignored). outs: [(dw, db | None)] destinations per job (else allocated, beta = 0).
+    Returns [(dw, db)]. ws: one uint8 workspace per job (the library is told the smallest of their sizes); else job i's is the cached buffer
+    of slot "wgrad_batch{i}" (linear_wgrad_batch_ws_bytes)."""
+    lib = _lib.load()
+    n_jobs = len(jobs)
+    if n_jobs < 1:
+        raise ValueError("linear_wgrad_batch: no jobs")
+    m = jobs[0][0].shape[0]
+    x16 = jobs[-1][1].dtype == torch.float16
+    res, shapes = [], []
+    for i, (dy, x, dy_amax, x_amax) in enumerate(jobs):
+        half = x16 and i == n_jobs - 1
+        _chk(dy, "dy"); _chk(x, "x", dtype=torch.float16 if half else torch.float32)
+        _chk(dy_amax, "dy_amax"); _chk(x_amax, "x_amax", allow_none=half)
+        if dy.shape[0] != m or x.shape[0] != m:
+            raise ValueError("linear_wgrad_batch: every operand must have the same number of rows")
+        n, k = dy.shape[1], x.shape[1]
+        shapes.append((n, k))
+        if outs is None:
+            dw = torch.empty((n, k), dtype=torch.float32, device=dy.device)
+            db = torch.empty((n,), dtype=torch.float32, device=dy.device) if want_db else None
+        else:
+            dw, db = outs[i]
+            _chk(dw, "dw"); _chk(db, "db", allow_none=True)
+            if tuple(dw.shape) != (n, k) or (db is not None and db.numel() != n):
+                raise ValueError("linear_wgrad_batch: destination shapes must be dw [N,K], db [N]")
+        res.append((dw, db))
+    if outs is None:
+        beta = 0.0
+    if ws is None:
+        each = linear_wgrad_batch_ws_bytes(m, shapes)
+        wss = [_ws(each, jobs[0][0].device, f"wgrad_batch{i}") for i in range(n_jobs)]
+    else:
+        wss = list(ws)
+        for t in wss:
+            _chk(t, "ws", dtype=torch.uint8)
+        if len(wss) != n_jobs:
+            raise ValueError("linear_wgrad_batch: one workspace per job")
+        each = min(t.numel() for t in wss)
+    arr = (_lib.ToadWgradJob * n_jobs)()
+    for i, ((dy, x, dy_amax, x_amax), (dw, db), (n, k), wsi) in enumerate(zip(jobs, res, shapes, wss)):
+        arr[i] = _lib.ToadWgradJob(_p(dy), _p(dy_amax), _p(x), _p(x_amax), _p(dw), _p(db), n, k, _p(wsi))
+    with _timed("gemm_wgrad_batch"):
+        _lib.check(lib.toad_linear_wgrad_batch_f32(arr, n_jobs, m, float(beta), 1 if x16 else 0, each, _stream()), "toad_linear_wgrad_batch_f32")
+    return res
+
+
 def dropout_mask(n: int, drop_p: float, drop_seed: int, device) -> torch.Tensor:
     """The multiplier (0 or 1/(1-p)) the kernels apply to flat element e under ``drop_seed`` (never stored by them)."""
     out = torch.empty((n,), dtype=torch.float32, device=device)
