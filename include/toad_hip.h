@@ -87,6 +87,13 @@ size_t toad_relu_bits_bytes(int64_t M, int64_t N);
 enum { TOAD_BITS_READER = 1, TOAD_BITS_ADDEND = 2, TOAD_BITS_POOL = 4, TOAD_BITS_POOL_BATCHED = 8, TOAD_BITS_A16 = 16, TOAD_BITS_APT = 32,
        TOAD_BITS_SELF_MEASURE = 64, TOAD_BITS_ROWS = 128, TOAD_BITS_STEP_L1 = 256, TOAD_BITS_MULTI = 512 };
 int toad_relu_bits_plan(int64_t M, int64_t N, int64_t K, int flags, uint8_t *tile_map);
+/* The tile plan of ONE NT launch [M,K] x [N,K]^T (an additive extension of ABI 15: host side, touches no device, changes no launch), from the
+ * code that decides the launch. flags: those of toad_relu_bits_plan; a product the whole-slide calls cut into row chunks is TOAD_ESHAPE.
+ * out [2 + 8 * 4] ints: out[0] = 1 when the launch runs on half-height (128 x 256) tiles, one whole-K item per workgroup; out[1] = the fix-up
+ * launch behind it: 0 none, else the rows per thread of its instantiation (1 or 4); then for each of the 8 XCDs {rounds, rem, g, tiles}: its
+ * tiles (of the launch's height), the full rounds of 32 its workgroups run, the remainder tiles and the K-slices each of them is cut into
+ * (g = 1: whole; g = 0: no remainder). tests/nt_ref.py restates the plan; tests/test_nt_plans_host.py holds the two together. */
+int toad_nt_plan(int64_t M, int64_t N, int64_t K, int flags, int *out);
 
 /* Y[M,N] = act(X[M,K] W[N,K]^T + bias[N]).   bias may be NULL.
  * Replaces nn.Linear(+nn.ReLU): models/model_toad.py:59 and :62 (trunk, act=RELU) and the

@@ -43,6 +43,10 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert lib.toad_mil_arena_bytes(1000, 18, 384) > 1000 * (512 + 512 + 768 + 2) * 4
     assert lib.toad_mil_arena_bytes(1000, 18, 100) == 0 and lib.toad_mil_scratch_bytes(0, 18, 384) == 0
     assert lib.toad_relu_bits_bytes(100000, 512) == 391 * 2 * 8192 and lib.toad_relu_bits_bytes(1, 4) == 8192
+    # the host-side plan query of one NT launch (additive to ABI 15; tests/test_nt_plans_host.py holds its values)
+    plan = (ctypes.c_int * 34)()
+    assert lib.toad_nt_plan(100000, 512, 1024, 0, None) == -1 and lib.toad_nt_plan(100000, 512, 1000, 0, ctypes.addressof(plan)) == -2
+    assert lib.toad_nt_plan(100000, 512, 1024, 0, ctypes.addressof(plan)) == 0 and plan[0] == 0 and sum(plan[5::4]) == 391 * 2
     offs = (ctypes.c_int64 * 18)()
     assert lib.toad_mil_arena_layout(100000, 18, 384, offs) == 0
     o = list(offs)

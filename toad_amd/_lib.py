@@ -46,6 +46,7 @@ SIGNATURES = {
     "toad_linear_ws_bytes": (SZ, [I64, I64, I64]),
     "toad_relu_bits_bytes": (SZ, [I64, I64]),
     "toad_relu_bits_plan": (I, [I64, I64, I64, I, P]),
+    "toad_nt_plan": (I, [I64, I64, I64, I, P]),
     "toad_linear_act_fwd_f32": (I, [P, P, P, P, I64, I64, I64, I, F, U64, P, P, P, P, SZ, P]),
     "toad_linear_dgrad_f32": (I, [P, P, P, P, F, P, I64, I64, I64, P, P, P, I, P, P, P, P, SZ, P]),
     "toad_dropout_mask_f32": (I, [P, I64, F, U64, P]),

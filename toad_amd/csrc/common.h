@@ -129,6 +129,9 @@ struct NtRoute { int rc; const char *why; bool half, read_bits; };
 NtRoute nt_route(int64_t M, int64_t N, int64_t K, int a_mode, bool run_mode, bool addend, int pool_T, bool mask_src, bool mask_bits, int a_stride,
                  int y_stride, bool a16_half = false);      // a16_half: an fp16 A operand follows nt_half_tiles too (the multi-slide calls; launch_nt_h2)
 void nt_bits_tile_map(int64_t M, int64_t N, int64_t K, const NtRoute &r, unsigned char *tile_map);
+// out[2 + 8 * 4]: what ONE launch on route `r` runs - half, the fix-up instantiation (0 = no fix-up launch, 1, 4), then per XCD the rounds, remainder
+// tiles, K-slices per remainder tile and tiles of the plan its workgroups walk (nt_plan; host only, toad_nt_plan)
+void nt_launch_plan(int64_t M, int64_t N, int64_t K, const NtRoute &r, int *out);
 bool nt_run_ok(int64_t M, int64_t N, int64_t K);       // the first GEMM may measure its fp32 A operand itself (gemm_h2.inc AMODE 3)
 size_t h2_planes_bytes(int64_t N, int64_t K);
 size_t h2_binv_bytes(int64_t N);

@@ -177,6 +177,23 @@ void nt_bits_tile_map(int64_t M, int64_t N, int64_t K, const NtRoute &r, unsigne
     }
 }
 
+// The plan of ONE launch of launch_nt_h2 on route `r`, for the host-side query toad_nt_plan (step.hip): per XCD what gemm_nt_h2_big_kernel gets from
+// nt_plan (half-height launches pass their 128-row tile count and never split), and the fix-up launch that follows (the launcher's rule: only
+// XCDs that split count, nt_fixup_h2_kernel<4> from nine remainder tiles on). Launches nothing.
+void nt_launch_plan(int64_t M, int64_t N, int64_t K, const NtRoute &r, int *out) {
+    const int tiles_m = (int)(r.half ? (M + 127) / 128 : (M + PB - 1) / PB), tiles_n = (int)((N + PB - 1) / PB);
+    int max_rem = 0, rem_all = 0;
+    for (int x = 0; x < kNumXCD; ++x) {
+        NtPlan pl = nt_plan(x, tiles_m, tiles_n, (int)(K / BK));
+        if (r.half) pl.g = pl.rem > 0 ? 1 : 0;
+        if (pl.g > 1) { rem_all += pl.rem; if (pl.rem > max_rem) max_rem = pl.rem; }
+        int *o = out + 2 + 4 * x;
+        o[0] = pl.rounds; o[1] = pl.rem; o[2] = pl.g; o[3] = pl.tiles;
+    }
+    out[0] = r.half ? 1 : 0;
+    out[1] = max_rem > 0 ? (rem_all > 8 ? 4 : 1) : 0;
+}
+
 // split up to 6 weight operands into planes + inverse row scales with ONE launch
 int launch_split_h2(const H2Operand *ops, int n, float *zero, int zero_n, hipStream_t st, const char *what, float *zero2, int zero2_n) {
     H2SplitBatch b;

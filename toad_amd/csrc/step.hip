@@ -329,14 +329,12 @@ struct StreamEvents {
 
 using namespace toad;
 
-// Host-side query of the one-bit ReLU image plan (include/toad_hip.h; no device needed): the tiles whose bit words ONE launch_nt_h2 launch - or,
-// with TOAD_BITS_ROWS, the launches nt_rows makes of it - writes (forward) or reads (dgrad), from the code that decides the launch (nt_route,
-// nt_bits_tile_map, nt_row_chunks, step_dgrad1_reads_bits).
-extern "C" int toad_relu_bits_plan(int64_t M, int64_t N, int64_t K, int flags, uint8_t *tile_map) {
-    const char *what = "toad_relu_bits_plan";
+// the flags of the two host-side plan queries below -> the launch(es) they describe
+struct NtQuery { int a_mode, pool_T; bool reader, bits, rows, multi, run_mode, addend; };
+static int nt_query(int64_t M, int64_t N, int64_t K, int flags, const char *what, NtQuery &q) {
     const int known = TOAD_BITS_READER | TOAD_BITS_ADDEND | TOAD_BITS_POOL | TOAD_BITS_POOL_BATCHED | TOAD_BITS_A16 | TOAD_BITS_APT |
                       TOAD_BITS_SELF_MEASURE | TOAD_BITS_ROWS | TOAD_BITS_STEP_L1 | TOAD_BITS_MULTI;
-    if (!tile_map || (flags & ~known) || ((flags & TOAD_BITS_A16) && (flags & TOAD_BITS_APT)) || ((flags & TOAD_BITS_POOL) && (flags & TOAD_BITS_POOL_BATCHED))) {
+    if ((flags & ~known) || ((flags & TOAD_BITS_A16) && (flags & TOAD_BITS_APT)) || ((flags & TOAD_BITS_POOL) && (flags & TOAD_BITS_POOL_BATCHED))) {
         set_error("%s: bad argument", what); return TOAD_EINVAL;
     }
     // TOAD_BITS_MULTI: the pair as the ragged multi-slide calls launch it (multi_forward_body / multi_backward_body): ONE launch each, no row chunks,
@@ -356,17 +354,48 @@ extern "C" int toad_relu_bits_plan(int64_t M, int64_t N, int64_t K, int flags, u
     if (x_mode != TOAD_X_F32 && rows) ok = ok && M <= kChunkRows && h2_nt_ok(M, kL, kL0, kL0, kL);      // (an fp16 / prepared bag is ONE launch: nt_rows refuses to chunk it)
     if (multi && x_mode == TOAD_X_F16) ok = ok && toad_mil_multi_x16_ok(M);                              // (the totals the fp16 multi-slide calls take)
     if (!ok) { set_error("%s: not a shape of the fp16 two-piece NT kernel (toad_linear_h2_ok)", what); return TOAD_ESHAPE; }
+    q.a_mode = a_mode;
+    q.pool_T = (flags & TOAD_BITS_POOL_BATCHED) ? (2 | (8 << 8)) : (flags & TOAD_BITS_POOL) ? 2 : 0;
+    q.reader = reader;
+    q.bits = reader && (!step_l1 || multi || step_dgrad1_reads_bits(x_mode, M));          // (the step hands the image to its dgrad or not)
+    q.rows = rows;
+    q.multi = multi;
+    q.run_mode = (flags & TOAD_BITS_SELF_MEASURE) != 0;
+    q.addend = (flags & TOAD_BITS_ADDEND) != 0;
+    return TOAD_OK;
+}
+
+// Host-side query of the one-bit ReLU image plan (include/toad_hip.h; no device needed): the tiles whose bit words ONE launch_nt_h2 launch - or,
+// with TOAD_BITS_ROWS, the launches nt_rows makes of it - writes (forward) or reads (dgrad), from the code that decides the launch (nt_route,
+// nt_bits_tile_map, nt_row_chunks, step_dgrad1_reads_bits).
+extern "C" int toad_relu_bits_plan(int64_t M, int64_t N, int64_t K, int flags, uint8_t *tile_map) {
+    const char *what = "toad_relu_bits_plan";
+    if (!tile_map) { set_error("%s: bad argument", what); return TOAD_EINVAL; }
+    NtQuery q;
+    TOAD_TRY(nt_query(M, N, K, flags, what, q));
     const int tiles_n = (int)((N + 255) / 256);
     memset(tile_map, 0, (size_t)((M + 255) / 256) * tiles_n);
-    const bool bits = reader && (!step_l1 || multi || step_dgrad1_reads_bits(x_mode, M));          // (the step hands the image to its dgrad or not)
-    const int pool_T = (flags & TOAD_BITS_POOL_BATCHED) ? (2 | (8 << 8)) : (flags & TOAD_BITS_POOL) ? 2 : 0;
-    const int n_chunks = rows ? nt_row_chunks(M) : 1;
+    const int n_chunks = q.rows ? nt_row_chunks(M) : 1;
     for (int j = 0; j < n_chunks; ++j) {
-        const int64_t c0 = rows ? nt_row_chunk_first(j) : 0, m = rows ? nt_row_chunk_rows(M, j) : M;
-        const NtRoute r = nt_route(m, N, K, a_mode, (flags & TOAD_BITS_SELF_MEASURE) != 0, (flags & TOAD_BITS_ADDEND) != 0, pool_T, reader, bits, 1, 1, multi);
+        const int64_t c0 = q.rows ? nt_row_chunk_first(j) : 0, m = q.rows ? nt_row_chunk_rows(M, j) : M;
+        const NtRoute r = nt_route(m, N, K, q.a_mode, q.run_mode, q.addend, q.pool_T, q.reader, q.bits, 1, 1, q.multi);
         if (r.rc) { set_error("%s: %s", what, r.why); return r.rc; }
-        if (!reader || r.read_bits) nt_bits_tile_map(m, N, K, r, tile_map + (c0 / H2_ROWBLK) * tiles_n);
+        if (!q.reader || r.read_bits) nt_bits_tile_map(m, N, K, r, tile_map + (c0 / H2_ROWBLK) * tiles_n);
     }
+    return TOAD_OK;
+}
+
+// Host-side query of the plan of ONE NT launch (include/toad_hip.h; no device needed): nt_route decides the tile height, nt_launch_plan reads nt_plan
+// as the kernel and the launcher do. A product that the whole-slide calls would cut into row chunks is not one launch: TOAD_ESHAPE.
+extern "C" int toad_nt_plan(int64_t M, int64_t N, int64_t K, int flags, int *out) {
+    const char *what = "toad_nt_plan";
+    if (!out) { set_error("%s: bad argument", what); return TOAD_EINVAL; }
+    NtQuery q;
+    TOAD_TRY(nt_query(M, N, K, flags, what, q));
+    if (q.rows && nt_row_chunks(M) > 1) { set_error("%s: more than one launch (row chunks)", what); return TOAD_ESHAPE; }
+    const NtRoute r = nt_route(M, N, K, q.a_mode, q.run_mode, q.addend, q.pool_T, q.reader, q.bits, 1, 1, q.multi);
+    if (r.rc) { set_error("%s: %s", what, r.why); return r.rc; }
+    nt_launch_plan(M, N, K, r, out);
     return TOAD_OK;
 }
 
