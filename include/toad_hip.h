@@ -661,7 +661,8 @@ int toad_region_heat_pyramid_windows_u8(const ToadHeatPyramidWindow *windows /* 
  *   The order is closing, components, holes: after 6b every remaining component is kept, so a hole never needs to know its enclosing component, and an
  *   island removed in 6b merges into the hole around it before 6c counts that hole. Areas are pixel counts of the unfilled component - CLAM's
  *   contourArea(outer) - sum(contourArea(holes)) but for the polygon-versus-pixel difference; from CLAM's units: a_t * 512^2 / (level downsample * down)^2.
- * max_n_holes, polygon areas and several regions per call are not done. All calls are asynchronous on `stream`, allocate nothing and do not synchronise;
+ * max_n_holes, polygon areas and several regions per call are not done - but for steps 1 and 2, the only ones that read the region, which
+ * toad_regions_saturation_u8 runs for a list of windows; the steps behind them run once, on the assembled plane. All calls are asynchronous on `stream`, allocate nothing and do not synchronise;
  * every refusal comes before any device access. */
 
 /* plane uint8 [Hp][Wp] with row pitch plane_pitch >= Wp bytes (TOAD_ESHAPE otherwise), any base address = steps 1 and 2. region and pitch as for
@@ -671,6 +672,22 @@ int toad_region_heat_pyramid_windows_u8(const ToadHeatPyramidWindow *windows /* 
  * returns TOAD_OK and launches nothing. One streaming pass: 3 * Hr * Wr bytes read, Hp * Wp written. */
 int toad_region_saturation_u8(const unsigned char *region, int64_t pitch, int Hr, int Wr, int down, int val_min, unsigned char *plane,
                               int64_t plane_pitch, void *stream);
+
+/* Steps 1 and 2 for a LIST of n windows in one call (additive to ABI 15 too): plane k is byte for byte what toad_region_saturation_u8 writes for window k
+ * with the same down and val_min - the strips or blocks a slide arrives in, each into its rows and columns of the slide's one plane (plane row r depends on
+ * the rows r * down .. (r + 1) * down only, so a plane put together from windows that each hold whole boxes IS the plane of the whole slide, and the median,
+ * Otsu, closing and component steps behind it see across the seams). `windows` is a HOST array, read during the call and not afterwards; region and plane
+ * are device addresses. Checks, in this order, nothing being launched unless all pass: windows == NULL with n > 0, then n < 0 (TOAD_EINVAL); val_min and
+ * down with toad_region_saturation_u8's messages; window by window that entry's own checks in its order - null pointers, shape, region pitch, plane pitch -
+ * the first failing window winning, its message starting with "window k:"; then the workgroups of the whole list, which must stay below 2^31
+ * (TOAD_ESHAPE). A window with Hr < down or Wr < down writes nothing and the others are still written; n == 0 returns TOAD_OK and launches nothing.
+ * Planes that overlap each other are the caller's business. Per window nothing outside plane + y * plane_pitch + [0, Wr / down), y < Hr / down, is written,
+ * and nothing outside the rows and columns that some box consumes is read. The descriptors travel by value in the kernel argument, 32 a launch
+ * (sat_plane_list_kernel in csrc/tissue_seg.hip): a list of n windows that have a plane pixel is ceil(n / 32) launches inside this one call, with no
+ * allocation, no host synchronisation, no copy, no atomics and no device memory dereferenced on the host. Not done: a list form of the median, cell and
+ * component steps (they run once, on the assembled plane), windows with a down or val_min of their own. */
+typedef struct { const unsigned char *region; int64_t pitch; int Hr, Wr; unsigned char *plane; int64_t plane_pitch; } ToadSatWindow;
+int toad_regions_saturation_u8(const ToadSatWindow *windows /* HOST array */, int n, int down, int val_min, void *stream);
 
 /* dst uint8 [Hp][Wp] = the k x k median of src [Hp][Wp] (step 3); both with any base address and any pitch >= Wp, Hp, Wp >= 1 (TOAD_ESHAPE otherwise). src
  * and dst must not overlap (TOAD_EINVAL). hist may be NULL; otherwise int32 [256], 4-byte aligned (TOAD_EALIGN), and after the call hist = the histogram

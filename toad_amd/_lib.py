@@ -29,6 +29,11 @@ class ToadHeatPyramidWindow(ctypes.Structure):
                 ("out_pitches", c_int64 * 6)]
 
 
+class ToadSatWindow(ctypes.Structure):
+    """One window of toad_regions_saturation_u8's HOST array (include/toad_hip.h): region and plane are device addresses."""
+    _fields_ = [("region", c_void_p), ("pitch", c_int64), ("Hr", c_int), ("Wr", c_int), ("plane", c_void_p), ("plane_pitch", c_int64)]
+
+
 class ToadWgradJob(ctypes.Structure):
     """One job of toad_linear_wgrad_batch_f32's HOST array (include/toad_hip.h): every pointer is a device address."""
     _fields_ = [("dY", c_void_p), ("dy_amax", c_void_p), ("X", c_void_p), ("x_amax", c_void_p), ("dW", c_void_p), ("db", c_void_p),
@@ -142,6 +147,8 @@ SIGNATURES = {
     "toad_region_saturation_u8": (I, [P, I64, I, I, I, I, P, I64, P]),
     "toad_plane_median_u8": (I, [P, I64, I, I, I, P, I64, P, P]),
     "toad_plane_cells_u8": (I, [P, I64, I, I, I, I, P, P]),
+    # ... and its saturation plane for a list of windows in one call (windows: a HOST array of n ToadSatWindow): additive to ABI 15
+    "toad_regions_saturation_u8": (I, [ctypes.POINTER(ToadSatWindow), I, I, I, P]),
     # ... and what follows its threshold, closing and the component / hole area filters (csrc/tissue_morph.hip): additive to ABI 15
     "toad_plane_close_u8": (I, [P, I64, I, I, I, I, P, I64, P]),
     "toad_plane_components_u8": (I, [P, I64, I, I, I, I, P, P, P]),

@@ -13,8 +13,10 @@
 //   cells       counts[gy][gx] = the pixels > thresh (THRESH_BINARY) of every cell x cell cell of a plane, cells anchored at (0, 0), partial edge cells
 //               counting the pixels that exist - the table toad_tissue_tile_counts sums over a lattice given in plane units.
 //
-// Three kernels:
+// Four kernels:
 //   sat_plane_kernel<DOWN>    one streaming pass over the region (the 100 MB one) -> the uint8 saturation plane.
+//   sat_plane_list_kernel<DOWN>   the same pass over a LIST of windows (strips or blocks of a slide, each into its rows and columns of one plane): descriptors
+//                             by value, the same body (sat_plane_body.inc).
 //   plane_median_kernel<K>    a 64 x 4 output tile and its K - 1 halo staged in LDS as bytes, the rank taken by bisection over the 8 value bits.
 //   plane_cells_kernel<CELL>  tissue_cells_kernel's work split on one byte per pixel.
 #include "region_u8.h"
@@ -49,112 +51,44 @@ __device__ __forceinline__ int sg_byte(const unsigned (&w)[3], int k) { return (
 // stands in front of the r < rows test (rows that do not exist must be zeros too) and not in the byte-load arm. With the helper called instead, hipcc
 // lays sat_plane_kernel<1> out differently and its PLAIN path - the same instructions - ran 0.8 % slower on a 4096 x 8192 region in 6 of 6 alternating
 // runs, the parent's own runs spreading by 0.2 % (profiles/r13a_region_refactor_ab.md, "sat_plane_kernel through load_px4"). Written out, DOWN = 1 and 2
-// compile to the parent's code.
+// compile to the parent's code. The body lies in sat_plane_body.inc, which sat_plane_list_kernel includes too (an included file and not a device
+// function, for the same reason: profiles/tissue_strips_isa.md compares the six instantiations with what the kernel compiled to when the body stood here).
 template <int DOWN>
 __global__ __launch_bounds__(256) void sat_plane_kernel(const unsigned char *__restrict__ region, int64_t pitch, int Hi, int Wi, int vmin,
                                                         unsigned char *__restrict__ plane, int64_t ppitch, unsigned nchunks) {
-    constexpr int RB = strip_rows(DOWN), RW = RB / 4;              // rows per workgroup, per wave
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned chunk = blockIdx.x % nchunks, rb = blockIdx.x / nchunks;
-    const unsigned x = chunk * 256u + (unsigned)lane * 4u, off = 3u * x;
-    const int64_t y0 = (int64_t)rb * RB + wave * RW;               // first row of this wave (may lie below Hi: then it reads and writes nothing)
-    const unsigned char *src = region + y0 * pitch + off;
-    unsigned w[RW][3];
-    int rows = RW, npx = 4;                                        // rows of this wave and pixels of this lane that are consumed
-    if (chunk * 256u + 256u <= (unsigned)Wi && y0 + RW <= Hi) {    // wave-uniform: all 768 bytes of all RW rows are consumed
+    const unsigned bid = blockIdx.x;
+#include "sat_plane_body.inc"
+}
+
+// ---- a list of windows in one launch: toad_regions_saturation_u8 ----
+// The list form of sat_plane_kernel, built as heat_blend_px_list_kernel is (heatmap.hip): the windows share DOWN and vmin and each has a descriptor of its
+// own; the descriptors travel by value in the kernel argument - no device table, no upload. The grid is the windows' workgroups one after the other,
+// descriptor k owning workgroups first[k] .. first[k + 1]; descriptors from n on carry first = 0xFFFFFFFF, above every workgroup index, so the search needs
+// no n: five uniform steps of a binary search over the 32 prefixes, scalar loads from the kernel argument, once per workgroup. From there on a workgroup is
+// one of its window's: chunk and rb from its index inside the window, and the body sat_plane_kernel runs. The grid is exact: every workgroup has a window.
+// Windows without a workgroup (Hr < down or Wr < down) never reach a descriptor. No atomics, no scratch, and the LDS of the single form.
+constexpr int SAT_LIST_MAX = 32;                                     // 32 descriptors of 48 bytes and vmin: 1.5 KB of the 4 KB a kernel argument may have
+struct SatListWin {
+    const unsigned char *region; int64_t pitch; unsigned char *plane; int64_t ppitch;
+    int Hi, Wi; unsigned nchunks, first;
+};
+struct SatListArgs { SatListWin w[SAT_LIST_MAX]; };
+static_assert(sizeof(SatListArgs) + sizeof(int) <= 4096, "the descriptors travel in the kernel argument");
+
+template <int DOWN>
+__global__ __launch_bounds__(256) void sat_plane_list_kernel(const SatListArgs l, int vmin) {
+    static_assert(SAT_LIST_MAX == 32, "five steps search 32 prefixes");
+    int k = 0;
 #pragma unroll
-        for (int r = 0; r < RW; ++r)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) w[r][k] = *reinterpret_cast<const u32_a1 *>(src + r * pitch + 4 * k);
-    } else {
-        rows = (int)max((int64_t)0, min((int64_t)RW, (int64_t)Hi - y0));
-        npx = x < (unsigned)Wi ? min(4, Wi - (int)x) : 0;
-#pragma unroll
-        for (int r = 0; r < RW; ++r) {
-            w[r][0] = w[r][1] = w[r][2] = 0;
-            if (r < rows) {                                        // load_px4(src + r * pitch, npx, w[r]), written out: see above
-                const unsigned char *p = src + r * pitch;
-                if (npx == 4) {
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) w[r][k] = *reinterpret_cast<const u32_a1 *>(p + 4 * k);
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 9; ++k)
-                        if (k < 3 * npx) w[r][k >> 2] |= (unsigned)p[k] << (8 * (k & 3));
-                }
-            }
-        }
-    }
-    if constexpr (DOWN == 1) {
-        unsigned char *dst = plane + y0 * ppitch + x;
-#pragma unroll
-        for (int r = 0; r < RW; ++r) {
-            unsigned o = 0;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) o |= sat_byte(sg_byte(w[r], 3 * p), sg_byte(w[r], 3 * p + 1), sg_byte(w[r], 3 * p + 2), vmin) << (8 * p);
-            if (r < rows) {
-                unsigned char *d = dst + r * ppitch;
-                if (npx == 4) {
-                    *reinterpret_cast<u32_a1 *>(d) = o;
-                } else {
-#pragma unroll
-                    for (int p = 0; p < 3; ++p)
-                        if (p < npx) d[p] = (unsigned char)(o >> (8 * p));
-                }
-            }
-        }
-    } else if constexpr (DOWN == 2) {
-        unsigned char *dst = plane + (y0 >> 1) * ppitch + (x >> 1);
-#pragma unroll
-        for (int q = 0; q < RW / 2; ++q) {
-            unsigned o = 0;
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                int s[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    s[c] = (sg_byte(w[2 * q], 6 * p + c) + sg_byte(w[2 * q], 6 * p + 3 + c) + sg_byte(w[2 * q + 1], 6 * p + c) +
-                            sg_byte(w[2 * q + 1], 6 * p + 3 + c) + 2) >> 2;
-                o |= sat_byte(s[0], s[1], s[2], vmin) << (8 * p);
-            }
-            if (2 * q < rows) {                                    // rows is even: Hi and y0 are
-                unsigned char *d = dst + q * ppitch;
-                if (npx == 4) *reinterpret_cast<u16_a1 *>(d) = (unsigned short)o;
-                else if (npx == 2) d[0] = (unsigned char)o;
-            }
-        }
-    } else {
-        constexpr int LANES = DOWN / 4, SH = DOWN == 4 ? 4 : DOWN == 8 ? 6 : DOWN == 16 ? 8 : 10;      // lanes per box, log2(DOWN^2)
-        unsigned b[12];                                            // the 12 column sums over the wave's rows, each at most 8 * 255
-        column_sums<RW>(w, b);
-        int s[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) s[c] = lanes_allreduce_sum<LANES>((int)(b[c] + b[c + 3] + b[c + 6] + b[c + 9]));
-        if constexpr (DOWN == 4) {
-            if (rows > 0 && npx == 4)
-                plane[(y0 >> 2) * ppitch + (x >> 2)] = (unsigned char)sat_byte((s[0] + 8) >> 4, (s[1] + 8) >> 4, (s[2] + 8) >> 4, vmin);
-        } else {
-            constexpr int NB = RB / DOWN, WPB = 4 / NB, CPR = 64 / LANES;      // box rows per workgroup, waves per box row, boxes per chunk
-            __shared__ int part[3][4][64];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) part[c][wave][lane] = s[c];
-            __syncthreads();
-            if (tid < NB * CPR) {
-                const int band = tid / CPR, bx = tid - band * CPR;
-                int m[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    int t = 0;
-#pragma unroll
-                    for (int k = 0; k < WPB; ++k) t += part[c][band * WPB + k][bx * LANES];
-                    m[c] = (t + (1 << (SH - 1))) >> SH;
-                }
-                const int64_t oy = (int64_t)rb * NB + band;
-                const unsigned ox = chunk * CPR + bx;
-                if (oy * DOWN < Hi && ox * DOWN < (unsigned)Wi) plane[oy * ppitch + ox] = (unsigned char)sat_byte(m[0], m[1], m[2], vmin);
-            }
-        }
-    }
+    for (int step = SAT_LIST_MAX / 2; step >= 1; step >>= 1)
+        if (l.w[k + step].first <= blockIdx.x) k += step;
+    const SatListWin &win = l.w[k];
+    const unsigned char *__restrict__ region = win.region;
+    unsigned char *__restrict__ plane = win.plane;
+    const int64_t pitch = win.pitch, ppitch = win.ppitch;
+    const int Hi = win.Hi, Wi = win.Wi;
+    const unsigned nchunks = win.nchunks, bid = blockIdx.x - win.first;
+#include "sat_plane_body.inc"
 }
 
 // Per byte of x: bit 7 of the result is set iff the byte >= the byte of t at that place (unsigned); the other bits are garbage. d compares the low 7
@@ -315,6 +249,62 @@ extern "C" int toad_region_saturation_u8(const unsigned char *region, int64_t pi
     }
 #undef TOAD_SAT_LAUNCH
     return check_launch(what);
+}
+
+// The list entry: what the windows share first (val_min, down: the single entry's checks and messages), then window by window the single entry's checks of
+// what each window has of its own, in its order, the first failing window winning under "window k:"; then the workgroup count of the whole list. Nothing is
+// launched before all of that has passed. Two walks over the host array, no allocation: the first checks and counts, the second fills SAT_LIST_MAX
+// descriptors at a time and launches them.
+extern "C" int toad_regions_saturation_u8(const ToadSatWindow *windows, int n, int down, int val_min, void *stream) {
+    const char *what = "toad_regions_saturation_u8";
+    if (n > 0 && !windows) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (n < 0) { set_error("%s: n = %d windows", what, n); return TOAD_EINVAL; }
+    if (int rc = check_u8(what, "val_min", val_min)) return rc;
+    if (!seg_down_ok(down)) { set_error("%s: down = %d is not one of 1, 2, 4, 8, 16, 32", what, down); return TOAD_ESHAPE; }
+    const int rb = strip_rows(down);
+    // a window's workgroups: 0 where it has no plane pixel
+    auto geometry = [&](const ToadSatWindow &w, int &Hi, int &Wi, int64_t &nchunks) {
+        Hi = w.Hr / down * down; Wi = w.Wr / down * down;
+        nchunks = ((int64_t)Wi + 255) / 256;
+        return nchunks * (((int64_t)Hi + rb - 1) / rb);
+    };
+    int64_t blocks = 0;
+    for (int k = 0; k < n; ++k) {
+        const ToadSatWindow &w = windows[k];
+        char who[80];
+        snprintf(who, sizeof who, "window %d: %s", k, what);
+        if (!w.region || !w.plane) { set_error("%s: null pointer", who); return TOAD_EINVAL; }
+        if (int rc = check_hw(who, "Hr", w.Hr, "Wr", w.Wr)) return rc;
+        if (int rc = check_region_pitch(who, w.pitch, w.Wr)) return rc;
+        if (int rc = check_plane_pitch(who, w.Wr / down, "plane_pitch", w.plane_pitch)) return rc;
+        int Hi, Wi;
+        int64_t nchunks;
+        blocks += geometry(w, Hi, Wi, nchunks);                      // one window: below 2^50 ...
+        if (blocks > (1ll << 31)) blocks = 1ll << 31;                // ... and the sum saturates where it is refused
+    }
+    if (int rc = check_blocks(what, "list of regions", blocks)) return rc;
+    if (blocks == 0) return TOAD_OK;
+    SatListArgs l;
+    for (int k = 0; k < n;) {
+        int m = 0;
+        unsigned grid = 0;
+        for (; k < n && m < SAT_LIST_MAX; ++k) {
+            const ToadSatWindow &w = windows[k];
+            int Hi, Wi;
+            int64_t nchunks;
+            const int64_t b = geometry(w, Hi, Wi, nchunks);
+            if (b == 0) continue;
+            l.w[m++] = {w.region, w.pitch, w.plane, w.plane_pitch, Hi, Wi, (unsigned)nchunks, grid};
+            grid += (unsigned)b;
+        }
+        if (m == 0) break;
+        for (int j = m; j < SAT_LIST_MAX; ++j) { l.w[j] = {}; l.w[j].first = 0xFFFFFFFFu; }      // above every workgroup index: the search stops short of them
+#define TOAD_SAT_LIST(D) case D: hipLaunchKernelGGL(sat_plane_list_kernel<D>, dim3(grid), dim3(256), 0, (hipStream_t)stream, l, val_min); break;
+        switch (down) { TOAD_SAT_LIST(1) TOAD_SAT_LIST(2) TOAD_SAT_LIST(4) TOAD_SAT_LIST(8) TOAD_SAT_LIST(16) TOAD_SAT_LIST(32) }
+#undef TOAD_SAT_LIST
+        if (int rc = check_launch(what)) return rc;
+    }
+    return TOAD_OK;
 }
 
 extern "C" int toad_plane_median_u8(const unsigned char *src, int64_t src_pitch, int Hp, int Wp, int k, unsigned char *dst, int64_t dst_pitch, int *hist,

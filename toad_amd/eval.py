@@ -296,7 +296,7 @@ def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region
     ``{down: tensor}`` and ``out`` a dict of that kind or None; one selection, one scoring, one cell table and one read of the region
     (``heatmap.attention_pyramid``), each level byte for byte the call with that ``down``; the lattice's cell must be at least the largest level and,
     with ``tissue_mask=True``, the segment ``down`` a multiple of it (ValueError otherwise, before anything is launched). A slide
-    that arrives strip by strip: ``slide_attention_heatmap`` (no seams, one colour scale); the segmented selector there still works on one region."""
+    that arrives strip by strip: ``slide_attention_heatmap`` (no seams, one colour scale); ``segment=`` and ``tissue_mask=`` there select on the slide's plane, put together from the strips."""
     from .heatmap import attention_canvas, attention_pyramid, blur_taps
     from .tissue import _lattice_args, lattice_cell
     levels = None                                                   # a sequence of levels: one scoring, one cell table, one read of the region
@@ -338,7 +338,7 @@ def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region
 def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_hw, tile=256, stride=None, origin=(0, 0), origins=None,
                             min_fraction: float = 0.25, sat_thresh: int = 8, val_min: int = 0, bag_dtype: torch.dtype = torch.float16, alpha=102,
                             down: int = 1, lut=None, out=None, smooth: bool = False, mask=None, thresh=None, binarize: bool = False, blur=False, shrink=1,
-                            batch_render: bool = False, batch_levels: bool = False):
+                            batch_render: bool = False, batch_levels: bool = False, segment: Optional[dict] = None, tissue_mask: bool = False):
     """``(origins, scores, canvas)`` of a slide of ``slide_hw`` = (Hs, Ws) pixels that arrives from the decoder strip by strip: what
     ``region_tissue_attention_heatmap`` gives for one region, with no seam where two strips meet. ``strips`` is a sequence of ``(region, y_k)`` - a
     decoded uint8 [H_k,Ws,3] full-width strip on the device and the slide row of its first row - sorted, each abutting or overlapping the one before,
@@ -370,13 +370,23 @@ def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_
     the region, its rows of every level's slide canvas as its ``outs`` - and so one launch per ``ops.HEAT_PYR_LIST_MAX`` strips and one read of every
     strip; the dict ``{down: canvas}`` is byte for byte what the walk gives. With an int ``down`` it is a ValueError: that is ``batch_render``.
 
-    Not done here: the segmented selector across strips - its median, closing and component steps reach across strip seams, so
-    ``tissue.segmented_tissue_origins`` still works on one region per call; make that selection on an overview level and pass it in through
-    ``origins=`` and ``mask=``. Blocks that are not full-width strips (``heatmap.window_canvas`` renders any window; this walk does not), and the
-    "not done" list of ``region_tissue_attention_heatmap`` except seams."""
+    ``segment``: None selects per strip with ``tissue_origins``, as above; a dict of the keys ``region_tissue_attention_heatmap`` takes (``down``,
+    ``median``, ``sat_thresh``, ``val_min``, ``close``, ``min_area``, ``min_hole``; the same defaults) selects with CLAM's recipe ON THE WHOLE SLIDE:
+    before pass 1 the strips are read once, in one launch, for the slide's saturation plane (``tissue.slide_saturation`` - only that step touches the
+    pixels, and a plane put together from strips is the plane of the slide), and ``tissue.segmented_slide_origins`` runs the median, Otsu, the closing,
+    the component filters and the tile sums once on it - they see across the seams, and there is one read-back for the slide. The tiles then take the
+    ``origins=`` route: each strip extracts the lattice rows it owns, with one percentile ranking. Every plane row of the segment ``down`` must lie whole
+    in one strip (``tissue.plane_strip_plan``: strips meet at multiples of it or overlap enough). ``tissue_mask=True`` (CLAM's ``segment=True``) hands
+    that selection's ``(plane, t, segment down)`` to pass 2 as ``mask``; the segment ``down`` must be a multiple of the canvas ``down`` (of the
+    largest level). ValueError before anything is launched: ``segment`` together with ``origins``, ``tissue_mask=True`` without a ``segment`` dict or
+    together with ``mask``, the multiple rule, and what ``plane_strip_plan`` and the segmented lattice rule (multiples of 4 * segment ``down``) refuse.
+    With ``segment=None`` and ``tissue_mask=False`` every path, message and byte is what it was.
+
+    Not done here: blocks that are not full-width strips (``heatmap.window_canvas`` renders any window and ``ops.regions_saturation`` takes any
+    windows; this walk does not), and the "not done" list of ``region_tissue_attention_heatmap`` except seams."""
     from .heatmap import slide_cells, strip_plan, window_canvas, window_pyramid, windows_canvas, windows_pyramid
     from .heatmap import blur_taps
-    from .tissue import _lattice_args, lattice_cell, tissue_origins
+    from .tissue import _lattice_args, lattice_cell, segmented_slide_origins, tissue_origins
     hs, ws = slide_hw
     h, w, sy, sx, x0, y0 = _lattice_args(tile, stride, origin)
     if shrink != 1:                                                 # refuse what the second pass would refuse before the extractor runs
@@ -405,6 +415,28 @@ def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_
     elif down in (8, 16, 32) and cell < down:
         raise ValueError(f"slide_attention_heatmap: down = {down} exceeds the lattice's cell = {cell}: a canvas box must lie in one cell")
     blur_taps(blur, (h, w), cell)
+    seg_kw = None
+    if tissue_mask and not isinstance(segment, dict):
+        raise ValueError("tissue_mask=True needs a segment dict: only tissue.segmented_tissue_origins leaves a mask plane on the device")
+    if segment is not None:
+        if not isinstance(segment, dict) or any(k not in _SEGMENT_KEYS for k in segment):
+            bad = segment if not isinstance(segment, dict) else sorted(k for k in segment if k not in _SEGMENT_KEYS)
+            raise ValueError(f"segment must be None or a dict with keys among {_SEGMENT_KEYS}, got {bad!r}")
+        if origins is not None:
+            raise ValueError("slide_attention_heatmap: segment selects the tiles, origins gives them: pass one of the two")
+        if tissue_mask and mask is not None:
+            raise ValueError("slide_attention_heatmap: tissue_mask=True renders with the selection's own mask plane: pass that or mask, not both")
+        seg_kw = dict(sat_thresh=sat_thresh, val_min=val_min)
+        seg_kw.update(segment)
+        seg_kw["down"] = seg_down = _segment_down(seg_kw)
+        if tissue_mask:
+            if levels is not None:
+                if not isinstance(seg_down, int) or seg_down % max(levels):
+                    raise ValueError(f"tissue_mask=True: the segment down = {seg_down!r} must be a multiple of the largest canvas down = {max(levels)} (a canvas "
+                                     "box must lie in one mask pixel)")
+            elif down not in (1, 2, 4, 8, 16, 32) or not isinstance(seg_down, int) or seg_down % down:
+                raise ValueError(f"tissue_mask=True: the segment down = {seg_down!r} must be a multiple of the canvas down = {down!r} (a canvas box must lie "
+                                 "in one mask pixel)")
     shapes = []
     for k, (region, y) in enumerate(strips):
         if region.dim() != 3 or region.shape[1] != ws or region.shape[2] != 3:
@@ -412,7 +444,14 @@ def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_
         shapes.append((y, region.shape[0]))
     plan = strip_plan((hs, ws), shapes, (h, w), (sy, sx), (x0, y0), down)
     device = strips[0][0].device
-    if origins is not None:
+    given = None
+    if seg_kw is not None:                                          # one selection on the slide's plane: one read of the strips, one read-back
+        given, (plane, t) = segmented_slide_origins(strips, (hs, ws), tile=(h, w), stride=(sy, sx), min_fraction=min_fraction, origin=(x0, y0),
+                                                    return_mask=True, **seg_kw)
+        rows = (given[:, 1] - y0) // sy
+        if tissue_mask and plane is not None:
+            mask = (plane, t, seg_kw["down"])
+    elif origins is not None:
         given = np.asarray(origins)
         if given.ndim != 2 or given.shape[1] != 2 or given.dtype.kind not in "iu":
             raise ValueError(f"slide_attention_heatmap: origins must be [B,2] integers (x, y) in slide coordinates, got shape {given.shape} dtype {given.dtype}")
@@ -427,7 +466,7 @@ def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_
         j0, j1 = p["rows"]
         if j1 == j0:
             continue
-        if origins is None:
+        if given is None:
             local = tissue_origins(region, tile=(h, w), stride=(sy, sx), min_fraction=min_fraction, sat_thresh=sat_thresh, val_min=val_min, origin=p["origin"])
         else:
             local = given[(rows >= j0) & (rows < j1)] - np.array([0, y], dtype=np.int64)

@@ -1471,6 +1471,56 @@ def region_saturation(region: torch.Tensor, down: int, val_min: int = 0, out=Non
     return out
 
 
+SAT_LIST_MAX = 32                      # the windows one launch of regions_saturation takes (csrc/tissue_seg.hip): a longer list is more launches in the one call
+
+
+def regions_saturation(regions, down: int, val_min: int = 0, outs=None) -> tuple:
+    """region_saturation for a LIST of windows in ONE library call and one launch per SAT_LIST_MAX windows (toad_regions_saturation_u8;
+    include/toad_hip.h): a tuple of uint8 [Hr_k // down, Wr_k // down] planes, each byte for byte what region_saturation gives for ``regions[k]`` with
+    the same ``down`` and ``val_min``. ``regions`` is a sequence of uint8 [Hr,Wr,3] views on one device, of any extents, pitches and alignment - the
+    strips or blocks a slide arrives in, or buffers of their own. ``outs`` is None or one uint8 [Hr_k // down, Wr_k // down] view per region with
+    stride(1) == 1 and any pitch, for example each strip's rows of the slide's one plane (``tissue.slide_saturation``); no plane may share storage with
+    its own region, and planes that overlap each other are the caller's business. The checks are region_saturation's, per region, with ValueErrors
+    that name the window's index, all before the library is called. A window without a plane row or column is returned empty and the others are still
+    written. No synchronisation, no copy to the device: the descriptors travel in the kernel argument. An empty list returns () and, like a list whose
+    planes are all empty, launches nothing."""
+    name = "regions_saturation"
+    if isinstance(regions, (str, bytes, torch.Tensor)) or not hasattr(regions, "__len__") or not hasattr(regions, "__iter__"):
+        raise ValueError(f"{name}: regions must be a sequence with one entry per window, got {type(regions).__name__}")
+    regions = tuple(regions)
+    n = len(regions)
+    if outs is not None:
+        if isinstance(outs, torch.Tensor) or not hasattr(outs, "__len__") or len(outs) != n:
+            raise ValueError(f"{name}: outs must be None or a sequence of {n} planes, one per window")
+        outs = tuple(outs)
+    if down not in SEG_DOWNS:
+        raise ValueError(f"{name}: down must be one of {SEG_DOWNS}, got {down!r}")
+    _u8_arg(name, "val_min", val_min)
+    planes, live = [], []
+    for k, region in enumerate(regions):
+        who = f"{name}: window {k}"
+        pitch, hr, wr = _region_pitch(region, who)
+        if region.device != regions[0].device:
+            raise ValueError(f"{who}: every region must be on one device ({regions[0].device}), got {region.device}")
+        hp, wp = hr // down, wr // down
+        if outs is None:
+            out = torch.empty((hp, wp), dtype=torch.uint8, device=region.device)
+        else:
+            out = outs[k]
+            if not isinstance(out, torch.Tensor) or out.device != region.device or tuple(out.shape) != (hp, wp):
+                raise ValueError(f"{who}: outs[{k}] must be a uint8 [{hp},{wp}] tensor on the region's device")
+            _plane_pitch(out, who)
+            if out.untyped_storage().data_ptr() == region.untyped_storage().data_ptr():
+                raise ValueError(f"{who}: outs[{k}] must not share storage with region (the plane is written while the region is read)")
+        planes.append(out)
+        if hp and wp:
+            live.append((region.data_ptr(), pitch, hr, wr, out.data_ptr(), _row_pitch(out, wp)))
+    if live:
+        host = (_lib.ToadSatWindow * len(live))(*(_lib.ToadSatWindow(*w) for w in live))
+        _lib.check(_lib.load().toad_regions_saturation_u8(host, len(live), down, val_min, _stream()), "toad_regions_saturation_u8")
+    return tuple(planes)
+
+
 def plane_median(plane: torch.Tensor, k: int, want_hist: bool = False):
     """The k x k median of a uint8 [Hp,Wp] plane (stride(1) == 1, any pitch >= Wp, any alignment): a new contiguous uint8 [Hp,Wp] on the device. The
     output is the (k k) // 2-th of the sorted k k values of the window around each pixel, coordinates clamped to the plane (replicate border, as

@@ -47,7 +47,13 @@ removed in 6b merges into the hole around it before 6c counts that hole. The are
 level 0): ``min_area = a_t * 512^2 / (level downsample * down)^2``, and ``min_hole`` from ``a_h`` alike.
 
 Dust, JPEG speckle and single saturated pixels on glass are tissue for the first selector and vanish under the median of the second. Not done:
-``max_n_holes``, polygon areas, several regions per call.
+``max_n_holes``, polygon areas.
+
+A slide that arrives in strips (``segment_tissue_strips``, ``segmented_slide_origins``; ``eval.slide_attention_heatmap(segment=...)``): only steps 1 and 2
+touch the slide's pixels, and plane row ``r`` depends on the slide rows ``r down .. (r + 1) down`` alone. So the plane is put together from the strips -
+``plane_strip_plan`` says which strip gives which rows, ``slide_saturation`` writes them in ONE launch for all strips (``ops.regions_saturation``,
+``sat_plane_list_kernel``) - and is byte for byte the plane of the whole slide, provided every plane row lies whole in some strip. Steps 3 to 7 then run
+once on that plane and see across the seams; there is one read-back for the slide. Several regions per call are done for steps 1 and 2 only.
 
 Conventions: ``tile`` = int or (H, W) as in ``ops.tile_shape``; ``stride`` = int or (sy, sx), the same order, default the tile shape;
 ``origin`` = (x, y) of the lattice's first tile, x first as in ``origins``.
@@ -211,7 +217,12 @@ def segment_tissue(region: torch.Tensor, down: int = 16, median: int = 7, sat_th
     one 64 x 16 tile - and the selection); ``min_hole`` 4 likewise; all three 9. No further synchronisation. An empty plane still launches nothing."""
     _seg_args(down, median, sat_thresh, val_min)
     active = _morph_args(close, min_area, min_hole)
-    sat = ops.region_saturation(region, down, val_min)
+    return _segment_plane(ops.region_saturation(region, down, val_min), median, sat_thresh, close, min_area, min_hole, active, return_threshold)
+
+
+def _segment_plane(sat: torch.Tensor, median, sat_thresh, close=0, min_area=0, min_hole=0, active=False, return_threshold=False):
+    """``segment_tissue`` from the saturation plane on (steps 3 to 6c): these steps do not care where the plane came from - one region, or a slide's
+    strips (``slide_saturation``). The arguments have been checked."""
     if sat_thresh == "otsu":
         plane, hist = ops.plane_median(sat, median, want_hist=True)
         t = otsu_threshold(hist.cpu())                               # the 1 KB copy, the synchronisation
@@ -258,6 +269,14 @@ def segmented_tissue_origins(region: torch.Tensor, tile=256, stride=None, min_fr
     _seg_args(down, median, sat_thresh, val_min)
     active = _morph_args(close, min_area, min_hole)
     _, hr, wr = ops._region_pitch(region, "segmented_tissue_origins")
+    return _origins_on_plane(lambda: ops.region_saturation(region, down, val_min), hr, wr, tile, stride, min_fraction, down, median, sat_thresh, origin,
+                             return_counts, return_threshold, close, min_area, min_hole, active, return_mask)
+
+
+def _origins_on_plane(saturation, hr, wr, tile, stride, min_fraction, down, median, sat_thresh, origin, return_counts, return_threshold, close, min_area,
+                      min_hole, active, return_mask):
+    """``segmented_tissue_origins`` from the saturation plane on: ``saturation()`` gives the uint8 [hr // down, wr // down] plane of the hr x wr image the
+    lattice lies on and is called only where the lattice has a tile. The arguments have been checked."""
     h, w, sy, sx, x0, y0 = _lattice_args(tile, stride, origin)
     ph, pw, psy, psx, px0, py0 = _seg_lattice((h, w), (sy, sx), (x0, y0), down)
     nx, ny = lattice(hr, wr, (h, w), (sy, sx), (x0, y0))
@@ -265,7 +284,7 @@ def segmented_tissue_origins(region: torch.Tensor, tile=256, stride=None, min_fr
     counts, t = None, 0 if sat_thresh == "otsu" else sat_thresh
     mask = (None, t)
     if nx and ny:
-        plane, t = segment_tissue(region, down, median, sat_thresh, val_min)
+        plane, t = _segment_plane(saturation(), median, sat_thresh)
         cell = lattice_cell((ph, pw), (psy, psx), (px0, py0))
         mask = (_morph(plane, t, close, min_area, min_hole), 0) if active else (plane, t)
         cells = ops.plane_cells(mask[0], cell, mask[1])
@@ -273,3 +292,99 @@ def segmented_tissue_origins(region: torch.Tensor, tile=256, stride=None, min_fr
     origins, kept = _kept(counts, math.ceil(min_fraction * ph * pw), x0, y0, sx, sy)
     out = (origins,) + ((kept,) if return_counts else ()) + ((t,) if return_threshold else ()) + ((mask,) if return_mask else ())
     return out if len(out) > 1 else origins
+
+
+# ---- a slide that arrives in strips: the saturation plane is put together from the strips, everything behind it runs once on the slide's plane ----
+def plane_strip_plan(slide_hw, strips, down: int):
+    """Which strip gives which rows of the saturation plane of a slide of ``slide_hw`` = (Hs, Ws) pixels that arrives as full-width row strips. Host
+    arithmetic only. ``strips`` = [(y_k, H_k)] as in ``heatmap.strip_plan``: strip k holds the slide's rows y_k .. y_k + H_k, sorted, each abutting or
+    overlapping the one before, covering rows 0 .. Hs. One ``(p0, p1)`` per strip - the plane rows p0 <= r < p1 it gives; plane row r is made of the slide
+    rows r down .. (r + 1) down and of nothing else, and belongs to the FIRST strip that holds them all:
+
+        Hp = Hs // down,  p0_k = max(ceil(y_k / down), p1_{k-1}),  p1_k = max(p1_{k-1}, min((y_k + H_k) // down, Hp)),  p1_{-1} = 0
+
+    (a strip that has no row left to give is ``(p1_{k-1}, p1_{k-1})``). The strip's rows p0 down - y_k .. p1 down - y_k are the sub-region whose
+    ``ops.region_saturation`` IS rows p0 .. p1 of the slide's plane, byte for byte. Box rows below Hp down are dropped, as everywhere else.
+
+    ValueError, in ``heatmap.strip_plan``'s words, for strips that are not sorted, leave a gap or do not cover 0 .. Hs; for a plane row that lies whole
+    in no strip (its box rows straddle a seam: the strips must meet at multiples of ``down`` or overlap enough); and for a ``down`` outside 1 .. 32."""
+    hs, ws = slide_hw
+    if down not in ops.SEG_DOWNS:
+        raise ValueError(f"plane_strip_plan: down must be one of {ops.SEG_DOWNS}, got {down!r}")
+    strips = [(int(y), int(n)) for y, n in strips]
+    if not strips or strips[0][0] != 0 or strips[-1][0] + strips[-1][1] != hs:
+        raise ValueError(f"plane_strip_plan: the strips must cover rows 0 .. Hs = {hs}, got {strips!r}")
+    hp, plan, end, p1 = hs // down, [], 0, 0
+    for k, (y, n) in enumerate(strips):
+        if n < 1 or y + n <= end or (k and y <= strips[k - 1][0]):
+            raise ValueError(f"plane_strip_plan: strip {k} = (y, H) = {(y, n)} is empty or not sorted after the strips before it (rows up to {end})")
+        if y > end:
+            raise ValueError(f"plane_strip_plan: a gap between strip {k - 1}, which ends at row {end}, and strip {k}, which starts at row {y}")
+        first, last = -(-y // down), max(p1, min((y + n) // down, hp))
+        if last > p1 and first > p1:                                 # the strip has rows to give, and the next row to be given starts above it
+            raise ValueError(f"plane_strip_plan: plane row {p1} (slide rows {p1 * down} .. {(p1 + 1) * down}) lies whole in no strip: strip {k - 1} ends at "
+                             f"row {end} and strip {k} starts at row {y}; strips must meet at multiples of down = {down} or overlap by the rest of the box")
+        plan.append((min(max(first, p1), last), last))
+        end, p1 = y + n, last
+    return plan
+
+
+def _strip_shapes(name: str, strips, ws: int):
+    shapes = []
+    for k, (region, y) in enumerate(strips):
+        if not isinstance(region, torch.Tensor) or region.dim() != 3 or region.shape[1] != ws or region.shape[2] != 3:
+            got = tuple(region.shape) if isinstance(region, torch.Tensor) else type(region).__name__
+            raise ValueError(f"{name}: strip {k} must be a full-width uint8 [H_k,{ws},3] region, got {got}")
+        shapes.append((y, region.shape[0]))
+    return shapes
+
+
+def slide_saturation(strips, slide_hw, down: int, val_min: int = 0, batch: bool = True) -> torch.Tensor:
+    """The saturation plane of a slide of ``slide_hw`` = (Hs, Ws) pixels that arrives strip by strip: ONE contiguous uint8 [Hs // down, Ws // down] plane on
+    the device, byte for byte ``ops.region_saturation`` of the whole slide. ``strips`` is a sequence of ``(region, y_k)`` as in
+    ``eval.slide_attention_heatmap`` - a decoded uint8 [H_k,Ws,3] full-width strip on the device and the slide row of its first row. Each strip writes the
+    plane rows ``plane_strip_plan`` gives it (whose ValueErrors come before anything is launched), from the sub-region of its rows that holds their boxes.
+    ``batch=True``: one ``ops.regions_saturation`` call - one launch per ``ops.SAT_LIST_MAX`` strips; ``batch=False``: one
+    ``ops.region_saturation(..., out=view)`` call per strip. The bytes are the same. No synchronisation; every strip is read once."""
+    hs, ws = slide_hw
+    strips = list(strips)
+    plan = plane_strip_plan((hs, ws), _strip_shapes("slide_saturation", strips, ws), down)
+    if not isinstance(batch, bool):
+        raise ValueError(f"slide_saturation: batch must be a bool, got {batch!r}")
+    plane = torch.empty((hs // down, ws // down), dtype=torch.uint8, device=strips[0][0].device)
+    subs = [(region[p0 * down - y:p1 * down - y], plane[p0:p1]) for (region, y), (p0, p1) in zip(strips, plan) if p1 > p0]
+    if batch:
+        ops.regions_saturation([r for r, _ in subs], down, val_min, outs=[o for _, o in subs])
+    else:
+        for r, o in subs:
+            ops.region_saturation(r, down, val_min, out=o)
+    return plane
+
+
+def segment_tissue_strips(strips, slide_hw, down: int = 16, median: int = 7, sat_thresh=8, val_min: int = 0, close: int = 0, min_area: int = 0,
+                          min_hole: int = 0, return_threshold: bool = False):
+    """``segment_tissue`` of a slide that arrives strip by strip (``strips`` and ``slide_hw`` as in ``slide_saturation``): the same plane bytes and the
+    same ``t`` as on the whole slide, ``"otsu"`` included, with no seam - only the saturation plane reads the pixels, and that is put together from the
+    strips in one launch (``slide_saturation``); the median, the histogram, the closing and the component filters run once, on the slide's plane.
+    Launches and copies: ``segment_tissue``'s."""
+    _seg_args(down, median, sat_thresh, val_min)
+    active = _morph_args(close, min_area, min_hole)
+    return _segment_plane(slide_saturation(strips, slide_hw, down, val_min), median, sat_thresh, close, min_area, min_hole, active, return_threshold)
+
+
+def segmented_slide_origins(strips, slide_hw, tile=256, stride=None, min_fraction: float = 0.25, down: int = 16, median: int = 7, sat_thresh=8,
+                            val_min: int = 0, origin=(0, 0), return_counts: bool = False, return_threshold: bool = False, close: int = 0,
+                            min_area: int = 0, min_hole: int = 0, return_mask: bool = False):
+    """``segmented_tissue_origins`` of a slide that arrives strip by strip (``strips`` and ``slide_hw`` as in ``slide_saturation``): the result is what
+    that call gives on the whole slide - origins in SLIDE coordinates, row-major over the slide's lattice, and the counts, the threshold and the mask
+    plane of the whole slide where asked for. The strips are read once, in one launch, for the slide's saturation plane; everything behind it runs once
+    on that plane, so there is ONE read-back of ny nx int32 for the whole slide (and Otsu's 1 KB), not one per strip. The strips' ValueErrors
+    (``plane_strip_plan``) come before anything is launched, an empty lattice included."""
+    _min_fraction_arg(min_fraction)
+    _seg_args(down, median, sat_thresh, val_min)
+    active = _morph_args(close, min_area, min_hole)
+    hs, ws = slide_hw
+    strips = list(strips)
+    plane_strip_plan((hs, ws), _strip_shapes("segmented_slide_origins", strips, ws), down)
+    return _origins_on_plane(lambda: slide_saturation(strips, (hs, ws), down, val_min), hs, ws, tile, stride, min_fraction, down, median, sat_thresh,
+                             origin, return_counts, return_threshold, close, min_area, min_hole, active, return_mask)

@@ -13,8 +13,17 @@ tissue_bench.py (its slides, its rotation, its event timing, the arms alternated
     tissue_tile_fraction, same slides, same process, alternated; the margin the comparison allows is the spread between the two interleaved halves of the
     new selector's rounds plus two launches of a kernel with nothing to do (plane_cells on a 4 x 4 plane), measured here as well.
 
+  --strips (instead of the above; down = 1 and 16 unless --downs says otherwise): the saturation plane of that slide when it arrives in pieces
+  (ops.regions_saturation, sat_plane_list_kernel), same slides, same rotation, same event timing, the arms alternated in one process:
+      S0        ops.region_saturation on the whole slide into one plane
+      S4 / S16  4 full-width strips / a 4 x 4 grid of blocks, one ops.region_saturation call each into its view of one plane
+      L4 / L16  the same strips / blocks through ONE ops.regions_saturation call
+      C4 / C16  the library entry toad_regions_saturation_u8 on a host array built once (no Python per window)
+    every arm's plane is checked torch.equal to S0's before anything is timed. Pass: L4 < S4 and L16 < S16 by more than the spread between the two
+    interleaved halves of S0's rounds; C / S0 and L / S0 are reported without a bar.
+
 Prints one JSON line per result; --out FILE keeps them.
-usage: tissue_seg_bench.py [--seconds S] [--downs 1,4,16] [--out FILE]"""
+usage: tissue_seg_bench.py [--seconds S] [--downs 1,4,16] [--strips] [--out FILE]"""
 import argparse
 import json
 import os
@@ -28,7 +37,7 @@ import tools.ab.select_lib                     # noqa: E402,F401  (TOAD_HIP_LIB=
 
 from extract_u8_bench import alternate, median      # noqa: E402
 from tissue_bench import HR, WR, TILE, Rotating, make_slide      # noqa: E402
-from toad_amd import ops                                         # noqa: E402
+from toad_amd import _lib, ops                                   # noqa: E402
 from toad_amd.tissue import lattice_cell, tissue_tile_fraction   # noqa: E402
 
 K, SAT, VMIN = 7, 8, 0
@@ -121,15 +130,94 @@ def against_tissue_origins(slides, seconds, down=16):
                 new_within_old_plus_margin=bool(ms["new_selector"] <= ms["tissue_tile_fraction"] + margin))
 
 
+def pieces(slide, plane, down, ny, nx):
+    """The slide as ny x nx windows (cuts at multiples of 32, so every box lies in one window) and each window's rows and columns of `plane`."""
+    hs, ws = HR // ny, WR // nx
+    regions = [slide[j * hs:(j + 1) * hs, i * ws:(i + 1) * ws] for j in range(ny) for i in range(nx)]
+    outs = [plane[j * hs // down:(j + 1) * hs // down, i * ws // down:(i + 1) * ws // down] for j in range(ny) for i in range(nx)]
+    return regions, outs
+
+
+def strips_one_down(slides, down, seconds):
+    dev = slides[0].device
+    hp, wp = HR // down, WR // down
+    planes = [torch.empty((hp, wp), dtype=torch.uint8, device=dev) for _ in slides]
+    lib = _lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    grids = {"4": (4, 1), "16": (4, 4)}
+    work = {}
+    for name, (ny, nx) in grids.items():
+        per_slide = []
+        for s, p in zip(slides, planes):
+            regions, outs = pieces(s, p, down, ny, nx)
+            host = (_lib.ToadSatWindow * len(regions))(*(_lib.ToadSatWindow(r.data_ptr(), r.stride(0), r.shape[0], r.shape[1], o.data_ptr(), o.stride(0))
+                                                         for r, o in zip(regions, outs)))
+            per_slide.append((regions, outs, host, p))
+        work[name] = per_slide
+
+    def arm_s(w):
+        regions, outs, host, p = w
+        for r, o in zip(regions, outs):
+            ops.region_saturation(r, down, VMIN, out=o)
+        return p
+
+    def arm_l(w):
+        regions, outs, host, p = w
+        ops.regions_saturation(regions, down, VMIN, outs=outs)
+        return p
+
+    def arm_c(w):
+        regions, outs, host, p = w
+        _lib.check(lib.toad_regions_saturation_u8(host, len(regions), down, VMIN, stream), "toad_regions_saturation_u8")
+        return p
+
+    whole = list(zip(slides, planes))
+    same = True
+    for k, s in enumerate(slides):
+        want = ops.region_saturation(s, down, VMIN)
+        for name in grids:
+            for arm in (arm_s, arm_l, arm_c):
+                planes[k].fill_(0x7F)
+                same = same and bool(torch.equal(arm(work[name][k]), want))
+        del want
+    print(json.dumps(dict(kind="tissue_strips_progress", down=down, every_arm_equals_whole_slide=same)), flush=True)
+    arms = {"S0": Rotating(lambda w: ops.region_saturation(w[0], down, VMIN, out=w[1]), whole)}
+    for name in grids:
+        arms["S" + name] = Rotating(arm_s, work[name])
+        arms["L" + name] = Rotating(arm_l, work[name])
+        arms["C" + name] = Rotating(arm_c, work[name])
+    t, iters = alternate(arms, seconds, rounds=8)
+    ms = {k: median(v) for k, v in t.items()}
+    a = t["S0"]
+    a1, a2 = median(a[0::2]), median(a[1::2])
+    spread = abs(a1 - a2)
+    return dict(kind="tissue_strips", region=[HR, WR], down=down, plane=[hp, wp], region_bytes=3 * HR * WR, slides_rotated=len(slides), rounds=len(a),
+                iters_per_round=iters, ms={k: round(v, 5) for k, v in ms.items()}, ms_min={k: round(min(v), 5) for k, v in t.items()},
+                ms_max={k: round(max(v), 5) for k, v in t.items()}, s0_halves_ms=[round(a1, 5), round(a2, 5)], s0_spread_ms=round(spread, 5),
+                over_s0={k: round(ms[k] / ms["S0"], 4) for k in ms if k != "S0"},
+                l4_below_s4_beyond_spread=bool(ms["L4"] < ms["S4"] - spread), l16_below_s16_beyond_spread=bool(ms["L16"] < ms["S16"] - spread),
+                every_arm_equals_whole_slide=same)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=2.0)
-    ap.add_argument("--downs", default="1,4,16")
+    ap.add_argument("--downs", default="")
+    ap.add_argument("--strips", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     slides = [make_slide(s, dev) for s in range(4)]
-    downs = [int(d) for d in a.downs.split(",")]
+    downs = [int(d) for d in (a.downs or ("1,16" if a.strips else "1,4,16")).split(",")]
+    if a.strips:
+        res = []
+        for d in downs:
+            res.append(strips_one_down(slides, d, a.seconds))
+            print(json.dumps(res[-1]), flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(json.dumps(r) for r in res) + "\n")
+        return
     for d in downs:
         if TILE % (4 * d):
             raise SystemExit(f"down = {d}: the {TILE}-pixel tile is not a multiple of 4 * down")
