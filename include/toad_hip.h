@@ -408,6 +408,34 @@ int toad_resnet50_trunc_fwd_u8_region_box(const unsigned char *region, int64_t p
                                           const float *const *weights, const float *const *biases, float *feat, void *feat_f16, int B, int H, int W,
                                           int shrink, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- Tiles by origin from a LIST of regions: a slide as the decoder cut it, in strips or blocks (an additive extension of ABI 15) ----
+ * The three *_region_box_* calls above with the one region replaced by a list. The network scales every layer by an abs-max over the tiles of the call, so a
+ * tile's bag row depends on which tiles share its call: one call per strip gives other bits than one call on the whole slide. These calls take all strips at
+ * once - the same tiles in the same order give the same bits whatever the cut.
+ *   regions  HOST array of n descriptors, 1 <= n <= TOAD_TILE_REGIONS_MAX (TOAD_ESHAPE otherwise). Each is a region as above: its own device address, pitch
+ *            and extent; no alignment requirement. One image may appear several times, also as overlapping views. The descriptors travel by value in the
+ *            kernel argument (16 bytes each): no device table, no allocation, no synchronisation; the array is not referenced after the call returns.
+ *   tiles    DEVICE int32 [B][3], 4-byte aligned: (x, y, k) - the top-left pixel of tile b in the coordinates of region k. Any order, duplicates and overlaps
+ *            are allowed. 0 <= k < n and the tile (shrink H x shrink W at (x, y)) inside region k are THE CALLER'S DUTY, as for `origins`; the Python layer
+ *            (toad_amd.ops.check_region_origins) takes the triples on the host and checks every one.
+ * Each call is BITWISE its single-region twin - hence its tile twin - on the same tiles: padding is the tile's, no byte outside a tile (footprint) is read.
+ * Refusals, on the host, in this order, and nothing is launched unless all pass: a null pointer; n out of range; shrink; region by region everything the
+ * twin checks of its region (shape, pitch >= 3 Wr, the footprint fits, shrink H * pitch < 2^31) - the first failing region wins and the message names it
+ * ("region k: ..."); `tiles` not 4-byte aligned; then what the twin checks after its region (norm, B and the tile shape, 16-byte alignments, workspace). */
+typedef struct { const unsigned char *region; int64_t pitch; int Hr, Wr; } ToadTileRegion;   /* 24 bytes */
+#define TOAD_TILE_REGIONS_MAX 128
+/* toad_stem_pool_region_box_u8 for a list of regions (W == 256, H % 4 == 0): r[k] is one scalar load from the kernel argument per tile of a workgroup. */
+int toad_stem_pool_regions_u8(const ToadTileRegion *regions /* HOST */, int n, const int *tiles /* DEVICE int32 [B][3] = (x, y, k) */,
+                              const float *norm, const float *Wf, const float *bias, float *Yp, int B, int H, int W, int shrink,
+                              void *ws, size_t ws_bytes, void *stream);
+/* toad_tiles_u8_region_box_to_nchw_f32 for a list of regions: any B, H, W >= 1 with H*W < 2^31. */
+int toad_tiles_u8_regions_to_nchw_f32(const ToadTileRegion *regions, int n, const int *tiles, const float *norm, float *out,
+                                      int B, int H, int W, int shrink, void *stream);
+/* toad_resnet50_trunc_fwd_u8_region_box for a list of regions. Workspace: toad_resnet50_trunc_u8_ws_bytes(B, H, W), unchanged. */
+int toad_resnet50_trunc_fwd_u8_regions(const ToadTileRegion *regions, int n, const int *tiles, const float *norm,
+                                       const float *const *weights, const float *const *biases, float *feat, void *feat_f16,
+                                       int B, int H, int W, int shrink, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- Tissue selection: which tiles of a decoded region to read (an additive extension of ABI 15; the version number does not change) ----
  * The reference tree has no patching script: its bags come from CLAM's, which thresholds HSV saturation and keeps the tiles that hold tissue. The two
  * calls below produce the per-tile tissue-pixel counts from which the caller forms the `origins` of the region calls above; csrc/tissue.hip.

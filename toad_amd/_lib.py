@@ -34,6 +34,11 @@ class ToadSatWindow(ctypes.Structure):
     _fields_ = [("region", c_void_p), ("pitch", c_int64), ("Hr", c_int), ("Wr", c_int), ("plane", c_void_p), ("plane_pitch", c_int64)]
 
 
+class ToadTileRegion(ctypes.Structure):
+    """One region of the HOST array of the toad_*_regions_* extractor calls (include/toad_hip.h): region is a device address. 24 bytes."""
+    _fields_ = [("region", c_void_p), ("pitch", c_int64), ("Hr", c_int), ("Wr", c_int)]
+
+
 class ToadWgradJob(ctypes.Structure):
     """One job of toad_linear_wgrad_batch_f32's HOST array (include/toad_hip.h): every pointer is a device address."""
     _fields_ = [("dY", c_void_p), ("dy_amax", c_void_p), ("X", c_void_p), ("x_amax", c_void_p), ("dW", c_void_p), ("db", c_void_p),
@@ -123,6 +128,10 @@ SIGNATURES = {
     "toad_tiles_u8_region_box_to_nchw_f32": (I, [P, I64, I, I, P, P, P, I, I, I, I, P]),
     "toad_stem_pool_region_box_u8": (I, [P, I64, I, I, P, P, P, P, P, I, I, I, I, P, SZ, P]),
     "toad_resnet50_trunc_fwd_u8_region_box": (I, [P, I64, I, I, P, P, P, P, P, P, I, I, I, I, P, SZ, P]),
+    # ... and the same three for a list of regions (regions: a HOST array of n ToadTileRegion; tiles: device int32 [B][3] = (x, y, k)): additive to ABI 15
+    "toad_tiles_u8_regions_to_nchw_f32": (I, [ctypes.POINTER(ToadTileRegion), I, P, P, P, I, I, I, I, P]),
+    "toad_stem_pool_regions_u8": (I, [ctypes.POINTER(ToadTileRegion), I, P, P, P, P, P, I, I, I, I, P, SZ, P]),
+    "toad_resnet50_trunc_fwd_u8_regions": (I, [ctypes.POINTER(ToadTileRegion), I, P, P, P, P, P, P, I, I, I, I, P, SZ, P]),
     # ... and the stage in front of them, tissue-pixel counts per cell and per lattice tile of a region: additive to ABI 15
     "toad_region_tissue_cells_u8": (I, [P, I64, I, I, I, I, I, P, P]),
     "toad_tissue_tile_counts": (I, [P, I, I, I, I, I, I, I, I, I, I, I, P, P]),

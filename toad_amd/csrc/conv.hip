@@ -185,11 +185,19 @@ __global__ __launch_bounds__(256) void avgpool_nhwc_kernel(const float *__restri
 // SHRINK == 2 (REGION only): tile b is the (2 H, 2 W) footprint at its origin and pixel p of the H x W tile the integer mean of its 2 x 2 box,
 // (sum + 2) >> 2 - the tile toad::stem_halo_pool_kernel<SH_U8_REGION_BOX2> sees - read byte by byte (this is the staged route, not the hot one); the fma and
 // the stores are the tile form's.
+// LIST (REGION only): the tiles are read from a list of regions (src is not used): rg.tiles = int32 [B][3] = (x, y, k), the top-left pixel of tile b in the
+// coordinates of region k, and rg.r[k] = {base, pitch} of that region, by value in the kernel argument like the stem's (stem_halo.inc). Here b differs from
+// thread to thread, so the descriptor is read per lane; from the tile's base on the code is the region form's.
 struct TilesNoRegion {};
 struct TilesRegionArg { int64_t pitch; const int *origins; uint32_t W; };
-template <bool REGION, int SHRINK = 1>
+struct TilesRegionsArg { const int *tiles; uint32_t W; StemRegionDesc r[STEM_REGIONS_MAX]; };
+template <bool REGION, bool LIST> struct TilesLastArg { typedef TilesNoRegion type; };
+template <> struct TilesLastArg<true, false> { typedef TilesRegionArg type; };
+template <> struct TilesLastArg<true, true> { typedef TilesRegionsArg type; };
+template <bool REGION, int SHRINK = 1, bool LIST = false>
 __global__ __launch_bounds__(256) void tiles_u8_nhwc_to_nchw_kernel(const unsigned char *__restrict__ src, float *__restrict__ out, uint64_t B, uint32_t HW,
-                                                                    StemNorm nrm, typename std::conditional<REGION, TilesRegionArg, TilesNoRegion>::type rg) {
+                                                                    StemNorm nrm, typename TilesLastArg<REGION, LIST>::type rg) {
+    static_assert(REGION || !LIST, "a list of regions is a region form");
     const uint32_t gpi = (HW + 3) >> 2;                                   // groups per image
     const uint64_t total = B * gpi;
     const bool vec = (HW & 3u) == 0;
@@ -198,10 +206,19 @@ __global__ __launch_bounds__(256) void tiles_u8_nhwc_to_nchw_kernel(const unsign
         const uint32_t p0 = (uint32_t)(i - b * gpi) * 4, np = HW - p0 < 4 ? HW - p0 : 4;
         const unsigned char *s, *tile = nullptr;
         bool one_run = true;                                              // the group's 3 np bytes are contiguous
+        int64_t pitch = 0;                                                // the row pitch of the tile's region
         if constexpr (REGION) {
             const uint32_t y0 = p0 / rg.W, x0 = p0 - y0 * rg.W;
-            tile = src + (uint64_t)(uint32_t)rg.origins[2 * b + 1] * (uint64_t)rg.pitch + (uint64_t)(uint32_t)rg.origins[2 * b] * 3;
-            s = tile + (uint64_t)y0 * (uint64_t)rg.pitch + x0 * 3;
+            if constexpr (LIST) {
+                const int *t3 = rg.tiles + 3 * b;
+                const StemRegionDesc &d = rg.r[t3[2]];
+                pitch = d.pitch;
+                tile = d.base + (uint64_t)(uint32_t)t3[1] * (uint64_t)pitch + (uint64_t)(uint32_t)t3[0] * 3;
+            } else {
+                pitch = rg.pitch;
+                tile = src + (uint64_t)(uint32_t)rg.origins[2 * b + 1] * (uint64_t)pitch + (uint64_t)(uint32_t)rg.origins[2 * b] * 3;
+            }
+            s = tile + (uint64_t)y0 * (uint64_t)pitch + x0 * 3;
             one_run = x0 + np <= rg.W;
         } else {
             s = src + (b * HW + p0) * 3;
@@ -212,17 +229,17 @@ __global__ __launch_bounds__(256) void tiles_u8_nhwc_to_nchw_kernel(const unsign
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const uint32_t pe = p0 + e, ye = pe / rg.W, xe = pe - ye * rg.W;
-                const unsigned char *q = tile + (uint64_t)(2 * ye) * (uint64_t)rg.pitch + xe * 6;
+                const unsigned char *q = tile + (uint64_t)(2 * ye) * (uint64_t)pitch + xe * 6;
 #pragma unroll
                 for (int c = 0; c < 3; ++c)
-                    u[3 * e + c] = (uint32_t)e < np ? ((unsigned)q[c] + q[3 + c] + q[rg.pitch + c] + q[rg.pitch + 3 + c] + 2u) >> 2 : 0u;
+                    u[3 * e + c] = (uint32_t)e < np ? ((unsigned)q[c] + q[3 + c] + q[pitch + c] + q[pitch + 3 + c] + 2u) >> 2 : 0u;
             }
         } else if (!one_run) {
             if constexpr (REGION) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const uint32_t pe = p0 + e, ye = pe / rg.W, xe = pe - ye * rg.W;
-                    const unsigned char *q = tile + (uint64_t)ye * (uint64_t)rg.pitch + xe * 3;
+                    const unsigned char *q = tile + (uint64_t)ye * (uint64_t)pitch + xe * 3;
 #pragma unroll
                     for (int c = 0; c < 3; ++c) u[3 * e + c] = (uint32_t)e < np ? q[c] : 0u;
                 }
@@ -271,6 +288,8 @@ static void ext_cfg() {
         TOAD_ATTR(stem_halo_pool_kernel<SH_U8>, SH_SMEM);
         TOAD_ATTR(stem_halo_pool_kernel<SH_U8_REGION>, SH_SMEM);
         TOAD_ATTR(stem_halo_pool_kernel<SH_U8_REGION_BOX2>, SH_SMEM);
+        TOAD_ATTR(stem_halo_pool_kernel<SH_U8_REGIONS>, SH_SMEM);
+        TOAD_ATTR(stem_halo_pool_kernel<SH_U8_REGIONS_BOX2>, SH_SMEM);
         TOAD_ATTR(conv3x3_h2_halo_kernel<2>, 160 * 1024);
         TOAD_ATTR(conv3x3_h2_halo_kernel<4>, 160 * 1024);
 #undef TOAD_ATTR
@@ -462,12 +481,14 @@ static int stem_pool_from_tiles(const void *X, bool u8, const float *norm, const
                                 size_t ws_bytes, hipStream_t st, const char *what, const RegionSrc *rg = nullptr, int shrink = 1) {
     if (rg) X = rg->region;
     if (!X || (u8 && !norm) || !Wf || !Yp || !ws || (rg && !rg->origins)) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    const bool list = rg && rg->list;                                // a list of regions is checked in front of B and the tile shape (include/toad_hip.h)
+    if (list) { if (int rc = check_region_u8(*rg, H, W, what, shrink)) return rc; }
     if (B <= 0 || !stem_nchw_pool_ok(H, W)) {
         set_error("%s: needs W = 256 and H %% 4 == 0 (other tiles: %stoad_stem_s2d_nchw_f32 + toad_stem_conv_s2d_f32 + toad_maxpool3x3s2_nhwc_f32)", what,
-                  rg ? "toad_tiles_u8_region_to_nchw_f32 + " : u8 ? "toad_tiles_u8_nhwc_to_nchw_f32 + " : "");
+                  list ? "toad_tiles_u8_regions_to_nchw_f32 + " : rg ? "toad_tiles_u8_region_to_nchw_f32 + " : u8 ? "toad_tiles_u8_nhwc_to_nchw_f32 + " : "");
         return TOAD_ESHAPE;
     }
-    if (rg) { if (int rc = check_region_u8(*rg, H, W, what, shrink)) return rc; }
+    if (rg && !list) { if (int rc = check_region_u8(*rg, H, W, what, shrink)) return rc; }
     const int64_t M = (int64_t)B * (H / 2) * 128;
     if (M >= (1ll << 31)) { set_error("%s: batch too large for 32-bit offsets (split it)", what); return TOAD_ESHAPE; }
     if (u8) { if (int rc = check_norm_u8(norm, what)) return rc; }
@@ -485,7 +506,17 @@ static int stem_pool_from_tiles(const void *X, bool u8, const float *norm, const
     if (u8) {
         StemNorm nrm;
         for (int c = 0; c < 3; ++c) { nrm.a[c] = norm[c]; nrm.b[c] = norm[3 + c]; }
-        if (rg && shrink == 2)
+        if (list) {
+            StemRegionsArg la;
+            la.nrm = nrm; la.tiles = rg->origins;
+            fill_region_descs(*rg, la.r);
+            if (shrink == 2)
+                hipLaunchKernelGGL(stem_halo_pool_kernel<SH_U8_REGIONS_BOX2>, grid, dim3(256), SH_SMEM, st, static_cast<const unsigned char *>(nullptr), planes, binv, bias, Yp, B, H,
+                                   y_gmax, tiles, la);
+            else
+                hipLaunchKernelGGL(stem_halo_pool_kernel<SH_U8_REGIONS>, grid, dim3(256), SH_SMEM, st, static_cast<const unsigned char *>(nullptr), planes, binv, bias, Yp, B, H,
+                                   y_gmax, tiles, la);
+        } else if (rg && shrink == 2)
             hipLaunchKernelGGL(stem_halo_pool_kernel<SH_U8_REGION_BOX2>, grid, dim3(256), SH_SMEM, st, rg->region, planes, binv, bias, Yp, B, H, y_gmax, tiles,
                                StemRegionArg{nrm, (int)rg->pitch, rg->origins});
         else if (rg)
@@ -605,6 +636,12 @@ extern "C" int toad_stem_pool_region_box_u8(const unsigned char *region, int64_t
     return ext_stem_region_u8_pool(RegionSrc{region, pitch, Hr, Wr, origins}, norm, Wf, bias, Yp, nullptr, B, H, W, ws, ws_bytes, (hipStream_t)stream,
                                    "toad_stem_pool_region_box_u8", shrink);
 }
+// toad_stem_pool_region_box_u8 for a list of regions (stem_u8.h: check_regions_u8)
+extern "C" int toad_stem_pool_regions_u8(const ToadTileRegion *regions, int n, const int *tiles, const float *norm, const float *Wf, const float *bias, float *Yp,
+                                         int B, int H, int W, int shrink, void *ws, size_t ws_bytes, void *stream) {
+    return ext_stem_region_u8_pool(region_list_src(regions, n, tiles), norm, Wf, bias, Yp, nullptr, B, H, W, ws, ws_bytes, (hipStream_t)stream,
+                                   "toad_stem_pool_regions_u8", shrink);
+}
 
 // ---- the gathers, pools and tile converters as entry points --------------------------------------------------------
 extern "C" int toad_im2col_nhwc_f32(const float *X, float *cols, int B, int H, int W, int C, int kh, int kw, int stride,
@@ -673,7 +710,15 @@ static int launch_tiles_to_nchw(const unsigned char *src, const RegionSrc *rg, i
     const dim3 grid(grid_for((uint64_t)B * ((HW + 3) / 4)));
     if (!rg)
         hipLaunchKernelGGL(tiles_u8_nhwc_to_nchw_kernel<false>, grid, dim3(256), 0, st, src, out, (uint64_t)B, HW, nrm, TilesNoRegion{});
-    else if (shrink == 2)
+    else if (rg->list) {
+        TilesRegionsArg la;
+        la.tiles = rg->origins; la.W = (uint32_t)W;
+        fill_region_descs(*rg, la.r);
+        if (shrink == 2)
+            hipLaunchKernelGGL((tiles_u8_nhwc_to_nchw_kernel<true, 2, true>), grid, dim3(256), 0, st, static_cast<const unsigned char *>(nullptr), out, (uint64_t)B, HW, nrm, la);
+        else
+            hipLaunchKernelGGL((tiles_u8_nhwc_to_nchw_kernel<true, 1, true>), grid, dim3(256), 0, st, static_cast<const unsigned char *>(nullptr), out, (uint64_t)B, HW, nrm, la);
+    } else if (shrink == 2)
         hipLaunchKernelGGL((tiles_u8_nhwc_to_nchw_kernel<true, 2>), grid, dim3(256), 0, st, src, out, (uint64_t)B, HW, nrm, TilesRegionArg{rg->pitch, rg->origins, (uint32_t)W});
     else
         hipLaunchKernelGGL(tiles_u8_nhwc_to_nchw_kernel<true>, grid, dim3(256), 0, st, src, out, (uint64_t)B, HW, nrm, TilesRegionArg{rg->pitch, rg->origins, (uint32_t)W});
@@ -705,6 +750,11 @@ extern "C" int toad_tiles_u8_region_box_to_nchw_f32(const unsigned char *region,
 extern "C" int toad_tiles_u8_region_to_nchw_f32(const unsigned char *region, int64_t pitch, int Hr, int Wr, const int *origins, const float *norm, float *out, int B,
                                                 int H, int W, void *stream) {
     return region_to_nchw(RegionSrc{region, pitch, Hr, Wr, origins}, norm, out, B, H, W, (hipStream_t)stream, "toad_tiles_u8_region_to_nchw_f32");
+}
+// toad_tiles_u8_region_box_to_nchw_f32 for a list of regions
+extern "C" int toad_tiles_u8_regions_to_nchw_f32(const ToadTileRegion *regions, int n, const int *tiles, const float *norm, float *out, int B, int H, int W,
+                                                 int shrink, void *stream) {
+    return region_to_nchw(region_list_src(regions, n, tiles), norm, out, B, H, W, (hipStream_t)stream, "toad_tiles_u8_regions_to_nchw_f32", shrink);
 }
 
 extern "C" size_t toad_resnet50_trunc_ws_bytes(int B, int H, int W) {
@@ -843,9 +893,15 @@ static int trunc_entry(bool u8, const float *tiles_nchw, const unsigned char *ti
         set_error(u8 ? "%s: null pointer (feat and feat_f16 may not both be NULL)" : "%s: null pointer", what);
         return TOAD_EINVAL;
     }
+    const bool list = rg && rg->list;                                // a list of regions is checked in front of the plan (include/toad_hip.h)
+    RegionSrc seen{};                                                // ... once: the stem / the converter behind trunc_fwd take it as checked
+    if (list) {
+        TOAD_TRY(check_region_u8(*rg, H, W, what, shrink));
+        seen = *rg; seen.checked = true; rg = &seen;
+    }
     NetPlan p;
     if (!make_plan(B, H, W, p)) { set_error("%s: bad shape B=%d H=%d W=%d", what, B, H, W); return TOAD_ESHAPE; }
-    if (rg) TOAD_TRY(check_region_u8(*rg, H, W, what, shrink));
+    if (rg && !list) TOAD_TRY(check_region_u8(*rg, H, W, what, shrink));
     if (u8) TOAD_TRY(check_norm_u8(norm, what));
     if (ws_bytes < (u8 ? toad_resnet50_trunc_u8_ws_bytes(B, H, W) : toad_resnet50_trunc_ws_bytes(B, H, W))) { set_error("%s: workspace too small", what); return TOAD_EWORKSPACE; }
     if (!aligned16(ws) || (feat && !aligned16(feat)) || (feat16 && !aligned16(feat16))) {
@@ -883,4 +939,11 @@ extern "C" int toad_resnet50_trunc_fwd_u8_region_box(const unsigned char *region
                                                       int shrink, void *ws, size_t ws_bytes, void *stream) {
     return trunc_fwd_region(region, pitch, Hr, Wr, origins, norm, weights, biases, feat, feat_f16, B, H, W, shrink, ws, ws_bytes, stream,
                             "toad_resnet50_trunc_fwd_u8_region_box");
+}
+// toad_resnet50_trunc_fwd_u8_region_box for a list of regions: the same network behind the list forms of the stem / the converter
+extern "C" int toad_resnet50_trunc_fwd_u8_regions(const ToadTileRegion *regions, int n, const int *tiles, const float *norm, const float *const *weights,
+                                                   const float *const *biases, float *feat, void *feat_f16, int B, int H, int W, int shrink, void *ws,
+                                                   size_t ws_bytes, void *stream) {
+    const RegionSrc rg = region_list_src(regions, n, tiles);
+    return trunc_entry(true, nullptr, rg.region, &rg, shrink, norm, weights, biases, feat, feat_f16, B, H, W, ws, ws_bytes, stream, "toad_resnet50_trunc_fwd_u8_regions");
 }

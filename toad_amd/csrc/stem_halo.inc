@@ -68,26 +68,39 @@ constexpr int SH_TASKS = (SH_ROWS * SH_WS + 255) / 256;      // space-to-depth p
 //     uint8 form on those box-filtered tiles. The edge predicate stays the TILE's, in shrunk coordinates (padding is the tile's; no byte outside a footprint
 //     is read); the in-footprint offset 2 iy pitch + 6 ix stays 32-bit (the launcher refuses 2 H pitch >= 2^31). Not built: factors above 2, other filters,
 //     and a shrink on the tile forms.
+//   uint8 region LIST (stem_halo_pool_kernel<SH_U8_REGIONS>, <SH_U8_REGIONS_BOX2>): the slide as the decoder cut it, up to STEM_REGIONS_MAX regions of their own
+//     base address and pitch, and per tile a triple (x_b, y_b, k_b) in an int32 array [B][3] on the device: the tile's top-left pixel in the coordinates of
+//     region k_b. The descriptors {base, pitch} travel BY VALUE in the kernel argument (2 KB; no device table, no allocation): b is uniform over the
+//     workgroup, so the triple is three readfirstlane'd loads and r[k_b] a scalar load from the kernarg segment at a scalar index - no search, no scratch.
+//     The tile's base base_k + y_b pitch_k + 3 x_b is the 64-bit scalar of the region form, the in-tile offset stays 32-bit with pitch_k (the launcher
+//     refuses shrink H pitch_k >= 2^31 for every k). Every call of the loader takes the descriptor of ITS tile - the carry item of a workgroup's range (the
+//     tile above it) may lie in another region than the range's first tile. From the tile's base on it is the region form's code, the box form's for
+//     shrink = 2: the TILE's edge predicate, no byte outside a tile (footprint), plain loads. That every triple has 0 <= k_b < n and keeps its tile inside
+//     region k_b is the caller's duty, as for the origins.
 constexpr unsigned SH_U8_OUTSIDE = 0xFFFF0000u;              // upper half of a row's 2-byte word: the pixel pair lies outside the image
 typedef unsigned sh_u32_a2 __attribute__((aligned(2)));      // a 4-byte load from a 2-byte aligned address
-constexpr int SH_F32 = 0, SH_U8 = 1, SH_U8_REGION = 2, SH_U8_REGION_BOX2 = 3;   // the FORM parameter of the kernel
+constexpr int SH_F32 = 0, SH_U8 = 1, SH_U8_REGION = 2, SH_U8_REGION_BOX2 = 3, SH_U8_REGIONS = 4, SH_U8_REGIONS_BOX2 = 5;   // the FORM parameter of the kernel
 
 // (the constants are the LAST kernel argument, an empty struct in the fp32 form: that form's argument layout, registers and code are the ones it had as a
 //  plain kernel - 64 SGPRs, 242 VGPRs, no scratch; the uint8 form: 68 SGPRs, 218 VGPRs, no scratch; the region form, whose last argument also carries the
 //  pitch and the origins: 70 SGPRs, 217 VGPRs, no scratch; the box form, same arguments: 88 SGPRs, 220 VGPRs, no scratch; all 81,728 B of LDS, two workgroups
-//  per CU)
+//  per CU; the list forms, whose last argument carries the triples and the 128 descriptors: profiles/extract_regions_isa.md)
 struct StemNoNorm {};
 struct StemRegionArg { StemNorm nrm; int pitch; const int *origins; };      // origins: int32 [B][2] = (x, y) of each tile's top-left pixel
+struct StemRegionsArg { StemNorm nrm; const int *tiles; StemRegionDesc r[STEM_REGIONS_MAX]; };      // tiles: int32 [B][3] = (x, y, k), in region k's coordinates
 template <int FORM> struct StemLastArg { typedef StemNoNorm type; };
 template <> struct StemLastArg<SH_U8> { typedef StemNorm type; };
 template <> struct StemLastArg<SH_U8_REGION> { typedef StemRegionArg type; };
 template <> struct StemLastArg<SH_U8_REGION_BOX2> { typedef StemRegionArg type; };
+template <> struct StemLastArg<SH_U8_REGIONS> { typedef StemRegionsArg type; };
+template <> struct StemLastArg<SH_U8_REGIONS_BOX2> { typedef StemRegionsArg type; };
 template <int FORM>
 __global__ __launch_bounds__(256, 2) void stem_halo_pool_kernel(const typename std::conditional<FORM != SH_F32, unsigned char, float>::type *__restrict__ Xv,
                                                                 const unsigned short *__restrict__ Bp, const float *__restrict__ binv,
                                                                 const float *__restrict__ bias, float *Yp, int B, int H, float *y_gmax, int tiles,
                                                                 typename StemLastArg<FORM>::type nrm_arg) {
-    constexpr bool U8 = FORM != SH_F32, BOX2 = FORM == SH_U8_REGION_BOX2, REGION = FORM == SH_U8_REGION || BOX2;
+    constexpr bool U8 = FORM != SH_F32, LIST = FORM == SH_U8_REGIONS || FORM == SH_U8_REGIONS_BOX2, BOX2 = FORM == SH_U8_REGION_BOX2 || FORM == SH_U8_REGIONS_BOX2,
+                   REGION = FORM == SH_U8_REGION || LIST || BOX2;
     using Cfg = StreamCfg<2, 2>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     char *lds = reinterpret_cast<char *>(smem);
@@ -125,9 +138,19 @@ __global__ __launch_bounds__(256, 2) void stem_halo_pool_kernel(const typename s
     auto load_window = [&](int q, Raw &raw) __attribute__((always_inline)) {
         const int b = q / tpi, t = q - b * tpi;
         if constexpr (REGION) {
-            const int pitch = nrm_arg.pitch;
-            const int x_b = __builtin_amdgcn_readfirstlane(nrm_arg.origins[2 * b]), y_b = __builtin_amdgcn_readfirstlane(nrm_arg.origins[2 * b + 1]);
-            const unsigned char *img8 = X8 + ((int64_t)y_b * pitch + (int64_t)x_b * 3);
+            int pitch, x_b, y_b;
+            const unsigned char *reg8;
+            if constexpr (LIST) {                                // the tile's own region: three uniform loads, then one descriptor from the kernarg segment at a scalar index
+                x_b = __builtin_amdgcn_readfirstlane(nrm_arg.tiles[3 * b]), y_b = __builtin_amdgcn_readfirstlane(nrm_arg.tiles[3 * b + 1]);
+                const int k_b = __builtin_amdgcn_readfirstlane(nrm_arg.tiles[3 * b + 2]);
+                pitch = nrm_arg.r[k_b].pitch;
+                reg8 = nrm_arg.r[k_b].base;
+            } else {
+                pitch = nrm_arg.pitch;
+                x_b = __builtin_amdgcn_readfirstlane(nrm_arg.origins[2 * b]), y_b = __builtin_amdgcn_readfirstlane(nrm_arg.origins[2 * b + 1]);
+                reg8 = X8;
+            }
+            const unsigned char *img8 = reg8 + ((int64_t)y_b * pitch + (int64_t)x_b * 3);
 #pragma unroll
             for (int k = 0; k < SH_TASKS; ++k) {
                 int tc = tk[k];

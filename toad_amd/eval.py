@@ -335,10 +335,25 @@ def region_tissue_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, region
                                              mask=mask, thresh=thresh, binarize=binarize, blur=blur)
 
 
+def strip_triples(parts):
+    """The arguments of ONE ``forward_u8_regions`` call for the strips that own tiles: ``parts`` = [(region, local origins [B_k,2] = (x, y) in the strip's
+    coordinates), ...], only strips with at least one tile, in the walk's order -> (regions, triples int64 [sum B_k, 3] = (x, y, k)), k the position in
+    ``parts``. A strip without a tile must not be in the list: the call requires a tile to fit every region, and a remainder strip may be shorter."""
+    regions, triples = [], []
+    for k, (region, local) in enumerate(parts):
+        local = np.asarray(local, dtype=np.int64)
+        if local.ndim != 2 or local.shape[1] != 2 or local.shape[0] == 0:
+            raise ValueError(f"strip_triples: part {k} must bring [B,2] origins with B >= 1, got shape {local.shape}")
+        regions.append(region)
+        triples.append(np.concatenate([local, np.full((local.shape[0], 1), k, dtype=np.int64)], axis=1))
+    return regions, (np.concatenate(triples, axis=0) if triples else np.zeros((0, 3), dtype=np.int64))
+
+
 def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_hw, tile=256, stride=None, origin=(0, 0), origins=None,
                             min_fraction: float = 0.25, sat_thresh: int = 8, val_min: int = 0, bag_dtype: torch.dtype = torch.float16, alpha=102,
                             down: int = 1, lut=None, out=None, smooth: bool = False, mask=None, thresh=None, binarize: bool = False, blur=False, shrink=1,
-                            batch_render: bool = False, batch_levels: bool = False, segment: Optional[dict] = None, tissue_mask: bool = False):
+                            batch_render: bool = False, batch_levels: bool = False, segment: Optional[dict] = None, tissue_mask: bool = False,
+                            batch_extract: bool = False):
     """``(origins, scores, canvas)`` of a slide of ``slide_hw`` = (Hs, Ws) pixels that arrives from the decoder strip by strip: what
     ``region_tissue_attention_heatmap`` gives for one region, with no seam where two strips meet. ``strips`` is a sequence of ``(region, y_k)`` - a
     decoded uint8 [H_k,Ws,3] full-width strip on the device and the slide row of its first row - sorted, each abutting or overlapping the one before,
@@ -382,6 +397,17 @@ def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_
     together with ``mask``, the multiple rule, and what ``plane_strip_plan`` and the segmented lattice rule (multiples of 4 * segment ``down``) refuse.
     With ``segment=None`` and ``tissue_mask=False`` every path, message and byte is what it was.
 
+    ``batch_extract=True`` keeps pass 1's selection (per strip with ``tissue_origins``, the caller's ``origins=``, or ``segment=``) but takes the bag from
+    ONE ``extractor.forward_u8_regions`` call: the strips' tiles in the order above, as triples (x, y local to the strip, k) - ``strip_triples``. Only the
+    strips that own a tile are regions of that call, numbered k = 0, 1, ... in the strips' order: a strip that owns no lattice row or no tissue tile - a
+    last strip shorter than the tile, which only renders the slide's last rows - is skipped exactly as the per-strip walk skips it (the list call
+    requires a tile to fit every region it is given). The extractor scales every layer by an abs-max over the tiles of a call, so with per-strip calls a bag row depends on how the decoder cut the
+    slide; with the one call - chunked like the whole-slide call - it does not: with the same tiles ``scores`` is ``torch.equal`` to
+    ``attention_heatmap_scores(model, extractor.forward_u8_region(whole_slide, origins, ...), percentile=True)``. More strips than
+    ``ops.TILE_REGIONS_MAX`` is a ValueError before anything is launched - the limit counts ALL strips given, since which of them own a tile is known
+    only after the selection has run on the device - and a non-bool too. Independent of ``batch_render`` / ``batch_levels``; with
+    ``False`` every path, message and byte is what it was.
+
     Not done here: blocks that are not full-width strips (``heatmap.window_canvas`` renders any window and ``ops.regions_saturation`` takes any
     windows; this walk does not), and the "not done" list of ``region_tissue_attention_heatmap`` except seams."""
     from .heatmap import slide_cells, strip_plan, window_canvas, window_pyramid, windows_canvas, windows_pyramid
@@ -397,6 +423,13 @@ def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_
         raise ValueError(f"slide_attention_heatmap: batch_render must be a bool, got {batch_render!r}")
     if not isinstance(batch_levels, bool):
         raise ValueError(f"slide_attention_heatmap: batch_levels must be a bool, got {batch_levels!r}")
+    if not isinstance(batch_extract, bool):
+        raise ValueError(f"slide_attention_heatmap: batch_extract must be a bool, got {batch_extract!r}")
+    if batch_extract:
+        from .ops import TILE_REGIONS_MAX
+        if len(strips) > TILE_REGIONS_MAX:
+            raise ValueError(f"slide_attention_heatmap: batch_extract=True takes at most {TILE_REGIONS_MAX} strips (ops.TILE_REGIONS_MAX, the regions of one "
+                             f"extractor call), got {len(strips)}")
     levels = None                                                   # a sequence of levels: pass 2 renders them all in one walk over the strips
     if batch_levels and not isinstance(down, (tuple, list)):
         raise ValueError("slide_attention_heatmap: batch_levels=True takes a sequence of levels, not one down (one canvas for a list of windows: "
@@ -461,7 +494,7 @@ def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_
         if off.any():                                                # (outside the lattice along x, or given twice: slide_cells, after the first pass)
             bad = given[off][0]
             raise ValueError(f"slide_attention_heatmap: origin (x={int(bad[0])}, y={int(bad[1])}) is off the lattice or in none of the slide's lattice rows")
-    kept, bags = [], []
+    kept, bags, parts = [], [], []
     for (region, y), p in zip(strips, plan):                        # pass 1: the tiles each strip owns -> bag rows
         j0, j1 = p["rows"]
         if j1 == j0:
@@ -473,7 +506,13 @@ def slide_attention_heatmap(extractor, model: TOAD_fc_mtl_concat, strips, slide_
         if local.shape[0] == 0:
             continue
         kept.append(local + np.array([0, y], dtype=np.int64))
-        bags.append(extractor.forward_u8_region(region, local, tile=(h, w), out_dtype=bag_dtype, shrink=shrink))
+        if batch_extract:                                           # the strip's tiles go into the one call behind the loop
+            parts.append((region, local))
+        else:
+            bags.append(extractor.forward_u8_region(region, local, tile=(h, w), out_dtype=bag_dtype, shrink=shrink))
+    if parts:                                                       # ONE extractor call: its abs-max scopes are those of the whole slide's call
+        regions, triples = strip_triples(parts)
+        bags.append(extractor.forward_u8_regions(regions, triples, tile=(h, w), out_dtype=bag_dtype, shrink=shrink))
     if kept:
         found = np.concatenate(kept, axis=0)
         scores = attention_heatmap_scores(model, bags[0] if len(bags) == 1 else torch.cat(bags, dim=0), percentile=True)

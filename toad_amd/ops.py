@@ -1378,6 +1378,105 @@ def stem_pool_region_u8(region: torch.Tensor, origins, wf: torch.Tensor, b, tile
     return y
 
 
+TILE_REGIONS_MAX = 128                 # the regions one extractor call takes (include/toad_hip.h: TOAD_TILE_REGIONS_MAX)
+
+
+def check_region_origins(origins, shapes, h: int, w: int) -> torch.Tensor:
+    """The `origins` argument of the region-LIST calls, checked on the HOST: [B,3] integers (x, y, k), the top-left pixel of each tile in the coordinates of
+    region k, as a CPU tensor, a numpy array or a list -> a contiguous int32 CPU tensor. ``shapes`` = [(Hr, Wr), ...], one per region; every k must name one
+    of them and every h x w tile (the footprint, for a shrink) must lie inside ITS region: the kernels read where the triples point. A device tensor is
+    refused, as by check_origins. Raises before anything is launched."""
+    if isinstance(origins, torch.Tensor) and origins.device.type != "cpu":
+        raise ValueError("origins must be given on the host (a CPU tensor, a numpy array or a list): their bounds are checked before the launch, and "
+                         f"device values cannot be read without a synchronisation (got a tensor on {origins.device})")
+    o = torch.as_tensor(origins)
+    if o.is_floating_point() or o.is_complex() or o.dtype == torch.bool:
+        raise TypeError(f"origins must be integers (pixel coordinates and a region index), got {o.dtype}")
+    if o.dim() != 2 or o.shape[1] != 3:
+        raise ValueError(f"origins must be [B,3] = (x, y, k) per tile - k the index of the tile's region in the list - got {tuple(o.shape)}")
+    shapes = [(int(hr), int(wr)) for hr, wr in shapes]
+    n = len(shapes)
+    o = o.to(torch.int64)
+    if o.shape[0] == 0:
+        return o.to(torch.int32).contiguous()
+    bad_k = (o[:, 2] < 0) | (o[:, 2] >= n)
+    ext = torch.tensor(shapes if n else [(0, 0)], dtype=torch.int64)[o[:, 2].clamp(0, max(n - 1, 0))]        # [B,2] = (Hr, Wr) of each tile's region
+    bad = bad_k | (o[:, 0] < 0) | (o[:, 0] + w > ext[:, 1]) | (o[:, 1] < 0) | (o[:, 1] + h > ext[:, 0])
+    if bool(bad.any()):
+        i = int(torch.nonzero(bad)[0])
+        x, y, k = (int(v) for v in o[i])
+        if bool(bad_k[i]):
+            raise ValueError(f"origins[{i}] = (x={x}, y={y}, k={k}): k must name one of the {n} regions (0 .. {n - 1})")
+        raise ValueError(f"origins[{i}] = (x={x}, y={y}, k={k}): a {h} x {w} (H x W) tile there does not lie inside region {k}, which is "
+                         f"{shapes[k][0]} x {shapes[k][1]}")
+    return o.to(torch.int32).contiguous()
+
+
+def region_list_arg(regions, name: str):
+    """The `regions` argument of the region-LIST calls: a sequence of 1 .. TILE_REGIONS_MAX uint8 [Hr,Wr,3] device tensors on ONE device, each with its own
+    extent, pitch and base address (_region_pitch's checks per region; the error names the region) -> (ctypes array of ToadTileRegion, shapes, device).
+    The same tensor, or overlapping views of one image, may appear several times."""
+    if isinstance(regions, torch.Tensor) or not isinstance(regions, (list, tuple)):
+        raise TypeError(f"{name}: regions must be a list or tuple of uint8 [Hr,Wr,3] tensors (one region: the *_region call), got {type(regions).__name__}")
+    n = len(regions)
+    if n < 1 or n > TILE_REGIONS_MAX:
+        raise ValueError(f"{name}: {n} regions: one call takes 1 .. {TILE_REGIONS_MAX} (TILE_REGIONS_MAX); more regions per call are not built")
+    for k, r in enumerate(regions):
+        _region_pitch(r, f"{name}: regions[{k}]")
+        if r.device != regions[0].device:
+            raise ValueError(f"{name}: regions[{k}] is on {r.device}, regions[0] on {regions[0].device}: all regions of a call must be on one device")
+    arr, shapes = region_table(regions)
+    return arr, shapes, regions[0].device
+
+
+def region_table(regions):
+    """The HOST descriptor table of the region-LIST calls for regions that have passed their checks (region_list_arg; ResNet_Baseline.forward_u8_regions,
+    which refuses with its own exceptions) -> (ctypes array of ToadTileRegion, [(Hr, Wr), ...])."""
+    arr = (_lib.ToadTileRegion * len(regions))()
+    for k, r in enumerate(regions):
+        arr[k].region, arr[k].pitch, arr[k].Hr, arr[k].Wr = r.data_ptr(), _row_pitch(r, 3 * r.shape[1]), r.shape[0], r.shape[1]
+    return arr, [(r.shape[0], r.shape[1]) for r in regions]
+
+
+def _regions_args(regions, origins, tile, name: str, shrink=1):
+    """-> (descriptor array, n, H, W, triples on the device); H, W = the NETWORK tile, the triples are checked for the footprint (shrink H, shrink W)."""
+    check_shrink(shrink)
+    arr, shapes, dev = region_list_arg(regions, name)
+    (fh, fw), (h, w) = shrunk_tile(tile, shrink)
+    o = check_region_origins(origins, shapes, fh, fw)
+    if o.shape[0] == 0:
+        raise ValueError(f"{name}: no origins")
+    return arr, len(shapes), h, w, o.to(dev)
+
+
+def tiles_u8_regions_to_f32(regions, origins, tile=256, mean=IMAGENET_MEAN, std=IMAGENET_STD, shrink=1) -> torch.Tensor:
+    """tiles_u8_region_to_f32 for a LIST of regions: origins [B,3] = (x, y, k) on the host (check_region_origins), tile b read from regions[k] - bitwise
+    tiles_u8_to_f32(torch.stack([regions[k][y:y+H, x:x+W] for x, y, k in origins]), mean, std); shrink = 2: of the box-filtered footprints."""
+    arr, n, h, w, o = _regions_args(regions, origins, tile, "tiles_u8_regions_to_f32", shrink)
+    norm = norm_constants_u8(mean, std)
+    out = torch.empty((o.shape[0], 3, h, w), dtype=torch.float32, device=o.device)
+    _lib.check(_lib.load().toad_tiles_u8_regions_to_nchw_f32(arr, n, _p(o), norm, _p(out), o.shape[0], h, w, shrink, _stream()), "toad_tiles_u8_regions_to_nchw_f32")
+    return out
+
+
+def stem_pool_regions_u8(regions, origins, wf: torch.Tensor, b, tile=256, mean=IMAGENET_MEAN, std=IMAGENET_STD, shrink=1) -> torch.Tensor:
+    """stem_pool_region_u8 for a LIST of regions: origins [B,3] = (x, y, k) on the host, tile b (H, 256), H % 4 == 0, read from regions[k] - bitwise
+    stem_pool_nhwc_u8 on the stacked tiles (shrink = 2: on the box-filtered (2 H, 512) footprints). Padding is the tile's; every region is read in place
+    whatever its address and pitch."""
+    arr, n, h, w, o = _regions_args(regions, origins, tile, "stem_pool_regions_u8", shrink)
+    _chk(wf, "wf"); _chk(b, "b", allow_none=True)
+    if tuple(wf.shape) != (64, 192):
+        raise ValueError("stem_pool_regions_u8: expected a [64,192] space-to-depth weight")
+    norm = norm_constants_u8(mean, std)
+    bb = o.shape[0]
+    y = torch.empty((bb, h // 4, w // 4, 64), dtype=torch.float32, device=o.device)
+    lib = _lib.load()
+    ws = _ws(lib.toad_linear_ws_bytes(bb * (h // 2) * (w // 2), 64, 192), o.device)
+    _lib.check(lib.toad_stem_pool_regions_u8(arr, n, _p(o), norm, _p(wf), _p(b), _p(y), bb, h, w, shrink, _p(ws), ws.numel(), _stream()),
+               "toad_stem_pool_regions_u8")
+    return y
+
+
 TISSUE_CELLS = (64, 32, 16, 8, 4)      # the cell sizes of csrc/tissue.hip
 
 

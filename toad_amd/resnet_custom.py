@@ -21,7 +21,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .ops import IMAGENET_MEAN, IMAGENET_STD, _row_pitch, check_origins, check_shrink, norm_constants_u8, region_layout_ok, shrunk_tile, tile_shape
+from .ops import (IMAGENET_MEAN, IMAGENET_STD, TILE_REGIONS_MAX, _row_pitch, check_origins, check_region_origins, check_shrink, norm_constants_u8,
+                  region_layout_ok, region_table, shrunk_tile, tile_shape)
 
 __all__ = ["Bottleneck_Baseline", "ResNet_Baseline", "resnet50_baseline", "IMAGENET_MEAN", "IMAGENET_STD"]
 
@@ -262,6 +263,59 @@ class ResNet_Baseline(nn.Module):
             else:
                 _lib.check(lib.toad_resnet50_trunc_fwd_u8_region_box(region.data_ptr(), pitch, Hr, Wr, org[b0:b0 + nb].data_ptr(), norm, wp, bp, o32, o16,
                                                                      *tail[:3], shrink, *tail[3:]), "toad_resnet50_trunc_fwd_u8_region_box")
+        return self._chunked(out, H, W, lib.toad_resnet50_trunc_u8_ws_bytes, call)
+
+    def forward_u8_regions(self, regions, origins, tile=256, mean=IMAGENET_MEAN, std=IMAGENET_STD, out_dtype: torch.dtype = torch.float32,
+                           shrink=1) -> torch.Tensor:
+        """``forward_u8_region`` for a slide that arrives as a LIST of regions (strips, blocks, any windows) -> [B,1024] bag rows, fp32 or fp16.
+
+        ``regions``: a list or tuple of 1 .. ``ops.TILE_REGIONS_MAX`` uint8 [Hr,Wr,3] tensors on one HIP device, each laid out as ``forward_u8_region`` wants
+        its region, each with its own extent, pitch and base address; the same tensor or overlapping views of one image may appear several times.
+        ``origins``: [B,3] integers (x, y, k) on the HOST - the top-left pixel of tile b in the coordinates of ``regions[k]``; every k and every tile is
+        checked here before anything is launched (``ops.check_region_origins``). The result is bitwise
+        ``forward_u8(torch.stack([regions[k][y:y+H, x:x+W] for x, y, k in origins]), mean, std, out_dtype)`` - with ``shrink = 2`` ``forward_u8`` of the
+        box-filtered footprints, as ``forward_u8_region`` defines them. The network scales every layer by an abs-max over the tiles of a call, so a bag row
+        depends on the tiles that share its call: this call makes the cut of the slide invisible - the same tiles in the same order give the bits of
+        ``forward_u8_region`` on the whole slide. More than ``max_tiles_per_call`` triples run in chunks exactly as there: the triples are sliced, never
+        the regions, and every chunk gets the same list. Refusals in ``forward_u8_region``'s order - shrink, the model and the regions (RuntimeError, the
+        first offending region named), then the origins - with one addition in front of the model's: ``regions`` not being a list or tuple (TypeError) and
+        their count (ValueError), because every later check, the model's device test included, looks at ``regions[0]``."""
+        check_shrink(shrink)
+        if shrink != 1:
+            shrunk_tile(tile, shrink)
+        if isinstance(regions, torch.Tensor) or not isinstance(regions, (list, tuple)):
+            raise TypeError(f"forward_u8_regions expects a list or tuple of uint8 [Hr,Wr,3] regions (one region: forward_u8_region), got {type(regions).__name__}")
+        n = len(regions)
+        if n < 1 or n > TILE_REGIONS_MAX:
+            raise ValueError(f"forward_u8_regions: {n} regions: one call takes 1 .. {TILE_REGIONS_MAX} (ops.TILE_REGIONS_MAX); more regions per call are not built")
+
+        def problem(k, r):
+            return (f"forward_u8_regions expects uint8 [Hr,Wr,3] tensors, got {type(r).__name__} as regions[{k}]" if not isinstance(r, torch.Tensor) else
+                    f"forward_u8_regions expects uint8 regions, got {r.dtype} as regions[{k}]" if r.dtype != torch.uint8 else
+                    f"forward_u8_regions expects channels-last [Hr,Wr,3] regions, got {tuple(r.shape)} as regions[{k}]" if r.dim() != 3 or r.shape[2] != 3 else
+                    f"out_dtype must be torch.float32 or torch.float16, got {out_dtype}" if out_dtype not in (torch.float32, torch.float16) else
+                    f"expected uint8 [Hr,Wr,3] tensors on the HIP device (no CPU fallback), got regions[{k}] on {r.device}" if not r.is_cuda else
+                    f"forward_u8_regions expects regions with stride(2) == 1, stride(1) == 3 and a row pitch stride(0) >= 3 Wr (rows are read in place, "
+                    f"there is no hidden copy), got strides {tuple(r.stride())} for shape {tuple(r.shape)} as regions[{k}]" if not region_layout_ok(r) else
+                    f"regions[{k}] is on {r.device}, regions[0] on {regions[0].device}: all regions of a call must be on one device"
+                    if r.device != regions[0].device else None)
+        found = next((p for p in (problem(k, r) for k, r in enumerate(regions)) if p is not None), None)
+        self._ready(regions[0], found)
+        (FH, FW), (H, W) = shrunk_tile(tile, shrink)        # the footprint the triples are checked for, the tile the network and the chunking see
+        org = check_region_origins(origins, [(r.shape[0], r.shape[1]) for r in regions], FH, FW)
+        B = org.shape[0]
+        norm = norm_constants_u8(mean, std)
+        dev = regions[0].device
+        out = torch.empty(B, 1024, device=dev, dtype=out_dtype)
+        if B == 0:
+            return out
+        lib = _lib.load()
+        arr, _ = region_table(regions)                      # the HOST descriptor table: every chunk gets the same one
+        org = org.to(dev)                                   # int32 [B,3]: the one small copy of the call
+
+        def call(b0, nb, wp, bp, o32, o16, tail):           # the triples are sliced, never the regions
+            _lib.check(lib.toad_resnet50_trunc_fwd_u8_regions(arr, n, org[b0:b0 + nb].data_ptr(), norm, wp, bp, o32, o16, *tail[:3], shrink, *tail[3:]),
+                       "toad_resnet50_trunc_fwd_u8_regions")
         return self._chunked(out, H, W, lib.toad_resnet50_trunc_u8_ws_bytes, call)
 
 

@@ -13,11 +13,14 @@ extract_u8_bench.py (its event timing, its alternation of the arms inside one pr
     --stride 64 runs the same pair on the overlapping grid, where the tiles are 12 times the region.
   launches: four calls of ONE resident arm (--arm A | B | C) for a `rocprofv3 --kernel-trace --stats` run of its own: the stem instantiations' times.
 
+  --regions: the slide cut into 4 strips / 16 blocks, one forward_u8_region call per window against ONE forward_u8_regions call over all of them, and both
+    against the whole region; see regions(). Appends to profiles/extract_regions_bench.jsonl unless --out names another file.
+
   --shrink 2: 512 footprints of 512 x 512 read box-filtered to 256 x 256 (forward_u8_region(shrink=2)) against today's 256-pixel call and against torch
     glue in front of forward_u8; see shrunk().
 
 Prints one JSON line per result; --out FILE keeps them.
-usage: extract_region_bench.py [--resident] [--host-fed] [--launches --arm A|B|C] [--shrink 2] [--stride S] [--seconds S] [--steps K] [--out FILE]"""
+usage: extract_region_bench.py [--resident] [--host-fed] [--launches --arm A|B|C] [--shrink 2] [--regions] [--stride S] [--seconds S] [--steps K] [--out FILE]"""
 import argparse
 import json
 import os
@@ -111,6 +114,80 @@ def shrunk(seconds, shrink=2):
                  s_bitwise_g=same)]
 
 
+def regions(seconds):
+    """--regions: a slide that arrives cut. The resident 4096 x 8192 region, 512 tiles of 256 x 256 on the 16 x 32 grid:
+      arm A    forward_u8_region on the whole region (arm B of --resident): the yardstick, two interleaved halves for its spread;
+      arm L1   forward_u8_regions with that one region;
+      arm S4 / S16   one forward_u8_region call per 1024-row strip / per block of the 4 x 4 grid (128 / 32 tiles each), back to back in one bracket;
+      arm L4 / L16   the same windows through ONE forward_u8_regions call.
+    L1, L4, L16 are checked torch.equal to A before anything is timed; S4 / S16 have other abs-max scopes and need not equal A - whether they do is printed.
+    The stem launches alone (ops.stem_pool_region_u8 / stem_pool_regions_u8 with one region, the plane split and the output allocation included) are timed
+    in the same alternation. One JSON line per arm."""
+    from toad_amd import ops
+    dev = torch.device("cuda:0")
+    model = make_model()
+    region, origins = grid_region(TILE, dev)
+    gy, gx = GRID
+    xy = origins.tolist()
+
+    def windows(ny, nx):
+        """The ny x nx cut of the region: (views, per-window local origins, triples in the slide's row-major tile order)."""
+        hy, wx = gy // ny * TILE, gx // nx * TILE
+        views = [region[j * hy:(j + 1) * hy, i * wx:(i + 1) * wx] for j in range(ny) for i in range(nx)]
+        local = [[] for _ in views]
+        triples = []
+        for x, y in xy:
+            k = (y // hy) * nx + x // wx
+            local[k].append((x % wx, y % hy))
+            triples.append((x % wx, y % hy, k))
+        return views, [torch.tensor(o, dtype=torch.int32) for o in local], torch.tensor(triples, dtype=torch.int32)
+    v4, o4, t4 = windows(4, 1)
+    v16, o16, t16 = windows(4, 4)
+    t1 = torch.cat([origins, torch.zeros(origins.shape[0], 1, dtype=torch.int32)], dim=1)
+
+    def per_window(views, local):
+        return torch.cat([model.forward_u8_region(v, o) for v, o in zip(views, local)])
+    want = model.forward_u8_region(region, origins)
+    equal = {"L1": bool(torch.equal(model.forward_u8_regions([region], t1), want)), "L4": bool(torch.equal(model.forward_u8_regions(v4, t4), want)),
+             "L16": bool(torch.equal(model.forward_u8_regions(v16, t16), want))}
+    if not all(equal.values()):
+        raise SystemExit(f"the list call is not bitwise the whole-region call: {equal}")
+    # (S16's rows come block by block, not in the slide's order: compared as the set of rows of each tile)
+    order16 = torch.argsort(t16[:, 2].to(torch.int64), stable=True).to(dev)
+    equal["S4"] = bool(torch.equal(per_window(v4, o4), want))
+    equal["S16"] = bool(torch.equal(per_window(v16, o16), want[order16]))
+    wf, bias = model._folded[0][0], model._folded[1][0]
+    arms = {"A": lambda: model.forward_u8_region(region, origins), "L1": lambda: model.forward_u8_regions([region], t1),
+            "S4": lambda: [model.forward_u8_region(v, o) for v, o in zip(v4, o4)], "L4": lambda: model.forward_u8_regions(v4, t4),
+            "S16": lambda: [model.forward_u8_region(v, o) for v, o in zip(v16, o16)], "L16": lambda: model.forward_u8_regions(v16, t16),
+            "stem_region": lambda: ops.stem_pool_region_u8(region, origins, wf, bias, TILE),
+            "stem_regions": lambda: ops.stem_pool_regions_u8([region], t1, wf, bias, TILE)}
+    t, iters = alternate(arms, seconds)
+    a = t["A"]
+    a1, a2 = median(a[0::2]), median(a[1::2])
+    ma = median(a)
+    spread = abs(a1 - a2) / ma
+    n = origins.shape[0]
+    res = []
+    for arm, v in t.items():
+        m = median(v)
+        r = dict(kind="resident_regions", arm=arm, tiles=n, tile="256x256", region=list(region.shape[:2]), rounds=len(v), iters_per_round=iters, ms=round(m, 4),
+                 ms_min=round(min(v), 4), ms_max=round(max(v), 4), tiles_per_s=round(n / m * 1e3, 1))
+        if arm == "A":
+            r.update(arm_a_halves_ms=[round(a1, 4), round(a2, 4)], arm_a_spread=round(spread, 4))
+        elif arm == "stem_regions":
+            r.update(over_stem_region=round(m / median(t["stem_region"]), 4))
+        elif arm != "stem_region":
+            r.update(over_a=round(m / ma, 4), bitwise_a=equal[arm])
+        if arm == "L1":
+            r.update(within_1p02_a=bool(m <= 1.02 * ma))
+        if arm in ("L4", "L16"):
+            s = median(t["S" + arm[1:]])
+            r.update(over_s=round(m / s, 4), faster_than_s_beyond_spread=bool(m < s - spread * ma))
+        res.append(r)
+    return res
+
+
 def host_fed(stride, steps):
     dev = torch.device("cuda:0")
     model = make_model()
@@ -183,10 +260,14 @@ def main():
     ap.add_argument("--seconds", type=float, default=3.0)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--shrink", type=int, default=1, choices=(1, 2))
+    ap.add_argument("--regions", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    every = not (a.resident or a.host_fed or a.launches or a.shrink != 1)
+    every = not (a.resident or a.host_fed or a.launches or a.shrink != 1 or a.regions)
     res = []
+    if a.regions:
+        res += regions(a.seconds)
+        a.out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "extract_regions_bench.jsonl")
     if a.shrink != 1:
         res += shrunk(a.seconds, a.shrink)
     if a.launches:
