@@ -972,6 +972,32 @@ int toad_mil_multi_bwd_x16_f32(const float *const *params, float *const *grads, 
 int toad_bag_dequant_e4m3(const void *codes, void *out, int out_f32, int64_t n, int exp, void *stream);
 int toad_bag_quant_e4m3(const void *x, int x_f16, void *codes, int64_t n, int exp, void *stream);
 
+/* ---- e4m3 shards: a LIST of e4m3 bags in one call (an ADDITIVE extension of ABI 15 as well; csrc/bag_e4m3.hip) ----
+ * The bags of an optimiser step lie back to back: codes, and out or x, are contiguous [R, k] concatenations, R = row_offsets[nb], bag b being rows
+ * row_offsets[b] .. row_offsets[b + 1] with its own exponent exps[b]. row_offsets (nb + 1 entries) and exps (nb entries) are HOST arrays, read during the
+ * call; row_offsets[0] == 0, the offsets do not decrease, empty bags may stand anywhere. The descriptors of up to TOAD_E4M3_LIST_MAX non-empty bags travel
+ * by value in the kernel argument (element offset, count, head / body split, exponent, first workgroup; a workgroup finds its bag by a uniform binary
+ * search): no device table, no upload, no allocation, no synchronisation. A longer list is ceil(non-empty bags / TOAD_E4M3_LIST_MAX) launches inside the
+ * one call; nb == 0, or empty bags only, launches nothing. They serve the reference's bag load and device copy for a whole batch of slides
+ * (datasets/dataset_mtl_concat.py:369-373 -> utils/core_utils_mtl_concat.py:201-204): the shard crosses the link in one copy and one launch decodes it.
+ *
+ * toad_bags_dequant_e4m3: the bytes written are exactly those of nb calls of toad_bag_dequant_e4m3 on the bags' slices, each with its exps[b]. codes may lie
+ * at any byte address and k may be odd, so a bag starts at any byte: each bag has its own head / 16-code body / tail split. out is aligned to its element
+ * (TOAD_EALIGN otherwise). No byte outside [0, R k) of either array is read or written. Element offsets are 64-bit.
+ * toad_bags_quant_e4m3: the mirror image, bit for bit the per-bag toad_bag_quant_e4m3 (x aligned to its element).
+ * toad_bags_absmax_bits: amax_bits[b] (a DEVICE array of nb words, 4-byte aligned) = the fp32 bit pattern of the largest |x| of bag b, fp16 input up-cast
+ * exactly: the unsigned maximum of the sign-cleared patterns, so it does not depend on the order of the reduction; an Inf gives 0x7F800000, any NaN in the
+ * bag a pattern above that, an empty bag 0. What amax_bits held before does not matter: it is zeroed on the stream in front of the launch, and workgroups
+ * raise it with integer atomics.
+ *
+ * All three, before anything is launched: a NULL pointer, nb < 0, k <= 0, row_offsets[0] != 0, a decreasing offset ("bag i:" in the message) and an exps[i]
+ * outside -7 .. 15 ("bag i:") are TOAD_EINVAL; more elements than 64-bit byte offsets hold is TOAD_ESHAPE; then the alignments, TOAD_EALIGN.
+ * Not done: shards of fp16 / fp32 bags, exponents per row, GEMMs that read the codes themselves. */
+#define TOAD_E4M3_LIST_MAX 64   /* bags per launch: the 52 bags of a step are one launch */
+int toad_bags_dequant_e4m3(const void *codes, void *out, int out_f32, int64_t k, const int64_t *row_offsets, const int *exps, int nb, void *stream);
+int toad_bags_quant_e4m3(const void *x, int x_f16, void *codes, int64_t k, const int64_t *row_offsets, const int *exps, int nb, void *stream);
+int toad_bags_absmax_bits(const void *x, int x_f16, uint32_t *amax_bits, int64_t k, const int64_t *row_offsets, int nb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

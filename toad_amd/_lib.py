@@ -165,6 +165,10 @@ SIGNATURES = {
     # ... and bags as 8-bit e4m3 codes with one exponent, decoded behind their copy and quantised where they are made (csrc/bag_e4m3.hip): additive to ABI 15
     "toad_bag_dequant_e4m3": (I, [P, P, I, I64, I, P]),
     "toad_bag_quant_e4m3": (I, [P, I, P, I64, I, P]),
+    # ... and a list of such bags, back to back with one exponent each, in one call (row_offsets, exps: HOST arrays): additive to ABI 15
+    "toad_bags_dequant_e4m3": (I, [P, P, I, I64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int), I, P]),
+    "toad_bags_quant_e4m3": (I, [P, I, P, I64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int), I, P]),
+    "toad_bags_absmax_bits": (I, [P, I, P, I64, ctypes.POINTER(ctypes.c_int64), I, P]),
     # ... and the batched weight-gradient launch of the whole-slide calls on operands of the caller's choice (jobs: a HOST array of n ToadWgradJob;
     # a test/debug helper like toad_dropout_mask_f32): additive to ABI 15
     "toad_linear_wgrad_batch_f32": (I, [ctypes.POINTER(ToadWgradJob), I, I64, F, I, SZ, P]),

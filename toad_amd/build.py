@@ -18,7 +18,7 @@ SOURCES = ["capi.hip", "gemm_f32.hip", "gated_pool.hip", "heads.hip", "step.hip"
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "h2_arith.h"), os.path.join(CSRC, "stem_u8.h"), os.path.join(CSRC, "region_u8.h"),
            os.path.join(REPO, "include", "toad_hip.h")] + \
     [os.path.join(CSRC, f) for f in ("gemm_nt_f32.inc", "gemm_tn.inc", "gemm_h2.inc", "gemm_h2_epilogue.inc", "gemm_pt.inc", "gemm_narrow.inc", "gemm_stream.inc", "stem_halo.inc", "heat_thumb_body.inc",
-                                        "heat_pyramid_body.inc", "sat_plane_body.inc")]
+                                        "heat_pyramid_body.inc", "sat_plane_body.inc", "bag_dequant_e4m3_body.inc", "bag_quant_e4m3_body.inc")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast",
          "-I" + os.path.join(REPO, "include"), "-I" + CSRC, "-Wall", "-Wno-unused-function"]
 

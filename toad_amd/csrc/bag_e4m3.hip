@@ -21,6 +21,9 @@
 // at the first code whose address is 16-byte aligned and exists only if the other array is 16-byte aligned at that element too; what lies in front of it,
 // behind it, or - where there is no body - the whole array goes element by element. No access is wider than what it moves, so no byte outside [0, n) of
 // either array is touched. Element offsets are 64-bit. No LDS, no scratch, no atomics.
+//
+// Lists. The same two loops over a LIST of bags that lie back to back, each with its own exponent and its own split, in one launch, and the abs-max of
+// each bag of such a list (the one kernel here with LDS, 16 bytes, and an integer atomic): "a LIST of bags" below.
 #include "common.h"
 
 #include <hip/hip_fp16.h>
@@ -80,28 +83,7 @@ __global__ __launch_bounds__(kE4m3Threads) void bag_dequant_e4m3_kernel(const un
                                                                         int64_t head, int64_t nvec, int exp) {
     const unsigned scale2 = e4m3_scale2(exp);
     const int64_t gid = (int64_t)blockIdx.x * kE4m3Threads + threadIdx.x, stride = (int64_t)gridDim.x * kE4m3Threads;
-    for (int64_t v = gid; v < nvec; v += stride) {
-        const int64_t i = head + v * kE4m3Lane;
-        const u32x4 w = *reinterpret_cast<const u32x4 *>(codes + i);
-        unsigned h[8];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) e4m3_word_to_h4(w[j], scale2, h[2 * j], h[2 * j + 1]);
-        if constexpr (sizeof(OUT) == 2) {
-            u32x4 *o = reinterpret_cast<u32x4 *>(out + i);
-            o[0] = u32x4{h[0], h[1], h[2], h[3]};
-            o[1] = u32x4{h[4], h[5], h[6], h[7]};
-        } else {
-            f32x4 *o = reinterpret_cast<f32x4 *>(out + i);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                o[j] = f32x4{h16_bits_to_f32(h[2 * j]), h16_bits_to_f32(h[2 * j] >> 16), h16_bits_to_f32(h[2 * j + 1]), h16_bits_to_f32(h[2 * j + 1] >> 16)};
-        }
-    }
-    const int64_t body = nvec * kE4m3Lane, rest = n - body;
-    for (int64_t r = gid; r < rest; r += stride) {
-        const int64_t i = r < head ? r : r + body;
-        e4m3_store1(out, i, e4m3_pair_to_h2((unsigned)codes[i] << 8, scale2));
-    }
+#include "bag_dequant_e4m3_body.inc"
 }
 
 // x [n] -> codes [n]; head and nvec as above (codes + head and x + head both 16-byte aligned)
@@ -110,28 +92,94 @@ __global__ __launch_bounds__(kE4m3Threads) void bag_quant_e4m3_kernel(const IN *
                                                                       int64_t nvec, int exp) {
     const float scale = __builtin_bit_cast(float, (unsigned)(127 + exp) << 23);
     const int64_t gid = (int64_t)blockIdx.x * kE4m3Threads + threadIdx.x, stride = (int64_t)gridDim.x * kE4m3Threads;
+#include "bag_quant_e4m3_body.inc"
+}
+
+// ---- a LIST of bags in one launch (toad_bags_dequant_e4m3, toad_bags_quant_e4m3, toad_bags_absmax_bits): the bags lie back to back in one [R, k] array, each
+// with its own exponent. Descriptors travel BY VALUE in the kernel argument, as in sat_plane_list_kernel (tissue_seg.hip): bag j of the launch owns the
+// workgroups first .. first + nblocks; descriptors from the launch's count on carry first = 0xFFFFFFFF, above every workgroup index, so the search needs no
+// count: six uniform steps of a binary search over the 64 prefixes, scalar loads from the kernel argument, once per workgroup. From there on a workgroup is
+// one of its bag's and runs the loop of the single-bag kernel (the included body) with the bag's own head / body / tail split - a bag starts at any byte, so
+// the split is per bag - over the bag's own workgroups. Empty bags never reach a descriptor. The grid is exact: every workgroup has a bag.
+struct E4m3ListBag {
+    int64_t off, n, nvec;            // first element of the bag in the concatenation, its elements, the lanes of its body
+    unsigned first, nblocks;         // its workgroups
+    int head, exp, bag, pad_;        // elements in front of its body; its exponent; its place in the caller's list (the abs-max slot)
+};
+struct E4m3ListArgs { E4m3ListBag b[TOAD_E4M3_LIST_MAX]; };
+static_assert(sizeof(E4m3ListBag) == 48 && sizeof(E4m3ListArgs) + 2 * sizeof(void *) <= 4096, "the descriptors and two pointers travel in the kernel argument");
+
+__device__ __forceinline__ const E4m3ListBag &e4m3_list_bag(const E4m3ListArgs &l) {
+    static_assert(TOAD_E4M3_LIST_MAX == 64, "six steps search 64 prefixes");
+    int k = 0;
+#pragma unroll
+    for (int step = TOAD_E4M3_LIST_MAX / 2; step >= 1; step >>= 1)
+        if (l.b[k + step].first <= blockIdx.x) k += step;
+    return l.b[k];
+}
+
+template <typename OUT>
+__global__ __launch_bounds__(kE4m3Threads) void bags_dequant_e4m3_list_kernel(const E4m3ListArgs l, const unsigned char *__restrict__ cat_codes,
+                                                                              OUT *__restrict__ cat_out) {
+    const E4m3ListBag &w = e4m3_list_bag(l);
+    const unsigned char *__restrict__ codes = cat_codes + w.off;
+    OUT *__restrict__ out = cat_out + w.off;
+    const int64_t n = w.n, head = w.head, nvec = w.nvec;
+    const unsigned scale2 = e4m3_scale2(w.exp);
+    const int64_t gid = (int64_t)(blockIdx.x - w.first) * kE4m3Threads + threadIdx.x, stride = (int64_t)w.nblocks * kE4m3Threads;
+#include "bag_dequant_e4m3_body.inc"
+}
+
+template <typename IN>
+__global__ __launch_bounds__(kE4m3Threads) void bags_quant_e4m3_list_kernel(const E4m3ListArgs l, const IN *__restrict__ cat_x,
+                                                                            unsigned char *__restrict__ cat_codes) {
+    const E4m3ListBag &w = e4m3_list_bag(l);
+    const IN *__restrict__ x = cat_x + w.off;
+    unsigned char *__restrict__ codes = cat_codes + w.off;
+    const int64_t n = w.n, head = w.head, nvec = w.nvec;
+    const float scale = __builtin_bit_cast(float, (unsigned)(127 + w.exp) << 23);
+    const int64_t gid = (int64_t)(blockIdx.x - w.first) * kE4m3Threads + threadIdx.x, stride = (int64_t)w.nblocks * kE4m3Threads;
+#include "bag_quant_e4m3_body.inc"
+}
+
+// amax_bits[bag] = the largest sign-cleared bit pattern of the bag's elements, as an fp32 pattern: an unsigned maximum, so the order of the reduction does
+// not matter, +-Inf is 0x7F800000 and a NaN lies above it. fp16 patterns are ordered the same way, so their maximum is taken as 15-bit integers and
+// up-cast ONCE, by the workgroup's first lane (exact, subnormals included; a NaN stays a NaN). Here the body is 16-BYTE lanes from the first 16-byte
+// aligned element on (x is aligned to its element, so `head` whole elements lie in front of it), everything else element by element. A workgroup reduces in
+// registers, across its four waves through 16 bytes of LDS, and issues at most ONE integer atomic max; the caller's array was zeroed on the stream before
+// the launch (an all-zero bag, like an empty one, leaves its 0).
+constexpr int64_t kE4m3AbsmaxMaxBlocks = 256;   // per bag: a bag's workgroups all meet in ONE atomic word
+template <typename IN>
+__global__ __launch_bounds__(kE4m3Threads) void bags_absmax_list_kernel(const E4m3ListArgs l, const IN *__restrict__ cat_x, unsigned *__restrict__ amax_bits) {
+    constexpr int kPer = 16 / (int)sizeof(IN);
+    const E4m3ListBag &w = e4m3_list_bag(l);
+    const IN *__restrict__ x = cat_x + w.off;
+    const int64_t n = w.n, head = w.head, nvec = w.nvec;
+    const int64_t gid = (int64_t)(blockIdx.x - w.first) * kE4m3Threads + threadIdx.x, stride = (int64_t)w.nblocks * kE4m3Threads;
+    unsigned m = 0;
     for (int64_t v = gid; v < nvec; v += stride) {
-        const int64_t i = head + v * kE4m3Lane;
-        u32x4 c;
-        if constexpr (sizeof(IN) == 4) {
-            const f32x4 *p = reinterpret_cast<const f32x4 *>(x + i);
+        const u32x4 a = *reinterpret_cast<const u32x4 *>(x + head + v * kPer);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { const f32x4 a = p[j]; c[j] = e4m3_pack4(a[0], a[1], a[2], a[3], scale); }
-        } else {
-            const u32x4 *p = reinterpret_cast<const u32x4 *>(x + i);
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const u32x4 a = p[q];
-                c[2 * q] = e4m3_pack4(h16_bits_to_f32(a[0]), h16_bits_to_f32(a[0] >> 16), h16_bits_to_f32(a[1]), h16_bits_to_f32(a[1] >> 16), scale);
-                c[2 * q + 1] = e4m3_pack4(h16_bits_to_f32(a[2]), h16_bits_to_f32(a[2] >> 16), h16_bits_to_f32(a[3]), h16_bits_to_f32(a[3] >> 16), scale);
-            }
+        for (int j = 0; j < 4; ++j) {
+            if constexpr (sizeof(IN) == 4) m = max(m, a[j] & 0x7FFFFFFFu);
+            else m = max(max(m, a[j] & 0x7FFFu), (a[j] >> 16) & 0x7FFFu);
         }
-        *reinterpret_cast<u32x4 *>(codes + i) = c;
     }
-    const int64_t body = nvec * kE4m3Lane, rest = n - body;
+    const int64_t body = nvec * kPer, rest = n - body;
     for (int64_t r = gid; r < rest; r += stride) {
         const int64_t i = r < head ? r : r + body;
-        codes[i] = (unsigned char)e4m3_from_f32(e4m3_load1(x, i), scale);
+        if constexpr (sizeof(IN) == 4) m = max(m, reinterpret_cast<const unsigned *>(x)[i] & 0x7FFFFFFFu);
+        else m = max(m, (unsigned)reinterpret_cast<const unsigned short *>(x)[i] & 0x7FFFu);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
+    __shared__ unsigned red[kE4m3Threads / kWave];
+    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        m = max(max(red[0], red[1]), max(red[2], red[3]));
+        if constexpr (sizeof(IN) == 2) m = __builtin_bit_cast(unsigned, h16_bits_to_f32(m));
+        if (m) atomicMax(amax_bits + w.bag, m);
     }
 }
 
@@ -188,4 +236,125 @@ extern "C" int toad_bag_quant_e4m3(const void *x, int x_f16, void *codes, int64_
     else
         hipLaunchKernelGGL(bag_quant_e4m3_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float *)x, (unsigned char *)codes, n, head, nvec, exp);
     return check_launch(what);
+}
+
+// ---- the list entries. What the bags share first (pointers, nb, k, the first offset), then bag by bag, the first failing bag winning under "bag i:"; then
+// the alignment of the whole array. Nothing is launched before all of that has passed. Two walks over the host arrays, no allocation, no upload, no
+// synchronisation: the first checks, the second fills TOAD_E4M3_LIST_MAX descriptors of non-empty bags at a time and launches them.
+namespace toad {
+
+static int e4m3_list_check(const char *what, const void *a, const void *b, int64_t k, const int64_t *row_offsets, const int *exps, bool need_exps, int nb) {
+    if (!a || !b || !row_offsets || (need_exps && nb > 0 && !exps)) { set_error("%s: null pointer", what); return TOAD_EINVAL; }
+    if (nb < 0) { set_error("%s: nb = %d bags", what, nb); return TOAD_EINVAL; }
+    if (k <= 0) { set_error("%s: k = %lld must be positive", what, (long long)k); return TOAD_EINVAL; }
+    if (row_offsets[0] != 0) { set_error("%s: row_offsets[0] = %lld must be 0", what, (long long)row_offsets[0]); return TOAD_EINVAL; }
+    for (int i = 0; i < nb; ++i) {
+        if (row_offsets[i + 1] < row_offsets[i]) {
+            set_error("bag %d: %s: row_offsets decrease from %lld to %lld", i, what, (long long)row_offsets[i], (long long)row_offsets[i + 1]);
+            return TOAD_EINVAL;
+        }
+        if (need_exps && (exps[i] < kE4m3ExpMin || exps[i] > kE4m3ExpMax)) {
+            set_error("bag %d: %s: exp = %d outside %d .. %d", i, what, exps[i], kE4m3ExpMin, kE4m3ExpMax);
+            return TOAD_EINVAL;
+        }
+    }
+    if (row_offsets[nb] > (INT64_MAX >> 2) / k) {                    // R k elements of up to 4 bytes: offsets stay inside 64 bits
+        set_error("%s: %lld rows of %lld elements", what, (long long)row_offsets[nb], (long long)k);
+        return TOAD_ESHAPE;
+    }
+    return TOAD_OK;
+}
+
+// the second walk: plan(off, n, d) fills head, nvec and nblocks of a non-empty bag's descriptor, launch(l, grid) launches one filled argument
+template <typename Plan, typename Launch>
+static int e4m3_list_run(const char *what, int64_t k, const int64_t *row_offsets, const int *exps, int nb, Plan plan, Launch launch) {
+    E4m3ListArgs l;
+    for (int i = 0; i < nb;) {
+        int m = 0;
+        unsigned grid = 0;
+        for (; i < nb && m < TOAD_E4M3_LIST_MAX; ++i) {
+            const int64_t n = (row_offsets[i + 1] - row_offsets[i]) * k;
+            if (n == 0) continue;
+            E4m3ListBag &d = l.b[m++];
+            d = {};
+            d.off = row_offsets[i] * k; d.n = n; d.first = grid; d.exp = exps ? exps[i] : 0; d.bag = i;
+            plan(d);
+            grid += d.nblocks;
+        }
+        if (m == 0) break;
+        for (int j = m; j < TOAD_E4M3_LIST_MAX; ++j) { l.b[j] = {}; l.b[j].first = 0xFFFFFFFFu; }      // above every workgroup index: the search stops short of them
+        launch(l, grid);
+        if (int rc = check_launch(what)) return rc;
+    }
+    return TOAD_OK;
+}
+
+}  // namespace toad
+
+extern "C" int toad_bags_dequant_e4m3(const void *codes, void *out, int out_f32, int64_t k, const int64_t *row_offsets, const int *exps, int nb,
+                                      void *stream) {
+    const char *what = "toad_bags_dequant_e4m3";
+    if (int rc = e4m3_list_check(what, codes, out, k, row_offsets, exps, true, nb)) return rc;
+    const int elem = out_f32 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(out) & (uintptr_t)(elem - 1)) { set_error("%s: out must be %d-byte aligned", what, elem); return TOAD_EALIGN; }
+    auto plan = [&](E4m3ListBag &d) {
+        int64_t head;
+        e4m3_split((const unsigned char *)codes + d.off, (const unsigned char *)out + d.off * elem, elem, d.n, head, d.nvec);
+        d.head = (int)head; d.nblocks = e4m3_blocks(d.n, d.nvec);
+    };
+    auto launch = [&](const E4m3ListArgs &l, unsigned grid) {
+        if (out_f32)
+            hipLaunchKernelGGL(bags_dequant_e4m3_list_kernel<float>, dim3(grid), dim3(kE4m3Threads), 0, (hipStream_t)stream, l, (const unsigned char *)codes, (float *)out);
+        else
+            hipLaunchKernelGGL(bags_dequant_e4m3_list_kernel<__half>, dim3(grid), dim3(kE4m3Threads), 0, (hipStream_t)stream, l, (const unsigned char *)codes, (__half *)out);
+    };
+    return e4m3_list_run(what, k, row_offsets, exps, nb, plan, launch);
+}
+
+extern "C" int toad_bags_quant_e4m3(const void *x, int x_f16, void *codes, int64_t k, const int64_t *row_offsets, const int *exps, int nb, void *stream) {
+    const char *what = "toad_bags_quant_e4m3";
+    if (int rc = e4m3_list_check(what, x, codes, k, row_offsets, exps, true, nb)) return rc;
+    const int elem = x_f16 ? 2 : 4;
+    if (reinterpret_cast<uintptr_t>(x) & (uintptr_t)(elem - 1)) { set_error("%s: x must be %d-byte aligned", what, elem); return TOAD_EALIGN; }
+    auto plan = [&](E4m3ListBag &d) {
+        int64_t head;
+        e4m3_split((const unsigned char *)codes + d.off, (const unsigned char *)x + d.off * elem, elem, d.n, head, d.nvec);
+        d.head = (int)head; d.nblocks = e4m3_blocks(d.n, d.nvec);
+    };
+    auto launch = [&](const E4m3ListArgs &l, unsigned grid) {
+        if (x_f16)
+            hipLaunchKernelGGL(bags_quant_e4m3_list_kernel<__half>, dim3(grid), dim3(kE4m3Threads), 0, (hipStream_t)stream, l, (const __half *)x, (unsigned char *)codes);
+        else
+            hipLaunchKernelGGL(bags_quant_e4m3_list_kernel<float>, dim3(grid), dim3(kE4m3Threads), 0, (hipStream_t)stream, l, (const float *)x, (unsigned char *)codes);
+    };
+    return e4m3_list_run(what, k, row_offsets, exps, nb, plan, launch);
+}
+
+extern "C" int toad_bags_absmax_bits(const void *x, int x_f16, uint32_t *amax_bits, int64_t k, const int64_t *row_offsets, int nb, void *stream) {
+    const char *what = "toad_bags_absmax_bits";
+    if (int rc = e4m3_list_check(what, x, amax_bits, k, row_offsets, nullptr, false, nb)) return rc;
+    const int elem = x_f16 ? 2 : 4;
+    if (reinterpret_cast<uintptr_t>(x) & (uintptr_t)(elem - 1)) { set_error("%s: x must be %d-byte aligned", what, elem); return TOAD_EALIGN; }
+    if (!aligned4(amax_bits)) { set_error("%s: amax_bits must be 4-byte aligned", what); return TOAD_EALIGN; }
+    if (nb == 0) return TOAD_OK;
+    // every slot starts at 0, whatever it held: the kernels only ever raise it (one fill on the stream, in front of the launches)
+    if (hipMemsetAsync(amax_bits, 0, (size_t)nb * sizeof(uint32_t), (hipStream_t)stream) != hipSuccess) return check_launch(what);
+    const int per = 16 / elem;
+    auto plan = [&](E4m3ListBag &d) {
+        const uintptr_t at = reinterpret_cast<uintptr_t>(x) + (uintptr_t)d.off * (uintptr_t)elem;
+        int64_t head = (int64_t)(((16u - (unsigned)(at & 15u)) & 15u) / (unsigned)elem);
+        if (head > d.n) head = d.n;
+        d.nvec = (d.n - head) / per;
+        if (d.nvec == 0) head = 0;
+        d.head = (int)head;
+        const int64_t rest = d.n - d.nvec * per, work = d.nvec > rest ? d.nvec : rest, blocks = (work + kE4m3Threads - 1) / kE4m3Threads;
+        d.nblocks = (unsigned)(blocks > kE4m3AbsmaxMaxBlocks ? kE4m3AbsmaxMaxBlocks : blocks);
+    };
+    auto launch = [&](const E4m3ListArgs &l, unsigned grid) {
+        if (x_f16)
+            hipLaunchKernelGGL(bags_absmax_list_kernel<__half>, dim3(grid), dim3(kE4m3Threads), 0, (hipStream_t)stream, l, (const __half *)x, amax_bits);
+        else
+            hipLaunchKernelGGL(bags_absmax_list_kernel<float>, dim3(grid), dim3(kE4m3Threads), 0, (hipStream_t)stream, l, (const float *)x, amax_bits);
+    };
+    return e4m3_list_run(what, k, row_offsets, nullptr, nb, plan, launch);
 }

@@ -67,20 +67,27 @@ def hip_slide_grad(model, grads: Dict[str, torch.Tensor], slide: Slide, beta: fl
 
 
 def hip_batch_grad(model, grads: Dict[str, torch.Tensor], slides: Sequence[Slide], beta: float = 1.0, scale: float = 1.0,
-                   w_cls: float = 0.75, w_site: float = 0.25, xcat: Optional[torch.Tensor] = None, offsets=None):
+                   w_cls: float = 0.75, w_site: float = 0.25, xcat: Optional[torch.Tensor] = None, offsets=None, meta=None):
     """One library call for a whole shard of (small) slides: the trunk / attention GEMMs of forward and backward run once over the
     concatenated bags, pooling / heads / loss per slide (toad_mil_multi_step_f32). grads = beta*grads + scale * sum_b d loss_b.
     ``xcat`` / ``offsets``: the bags already concatenated on the device (an ingest buffer); else they are concatenated here.
     A shard whose bags are all fp16 runs as stored (toad_mil_multi_step_x16_f32: no up-cast, and no copy when the bags lie back to back in
     an fp16 landing buffer); any other mix of dtypes is up-cast to fp32 (``SlideShardedDP.accumulate`` cuts its runs where the dtype changes).
+    ``meta``: (sex float32 [B], label int64 [B], site int64 [B]) already as the call takes them, together with ``xcat`` / ``offsets``
+    (``SlideShardedDP.accumulate_batch``): ``slides`` is then not looked at and no tensor is made here.
     Returns the per-slide loss vectors [B, 3]."""
     from . import ops
     from .model_toad import _draw_dropout
     w = {k: v.detach() for k, v in model._weights().items()}
     drop_p, seed = _draw_dropout(model._dropout and model.training)
-    sex = torch.cat([s[1].to(torch.float32).reshape(1) for s in slides])
-    label = torch.cat([s[2].reshape(1) for s in slides])
-    site = torch.cat([s[3].reshape(1) for s in slides])
+    if meta is not None:
+        if xcat is None or offsets is None:
+            raise ValueError("hip_batch_grad: meta goes with xcat and offsets")
+        sex, label, site = meta
+    else:
+        sex = torch.cat([s[1].to(torch.float32).reshape(1) for s in slides])
+        label = torch.cat([s[2].reshape(1) for s in slides])
+        site = torch.cat([s[3].reshape(1) for s in slides])
     if xcat is None:
         loss, _, _ = ops.mil_multi_step(w, grads, beta, [s[0] for s in slides], sex, label, site, w_cls * scale, w_site * scale, drop_p, seed)
     else:
@@ -208,6 +215,50 @@ class SlideShardedDP:
             return losses
         return [self.slide_grad_fn(self.model, self.grads, s, 0.0 if (overwrite and i == 0) else 1.0, scale)
                 for i, s in enumerate(slides)]
+
+    def accumulate_batch(self, batch, global_slides: int, overwrite: bool = True):
+        """``accumulate`` for an ``ingest.BagBatch`` - bags that ARE one concatenation [R, K] with Python row offsets and [B] metadata tensors (a decoded
+        e4m3 shard). The cutting rule is ``accumulate``'s: runs of bags of 1 .. ``batch_max_patches`` patches up to ``batch_rows`` rows go through one
+        ragged multi-slide call each, a longer (or empty) bag alone through ``slide_grad_fn``. A run is a ROW SLICE of ``batch.bags`` with shifted
+        offsets and slices of sex / label / site: no torch.cat, no per-slide tensor, no walk over views. The library calls and their operands are those
+        of ``accumulate(batch.slides(), ...)``."""
+        self._check_flat()
+        offs, nb = batch.offsets, len(batch.offsets) - 1
+        if nb == 0:
+            if overwrite:
+                self.zero_grad()
+            return []
+        scale = 1.0 / float(global_slides)
+        rows_of = lambda b: offs[b + 1] - offs[b]                                           # noqa: E731
+        small = lambda b: 0 < rows_of(b) <= self.batch_max_patches                          # noqa: E731
+        slide = lambda b: (batch.bags[offs[b]:offs[b + 1]], batch.sex[b:b + 1], batch.label[b:b + 1], batch.site[b:b + 1])   # noqa: E731
+        if not (self.slide_grad_fn is hip_slide_grad and nb > 1 and sum(1 for b in range(nb) if small(b)) > 1):
+            return [self.slide_grad_fn(self.model, self.grads, slide(b), 0.0 if (overwrite and b == 0) else 1.0, scale) for b in range(nb)]
+        losses, first, i = [], True, 0
+        while i < nb:
+            j = i
+            while j < nb and small(j) and offs[j + 1] - offs[i] <= self.batch_rows:
+                j += 1
+            beta = 0.0 if (overwrite and first) else 1.0
+            if j - i >= 2:
+                lb = hip_batch_grad(self.model, self.grads, None, beta, scale, xcat=batch.bags[offs[i]:offs[j]], offsets=[o - offs[i] for o in offs[i:j + 1]],
+                                    meta=(batch.sex[i:j], batch.label[i:j], batch.site[i:j]))
+                losses.extend(lb[k] for k in range(j - i))
+            else:
+                j = i + 1
+                losses.append(self.slide_grad_fn(self.model, self.grads, slide(i), beta, scale))
+            first, i = False, j
+        return losses
+
+    def step_batch(self, batch, global_slides: int):
+        """``step`` for an ``ingest.BagBatch`` (``accumulate_batch``, the all-reduce, the optimiser)."""
+        losses = self.accumulate_batch(batch, global_slides)
+        self.reduce()
+        if self._flat_adam is not None:
+            self._flat_adam.step(self.flat_grad)
+        else:
+            self.optimizer.step()
+        return losses
 
     def reduce(self):
         """ONE all-reduce(SUM) of the flat 4.77 MB gradient bucket, enqueued on the current stream behind the last slide's backward

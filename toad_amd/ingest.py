@@ -27,6 +27,9 @@ e4m3 bags: a second wire format, 8 bits per feature (csrc/bag_e4m3.hip; DESIGN.m
 * Error: ``|decode(quantise(x)) - x| <= 2^-4 |x|`` where ``|x| * 2^exp >= 2^-6`` (half an ulp of a 4-bit significand) and ``<= 2^-10 * 2^-exp`` below
   (half the spacing of the e4m3 subnormals), for ``|x| * 2^exp <= 448``.
 The codes cross the link; the decode runs on the copy stream right behind each bag's copy, into the landing buffer that is there for fp16 / fp32 files.
+
+e4m3 shards (``E4M3Shard``, ``ShardPrefetcher``, ``BagBatch``, at the end of this file): the bags of one optimiser step as ONE record - one copy, one
+decode launch for all of them, each bag with its own exponent - for steps of many small bags, where the work per record and not the link bounds the feed.
 """
 from __future__ import annotations
 
@@ -260,3 +263,221 @@ class BagPrefetcher:
                         for u in ((t.planes, t.amax) if getattr(t, "is_prepared_bag", False) else (t,)):
                             u.record_stream(cur)
                 yield tensors
+
+
+# ---- e4m3 shards: the bags of one optimiser step in ONE record, one copy and one decode (csrc/bag_e4m3.hip, "a LIST of bags"; DESIGN.md "e4m3 bags") ----
+# File: torch.save({"e4m3_shard": codes as torch.float8_e4m3fn [R, K], "rows": int64 [B], "exp": int32 [B], "label": int64 [B], "site": int64 [B],
+# "sex": float32 [B]}) - tensors in a plain dict, so it loads with weights_only=True. Bag b is rows sum(rows[:b]) .. sum(rows[:b + 1]) of the codes, a bag
+# of the format above with exponent exp[b]. Per record BagPrefetcher pays a future, three pinned tensors, three copies, a staging allocation, a decode
+# launch and an event; a shard pays them once for all its bags.
+class E4M3Shard:
+    """Many e4m3 bags back to back: ``codes`` uint8 [R, K] (a ``torch.float8_e4m3fn`` tensor is taken as its bytes), ``rows`` and ``exps`` (lists of B
+    ints; bag i is the next rows[i] rows, with exponent exps[i]), ``label`` / ``site`` int64 [B], ``sex`` float32 [B]."""
+    __slots__ = ("codes", "rows", "exps", "label", "site", "sex")
+
+    def __init__(self, codes: torch.Tensor, rows, exps, label, site, sex):
+        if not isinstance(codes, torch.Tensor) or codes.dtype not in (torch.uint8, torch.float8_e4m3fn):
+            raise ValueError("E4M3Shard: codes must be a torch.uint8 or torch.float8_e4m3fn tensor")
+        if codes.dim() != 2:
+            raise ValueError(f"E4M3Shard: codes must be [rows, features], got {tuple(codes.shape)}")
+        rows = rows.tolist() if isinstance(rows, torch.Tensor) else list(rows)
+        exps = exps.tolist() if isinstance(exps, torch.Tensor) else list(exps)
+        b = len(rows)
+        if len(exps) != b:
+            raise ValueError(f"E4M3Shard: {b} row counts and {len(exps)} exponents")
+        for i, (r, e) in enumerate(zip(rows, exps)):
+            if not isinstance(r, int) or isinstance(r, bool) or r < 0:
+                raise ValueError(f"E4M3Shard: bag {i}: rows must be a non-negative int, got {r!r}")
+            if not isinstance(e, int) or isinstance(e, bool) or not -7 <= e <= 15:
+                raise ValueError(f"E4M3Shard: bag {i}: exp must be an int in -7 .. 15, got {e!r}")
+        if sum(rows) != codes.shape[0]:
+            raise ValueError(f"E4M3Shard: the bags have {sum(rows)} rows, the codes {codes.shape[0]}")
+        meta = []
+        for name, v, dt in (("label", label, torch.int64), ("site", site, torch.int64), ("sex", sex, torch.float32)):
+            v = torch.as_tensor(v)
+            if v.dim() != 1 or v.shape[0] != b:
+                raise ValueError(f"E4M3Shard: {name} must have one entry per bag ({b}), got shape {tuple(v.shape)}")
+            if (dt is torch.int64) == v.dtype.is_floating_point:
+                raise ValueError(f"E4M3Shard: {name} must be {'integers' if dt is torch.int64 else 'floating point'}, got {v.dtype}")
+            meta.append(v.to(dtype=dt).contiguous())
+        self.codes = codes.contiguous().view(torch.uint8)
+        self.rows, self.exps = rows, exps
+        self.label, self.site, self.sex = meta
+
+    def __len__(self) -> int:
+        return len(self.rows)
+
+    @property
+    def offsets(self):
+        """B + 1 row offsets: 0 first, the rows of the codes last."""
+        offs = [0]
+        for r in self.rows:
+            offs.append(offs[-1] + r)
+        return offs
+
+    def bag(self, i: int) -> E4M3Bag:
+        offs = self.offsets
+        return E4M3Bag(self.codes[offs[i]:offs[i + 1]], self.exps[i])
+
+    def records(self):
+        """The per-bag ``Record`` tuples (E4M3Bag, label, site, sex) BagPrefetcher takes: the same shard fed down the per-record path."""
+        return [(self.bag(i), int(self.label[i]), int(self.site[i]), float(self.sex[i])) for i in range(len(self))]
+
+
+_SHARD_KEYS = ("e4m3_shard", "rows", "exp", "label", "site", "sex")
+
+
+def _shard_from_dict(d: dict) -> E4M3Shard:
+    if any(k not in d for k in _SHARD_KEYS):
+        raise ValueError(f"an e4m3 shard is a dict with the keys {', '.join(_SHARD_KEYS)}, got {sorted(map(str, d))}")
+    for k, dt in (("rows", torch.int64), ("exp", torch.int32)):
+        if not isinstance(d[k], torch.Tensor) or d[k].dtype != dt or d[k].dim() != 1:
+            raise ValueError(f"an e4m3 shard's '{k}' is a {dt} [B] tensor")
+    for k in ("label", "site", "sex"):
+        if not isinstance(d[k], torch.Tensor):
+            raise ValueError(f"an e4m3 shard's '{k}' is a [B] tensor")
+    return E4M3Shard(d["e4m3_shard"], d["rows"], d["exp"], d["label"], d["site"], d["sex"])
+
+
+def save_shard_e4m3(path, shard: E4M3Shard) -> E4M3Shard:
+    """Write ``shard`` in the file form above."""
+    if not isinstance(shard, E4M3Shard):
+        raise ValueError("save_shard_e4m3: shard must be an E4M3Shard (quantise_shard makes one)")
+    torch.save({"e4m3_shard": shard.codes.cpu().view(torch.float8_e4m3fn), "rows": torch.tensor(shard.rows, dtype=torch.int64),
+                "exp": torch.tensor(shard.exps, dtype=torch.int32), "label": shard.label.cpu(), "site": shard.site.cpu(), "sex": shard.sex.cpu()}, path)
+    return shard
+
+
+def quantise_shard(bags, offsets, label, site, sex, exps=None) -> E4M3Shard:
+    """The shard of fp32 / fp16 bags, on whatever device they lie (``ops.bags_quantise_e4m3``). ``bags``: ONE [R, K] concatenation with ``offsets`` (B + 1
+    row offsets), or a list of [N_b, K] bags (``offsets=None``; they are concatenated here). ``exps=None`` picks each bag's exponent from its largest
+    magnitude, with one read-back for the whole shard. The codes stay on the device of the data; label / site / sex are kept on the host."""
+    from . import ops
+    if isinstance(bags, torch.Tensor):
+        if offsets is None:
+            raise ValueError("quantise_shard: a concatenation needs its row offsets")
+        x = bags
+    else:
+        bags = list(bags)
+        if offsets is not None:
+            raise ValueError("quantise_shard: a list of bags brings its own offsets: pass offsets=None")
+        if not bags or any(not isinstance(b, torch.Tensor) or b.dim() != 2 or b.shape[1] != bags[0].shape[1] for b in bags):
+            raise ValueError("quantise_shard: bags must be a non-empty list of [N, features] tensors of one width")
+        offsets = [0]
+        for b in bags:
+            offsets.append(offsets[-1] + b.shape[0])
+        x = torch.cat(bags)
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError("quantise_shard: the concatenation must be a [R, features] tensor")
+    if x.dtype not in (torch.float32, torch.float16):
+        x = x.to(torch.float32)
+    codes, exps = ops.bags_quantise_e4m3(x.contiguous(), offsets, exps)
+    offs = [int(o) for o in (offsets.tolist() if isinstance(offsets, torch.Tensor) else offsets)]
+    cpu = lambda v: v.cpu() if isinstance(v, torch.Tensor) else v                         # noqa: E731
+    return E4M3Shard(codes, [b - a for a, b in zip(offs, offs[1:])], exps, cpu(label), cpu(site), cpu(sex))
+
+
+def _load_shard(source) -> E4M3Shard:
+    if isinstance(source, (E4M3Shard, dict)):
+        s = source
+    elif callable(source):
+        s = source()
+    else:
+        s = torch.load(source, map_location="cpu", weights_only=True)
+    if isinstance(s, dict):
+        s = _shard_from_dict(s)
+    if not isinstance(s, E4M3Shard):
+        raise ValueError(f"a shard source must give an E4M3Shard or its dict, got {type(s).__name__}")
+    return s
+
+
+class BagBatch:
+    """What ShardPrefetcher yields: ``bags`` [R, K] (the decoded concatenation), ``offsets`` (Python list of B + 1 row offsets), ``sex`` float32 [B],
+    ``label`` / ``site`` int64 [B], all but the offsets on the device. ``SlideShardedDP.step_batch`` takes it as it is."""
+    __slots__ = ("bags", "offsets", "sex", "label", "site")
+
+    def __init__(self, bags, offsets, sex, label, site):
+        self.bags, self.offsets, self.sex, self.label, self.site = bags, offsets, sex, label, site
+
+    def __len__(self) -> int:
+        return len(self.offsets) - 1
+
+    def slides(self):
+        """The ``dp.Slide`` tuples (bag view, sex [1], label [1], site [1]) - NOT BagPrefetcher's order, which is (bag, label, site, sex)."""
+        o = self.offsets
+        return [(self.bags[o[i]:o[i + 1]], self.sex[i:i + 1], self.label[i:i + 1], self.site[i:i + 1]) for i in range(len(self))]
+
+
+class ShardPrefetcher:
+    """Iterate one ``BagBatch`` per shard, in order, with ``depth`` shards in flight. A source is an ``E4M3Shard``, its dict, a path or a callable. Per
+    shard, whatever the number of its bags: the host side (ONE future) pins the codes and two small metadata tensors (label and site as one int64 [2, B],
+    sex); the device side, on the copy stream, makes one copy of the codes, two metadata copies, ONE ``ops.bags_dequantise_e4m3`` into a [R, K] tensor of
+    ``dtype`` (fp16 or fp32) and one event. The consumer's stream waits on the event, the host does not. ``device="cpu"`` works through the CPU paths."""
+
+    def __init__(self, shards, device: Union[str, torch.device], depth: int = 2, workers: int = 2, dtype: torch.dtype = torch.float16):
+        self.shards = list(shards)
+        self.device = torch.device(device)
+        self.depth = max(1, int(depth))
+        self.workers = max(1, int(workers))
+        if dtype not in (torch.float16, torch.float32):
+            raise ValueError("ShardPrefetcher(dtype=...) must be torch.float16 or torch.float32")
+        self.dtype = dtype
+        self.on_gpu = self.device.type == "cuda"
+        self.copy_stream = torch.cuda.Stream(device=self.device) if self.on_gpu else None
+
+    def __len__(self) -> int:
+        return len(self.shards)
+
+    # -- stage 1 (worker thread): read + pin
+    def _stage_host(self, source):
+        s = _load_shard(source)
+        codes, meta, sx = s.codes, torch.stack([s.label, s.site]), s.sex
+        if self.on_gpu:                                         # page-locked so every copy is truly asynchronous
+            codes = codes if codes.is_pinned() else codes.pin_memory()
+            meta, sx = meta.pin_memory(), sx if sx.is_pinned() else sx.pin_memory()
+        return codes, s.offsets, s.exps, meta, sx
+
+    # -- stage 2 (consumer thread, copy stream): one copy, one decode
+    def _stage_device(self, host):
+        from . import ops
+        codes, offsets, exps, meta, sx = host
+        if not self.on_gpu:
+            return BagBatch(ops.bags_dequantise_e4m3(codes, offsets, exps, out_dtype=self.dtype), offsets, sx, meta[0], meta[1]), None
+        with torch.cuda.stream(self.copy_stream):
+            # (the staging tensor of the codes is allocated and dropped under the copy stream, so the allocator's stream ordering covers its reuse)
+            bags = ops.bags_dequantise_e4m3(codes.to(self.device, non_blocking=True), offsets, exps, out_dtype=self.dtype)
+            meta_d = meta.to(self.device, non_blocking=True)
+            sx_d = sx.to(self.device, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.copy_stream)
+        return BagBatch(bags, offsets, sx_d, meta_d[0], meta_d[1]), ev
+
+    def __iter__(self) -> Iterator[BagBatch]:
+        n = len(self.shards)
+        if n == 0:
+            return
+        with ThreadPoolExecutor(max_workers=self.workers) as pool:
+            host_futs = {}                                       # index -> future of the pinned host shard
+            dev_ready = {}                                       # index -> (batch, event)
+            next_host = 0
+
+            def top_up(upto: int):
+                nonlocal next_host
+                while next_host < min(n, upto):
+                    host_futs[next_host] = pool.submit(self._stage_host, self.shards[next_host])
+                    next_host += 1
+
+            top_up(self.depth + 1)
+            for i in range(n):
+                # issue the device copies of everything whose host stage is done, up to `depth` ahead
+                for jx in range(i, min(n, i + self.depth)):
+                    if jx not in dev_ready and jx in host_futs and (jx == i or host_futs[jx].done()):
+                        dev_ready[jx] = self._stage_device(host_futs.pop(jx).result())   # .result() re-raises loader errors
+                top_up(i + self.depth + 2)
+                batch, ev = dev_ready.pop(i)
+                if ev is not None:
+                    cur = torch.cuda.current_stream(self.device)
+                    cur.wait_event(ev)                          # consumer stream waits for the copy, the host does not
+                    for t in (batch.bags, batch.sex, batch.label):   # (label and site are rows of one tensor) allocator: do not recycle while in use
+                        t.record_stream(cur)
+                yield batch

@@ -2243,3 +2243,123 @@ def bag_quantise_e4m3(x: torch.Tensor, exp: Optional[int] = None) -> Tuple[torch
     if x.numel():
         _lib.check(_lib.load().toad_bag_quant_e4m3(_p(x), int(x.dtype == torch.float16), _p(codes), x.numel(), exp, _stream()), "toad_bag_quant_e4m3")
     return codes, exp
+
+
+# ---- e4m3 shards: a list of e4m3 bags back to back, one exponent each, in one call (csrc/bag_e4m3.hip, "a LIST of bags") -------------------------------
+E4M3_LIST_MAX = 64                         # TOAD_E4M3_LIST_MAX: bags per launch; a longer list is several launches inside the one call
+
+
+def _e4m3_offsets_arg(name: str, offsets, rows: int):
+    """-> the row offsets as a list of B + 1 ints: 0 first, non-decreasing, ``rows`` last."""
+    try:
+        offs = [int(o) for o in (offsets.tolist() if isinstance(offsets, torch.Tensor) else offsets)]
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: offsets must be B + 1 integers") from None
+    if len(offs) < 1 or offs[0] != 0:
+        raise ValueError(f"{name}: offsets must start with 0, got {offs[:1]}")
+    for i in range(len(offs) - 1):
+        if offs[i + 1] < offs[i]:
+            raise ValueError(f"{name}: bag {i}: offsets decrease from {offs[i]} to {offs[i + 1]}")
+    if offs[-1] != rows:
+        raise ValueError(f"{name}: offsets end at {offs[-1]}, the concatenation has {rows} rows")
+    return offs
+
+
+def _e4m3_exps_arg(name: str, exps, nb: int):
+    exps = exps.tolist() if isinstance(exps, torch.Tensor) else list(exps)
+    if len(exps) != nb:
+        raise ValueError(f"{name}: {len(exps)} exponents for {nb} bags")
+    for i, e in enumerate(exps):
+        if not isinstance(e, int) or isinstance(e, bool) or not E4M3_EXP_MIN <= e <= E4M3_EXP_MAX:
+            raise ValueError(f"{name}: bag {i}: exp must be an int in {E4M3_EXP_MIN} .. {E4M3_EXP_MAX}, got {e!r}")
+    return exps
+
+
+def bags_dequantise_e4m3(codes: torch.Tensor, offsets, exps, out: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float16) -> torch.Tensor:
+    """The fp16 / fp32 concatenation of a list of e4m3 bags that lie back to back (toad_bags_dequant_e4m3): bag b is rows offsets[b] .. offsets[b + 1] of
+    ``codes`` (contiguous [R, K] torch.uint8 or torch.float8_e4m3fn) and is decoded with exps[b], bit for bit what bag_dequantise_e4m3 gives on its slice.
+    ``offsets``: B + 1 ints, 0 first, non-decreasing, R last (empty bags anywhere); ``exps``: B ints in -7 .. 15. ``out`` as for the single call. On a
+    device tensor: ONE launch per E4M3_LIST_MAX non-empty bags on the current stream, no upload, no synchronisation. A CPU tensor goes bag by bag through
+    the single call's CPU path. Anything else is a ValueError, with the bag named."""
+    name = "bags_dequantise_e4m3"
+    if not isinstance(codes, torch.Tensor) or codes.dtype not in (torch.uint8, torch.float8_e4m3fn) or codes.dim() != 2 or not codes.is_contiguous():
+        raise ValueError(f"{name}: codes must be a contiguous [R, K] torch.uint8 or torch.float8_e4m3fn tensor")
+    offs = _e4m3_offsets_arg(name, offsets, codes.shape[0])
+    nb = len(offs) - 1
+    exps = _e4m3_exps_arg(name, exps, nb)
+    if out is None:
+        if out_dtype not in (torch.float16, torch.float32):
+            raise ValueError(f"{name}: out_dtype must be torch.float16 or torch.float32, got {out_dtype}")
+        out = torch.empty(codes.shape, dtype=out_dtype, device=codes.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype not in (torch.float16, torch.float32) or out.shape != codes.shape or not out.is_contiguous() \
+            or out.device != codes.device:
+        raise ValueError(f"{name}: out must be a contiguous fp16 or fp32 tensor of the codes' shape {tuple(codes.shape)} on their device")
+    if codes.numel() == 0:
+        return out
+    if not codes.is_cuda:
+        for b in range(nb):
+            if offs[b + 1] > offs[b]:
+                bag_dequantise_e4m3(codes[offs[b]:offs[b + 1]], exps[b], out=out[offs[b]:offs[b + 1]])
+        return out
+    _lib.check(_lib.load().toad_bags_dequant_e4m3(_p(codes), _p(out), int(out.dtype == torch.float32), codes.shape[1], (ctypes.c_int64 * (nb + 1))(*offs),
+                                                  (ctypes.c_int * nb)(*exps), nb, _stream()), "toad_bags_dequant_e4m3")
+    return out
+
+
+def _e4m3_list_x(name: str, x, offsets):
+    if not isinstance(x, torch.Tensor) or x.dtype not in (torch.float32, torch.float16) or x.dim() != 2 or not x.is_contiguous():
+        raise ValueError(f"{name}: x must be a contiguous [R, K] fp32 or fp16 tensor")
+    return _e4m3_offsets_arg(name, offsets, x.shape[0])
+
+
+def bags_absmax(x: torch.Tensor, offsets) -> torch.Tensor:
+    """-> uint32 [B] on x's device: the fp32 bit pattern of the largest |x| of each bag of the concatenation ``x`` (contiguous [R, K] fp32 or fp16; rows
+    offsets[b] .. offsets[b + 1] are bag b), fp16 up-cast exactly (toad_bags_absmax_bits). The unsigned maximum of the sign-cleared patterns: an Inf gives
+    0x7F800000, any NaN in the bag a pattern above it, an empty bag 0. One fill and one launch per E4M3_LIST_MAX non-empty bags on the current stream,
+    NO read-back. A CPU tensor takes the same call through torch ops, with identical bits for bags without a NaN."""
+    name = "bags_absmax"
+    offs = _e4m3_list_x(name, x, offsets)
+    nb = len(offs) - 1
+    if not x.is_cuda:
+        bits = torch.zeros(nb, dtype=torch.int64)
+        for b in range(nb):
+            if offs[b + 1] > offs[b] and x.shape[1]:
+                bits[b] = (x[offs[b]:offs[b + 1]].to(torch.float32).view(torch.int32).to(torch.int64) & 0x7FFFFFFF).max()
+        return bits.to(torch.int32).view(torch.uint32)         # (sign-cleared patterns fit int32; torch has few uint32 kernels)
+    if not x.numel():                                          # (an empty tensor has no address to pass)
+        return torch.zeros(nb, dtype=torch.int32, device=x.device).view(torch.uint32)
+    amax = torch.empty(nb, dtype=torch.int32, device=x.device)
+    if nb:
+        _lib.check(_lib.load().toad_bags_absmax_bits(_p(x), int(x.dtype == torch.float16), _p(amax), x.shape[1], (ctypes.c_int64 * (nb + 1))(*offs), nb,
+                                                     _stream()), "toad_bags_absmax_bits")
+    return amax.view(torch.uint32)
+
+
+def bags_quantise_e4m3(x: torch.Tensor, offsets, exps=None):
+    """-> (codes uint8 [R, K], exps list of B ints): the e4m3 bags of a concatenation of fp32 or fp16 bags (toad_bags_quant_e4m3), bag b - rows
+    offsets[b] .. offsets[b + 1] - with its own exponent, bit for bit what bag_quantise_e4m3 gives on its slice. ``exps=None``: e4m3_exponent of each bag's
+    largest magnitude, from bags_absmax and ONE read-back of B words (not one per bag); a NaN or an Inf in a bag is a ValueError naming the bag. With
+    ``exps`` given there is no synchronisation. On a device tensor: one launch per E4M3_LIST_MAX non-empty bags on the current stream. A CPU tensor goes
+    bag by bag through the single call's CPU path."""
+    import struct
+    name = "bags_quantise_e4m3"
+    offs = _e4m3_list_x(name, x, offsets)
+    nb = len(offs) - 1
+    if exps is None:
+        exps = []
+        for b, bits in enumerate(bags_absmax(x, offs).view(torch.int32).cpu().tolist()):
+            bits &= 0xFFFFFFFF
+            if bits >= 0x7F800000:
+                raise ValueError(f"{name}: bag {b}: a NaN or Inf in the bag (abs-max bits {bits:#010x})")
+            exps.append(e4m3_exponent(struct.unpack("<f", struct.pack("<I", bits))[0]))
+    exps = _e4m3_exps_arg(name, exps, nb)
+    codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    if not x.is_cuda:
+        for b in range(nb):
+            if offs[b + 1] > offs[b]:
+                codes[offs[b]:offs[b + 1]] = bag_quantise_e4m3(x[offs[b]:offs[b + 1]], exps[b])[0]
+        return codes, exps
+    if x.numel():
+        _lib.check(_lib.load().toad_bags_quant_e4m3(_p(x), int(x.dtype == torch.float16), _p(codes), x.shape[1], (ctypes.c_int64 * (nb + 1))(*offs),
+                                                    (ctypes.c_int * nb)(*exps), nb, _stream()), "toad_bags_quant_e4m3")
+    return codes, exps

@@ -12,9 +12,11 @@
   host_fed: 52 x 10,000-patch bags (--slides / --patches: another shape, 5 x 100,000 for one) from page-locked host memory through
       BagPrefetcher(depth=2, arena_rows=524288) into SlideShardedDP.step (one optimiser step per 52 slides). Three wires, alternated, three runs each:
       fp32 files landing in fp32 buffers, fp16 files and e4m3 files (8-bit codes, decoded behind each copy) landing in fp16 buffers: slides/s, link
-      GB/s. Together with --resident the rows carry the ratio to the resident x16 call of the same shape.
+      GB/s. Together with --resident the rows carry the ratio to the resident x16 call of the same shape. A fourth wire, "e4m3 shards": the same codes
+      as ONE ingest.E4M3Shard per optimiser step (one copy, one list decode) through ShardPrefetcher(depth=2) into SlideShardedDP.step_batch.
   dequant: the e4m3 decode and quantise kernels alone at 524,288 x 1024 and 10,000 x 1024 (device events, four buffer sets in rotation): us and moved
-      bytes/s; and the decode of one step's 520,000 rows as a share of that step's x16 multi-slide call.
+      bytes/s; and the decode of one step's 520,000 rows as a share of that step's x16 multi-slide call - as one launch over all rows, as 52 per-bag
+      launches, and as ONE list launch of 52 bags with an exponent each (ops.bags_dequantise_e4m3).
   launches: four calls of ONE arm (--arm A | B | ONE = the one-slide x16 step) at one shape, for a `rocprofv3 --kernel-trace --stats` run of
       its own: kernel names and counts per call show which weight-gradient and NT kernels the arm ran.
 
@@ -157,28 +159,36 @@ def one_slide(seconds):
 
 
 HAVE_E4M3 = "toad_bag_dequant_e4m3" in _lib.SIGNATURES
+HAVE_E4M3_LIST = "toad_bags_dequant_e4m3" in _lib.SIGNATURES
 
 
 def host_fed(steps=6, B=52, n=10000, arena_rows=524288, rounds=3):
     """Three wires - fp32 files into fp32 landing buffers, fp16 files and e4m3 files (ingest.E4M3Bag: the codes cross the link, the decode runs behind
     each copy) into fp16 ones - ALTERNATED, `rounds` runs of `steps` optimiser steps each. One row per wire with every run's figures, the medians, and
-    for the e4m3 wire whether its median slides/s lies above the fp16 wire's maximum."""
+    for the e4m3 wire whether its median slides/s lies above the fp16 wire's maximum. The fourth wire, e4m3_shard, carries the e4m3 wire's codes as one
+    ingest.E4M3Shard per step through ShardPrefetcher into step_batch; its row says whether its median lies above the e4m3 wire's maximum."""
     from toad_amd.dp import SlideShardedDP
-    from toad_amd.ingest import BagPrefetcher, E4M3Bag
+    from toad_amd.ingest import BagPrefetcher, E4M3Bag, E4M3Shard, ShardPrefetcher
     dev = torch.device("cuda:0")
     arena_rows = max(arena_rows, n)
     g = torch.Generator().manual_seed(3)
     seedbags = [torch.randn(n, 1024, generator=g) * 0.7 for _ in range(min(B, 4))]       # the values do not move the clock: four bags, copied round
     legs = {}
-    for wire, dt in (("fp32", torch.float32), ("fp16", torch.float16), ("e4m3", torch.uint8)):
-        if (wire != "fp32" and not HAVE_X16_MULTI) or (wire == "e4m3" and not HAVE_E4M3):
+    for wire, dt in (("fp32", torch.float32), ("fp16", torch.float16), ("e4m3", torch.uint8), ("e4m3_shard", torch.uint8)):
+        if (wire != "fp32" and not HAVE_X16_MULTI) or (wire.startswith("e4m3") and not HAVE_E4M3) or (wire == "e4m3_shard" and not HAVE_E4M3_LIST):
             continue
-        if wire == "e4m3":
+        if wire.startswith("e4m3"):
             src = [ops.bag_quantise_e4m3(b) for b in seedbags]
         else:
             src = [(b.to(dt), None) for b in seedbags]
         host = []
-        for i in range(B):                                       # one step's bags in page-locked memory, cycled step after step
+        if wire == "e4m3_shard":                                 # one step's bags as ONE record in page-locked memory, cycled step after step
+            hb = torch.empty((B * n, 1024), dtype=dt, pin_memory=True)
+            for i in range(B):
+                hb[i * n:(i + 1) * n].copy_(src[i % len(src)][0])
+            host = E4M3Shard(hb, [n] * B, [src[i % len(src)][1] for i in range(B)], torch.arange(B) % C, torch.arange(B) % 2,
+                             ((torch.arange(B) // 2) % 2).float())
+        for i in range(B if wire != "e4m3_shard" else 0):        # one step's bags in page-locked memory, cycled step after step
             hb = torch.empty((n, 1024), dtype=dt, pin_memory=True)
             hb.copy_(src[i % len(src)][0])
             host.append(E4M3Bag(hb, src[i % len(src)][1]) if wire == "e4m3" else hb)
@@ -188,6 +198,10 @@ def host_fed(steps=6, B=52, n=10000, arena_rows=524288, rounds=3):
         legs[wire] = dict(host=host, kw=kw, dp=dp, nbytes=B * n * 1024 * torch.empty((), dtype=dt).element_size(), runs=[], timed={}, calls=0)
 
     def run(leg, k):
+        if isinstance(leg["host"], E4M3Shard):
+            for batch in ShardPrefetcher([leg["host"]] * k, dev, depth=2, workers=2, dtype=torch.float16):
+                leg["dp"].step_batch(batch, B)
+            return
         recs = [(leg["host"][i % B], i % C, i % 2, float((i // 2) % 2)) for i in range(k * B)]
         batch = []
         for bag, lb, st, sx in BagPrefetcher(recs, dev, depth=2, workers=2, **leg["kw"]):
@@ -218,6 +232,9 @@ def host_fed(steps=6, B=52, n=10000, arena_rows=524288, rounds=3):
     if "e4m3" in by and "fp16" in by:
         by["e4m3"]["fp16_max_slides_per_s"] = max(by["fp16"]["slides_per_s_runs"])
         by["e4m3"]["median_above_fp16_max"] = bool(by["e4m3"]["slides_per_s"] > max(by["fp16"]["slides_per_s_runs"]))
+    if "e4m3_shard" in by and "e4m3" in by:
+        by["e4m3_shard"]["e4m3_max_slides_per_s"] = max(by["e4m3"]["slides_per_s_runs"])
+        by["e4m3_shard"]["median_above_e4m3_max"] = bool(by["e4m3_shard"]["slides_per_s"] > max(by["e4m3"]["slides_per_s_runs"]))
     del legs
     ops.release_workspaces()
     torch.cuda.empty_cache()
@@ -262,17 +279,29 @@ def dequant(seconds, step_shape=(52, 10000)):
         bags16 = [pool16[i * n:(i + 1) * n] for i in range(B)]
         codes = ops.bag_quantise_e4m3(pool16, 7)[0]
         land = torch.empty_like(pool16)
+        offs, exps = [i * n for i in range(B + 1)], [7] * B                # (one exponent so all three arms write the same bytes; the list kernel reads it per bag)
         sex = (torch.arange(B, device=dev) % 2).float()
         label = torch.arange(B, device=dev) % C
         site = (torch.arange(B, device=dev) // 2) % 2
-        t, iters = alternate({"x16_step": lambda: ops.mil_multi_step(w, gr, 0.0, bags16, sex, label, site, 0.75 / B, 0.25 / B),
-                              "decode_step_rows": lambda: ops.bag_dequantise_e4m3(codes, 7, out=land),
-                              "decode_per_bag": lambda: [ops.bag_dequantise_e4m3(codes[i * n:(i + 1) * n], 7, out=land[i * n:(i + 1) * n]) for i in range(B)]},
-                             seconds)
+        arms = {"x16_step": lambda: ops.mil_multi_step(w, gr, 0.0, bags16, sex, label, site, 0.75 / B, 0.25 / B),
+                "decode_step_rows": lambda: ops.bag_dequantise_e4m3(codes, 7, out=land),
+                "decode_per_bag": lambda: [ops.bag_dequantise_e4m3(codes[i * n:(i + 1) * n], 7, out=land[i * n:(i + 1) * n]) for i in range(B)]}
+        if HAVE_E4M3_LIST:
+            arms["decode_list"] = lambda: ops.bags_dequantise_e4m3(codes, offs, exps, out=land)
+        t, iters = alternate(arms, seconds)
         ms = {k: round(median(v), 4) for k, v in t.items()}
-        res.append(dict(kind="dequant_share", lib=select_lib.TAG, slides=B, patches=n, rows=B * n, ms=ms, iters_per_round=iters,
-                        decode_share_of_x16_step=round(ms["decode_step_rows"] / ms["x16_step"], 4),
-                        decode_per_bag_share_of_x16_step=round(ms["decode_per_bag"] / ms["x16_step"], 4)))
+        row = dict(kind="dequant_share", lib=select_lib.TAG, slides=B, patches=n, rows=B * n, ms=ms, iters_per_round=iters,
+                   decode_share_of_x16_step=round(ms["decode_step_rows"] / ms["x16_step"], 4),
+                   decode_per_bag_share_of_x16_step=round(ms["decode_per_bag"] / ms["x16_step"], 4))
+        if HAVE_E4M3_LIST:
+            one = t["decode_step_rows"]                                    # the single launch's interleaved halves: the spread a difference has to exceed
+            h1, h2 = median(one[0::2]), median(one[1::2])
+            row.update(ms_runs={k: [round(v, 4) for v in t[k]] for k in ("decode_step_rows", "decode_per_bag", "decode_list")},
+                       single_launch_halves_ms=[round(h1, 4), round(h2, 4)], single_launch_spread_ms=round(abs(h1 - h2), 4),
+                       list_over_single_launch=round(ms["decode_list"] / ms["decode_step_rows"], 4),
+                       list_over_per_bag=round(ms["decode_list"] / ms["decode_per_bag"], 4),
+                       list_faster_than_per_bag_beyond_spread=bool(ms["decode_per_bag"] - ms["decode_list"] > abs(h1 - h2)))
+        res.append(row)
     return res
 
 
